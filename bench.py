@@ -1,7 +1,15 @@
 """Bench: Msamples/s of nart's render path on glassSphere.json at 1920x1080, 256 spp (C3).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit,
+ms_per_step and the per-step timings the timed steps themselves recorded).  --full adds what
+takes runs of its own: the counter passes and the roofline, the cpu_baseline and the parity of
+the sampled buckets, the finiteness check of the image.  --dump-outputs DIR writes what the last
+timed step returned to its caller, the framebuffer, as DIR/image.npy (float32; above 48 MB a
+fixed, seeded sample of its pixels).  The inputs are the same from run to run, so two builds can
+be compared output for output.
 
 Without a launcher, --gpus N > 1 spawns the N rank processes itself (nart_amd.dist.spawn_ranks,
 before any GPU call); under a launcher, --gpus must equal WORLD_SIZE or the bench exits non-zero.
@@ -15,9 +23,9 @@ so the image is bit-identical for any N.  Total work is fixed as N grows ("stron
 
 value = W*H*spp*K / T (Msamples/s, camera samples, render.cpp:164-168 extra rows excluded),
 T = max over ranks of the barrier-bracketed wall time of the K steps.
-roofline: the path-tracing kernel's algorithmic bytes per launch (counter pass, SURVEY.md 8(d)
-per-sample figure) / its HIP-event duration.
-cpu_baseline: the oracle (line-faithful C restatement of the TBB tile renderer, oracle/) on a
+roofline (--full): the path-tracing kernel's algorithmic bytes per launch (counter pass, SURVEY.md
+8(d) per-sample figure) / its HIP-event duration.
+cpu_baseline (--full): the oracle (line-faithful C restatement of the TBB tile renderer, oracle/) on a
 bounded bucket sample of the same frame, timed on this host (rank 0, N=1 only).  The GPU's
 tiles of those buckets are compared with the oracle's bit for bit ("parity").
 The other BASELINE.json configs (C2 Cornell, C4 environment-lit textured scene, C5 volume) run
@@ -159,6 +167,85 @@ def workload_name(cfg, a, W, H, SPP):
     return "%s, resized to %dx%d %dspp (rehearsal, not the bench workload)" % (cfg["workload"], W, H, SPP)
 
 
+def roofline_figures(p, st, counters, counters16, n_sample, sample_stride, tiles_bytes, tag):
+    """--full: the roofline entry of the line, from the timed steps' stats `st`, the two counter
+    passes and the committed rocprofv3 summary of frame size `tag` (load_profile)."""
+    kernel_avg_ms = st.kernel_ms / max(1, st.kernel_launches)  # k_primary + k_render_rq per launch
+    primary_avg_ms = st.primary_ms / max(1, st.kernel_launches)
+    bps = bytes_per_sample(counters)
+    bps16 = bytes_per_sample(counters16)
+    per_launch_samples = st.traced_samples / max(1, st.kernel_launches)
+    achieved = bps * per_launch_samples / (kernel_avg_ms * 1e-3) / 1e9
+    prof, prof_src = load_profile(tag)
+    traffic = prof.get("hbm_bytes_per_launch") if prof else None
+    # The path kernels are latency/issue-bound, not HBM-bound: achieved/frac price the contract's
+    # ALGORITHMIC bytes (SURVEY.md 8(d): BVH nodes, triangles, rays, path state per sample) against
+    # the HBM ceiling, but those bytes are served from LDS/L1/L2 (a ~0.5 MB scene).  What HBM really
+    # moves is `traffic` (rocprofv3 2 x FETCH_SIZE + WRITE_SIZE per launch) -> measured_frac, and
+    # what limits the kernel shows in lane_utilization (SQ_THREAD_CYCLES_VALU / 64
+    # SQ_ACTIVE_INST_VALU: divergent lanes) and valu_busy.
+    # `bound` is the contract's ceiling class (no MFMA on this path, so "hbm"); `frac` is the
+    # contract's algorithmic fraction and is restated as `algorithmic_frac`, beside the measured
+    # `measured_frac`, so neither reads as the other (ADVICE r04).
+    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
+                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                "frac_kind": "algorithmic: contract bytes (SURVEY.md 8(d)) / kernel time / HBM peak; most of those "
+                             "bytes are served by LDS/L1/L2, so this is NOT measured HBM utilisation "
+                             "(that is measured_frac)",
+                "algorithmic_frac": round(achieved / HBM_PEAK_GBPS, 4),
+                "achieved_kind": "algorithmic bytes per launch (SURVEY.md 8(d) per-sample model x traced samples)",
+                "limiter_class": "latency",
+                "limiter": "latency/issue: dependent LDS/L2 loads in BVH traversal and divergent lanes "
+                           "(DESIGN.md section 4), not HBM bandwidth",
+                "measured_frac": (round(traffic / (kernel_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+                                  if traffic else None),
+                "lane_utilization": prof.get("lane_utilization") if prof else None,
+                "valu_busy": prof.get("valu_busy") if prof else None,
+                # issue-rate ceiling of the path kernel (DESIGN.md section 4): issue_frac =
+                # (SQ_ACTIVE_INST_VALU + SQ_INSTS_SALU) / SQ_WAVE_CYCLES, the fraction of a wave's
+                # issue slots (one per quad-cycle) it used; simd_valu_frac = the SIMD's VALU pipe
+                # (two wave64 instructions per quad-cycle) over its resident waves
+                "issue_frac": prof.get("issue_frac") if prof else None,
+                "simd_valu_frac": prof.get("simd_valu_frac") if prof else None,
+                "waves_per_simd": prof.get("waves_per_simd") if prof else None,
+                "traffic_source": prof_src,
+                "kernel": "k_render_volume_sm" if p.integrator == 1 else "k_primary + k_render_rq",
+                "kernel_avg_ms": round(kernel_avg_ms, 3), "bytes_per_sample": round(bps, 1),
+                "bytes_per_sample_source": {
+                    "spp": p.spp, "sample": "counter pass at the timed spp over %d buckets of this rank's share (the "
+                                            "cpu_baseline sample: every %dth bucket)" % (n_sample, sample_stride),
+                    "cross_check_16spp_whole_share": round(bps16, 1),
+                    "ratio_16spp_over_timed": round(bps16 / bps, 4)},
+                "rays_per_s": round((counters["rays_extend"] + counters["rays_shadow"]) /
+                                    max(1, counters["traced_samples"]) * per_launch_samples /
+                                    (kernel_avg_ms * 1e-3), 1)}
+    ratios = kernel_ratios(prof, per_launch_samples, tiles_bytes)
+    if ratios:
+        roofline["other_kernels"] = ratios
+    if p.integrator != 1:
+        # the path tracing is two launches (camera rays, then the path kernel); the counters and
+        # the time above cover both, the rocprofv3 summary lists them separately
+        roofline["kernel_split_ms"] = {"k_primary": round(primary_avg_ms, 3),
+                                       "k_render_rq": round(kernel_avg_ms - primary_avg_ms, 3)}
+    return roofline
+
+
+DUMP_LIMIT = 48 << 20 # bytes of DIR/image.npy; larger framebuffers (4K) are sampled
+
+
+def dump_outputs(d, image):
+    """--dump-outputs: the framebuffer the last timed step returned (float32 Pixels, extra rows
+    included) as DIR/image.npy; above DUMP_LIMIT a fixed sample of its pixels (seed 0, in raster
+    order), the same pixels for every run of the same frame size."""
+    os.makedirs(d, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.nbytes > DUMP_LIMIT:
+        px = img.reshape(-1, img.shape[-1])
+        k = DUMP_LIMIT // (4 * img.shape[-1])
+        img = px[np.sort(np.random.default_rng(0).choice(len(px), size=k, replace=False))]
+    np.save(os.path.join(d, "image.npy"), img)
+
+
 def one_process_main(a, cfg, W, H, SPP):
     """--one-process: the whole frame through nart_hip_render_device on a multi-device context
     (the path the C ABI and the `nart` CLI ship): per-device host threads render their lattice
@@ -190,15 +277,17 @@ def one_process_main(a, cfg, W, H, SPP):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     value = W * H * SPP * a.steps / dt / 1e6
-    n_img = g.total_height * g.total_width * 5
-    image = torch.empty(n_img, dtype=torch.float32, device="cuda:0")
-    # copy the context's device image into a torch tensor (device to device, after the timed steps)
-    import ctypes
-    hip = ctypes.CDLL("libamdhip64.so")
-    rc = hip.hipMemcpy(ctypes.c_void_p(image.data_ptr()), ctypes.c_void_p(dptr), ctypes.c_size_t(n_img * 4),
-                       ctypes.c_int(3))  # hipMemcpyDeviceToDevice
-    assert rc == 0, rc
-    image = image.view(g.total_height, g.total_width, 5)
+    image = None
+    if a.full or a.dump_image or a.dump_outputs:
+        # copy the context's device image into a torch tensor (device to device, after the timed steps)
+        import ctypes
+        n_img = g.total_height * g.total_width * 5
+        image = torch.empty(n_img, dtype=torch.float32, device="cuda:0")
+        hip = ctypes.CDLL("libamdhip64.so")
+        rc = hip.hipMemcpy(ctypes.c_void_p(image.data_ptr()), ctypes.c_void_p(dptr), ctypes.c_size_t(n_img * 4),
+                           ctypes.c_int(3))  # hipMemcpyDeviceToDevice
+        assert rc == 0, rc
+        image = image.view(g.total_height, g.total_width, 5)
     out = {
         "metric": "Msamples/s at %dx%dx%dspp (%s)" % (W, H, SPP, os.path.basename(path)),
         "value": round(value, 3), "unit": "Msamples/s", "n_gpus": a.gpus, "steps": a.steps, "warmup": a.warmup,
@@ -216,10 +305,13 @@ def one_process_main(a, cfg, W, H, SPP):
         "splat_ms_per_step": round(st.splat_ms / a.steps, 3),
         "latin_ms_per_step": round(st.latin_ms / a.steps, 3),
         "schedule": st.schedule_names(),
-        "image_finite": bool(torch.isfinite(image).all().item()),
     }
+    if a.full:
+        out["image_finite"] = bool(torch.isfinite(image).all().item())
     if a.dump_image:
         np.save(a.dump_image, image.cpu().numpy())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, image.cpu().numpy())
     print(json.dumps(out), flush=True)
 
 
@@ -229,7 +321,12 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: counter passes and roofline, "
+                         "cpu_baseline and parity (N=1), image_finite")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and parity")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's framebuffer to DIR/image.npy (float32)")
     # smaller frames of the same scene (multi-rank rehearsals and tests; not a bench line)
     ap.add_argument("--size", default=None, help="WxHxSPP override, e.g. 320x180x8")
     ap.add_argument("--dump-image", default=None, help="rank 0 saves the combined float32 image (.npy)")
@@ -238,6 +335,8 @@ def main():
                          "(nart_hip_create_multi: per-device threads, RCCL ncclSend/ncclRecv gather to device 0, "
                          "INTEGRATION.md 3a) instead of one rank per GPU")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[a.config]
     W, H, SPP = cfg["w"], cfg["h"], cfg["spp"]
     if a.size:
@@ -316,7 +415,7 @@ def main():
             import torch.distributed as td
             td.barrier()
 
-    # counter passes (not timed): algorithmic bytes per sample.  The figure priced in the roofline
+    # counter passes (--full, not timed): algorithmic bytes per sample.  The figure priced in the roofline
     # comes from the timed configuration itself (full spp) on the cpu_baseline bucket sample of this
     # rank's share; a 16-spp pass over the whole share is reported beside it as a cross-check.
     def counter_pass(ids, spp):
@@ -331,12 +430,13 @@ def main():
         del ctiles
         return cst.as_dict()
 
-    sample_ids, sample_stride = cpu_sample_ids(p, cfg["stride"])
-    mine_sample = np.intersect1d(mine, sample_ids).astype(np.uint32)
-    if len(mine_sample) == 0:
-        mine_sample = mine[:1]
-    counters = counter_pass(mine_sample, SPP)
-    counters16 = counter_pass(mine, min(16, SPP))
+    if a.full:
+        sample_ids, sample_stride = cpu_sample_ids(p, cfg["stride"])
+        mine_sample = np.intersect1d(mine, sample_ids).astype(np.uint32)
+        if len(mine_sample) == 0:
+            mine_sample = mine[:1]
+        counters = counter_pass(mine_sample, SPP)
+        counters16 = counter_pass(mine, min(16, SPP))
 
     for _ in range(a.warmup):
         step(nart_amd.RenderStats())
@@ -364,65 +464,9 @@ def main():
 
     samples_total = W * H * SPP * a.steps
     value = samples_total / dt / 1e6
-    kernel_avg_ms = st.kernel_ms / max(1, st.kernel_launches)  # k_primary + k_render_rq per launch
-    primary_avg_ms = st.primary_ms / max(1, st.kernel_launches)
-    bps = bytes_per_sample(counters)
-    bps16 = bytes_per_sample(counters16)
-    per_launch_samples = st.traced_samples / max(1, st.kernel_launches)
-    achieved = bps * per_launch_samples / (kernel_avg_ms * 1e-3) / 1e9
-    prof, prof_src = load_profile("%dx%dx%d" % (W, H, SPP))
-    traffic = prof.get("hbm_bytes_per_launch") if prof else None
-    # The path kernels are latency/issue-bound, not HBM-bound: achieved/frac price the contract's
-    # ALGORITHMIC bytes (BVH nodes, triangles, rays, path state per sample) against
-    # the HBM ceiling, but those bytes are served from LDS/L1/L2 (a ~0.5 MB scene).  What HBM really
-    # moves is `traffic` (rocprofv3 2 x FETCH_SIZE + WRITE_SIZE per launch) -> measured_frac, and
-    # what limits the kernel shows in lane_utilization (SQ_THREAD_CYCLES_VALU / 64
-    # SQ_ACTIVE_INST_VALU: divergent lanes) and valu_busy.
-    # `bound` is the contract's ceiling class (no MFMA on this path, so "hbm"); `frac` is the
-    # contract's algorithmic fraction and is restated as `algorithmic_frac`, beside the measured
-    # `measured_frac`, so neither reads as the other.
-    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                "frac_kind": "algorithmic: contract bytes (SURVEY.md 8(d)) / kernel time / HBM peak; most of those "
-                             "bytes are served by LDS/L1/L2, so this is NOT measured HBM utilisation "
-                             "(that is measured_frac)",
-                "algorithmic_frac": round(achieved / HBM_PEAK_GBPS, 4),
-                "achieved_kind": "algorithmic bytes per launch (SURVEY.md 8(d) per-sample model x traced samples)",
-                "limiter_class": "latency",
-                "limiter": "latency/issue: dependent LDS/L2 loads in BVH traversal and divergent lanes "
-                           "(DESIGN.md section 4), not HBM bandwidth",
-                "measured_frac": (round(traffic / (kernel_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-                                  if traffic else None),
-                "lane_utilization": prof.get("lane_utilization") if prof else None,
-                "valu_busy": prof.get("valu_busy") if prof else None,
-                # issue-rate ceiling of the path kernel: issue_frac =
-                # (SQ_ACTIVE_INST_VALU + SQ_INSTS_SALU) / SQ_WAVE_CYCLES, the fraction of a wave's
-                # issue slots (one per quad-cycle) it used; simd_valu_frac = the SIMD's VALU pipe
-                # (two wave64 instructions per quad-cycle) over its resident waves
-                "issue_frac": prof.get("issue_frac") if prof else None,
-                "simd_valu_frac": prof.get("simd_valu_frac") if prof else None,
-                "waves_per_simd": prof.get("waves_per_simd") if prof else None,
-                "traffic_source": prof_src,
-                "kernel": "k_render_volume_sm" if p.integrator == 1 else "k_primary + k_render_rq",
-                "kernel_avg_ms": round(kernel_avg_ms, 3), "bytes_per_sample": round(bps, 1),
-                "bytes_per_sample_source": {
-                    "spp": SPP, "sample": "counter pass at the timed spp over %d buckets of this rank's share (the "
-                                          "cpu_baseline sample: every %dth bucket)" % (len(mine_sample), sample_stride),
-                    "cross_check_16spp_whole_share": round(bps16, 1),
-                    "ratio_16spp_over_timed": round(bps16 / bps, 4)},
-                "rays_per_s": round((counters["rays_extend"] + counters["rays_shadow"]) /
-                                    max(1, counters["traced_samples"]) * per_launch_samples /
-                                    (kernel_avg_ms * 1e-3), 1)}
-    ratios = kernel_ratios(prof, per_launch_samples, nb * tpx * 20.0)
-    if ratios:
-        roofline["other_kernels"] = ratios
-    if p.integrator != 1:
-        # the path tracing is two launches (camera rays, then the path kernel); the counters and
-        # the time above cover both, the rocprofv3 summary lists them separately
-        roofline["kernel_split_ms"] = {"k_primary": round(primary_avg_ms, 3),
-                                       "k_render_rq": round(kernel_avg_ms - primary_avg_ms, 3)}
+    roofline = roofline_figures(p, st, counters, counters16, len(mine_sample), sample_stride, nb * tpx * 20.0,
+                                "%dx%dx%d" % (W, H, SPP)) if a.full else None
     if rank == 0:
-        img_ok = bool(torch.isfinite(image).all().item()) and bool(torch.equal(image.cpu(), image_host))
         out = {
             "metric": "Msamples/s at %dx%dx%dspp (%s)" % (W, H, SPP, os.path.basename(path)),
             "value": round(value, 3),
@@ -443,7 +487,6 @@ def main():
                        "torch.distributed gather of the ranks' device tiles to rank 0 over %s, one process per GPU "
                        "(nart_amd/dist.py BucketShard); the C ABI's multi-device context gathers with its own "
                        "ncclSend/ncclRecv group instead (bench.py --one-process)" % {"nccl": "RCCL"}.get(backend, backend)),
-            "roofline": roofline,
             "kernel_ms_per_step": round(st.kernel_ms / a.steps, 3),
             "splat_ms_per_step": round(st.splat_ms / a.steps, 3),
             "latin_ms_per_step": round(st.latin_ms / a.steps, 3),
@@ -451,15 +494,18 @@ def main():
             "timing_boundary": "framebuffer on the host: each timed step ends with rank 0's combined float32 image "
                                "(%d x %d Pixels) copied to pinned host memory (host_copy_ms), as Render() returns "
                                "std::vector<Pixel> (render.cpp:114-206)" % (g.total_width, g.total_height),
-            "image_finite": img_ok,
             "per_rank_ms": [{"rank": r, "step_wall_ms": round(float(v[0]) / a.steps * 1e3, 3),
                              "render_ms": round(float(v[1]), 3), "gather_ms": round(float(v[2]), 3)}
                             for r, v in enumerate(t.cpu() for t in per_rank)],
-            "counters_per_sample": {k: round(counters[k] / max(1, counters["traced_samples"]), 3)
-                                    for k in ("rays_extend", "rays_shadow", "node_visits", "tri_tests",
-                                              "bounces", "octree_checks", "octree_replays")},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full:
+            out["roofline"] = roofline
+            out["image_finite"] = (bool(torch.isfinite(image).all().item())
+                                   and bool(torch.equal(image.cpu(), image_host)))
+            out["counters_per_sample"] = {k: round(counters[k] / max(1, counters["traced_samples"]), 3)
+                                          for k in ("rays_extend", "rays_shadow", "node_visits", "tri_tests",
+                                                    "bounces", "octree_checks", "octree_replays")}
+        if a.full and world == 1 and not a.no_cpu_baseline:
             ids, stride = cpu_sample_ids(p, cfg["stride"])
             out["cpu_baseline"], ref_tiles = cpu_baseline(scene, p, ids, stride)
             out["vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
@@ -470,6 +516,8 @@ def main():
                              "max_abs_diff": float(diff.max()), "rmse": float(np.sqrt((diff ** 2).mean()))}
         if a.dump_image:
             np.save(a.dump_image, image.cpu().numpy())
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, image_host.numpy())  # what the last timed step left on the host
         print(json.dumps(out), flush=True)
     if dist:
         import torch.distributed as td

@@ -81,7 +81,7 @@ def test_bench_spawned_ranks_on_one_gpu(gpu, glass_scene, tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--size", "200x120x8",
-                        "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--dump-image", out],
+                        "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--dump-image", out],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -112,7 +112,7 @@ def test_bench_one_process_multi_device(gpu, glass_scene, tmp_path, n):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--one-process", "--gpus", str(n),
-                        "--size", "200x120x8", "--steps", "2", "--warmup", "1", "--dump-image", out],
+                        "--size", "200x120x8", "--steps", "2", "--warmup", "1", "--full", "--dump-image", out],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -172,41 +172,42 @@ def test_materials_scene_ingests(built, tmp_path):
     assert c["materials"] == 7 and c["lights"] == 2 and c["textures"] >= 3
 
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "input", "scenes")), reason="reference checkout not present")
 @pytest.mark.parametrize("name", ["glassSphere", "ring", "veach"])
 def test_packed_reference_scene_equals_original(built, tmp_path, name):
     """assets/<name>.npz materialises to a scene that renders bit-identically (oracle, every
-    session) to the reference's own input/scenes/<name>.json loaded from its checkout."""
+    session) to the reference's own input/scenes/<name>.json loaded from its checkout: the
+    original's counts, sessions and framebuffers are recorded in
+    tests/golden/reference_scene_<name>.npz (tools/make_golden_reference_inputs.py)."""
     import numpy as np
     import nart_amd
     import oracle
     from nart_amd import scenes
-    packed = nart_amd.Scene(scenes.reference_scene(name, str(tmp_path)))
-    cwd = os.getcwd()
-    os.chdir(REF)  # the reference's paths are relative to its root ("input//meshes//...")
-    try:
-        orig = nart_amd.Scene(os.path.join("input", "scenes", name + ".json"))
-        sessions = nart_amd.load_sessions(os.path.join("input", "scenes", name + ".json"))
-    finally:
-        os.chdir(cwd)
-    assert packed.counts() == orig.counts()
-    for p in sessions:
+    orig = np.load(os.path.join(GOLDEN, "reference_scene_%s.npz" % name), allow_pickle=False)
+    path = scenes.reference_scene(name, str(tmp_path))
+    packed = nart_amd.Scene(path)
+    sessions = nart_amd.load_sessions(path)
+    c = packed.counts()
+    assert [c[k] for k in sorted(c)] == orig["counts"].tolist()
+    assert len(sessions) == len(orig["sessions"])
+    for k, p in enumerate(sessions):
+        assert bytes(p) == orig["sessions"][k].tobytes()
         p.image_width, p.image_height, p.spp = 40, 24, 2
         a = oracle.Oracle(packed).render(p)
-        b = oracle.Oracle(orig).render(p)
-        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+        b = orig["image_%d" % k]
+        assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "input", "textures")), reason="reference checkout not present")
 @pytest.mark.parametrize("rel,shape", [("glassIceWater/iceCube_normal.exr", (512, 512)),
                                        ("glassIceWater/iceCube_roughness.exr", (512, 512)),
-                                       ("glassIceWater/glass_roughness.exr", (4096, 4096)),
-                                       ("cameraLens/lens_roughness.exr", (4096, 4096))])
+                                       ("glassIceWater/glass_roughness.exr", (1024, 4096)),
+                                       ("cameraLens/lens_roughness.exr", (1024, 4096))])
 def test_piz_textures_decode(built, rel, shape):
-    """PIZ (wavelet + Huffman) textures the reference ships (HALF BGR, HALF Y, FLOAT Y): every
+    """PIZ (wavelet + Huffman) textures the reference ships (HALF BGR, HALF Y, FLOAT Y; kept in
+    tests/golden/piz/, the 4096^2 ones cut to their first 1,024 scanlines, chunks byte for byte:
+    tools/make_golden_reference_inputs.py): every
     chunk's Huffman stream must decode to exactly the chunk's sample count (the decoder rejects
     anything else), values are finite, in the texture's [0, 1] range and spatially smooth (a
     wrong wavelet or LUT step yields noise).  No PIZ encoder or OpenEXR is available here; the texel
@@ -214,7 +215,7 @@ def test_piz_textures_decode(built, rel, shape):
     tests/test_ingestion_independent.py::test_piz_textures_independently."""
     import numpy as np
     import nart_amd
-    a = nart_amd.read_exr(os.path.join(REF, "input", "textures", rel))
+    a = nart_amd.read_exr(os.path.join(GOLDEN, "piz", os.path.basename(rel)))
     assert a.shape == shape + (4,)
     rgb = a[..., :3]
     assert np.isfinite(rgb).all() and rgb.min() >= 0.0 and rgb.max() <= 1.0

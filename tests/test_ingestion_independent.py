@@ -134,10 +134,9 @@ def test_writer_output_decodes_independently(built, tmp_path, compression):
     assert np.array_equal(halves, want)
 
 
-REF_TEX = "/root/reference/input/textures"
+REF_TEX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "piz")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_TEX), reason="reference checkout not present")
 @pytest.mark.parametrize("rel,rows", [("glassIceWater/iceCube_normal.exr", 512),
                                       ("glassIceWater/iceCube_roughness.exr", 512),
                                       ("glassIceWater/glass_roughness.exr", 64),
@@ -147,9 +146,10 @@ def test_piz_textures_independently(built, rel, rows):
     BGR, HALF Y, FLOAT Y -> halves) decoded by the product's reader (host/exr_piz.cpp) and by the
     test-side PIZ restatement (tests/exr_piz_py.py: canonical Huffman by code length, numpy
     wavelet levels, reverse LUT) must agree half for half -- the whole 512^2 textures, the first
-    PIZ chunks of the 4096^2 ones (pure Python is slow)."""
+    PIZ chunks of the 4096^2 ones (pure Python is slow).  The files are kept in tests/golden/piz/
+    (tools/make_golden_reference_inputs.py)."""
     import nart_amd
-    path = os.path.join(REF_TEX, rel)
+    path = os.path.join(REF_TEX, os.path.basename(rel))
     mine, hdr = exr_py.read_rgba_halves(path, max_rows=rows)
     assert hdr["compression"] == exr_py.PIZ
     prod = nart_amd.read_exr(path).astype(np.float16).view(np.uint16)

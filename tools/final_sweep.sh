@@ -18,7 +18,7 @@ done
 mkdir -p gpurun_out/${TAG}_profiles && cp profiles/${TAG}_* profiles/pmc_latest*.json gpurun_out/${TAG}_profiles/
 for c in $CONFIGS; do
     name=${c%%:*}
-    if [ $name = c4 ]; then step bench_c4 400 python -u bench.py --config c4 --steps 2
-    else step bench_$name 300 python -u bench.py --config $name; fi
+    if [ $name = c4 ]; then step bench_c4 400 python -u bench.py --full --config c4 --steps 2
+    else step bench_$name 300 python -u bench.py --full --config $name; fi
 done
 echo "${TAG} sweep done"

@@ -11,10 +11,10 @@ if [ "$PART" = part1 ]; then
     [ -f tests/golden/frame_c4.npz ] || DESEL="--deselect tests/test_gpu_frames.py::test_whole_frame_matches_oracle_digests[c4]"
     step pytest 700 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread $DESEL
     step smoke 120 python -u -c "import __graft_entry__ as g; g.smoke()"
-    step bench 300 python -u bench.py
-    step bench_c2 300 python -u bench.py --config c2
-    step bench_c5 300 python -u bench.py --config c5
-    step bench_c4 400 python -u bench.py --config c4 --steps 2
+    step bench 300 python -u bench.py --full
+    step bench_c2 300 python -u bench.py --full --config c2
+    step bench_c5 300 python -u bench.py --full --config c5
+    step bench_c4 400 python -u bench.py --full --config c4 --steps 2
 elif [ "$PART" = part2 ]; then
     step shard_c3 300 python -u tools/shard_perf.py --config c3 --ns 1 2 4 8 --reps 2
     step shard_c5 300 python -u tools/shard_perf.py --config c5 --ns 1 2 4 8 --reps 2
