@@ -114,6 +114,43 @@ int nart_hip_render_device(nart_ctx* ctx, const nart_render_params* p, const nar
 int nart_hip_render(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image,
                     nart_render_stats* stats);
 
+/* First-hit AOVs (no reference counterpart): denoiser guide images of the first surface each
+   camera sample sees.  The first hit is the triangle Scene::Intersect returns at bounce 0 -- the
+   reference octree's answer, bounded by the nearest analytic light in front of it
+   (pathintegrator.cpp:167-184); a sample whose camera ray meets a light first, or nothing, is a
+   miss, and nested-dielectric validity (IsectIsValid) is not applied.  Per sample
+       albedo record {albedo.rgb, hit}:   the hit material's colour pattern at the hit's st (rho_d for
+                                          Lambert and plastic, rho_s for specular and glossy, tau for
+                                          glass: the texel the BSDF reads); hit = 1
+       normal record {normal.xyz, depth}: the normalised shading normal of the BSDF frame (world
+                                          space, normal map applied, not flipped towards the camera)
+                                          and the hit's t as Triangle::Intersect computes it (the
+                                          distance from the camera: the ray direction is unit length)
+   and all zeros for a miss.  Each record stream is splatted and combined exactly as Li_alpha is
+   (AddSample, render.cpp:23-70; tile combine :183-203) into a nart_pixel image of totalW*totalH:
+   contribution / filter_weight_sum is the filtered AOV.  The normal image is therefore a filtered
+   average of unit normals and is NOT renormalised.
+
+   nart_hip_render_aovs: aovs = NART_AOV_* bits, each needing its host buffer (totalW*totalH
+   nart_pixel); image = the beauty, bit-identical to nart_hip_render's, or null for an AOV-only
+   render (LatinSquare, camera rays and the AOV passes: no path kernel).  aov_ms, if non-null,
+   receives the device time of the AOV record and AOV splat kernels.  A render without AOV bits
+   launches exactly what nart_hip_render launches.  NART_E_INVALID: null ctx or p, a bit without its
+   buffer, an unknown bit, or nothing requested; NART_E_UNSUPPORTED: the volume integrator (no
+   surfaces).  Multi-device contexts gather the AOV tiles with the beauty's gather. */
+#define NART_AOV_ALBEDO 0x1u   /* contribution = {albedo.rgb, hit}    */
+#define NART_AOV_NORMAL 0x2u   /* contribution = {normal.xyz, depth}  */
+int nart_hip_render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_pixel* image,
+                         nart_pixel* albedo, nart_pixel* normal, nart_render_stats* stats, double* aov_ms);
+
+/* Debug / parity, as nart_hip_render_samples: the per-sample AOV records of pixels [x0,x0+w) x
+   [y0,y0+h) in total-image coordinates (extra rows included) into host
+   out8[((y-y0)*w + (x-x0))*spp + s][8] = albedo record then normal record; tri (optional) receives
+   the first-hit triangle index or 0xFFFFFFFF.  Runs LatinSquare, the camera rays and the record
+   kernel only. */
+int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w,
+                                uint32_t h, float* out8, uint32_t* tri);
+
 /* Multi-GPU building block: render the listed buckets (bucket id = by*nBucketsX + bx) into
    device-resident tiles d_tiles[i] (tile_size^2 nart_pixel each, same order as the list) on
    `stream` (a hipStream_t, may be 0).  bucket_ids is a host array.  Asynchronous w.r.t. the

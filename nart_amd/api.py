@@ -94,6 +94,23 @@ class _Texture(ctypes.Structure):
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("rgba", _P)]
 
 
+class Pattern(ctypes.Structure):
+    """nart_pattern (include/nart_scene.h)."""
+    _fields_ = [("type", ctypes.c_int32), ("value", ctypes.c_float * 3), ("texture", ctypes.c_int32),
+                ("is_roughness", ctypes.c_int32)]
+
+
+class Material(ctypes.Structure):
+    """nart_material (include/nart_scene.h)."""
+    _fields_ = [("type", ctypes.c_int32), ("has_normal", ctypes.c_int32), ("rho_d", Pattern), ("rho_s", Pattern),
+                ("tau", Pattern), ("eta", Pattern), ("alpha", Pattern), ("normal", Pattern)]
+
+
+MAT_LAMBERT, MAT_SPECULAR, MAT_GLASS, MAT_GLOSSY, MAT_PLASTIC = range(5)  # NART_MAT_*
+PTN_CONSTANT, PTN_TEXTURE = 0, 1  # NART_PTN_*
+AOV_ALBEDO, AOV_NORMAL = 0x1, 0x2  # NART_AOV_* (include/nart_hip.h)
+
+
 class _BlobHead(ctypes.Structure):
     """Leading fields of nart_scene_blob (include/nart_scene.h)."""
     _fields_ = [("num_triangles", ctypes.c_uint32), ("num_meshes", ctypes.c_uint32),
@@ -127,6 +144,10 @@ _HIP_SIGS = {
     "nart_hip_destroy": (None, [_P]),
     "nart_hip_last_error": (ctypes.c_char_p, [_P]),
     "nart_hip_render": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), _P, ctypes.POINTER(RenderStats)]),
+    "nart_hip_render_aovs": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, _P, _P, _P,
+                                            ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_aov_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, ctypes.c_uint32,
+                                                   ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "nart_hip_render_device": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(_P),
                                               ctypes.POINTER(RenderStats)]),
     "nart_hip_render_buckets_async": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(ctypes.c_uint32),
@@ -316,6 +337,26 @@ class Scene:
         h = self._view()
         return float(h.cam_fov), np.array(list(h.cam_m), np.float32)
 
+    def materials(self):
+        """Copies of the blob's nart_material records (Material: type, has_normal and the Pattern
+        fields rho_d, rho_s, tau, eta, alpha, normal), in scene order."""
+        h = self._view()
+        src = ctypes.cast(h.materials, ctypes.POINTER(Material))
+        out = []
+        for i in range(h.num_materials):
+            m = Material()
+            ctypes.pointer(m)[0] = src[i]
+            out.append(m)
+        return out
+
+    def meshes(self):
+        """(n, 4) uint32 copy of the blob's nart_mesh records: first_tri, num_tris, material, priority."""
+        h = self._view()
+        if not h.num_meshes:
+            return np.zeros((0, 4), np.uint32)
+        return np.ctypeslib.as_array(ctypes.cast(h.meshes, ctypes.POINTER(ctypes.c_uint32)),
+                                     shape=(h.num_meshes * 4,)).copy().reshape(-1, 4)
+
     def textures(self):
         """Loaded textures as (H, W, 4) uint16 half bit patterns (top row first), in load order."""
         h = self._view()
@@ -447,6 +488,37 @@ class HipRenderer:
         st = stats if stats is not None else RenderStats()
         self._check(self._lib.nart_hip_render(self._ctx, ctypes.byref(p), img.ctypes.data, ctypes.byref(st)))
         return img
+
+    def render_aovs(self, p, albedo=True, normal=True, beauty=True, stats=None):
+        """First-hit AOVs (nart_hip_render_aovs): a dict with (totalH, totalW, 5) float32 images under
+        "albedo" ({albedo.rgb, coverage}), "normal" ({shading normal.xyz, depth}: a filtered average,
+        not renormalised) and "beauty" (bit-identical to render()), each only if requested, plus
+        "aov_ms", the device time of the AOV kernels.  finalize() of an image is the filtered AOV.
+        beauty=False renders the AOVs alone (no path kernel)."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        out = {}
+        for name, want in (("beauty", beauty), ("albedo", albedo), ("normal", normal)):
+            if want:
+                out[name] = np.empty(shape, np.float32)
+        ptr = lambda name: out[name].ctypes.data if name in out else None
+        st = stats if stats is not None else RenderStats()
+        ms = ctypes.c_double()
+        mask = (AOV_ALBEDO if albedo else 0) | (AOV_NORMAL if normal else 0)
+        self._check(self._lib.nart_hip_render_aovs(self._ctx, ctypes.byref(p), mask, ptr("beauty"), ptr("albedo"),
+                                                   ptr("normal"), ctypes.byref(st), ctypes.byref(ms)))
+        out["aov_ms"] = ms.value
+        return out
+
+    def render_aov_samples(self, p, x0, y0, w, h):
+        """Per-sample AOV records of a rect in total-image coordinates (nart_hip_render_aov_samples):
+        (h, w, spp, 8) float32 = {albedo.rgb, hit, normal.xyz, depth} and (h, w, spp) uint32 first-hit
+        triangle indices (0xFFFFFFFF: miss)."""
+        out = np.empty((h, w, p.spp, 8), np.float32)
+        tri = np.empty((h, w, p.spp), np.uint32)
+        self._check(self._lib.nart_hip_render_aov_samples(self._ctx, ctypes.byref(p), x0, y0, w, h, out.ctypes.data,
+                                                          tri.ctypes.data))
+        return out, tri
 
     def render_device(self, p, stats=None):
         """Whole session, image left on the (first) device: returns its device address (totalH x

@@ -973,6 +973,78 @@ __global__ __launch_bounds__(256, NART_PRIMARY_WAVES) void k_primary(DScene S, R
     }
 }
 
+// ---------------------------------------------------------------- first-hit AOVs
+// Denoiser guide records of the first surface each camera ray sees (DESIGN.md "First-hit AOVs"),
+// from k_primary's hit[] (closest triangle or NO_HIT per sample; a ray that meets an analytic light
+// first, or nothing, is a miss).  One float4 per sample, indexed like the samples, so that the
+// splat kernels consume it exactly as they consume Li_alpha:
+//   AOV_ALBEDO  {albedo.rgb, 1}: the material's colour pattern at the hit's st -- rho_d (Lambert,
+//               plastic), rho_s (specular, glossy), tau (glass): the texel create_bsdf reads
+//   AOV_NORMAL  {n.xyz, t}: the normalised shading normal of create_bsdf's frame (world space,
+//               normal map applied, not flipped towards the camera) and Triangle::Intersect's
+//               plane distance t (geometry.cpp:33-40) with the traversal's operation order: n and
+//               dot(v0, n) as the test records hold them (bvh_build.cpp, lbvh.h k_lbvh_tris)
+// A miss is all zeros.  Lane = traced pixel, looping over its samples with k_primary's two
+// access patterns; no traversal, no LDS, no atomics.
+enum { AOV_ALBEDO = 0, AOV_NORMAL = 1 };
+
+template <int REC>
+ND float4 aov_record(const DScene& S, const RenderArgs& A, uint32_t px, uint32_t py, float2 sm, uint32_t g) {
+    if (g == NO_HIT) return make_float4(0.f, 0.f, 0.f, 0.f);
+    const Ray ray = cast_ray(S, F2(sm.x, sm.y), A.W, A.H, px, py);
+    Isect is;
+    fill_isect(S, ray, g, is);
+    if (REC == AOV_ALBEDO) {
+        const DMaterial& m = cst(S.mats)[is.mat];
+        const int32_t t = m.type;
+        const DPattern& p = (t == NART_MAT_SPECULAR || t == NART_MAT_GLOSSY) ? m.rho_s : (t == NART_MAT_GLASS ? m.tau : m.rho_d);
+        const f3 a = ptn_value<FT_ALL>(S, p, is.st);
+        return make_float4(a.x, a.y, a.z, 1.f);
+    }
+    BSDF bs;
+    create_bsdf<FT_ALL>(S, is, 1.f, bs);
+    const f3 n = normalize(bs.n);
+    const nart_triangle& T = S.tris[g];
+    const f3 v0 = load3(T.v0);
+    const f3 pn = cross(sub(load3(T.v1), v0), sub(load3(T.v2), v0));
+    const float t = (dot(v0, pn) - dot(ray.o, pn)) / dot(ray.d, pn);
+    return make_float4(n.x, n.y, n.z, t);
+}
+
+template <int REC>
+__global__ __launch_bounds__(256) void k_aov(DScene S, RenderArgs A, const uint32_t* hit, float4* out) {
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= A.n_slots) return;
+    const uint32_t xy = A.slot_xy[slot];
+    const uint32_t px = xy & 0xFFFFu, py = xy >> 16;
+    const SlotSO so = A.slot_so[slot];
+    if (so.stride == 1u && (A.spp & 7u) == 0u && (so.first & 7u) == 0u) {
+        // pixel-major rows: 8 samples (64 B) and 8 hits (32 B) per read, and the lane's eight
+        // records go to 128 contiguous bytes (k_primary's layout and alignment conditions)
+        const float4* sp = reinterpret_cast<const float4*>(A.samples + so.first);
+        const uint4* hp = reinterpret_cast<const uint4*>(hit + so.first);
+        float4* op = out + so.first;
+        for (uint32_t c = 0; c < A.spp / 8u; ++c) {
+            const float4 q0 = sp[4 * c], q1 = sp[4 * c + 1], q2 = sp[4 * c + 2], q3 = sp[4 * c + 3];
+            const uint4 h0 = hp[2 * c], h1 = hp[2 * c + 1];
+            // one call site for the eight samples (as k_primary): the record code is not duplicated
+#pragma unroll 1
+            for (uint32_t k = 0; k < 8u; ++k) {
+                const float4 q = k < 2u ? q0 : (k < 4u ? q1 : (k < 6u ? q2 : q3));
+                const uint4 h = k < 4u ? h0 : h1;
+                const uint32_t kk = k & 3u;
+                const uint32_t g = kk == 0u ? h.x : (kk == 1u ? h.y : (kk == 2u ? h.z : h.w));
+                op[8u * c + k] = aov_record<REC>(S, A, px, py, (k & 1u) ? make_float2(q.z, q.w) : make_float2(q.x, q.y), g);
+            }
+        }
+    } else {
+        for (uint32_t s = 0; s < A.spp; ++s) {
+            const uint64_t idx = so.first + (uint64_t)s * so.stride;
+            out[idx] = aov_record<REC>(S, A, px, py, A.samples[idx], hit[idx]);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- path tracing with a wave ray queue
 // k_render_rq: the same per-lane path state machine as k_render (one lane per traced pixel,
 // its samples in order on one RNG stream), but the lanes of a wave share their rays.  Shading

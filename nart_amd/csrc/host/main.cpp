@@ -8,11 +8,16 @@
 //                   (nart_hip_create_multi); the image is bit-identical for any N.
 //   --devices a,b   an explicit device list (repeats allowed: a rehearsal on fewer GPUs)
 //   --device d      first (or only) device; NART_DEVICE sets the default, which is 0
+//   --aovs          also write the first-hit AOVs of every session (nart_hip_render_aovs) through the
+//                   same EXR writer: <out>.albedo.exr (RGB albedo, A coverage) and <out>.normal.exr
+//                   (RGB shading normal, filtered and not renormalised; A depth), in half precision;
+//                   <out>_<n>.albedo.exr / <out>_<n>.normal.exr with several sessions
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../../include/nart_hip.h"
@@ -90,11 +95,22 @@ bool take_device_flags(std::vector<char*>& args, std::vector<int>& devices) {
     return true;
 }
 
+// Removes --aovs from argv; true if it was there.
+bool take_aov_flag(std::vector<char*>& args) {
+    std::vector<char*> kept;
+    for (char* a : args)
+        if (std::strcmp(a, "--aovs")) kept.push_back(a);
+    const bool found = kept.size() != args.size();
+    args = kept;
+    return found;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[]) {
     std::vector<char*> args(argv, argv + argc);
     std::vector<int> devices;
+    const bool aovs = take_aov_flag(args);
     if (!take_device_flags(args, devices)) return EXIT_FAILURE;
     if (args.size() < 3) {
         std::fprintf(stderr, "Too few arguments given.\nUsage example: %s <scene file> <output path>\n", argv[0]);
@@ -132,17 +148,38 @@ int main(int argc, char* argv[]) {
         nart_session_geometry g;
         nart_session_geometry_of(&p, &g);
         std::vector<nart_pixel> image((size_t)g.total_width * g.total_height);
-        rc = nart_hip_render(ctx, &p, image.data(), nullptr);
+        std::vector<nart_pixel> albedo, normal;
+        if (aovs) {
+            albedo.resize(image.size());
+            normal.resize(image.size());
+            rc = nart_hip_render_aovs(ctx, &p, NART_AOV_ALBEDO | NART_AOV_NORMAL, image.data(), albedo.data(),
+                                      normal.data(), nullptr, nullptr);
+        } else {
+            rc = nart_hip_render(ctx, &p, image.data(), nullptr);
+        }
         if (rc != NART_OK) {
             std::fprintf(stderr, "Error: render failed (%d): %s\n", rc, nart_hip_last_error(ctx));
             return EXIT_FAILURE;
         }
         // main.cpp:44-49: <out>.exr for one session, <out>_<n>.exr for several
-        std::string path = std::string(args[2]) + (n == 1 ? std::string(".exr") : "_" + std::to_string(k++) + ".exr");
+        const std::string stem = std::string(args[2]) + (n == 1 ? std::string() : "_" + std::to_string(k++));
+        std::string path = stem + ".exr";
         std::printf("Writing to %s...\n", path.c_str());
         if (nart_write_exr(path.c_str(), &p, image.data(), 3) != NART_OK) {
             std::fprintf(stderr, "%s\n", nart_scene_last_error());
             return EXIT_FAILURE;
+        }
+        if (aovs) {
+            const std::pair<const char*, const nart_pixel*> extra[2] = {{".albedo.exr", albedo.data()},
+                                                                        {".normal.exr", normal.data()}};
+            for (const auto& e : extra) {
+                path = stem + e.first;
+                std::printf("Writing to %s...\n", path.c_str());
+                if (nart_write_exr(path.c_str(), &p, e.second, 3) != NART_OK) {
+                    std::fprintf(stderr, "%s\n", nart_scene_last_error());
+                    return EXIT_FAILURE;
+                }
+            }
         }
         std::chrono::duration<float> d = std::chrono::high_resolution_clock::now() - start;
         std::printf("Completed in %gs\n", d.count());

@@ -142,8 +142,30 @@ int ensure_dev(nart_ctx* ctx, int dev, void*& buf, size_t& cap, size_t bytes, co
 
 // Render(), multi-device: shard, render concurrently, gather to device 0, combine, copy out (image
 // null: the combined image stays in ctx->d_image on device 0, nart_hip_render_device).
-int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, nart_render_stats* stats) {
+// The gather runs over a list of tile buffers: the beauty (unless beauty is false: an AOV-only
+// render) and each first-hit AOV requested through aov_images[k] (host images, null: not requested;
+// nart_hip_render_aovs).  Every device keeps its buffers' slabs back to back in sub_tiles[d], all are
+// gathered in the one RCCL group (or by device copies), and each buffer is then permuted and
+// combined on device 0 in turn.  aov_ms: the slowest device's AOV time.
+int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, nart_render_stats* stats,
+                 nart_pixel* const* aov_images = nullptr, bool beauty = true, double* aov_ms = nullptr) {
     const uint32_t n = (uint32_t)ctx->subs.size();
+    // the tile buffers of this render: -1 the beauty, k >= 0 AOV k; host destinations alongside
+    std::vector<int> kinds;
+    std::vector<nart_pixel*> dsts;
+    if (beauty) {
+        kinds.push_back(-1);
+        dsts.push_back(image);
+    }
+    for (int k = 0; aov_images && k < 2; ++k)
+        if (aov_images[k]) {
+            kinds.push_back(k);
+            dsts.push_back(aov_images[k]);
+        }
+    const size_t K = kinds.size();
+    const bool want_aov = K > (beauty ? 1u : 0u);
+    if (want_aov && p && p->integrator == NART_INTEGRATOR_VOLUME)
+        return fail(ctx, NART_E_UNSUPPORTED, "first-hit AOVs need surfaces: the volume integrator has none");
     if (ctx->rccl_broken)
         return fail(ctx, NART_E_RCCL, "an earlier RCCL gather of this context failed; destroy it and create a new one");
     int rc = check_params(ctx->subs[0], p);
@@ -155,13 +177,13 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, 
     std::vector<std::vector<uint32_t>> ids(n);
     for (uint32_t d = 0; d < n; ++d) {
         ids[d] = shard_ids(g.n_buckets_x, nb, n, d);
-        const size_t bytes = std::max<size_t>(1, ids[d].size()) * tile_floats * 4;
+        const size_t bytes = std::max<size_t>(1, ids[d].size()) * tile_floats * 4 * K;
         if ((rc = ensure_dev(ctx, ctx->devs[d], ctx->sub_tiles[d], ctx->sub_cap[d], bytes, "device tiles"))) return rc;
     }
     const int dev0 = ctx->devs[0];
     const size_t all_bytes = (size_t)nb * tile_floats * 4;
     const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
-    if ((rc = ensure_dev(ctx, dev0, ctx->d_gather, ctx->cap_gather, all_bytes, "gathered tiles")) ||
+    if ((rc = ensure_dev(ctx, dev0, ctx->d_gather, ctx->cap_gather, all_bytes * K, "gathered tiles")) ||
         (rc = ensure_dev(ctx, dev0, ctx->d_byid, ctx->cap_byid, all_bytes, "tiles by bucket id")) ||
         (rc = ensure_dev(ctx, dev0, ctx->d_image, ctx->cap_image, img_bytes, "image")))
         return rc;
@@ -169,6 +191,7 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, 
     // 1. every device renders its buckets (one host thread each, like the TBB task group)
     std::vector<int> rcs(n, NART_OK);
     std::vector<nart_render_stats> st(n);
+    std::vector<AovRequest> areq(n);
     std::vector<std::thread> th;
     auto work = [&](uint32_t d) {
         if (ids[d].empty()) return;
@@ -176,8 +199,14 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, 
             rcs[d] = NART_E_HIP;
             return;
         }
+        // buffer i of the list: slab i of sub_tiles[d]
+        const size_t slab = ids[d].size() * tile_floats;
+        areq[d].beauty = beauty;
+        for (size_t i = 0; i < K; ++i)
+            if (kinds[i] >= 0) areq[d].tiles[kinds[i]] = static_cast<float*>(ctx->sub_tiles[d]) + i * slab;
         rcs[d] = render_buckets(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(),
-                                static_cast<float*>(ctx->sub_tiles[d]), ctx->streams[d], &st[d]);
+                                static_cast<float*>(ctx->sub_tiles[d]), ctx->streams[d], &st[d],
+                                want_aov ? &areq[d] : nullptr);
         if (rcs[d] == NART_OK && hipStreamSynchronize(ctx->streams[d]) != hipSuccess) rcs[d] = NART_E_HIP;
     };
     for (uint32_t d = 0; d < n; ++d) std::memset(&st[d], 0, sizeof(st[d]));
@@ -220,13 +249,16 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, 
             for (uint32_t d = 0; d < n; ++d)
                 if (!ids[d].empty()) last = d;
             const int bad_peer = ctx->debug_fault == 1 ? (int)n : 0;
-            for (uint32_t d = 0; d < n; ++d) {
-                if (ids[d].empty()) continue;
-                const size_t cnt = ids[d].size() * tile_floats;
-                note(R.Send(ctx->sub_tiles[d], cnt, ncclFloat32, d == last ? bad_peer : 0, ctx->comms[d], ctx->streams[d]),
-                     "ncclSend");
-                note(R.Recv(slabs + first_b[d] * tile_floats, cnt, ncclFloat32, (int)d, ctx->comms[0], s0), "ncclRecv");
-            }
+            for (size_t i = 0; i < K; ++i)
+                for (uint32_t d = 0; d < n; ++d) {
+                    if (ids[d].empty()) continue;
+                    const size_t cnt = ids[d].size() * tile_floats;
+                    note(R.Send(static_cast<const float*>(ctx->sub_tiles[d]) + i * cnt, cnt, ncclFloat32,
+                                d == last ? bad_peer : 0, ctx->comms[d], ctx->streams[d]),
+                         "ncclSend");
+                    note(R.Recv(slabs + (i * nb + first_b[d]) * tile_floats, cnt, ncclFloat32, (int)d, ctx->comms[0], s0),
+                         "ncclRecv");
+                }
             note(R.GroupEnd(), "ncclGroupEnd");
         }
         ctx->debug_fault = 0;
@@ -247,10 +279,12 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, 
         HIPCHK(hipSetDevice(dev0));
     } else {
         HIPCHK(hipSetDevice(dev0));
-        for (uint32_t d = 0; d < n; ++d)
-            if (!ids[d].empty())
-                HIPCHK(hipMemcpyPeerAsync(slabs + first_b[d] * tile_floats, dev0, ctx->sub_tiles[d], ctx->devs[d],
-                                          ids[d].size() * tile_floats * 4, s0));
+        for (size_t i = 0; i < K; ++i)
+            for (uint32_t d = 0; d < n; ++d)
+                if (!ids[d].empty())
+                    HIPCHK(hipMemcpyPeerAsync(slabs + (i * nb + first_b[d]) * tile_floats, dev0,
+                                              static_cast<const float*>(ctx->sub_tiles[d]) + i * ids[d].size() * tile_floats,
+                                              ctx->devs[d], ids[d].size() * tile_floats * 4, s0));
     }
 
     // 3. bucket-id order, raster-order combine on device 0, image to the host
@@ -259,14 +293,20 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, 
     for (uint32_t d = 0; d < n; ++d) map.insert(map.end(), ids[d].begin(), ids[d].end());
     if ((rc = ensure_dev(ctx, dev0, ctx->d_slab_map, ctx->cap_slab_map, (size_t)nb * 4, "slab map"))) return rc;
     HIPCHK(hipMemcpyAsync(ctx->d_slab_map, map.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s0));
-    hipLaunchKernelGGL(k_unshard, dim3(nb), dim3(256), 0, s0, slabs, static_cast<float*>(ctx->d_byid),
-                       static_cast<const uint32_t*>(ctx->d_slab_map), nb, (uint32_t)tile_floats);
-    HIPCHK(hipGetLastError());
-    if ((rc = nart_hip_combine_async(ctx->subs[0], p, static_cast<const nart_pixel*>(ctx->d_byid),
-                                     static_cast<nart_pixel*>(ctx->d_image), s0)))
-        return fail(ctx, rc, ctx->subs[0]->err);
-    if (image) HIPCHK(hipMemcpyAsync(image, ctx->d_image, img_bytes, hipMemcpyDeviceToHost, s0));
+    // (stream order lets the buffers share d_byid and d_image)
+    for (size_t i = 0; i < K; ++i) {
+        hipLaunchKernelGGL(k_unshard, dim3(nb), dim3(256), 0, s0, slabs + i * nb * tile_floats,
+                           static_cast<float*>(ctx->d_byid), static_cast<const uint32_t*>(ctx->d_slab_map), nb,
+                           (uint32_t)tile_floats);
+        HIPCHK(hipGetLastError());
+        if ((rc = nart_hip_combine_async(ctx->subs[0], p, static_cast<const nart_pixel*>(ctx->d_byid),
+                                         static_cast<nart_pixel*>(ctx->d_image), s0)))
+            return fail(ctx, rc, ctx->subs[0]->err);
+        if (dsts[i]) HIPCHK(hipMemcpyAsync(dsts[i], ctx->d_image, img_bytes, hipMemcpyDeviceToHost, s0));
+    }
     HIPCHK(hipStreamSynchronize(s0));
+    if (aov_ms)
+        for (uint32_t d = 0; d < n; ++d) *aov_ms = std::max(*aov_ms, areq[d].ms);
     if (stats) {
         nart_render_stats m;
         std::memset(&m, 0, sizeof(m));

@@ -74,6 +74,8 @@ struct nart_ctx {
     size_t cap_slots = 0, cap_samples = 0, cap_buckets = 0;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ev[4]: after k_primary
     bool primary_ran = false;  // the last dispatch launched k_primary (ev[4] recorded)
+    bool prim_valid = false;   // d_prim holds the current batch's camera-ray hits (first-hit AOVs)
+    hipEvent_t ev_aov[2] = {nullptr, nullptr};  // around the AOV passes of a batch (render_buckets)
     uint32_t sched = 0;        // NART_SCHED_* bits of the current render (nart_render_stats::schedule)
     bool events = false;
     // megakernel work queue (launch_render)
@@ -752,6 +754,7 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, hipStream_t st) {
             ctx->primary_ran = true;
         }
         ctx->sched |= NART_SCHED_PRIMARY;
+        ctx->prim_valid = true;
         brq.prim = ctx->d_prim;
     }
     // one ray-queue block per CU (2 or 3 waves per SIMD); the lean build keeps lean_stack(ctx)
@@ -1282,11 +1285,52 @@ int launch_latin(nart_ctx* ctx, const RenderArgs& ra, hipStream_t st) {
 }
 
 
-// Render a bucket list into device tiles (list order).  Shared by all entry points.
+// ---------------------------------------------------------------- first-hit AOVs
+// A render's AOV request (nart_hip_render_aovs): tiles[k] receives the splatted records of AOV k
+// (AOV_ALBEDO, AOV_NORMAL; null: not requested), laid out like the beauty tiles.  beauty false: an
+// AOV-only render, which launches no path kernel.  ms: device time of the k_aov + AOV splat launches.
+struct AovRequest {
+    float* tiles[2] = {nullptr, nullptr};
+    bool beauty = true;
+    double ms = 0.0;
+};
+
+// Camera-ray hits of the batch in `a` into ctx->d_prim, for AOVs of a dispatch that did not run
+// k_primary itself (variant 3, the LDS fallback, an AOV-only render): the generic build, launched
+// as launch_render launches it.
+int launch_aov_primary(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
+    RenderArgs pa = a;
+    pa.packet = env_num("NART_PRIMARY_PACKET", 1.0) != 0.0 ? 1u : 0u;
+    const size_t lds = (size_t)ctx->stack_depth * 256 * 8;
+    const void* f = ctx->has_env ? (const void*)k_primary<false, true, FT_ALL> : (const void*)k_primary<false, false, FT_ALL>;
+    HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    const dim3 grid((a.n_slots + 255) / 256), block(256);
+    if (ctx->has_env) hipLaunchKernelGGL((k_primary<false, true, FT_ALL>), grid, block, lds, st, ctx->scene, pa, ctx->d_prim);
+    else hipLaunchKernelGGL((k_primary<false, false, FT_ALL>), grid, block, lds, st, ctx->scene, pa, ctx->d_prim);
+    HIPCHK(hipGetLastError());
+    ctx->prim_valid = true;
+    return NART_OK;
+}
+
+// Per-sample records of AOV `rec` of the batch in `a` (ctx->d_prim valid) into `out`.
+int launch_aov(nart_ctx* ctx, const RenderArgs& a, int rec, float4* out, hipStream_t st) {
+    const dim3 grid((a.n_slots + 255) / 256), block(256);
+    if (rec == AOV_ALBEDO) hipLaunchKernelGGL((k_aov<AOV_ALBEDO>), grid, block, 0, st, ctx->scene, a, ctx->d_prim, out);
+    else hipLaunchKernelGGL((k_aov<AOV_NORMAL>), grid, block, 0, st, ctx->scene, a, ctx->d_prim, out);
+    HIPCHK(hipGetLastError());
+    return NART_OK;
+}
+
+// Render a bucket list into device tiles (list order).  Shared by all entry points.  With `aov`
+// each batch also splats the requested first-hit AOV records (k_aov into ctx->d_L, which the beauty
+// splat has consumed by then: no extra per-sample memory) into the request's tiles.
 int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n, float* d_tiles,
-                   hipStream_t st, nart_render_stats* stats) {
+                   hipStream_t st, nart_render_stats* stats, AovRequest* aov = nullptr) {
     int rc = check_params(ctx, p);
     if (rc) return rc;
+    const bool beauty = !aov || aov->beauty;
+    if (aov && p->integrator == NART_INTEGRATOR_VOLUME)
+        return fail(ctx, NART_E_UNSUPPORTED, "first-hit AOVs need surfaces: the volume integrator has none");
     HIPCHK(hipSetDevice(ctx->device));
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
@@ -1346,6 +1390,9 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         for (auto& e : ctx->ev) HIPCHK(hipEventCreate(&e));
         ctx->events = true;
     }
+    if (aov)
+        for (auto& e : ctx->ev_aov)
+            if (!e) HIPCHK(hipEventCreate(&e));
     const size_t limit = batch_slot_limit(ctx, p->spp);
     const uint32_t tpx = g.tile_size * g.tile_size;
     double kernel_ms = 0.0, splat_ms = 0.0, latin_ms = 0.0, primary_ms = 0.0;
@@ -1405,15 +1452,18 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         if (rc) return rc;
         HIPCHK(hipEventRecord(ctx->ev[0], st));
         ctx->primary_ran = false;
-        rc = dispatch_render(ctx, ra, p->integrator, st);
-        if (rc) return rc;
+        ctx->prim_valid = false;
+        if (beauty) {
+            rc = dispatch_render(ctx, ra, p->integrator, st);
+            if (rc) return rc;
+        }
         HIPCHK(hipEventRecord(ctx->ev[1], st));
         SplatArgs sa;
         sa.bucket_ids = ctx->d_bucket_ids;
         sa.bucket_base = ctx->d_bucket_base;
         sa.samples = ctx->d_samples;
         sa.Lout = ctx->d_L;
-        sa.tiles = d_tiles + (size_t)b0 * tpx * 5;
+        sa.tiles = beauty ? d_tiles + (size_t)b0 * tpx * 5 : nullptr;
         sa.table = ctx->d_table;
         sa.thr = thr_ok ? ctx->d_table + 64 : nullptr;
         sa.idx_scale = 64.f / p->filter_width;
@@ -1444,6 +1494,8 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         // splat modes (all bit-identical): 4 skewed time, 3 four tile pixels per lane (power-of-two
         // buckets); 1 / 0 one tile pixel per lane with the threshold / direct filter-index arithmetic
         // (any bucket size; 2 selects 1 since the compare-only one-pixel kernel was retired)
+        // sa.Lout into sa.tiles: the beauty, then each requested AOV's records, by the same kernel
+        auto splat = [&]() -> int {
         if (rows) {
             ctx->sched |= NART_SCHED_SPLAT_ROWS;
             const uint32_t U = g.tile_size * (2 * g.filter_bounds + 1), ub = std::max(1u, 512u / U);
@@ -1476,9 +1528,29 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         else if (sa.thr && splat_mode >= 1) hipLaunchKernelGGL(k_splat<1>, sg, dim3(256), 0, st, sa);
         else hipLaunchKernelGGL(k_splat<0>, sg, dim3(256), 0, st, sa);
         HIPCHK(hipGetLastError());
+        return NART_OK;
+        };
+        if (beauty && (rc = splat())) return rc;
         HIPCHK(hipEventRecord(ctx->ev[2], st));
+        if (aov) {
+            // the dispatch's own camera-ray hits where it traced them first, else k_primary now
+            if (!ctx->prim_valid && (rc = launch_aov_primary(ctx, ra, st))) return rc;
+            HIPCHK(hipEventRecord(ctx->ev_aov[0], st));
+            for (int k = 0; k < 2; ++k) {
+                if (!aov->tiles[k]) continue;
+                if ((rc = launch_aov(ctx, ra, k, ctx->d_L, st))) return rc;
+                sa.tiles = aov->tiles[k] + (size_t)b0 * tpx * 5;
+                if ((rc = splat())) return rc;
+            }
+            HIPCHK(hipEventRecord(ctx->ev_aov[1], st));
+            HIPCHK(hipEventSynchronize(ctx->ev_aov[1]));
+        }
         HIPCHK(hipEventSynchronize(ctx->ev[2]));
         float ms = 0.f;
+        if (aov) {
+            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_aov[0], ctx->ev_aov[1]));
+            aov->ms += ms;
+        }
         HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
         kernel_ms += ms;
         if (ctx->primary_ran) {
@@ -1489,7 +1561,7 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         splat_ms += ms;
         HIPCHK(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[0]));
         latin_ms += ms;
-        ++launches;
+        if (beauty) ++launches;
         b0 = b1;
     }
     if (stats) {
@@ -1879,6 +1951,8 @@ void nart_hip_destroy(nart_ctx* ctx) {
     for (void* b : ctx->env_bufs) hipFree(b);
     if (ctx->events)
         for (auto& e : ctx->ev) hipEventDestroy(e);
+    for (auto& e : ctx->ev_aov)
+        if (e) hipEventDestroy(e);
     delete ctx;
 }
 
@@ -2008,6 +2082,117 @@ int nart_hip_render(nart_ctx* ctx, const nart_render_params* p, nart_pixel* imag
     hipFree(d_img);
     if (stats) stats->render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
+}
+
+int nart_hip_render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_pixel* image,
+                         nart_pixel* albedo, nart_pixel* normal, nart_render_stats* stats, double* aov_ms) {
+    if (!ctx || !p) return NART_E_INVALID;
+    if (aovs & ~(NART_AOV_ALBEDO | NART_AOV_NORMAL)) return fail(ctx, NART_E_INVALID, "unknown AOV bit");
+    if (((aovs & NART_AOV_ALBEDO) && !albedo) || ((aovs & NART_AOV_NORMAL) && !normal))
+        return fail(ctx, NART_E_INVALID, "an AOV is requested without its image buffer");
+    if (!aovs && !image) return fail(ctx, NART_E_INVALID, "neither the beauty nor an AOV is requested");
+    if (!aovs) return nart_hip_render(ctx, p, image, stats);
+    if (p->integrator == NART_INTEGRATOR_VOLUME)
+        return fail(ctx, NART_E_UNSUPPORTED, "first-hit AOVs need surfaces: the volume integrator has none");
+    nart_pixel* const aimg[2] = {(aovs & NART_AOV_ALBEDO) ? albedo : nullptr, (aovs & NART_AOV_NORMAL) ? normal : nullptr};
+    if (aov_ms) *aov_ms = 0.0;
+    auto t0 = std::chrono::steady_clock::now();
+    auto done = [&](int rc) {
+        if (stats) stats->render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return rc;
+    };
+    if (!ctx->subs.empty()) return done(render_multi(ctx, p, image, stats, aimg, image != nullptr, aov_ms));
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const uint32_t nb = g.n_buckets_x * g.n_buckets_y;
+    std::vector<uint32_t> ids(nb);
+    for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
+    // tile buffers back to back: the beauty (if any), then the requested AOVs
+    const size_t tile_floats = (size_t)nb * g.tile_size * g.tile_size * 5;
+    const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
+    nart_pixel* dst[3] = {image, aimg[0], aimg[1]};
+    float* tiles[3] = {nullptr, nullptr, nullptr};
+    size_t nbuf = 0;
+    for (int k = 0; k < 3; ++k)
+        if (dst[k]) ++nbuf;
+    void *d_tiles = nullptr, *d_img = nullptr;
+    if ((rc = dmalloc(ctx, &d_tiles, nbuf * tile_floats * sizeof(float), "tiles"))) return rc;
+    if ((rc = dmalloc(ctx, &d_img, img_bytes, "image"))) {
+        hipFree(d_tiles);
+        return rc;
+    }
+    for (int k = 0, i = 0; k < 3; ++k)
+        if (dst[k]) tiles[k] = static_cast<float*>(d_tiles) + (size_t)(i++) * tile_floats;
+    AovRequest rq;
+    rq.beauty = image != nullptr;
+    rq.tiles[0] = tiles[1];
+    rq.tiles[1] = tiles[2];
+    rc = render_buckets(ctx, p, ids.data(), nb, tiles[0], 0, stats, &rq);
+    for (int k = 0; k < 3 && !rc; ++k) {
+        if (!dst[k]) continue;
+        rc = nart_hip_combine_async(ctx, p, reinterpret_cast<const nart_pixel*>(tiles[k]), (nart_pixel*)d_img, 0);
+        if (!rc && hipMemcpy(dst[k], d_img, img_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(ctx, NART_E_HIP, "copy image");
+    }
+    hipFree(d_tiles);
+    hipFree(d_img);
+    if (aov_ms) *aov_ms = rq.ms;
+    return done(rc);
+}
+
+int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w,
+                                uint32_t h, float* out8, uint32_t* tri) {
+    if (!ctx || !p || !out8) return NART_E_INVALID;
+    if (!ctx->subs.empty()) {  // per-sample debugging runs on the first device
+        const int rc = nart_hip_render_aov_samples(ctx->subs[0], p, x0, y0, w, h, out8, tri);
+        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
+    }
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    if (p->integrator == NART_INTEGRATOR_VOLUME)
+        return fail(ctx, NART_E_UNSUPPORTED, "first-hit AOVs need surfaces: the volume integrator has none");
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    if ((uint64_t)x0 + w > g.total_width || (uint64_t)y0 + h > g.total_height || !w || !h)
+        return fail(ctx, NART_E_INVALID, "rect out of range");
+    std::vector<uint32_t> xy;
+    for (uint32_t y = y0; y < y0 + h; ++y)
+        for (uint32_t x = x0; x < x0 + w; ++x) xy.push_back(x | (y << 16));
+    const uint32_t n = (uint32_t)xy.size();
+    rc = ensure(ctx, n, p->spp, 1);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(ctx->d_slot_xy, xy.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_slot_rows, dim3((n + 255) / 256), dim3(256), 0, 0, n, p->spp, ctx->d_slot_so);
+    RenderArgs ra;
+    ra.slot_xy = ctx->d_slot_xy;
+    ra.slot_so = ctx->d_slot_so;
+    ra.samples = ctx->d_samples;
+    ra.rng0 = ctx->d_rng;
+    ra.Lout = ctx->d_L;
+    ra.n_slots = n;
+    ra.spp = p->spp;
+    ra.bounces = p->bounces;
+    ra.W = p->image_width;
+    ra.H = p->image_height;
+    ra.totalW = g.total_width;
+    ra.stack_depth = ctx->stack_depth;
+    ra.lds_nodes = 0;
+    ra.gamma = p->roughening_factor * p->roughening_factor;
+    ra.counters = nullptr;  // k_primary<false, ...> and k_aov count nothing
+    if ((rc = launch_latin(ctx, ra, 0)) || (rc = launch_aov_primary(ctx, ra, 0))) return rc;
+    const size_t ns = (size_t)n * p->spp;
+    std::vector<float> rec(ns * 4);
+    for (int k = 0; k < 2; ++k) {
+        if ((rc = launch_aov(ctx, ra, k, ctx->d_L, 0))) return rc;
+        HIPCHK(hipMemcpy(rec.data(), ctx->d_L, ns * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < ns; ++i) std::memcpy(out8 + i * 8 + 4 * k, rec.data() + i * 4, 4 * sizeof(float));
+    }
+    if (tri) HIPCHK(hipMemcpy(tri, ctx->d_prim, ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return NART_OK;
 }
 
 int nart_hip_render_device(nart_ctx* ctx, const nart_render_params* p, const nart_pixel** d_image,
