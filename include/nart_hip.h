@@ -151,6 +151,91 @@ int nart_hip_render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t ao
 int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w,
                                 uint32_t h, float* out8, uint32_t* tri);
 
+/* Edge-avoiding a-trous denoiser driven by the first-hit AOVs (no reference counterpart).
+
+   The filter works on the cropped image_width x image_height image: pixel (x, y) is total-image
+   pixel (x + fb, y + fb), fb = filter_bounds.  All arithmetic is float32 + - * / sqrt and
+   comparisons, in exactly the order written here (the build contracts nothing and divides and takes
+   roots correctly rounded), so that a numpy restatement (tests/denoise_py.py) gives the same bits.
+   max(a, b) means a > b ? a : b and min(a, b) means a < b ? a : b; sums run in the order given,
+   starting from 0.
+
+   Prepare (k_dn_prepare), per pixel, from the beauty, albedo and normal nart_pixel images
+   (contribution rgba, filter_weight_sum w):
+       c    = beauty.rgba / beauty.w           (0 if beauty.w <= 0)
+       a    = albedo.rgb / albedo.w, cov = albedo.a / albedo.w     (0 if albedo.w <= 0)
+       hs   = albedo.a                         (sum of weight * hit)
+       z    = normal.w / hs, n = normal.xyz / hs;  a pixel with hs <= 0 or z == 0 is EMPTY: n = 0, z = 0
+              (no surface has depth 0; the kernels recognise an empty pixel by z == 0)
+       a_d  = max(a + (1 - cov), albedo_floor) per channel      (a miss counts as albedo 1)
+       s    = c.rgb / a_d;  luminance l(s) = (0.2126 s.r + 0.7152 s.g) + 0.0722 s.b
+       slope = sx + sy; sx = min(|z - z_left|, |z_right - z|), at an image border the one that
+              exists, 0 if the axis has one pixel; sy likewise (up, down)
+   A pixel whose c.rgb has a non-finite component is INVALID: s = 0.  An invalid pixel has weight 0 as
+   a tap everywhere (also as its own centre tap) and counts as variance 0 in the variance blur; as
+   a centre it uses d_l = 0.  A pass that leaves it with sum(w) > 0 makes it valid with that pass's
+   result; otherwise its signal stays 0 and it stays invalid.  The variance pass leaves it as it is.
+
+   Guide terms of centre p and tap q at offset (dx, dy), cheb = max(|dx|, |dy|) (pixels, as float):
+       w_n = 1 if both are empty, else min(1, max(0, (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z)),
+             then w_n = w_n * w_n, normal_squarings times
+       d_g = |z_p - z_q| / ((sigma_depth * (slope_p * cheb) + depth_eps * max(z_p, z_q)) + 1e-30)
+             + |cov_p - cov_q| / sigma_coverage
+       f(d) = t8: t = max(0, 1 - d * 0.125), t2 = t * t, t4 = t2 * t2, t8 = t4 * t4
+   The centre tap of a valid pixel has w_n * f = 1.  Taps outside the image are skipped.
+
+   Variance (k_dn_variance), 7x7, dy outer and dx inner, both ascending:
+       u = w_n * f(d_g);  su += u, sl += u * l_q, sl2 += u * (l_q * l_q)
+       m1 = sl / su, m2 = sl2 / su, v = max(0, m2 - m1 * m1)
+   A-trous pass i = 0 .. iterations-1 (k_dn_atrous), step = 2^i, taps (dx, dy) = (ix, iy) * step for
+   ix, iy in -2..2, iy outer, h = [1/16, 1/4, 3/8, 1/4, 1/16]:
+       vb  = sum over dy, dx in -1..1 (dy outer, coordinates clamped to the image) of
+             (k[dy] * k[dx]) * max(v_q, 0), k = [1/4, 1/2, 1/4]
+       d_l = |l_p - l_q| / (sigma_color * sqrt(vb) + 1e-6)
+       w   = (h[ix] * h[iy]) * (w_n * f(d_g + d_l))          (centre tap: h[0] * h[0] = 9/64)
+       sw += w, ss += w * s_q (per channel), sv += (w * w) * v_q
+       s' = ss / sw, v' = sv / (sw * sw)
+   Signal and variance ping-pong between the passes; the guides are constant.
+   Finalise (k_dn_finalize): out.rgb = s * a_d, out.a = c.a (alpha passes through).
+
+   The output is a nart_pixel image of totalW x totalH: cropped pixels {rgb, alpha, 1}, border
+   pixels all zero, so nart_write_exr and contribution / filter_weight_sum work on it unchanged.
+   The image is a pure function of the inputs and the parameters: no atomics, any launch shape. */
+typedef struct nart_denoise_params {
+    uint32_t iterations;       /* a-trous passes, 1..8: the last step is 2^(iterations-1)  default 5    */
+    uint32_t normal_squarings; /* w_n = clamp(dot)^(2^normal_squarings)                    default 5    */
+    float sigma_color;         /* luminance distance in standard deviations                default 4    */
+    float sigma_depth;         /* depth distance in units of the local depth slope         default 1    */
+    float depth_eps;           /* relative depth tolerance on flat surfaces                default 1e-3 */
+    float sigma_coverage;      /* coverage distance                                        default 0.05 */
+    float albedo_floor;        /* least albedo a pixel is demodulated by                   default 0.01 */
+} nart_denoise_params;
+void nart_hip_denoise_params_init(nart_denoise_params* dp);
+
+/* Denoise host images: beauty, albedo and normal are nart_pixel images of totalW*totalH as
+   nart_hip_render_aovs returns them (any integrator may have made the beauty), out receives the
+   denoised image.  dp null: the defaults.  denoise_ms, if non-null, receives the device time of the
+   denoise kernels.  Multi-device contexts run it on their first device.  NART_E_INVALID: a null
+   ctx, p, image or out, iterations outside 1..8, a sigma, depth_eps or albedo_floor that is not > 0,
+   normal_squarings > 16. */
+int nart_hip_denoise(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                     const nart_pixel* beauty, const nart_pixel* albedo, const nart_pixel* normal, nart_pixel* out,
+                     double* denoise_ms);
+
+/* Render the beauty and both first-hit AOVs and denoise them on the device: the three images never
+   pass through the host.  out receives the denoised image; image, if non-null, the noisy beauty,
+   bit-identical to nart_hip_render's.  Multi-device contexts denoise on their first device after
+   the gather.  Errors as nart_hip_denoise (image may be null); NART_E_UNSUPPORTED: the volume
+   integrator (no first-hit AOVs).  A render without denoising launches exactly what it launched
+   before. */
+int nart_hip_render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                             nart_pixel* image, nart_pixel* out, nart_render_stats* stats, double* denoise_ms);
+
+/* Device times (ms) of the last denoise of this context, kernel by kernel: prepare, variance, the
+   a-trous passes (pass_ms[8], zero beyond the iterations run) and finalise.  Any pointer may be null. */
+int nart_hip_denoise_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
+                             double* finalize_ms);
+
 /* Multi-GPU building block: render the listed buckets (bucket id = by*nBucketsX + bx) into
    device-resident tiles d_tiles[i] (tile_size^2 nart_pixel each, same order as the list) on
    `stream` (a hipStream_t, may be 0).  bucket_ids is a host array.  Asynchronous w.r.t. the

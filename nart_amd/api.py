@@ -89,6 +89,25 @@ class RenderStats(ctypes.Structure):
 _P = ctypes.c_void_p
 
 
+class DenoiseParams(ctypes.Structure):
+    """nart_denoise_params (include/nart_hip.h); DenoiseParams.defaults() is
+    nart_hip_denoise_params_init, keyword arguments override single fields."""
+    _fields_ = [("iterations", ctypes.c_uint32), ("normal_squarings", ctypes.c_uint32),
+                ("sigma_color", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("depth_eps", ctypes.c_float),
+                ("sigma_coverage", ctypes.c_float), ("albedo_floor", ctypes.c_float)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        dp = cls()
+        hip_lib().nart_hip_denoise_params_init(ctypes.byref(dp))
+        for k, v in kw.items():
+            setattr(dp, k, v)
+        return dp
+
+    def __repr__(self):
+        return "DenoiseParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
 class _Texture(ctypes.Structure):
     """nart_texture (include/nart_scene.h)."""
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("rgba", _P)]
@@ -148,6 +167,13 @@ _HIP_SIGS = {
                                             ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_aov_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, ctypes.c_uint32,
                                                    ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
+    "nart_hip_denoise_params_init": (None, [ctypes.POINTER(DenoiseParams)]),
+    "nart_hip_denoise": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams), _P, _P, _P, _P,
+                                        ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_denoised": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams), _P, _P,
+                                                ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_denoise_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_device": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(_P),
                                               ctypes.POINTER(RenderStats)]),
     "nart_hip_render_buckets_async": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(ctypes.c_uint32),
@@ -519,6 +545,50 @@ class HipRenderer:
         self._check(self._lib.nart_hip_render_aov_samples(self._ctx, ctypes.byref(p), x0, y0, w, h, out.ctypes.data,
                                                           tri.ctypes.data))
         return out, tri
+
+    def denoise(self, p, beauty, albedo, normal, params=None):
+        """Denoise host images (nart_hip_denoise): beauty, albedo and normal are (totalH, totalW, 5)
+        float32 images as render_aovs() returns them; params a DenoiseParams (None: the defaults).
+        Returns the denoised (totalH, totalW, 5) image: {rgb, alpha, 1} in the cropped window, zero
+        in the border, so finalize() and write_exr() take it as they take a render."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        src = [np.ascontiguousarray(a, dtype=np.float32) for a in (beauty, albedo, normal)]
+        for a in src:
+            if a.shape != shape:
+                raise ValueError("denoise: image of shape %s, expected %s" % (a.shape, shape))
+        out = np.empty(shape, np.float32)
+        self._check(self._lib.nart_hip_denoise(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
+                                               src[0].ctypes.data, src[1].ctypes.data, src[2].ctypes.data,
+                                               out.ctypes.data, None))
+        return out
+
+    def render_denoised(self, p, params=None, beauty=True, stats=None):
+        """Render the beauty and both first-hit AOVs and denoise them on the device
+        (nart_hip_render_denoised): a dict with "denoised", "beauty" (the noisy image, bit-identical to
+        render(); only if requested) and "denoise_ms", the device time of the denoise kernels."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        out = {"denoised": np.empty(shape, np.float32)}
+        if beauty:
+            out["beauty"] = np.empty(shape, np.float32)
+        st = stats if stats is not None else RenderStats()
+        ms = ctypes.c_double()
+        self._check(self._lib.nart_hip_render_denoised(self._ctx, ctypes.byref(p),
+                                                       ctypes.byref(params) if params else None,
+                                                       out["beauty"].ctypes.data if beauty else None,
+                                                       out["denoised"].ctypes.data, ctypes.byref(st), ctypes.byref(ms)))
+        out["denoise_ms"] = ms.value
+        return out
+
+    def denoise_timings(self):
+        """Device times (ms) of the last denoise, kernel by kernel (nart_hip_denoise_timings):
+        {"prepare", "variance", "passes": [8], "finalize"}."""
+        a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        passes = (ctypes.c_double * 8)()
+        self._check(self._lib.nart_hip_denoise_timings(self._ctx, ctypes.byref(a), ctypes.byref(b), passes,
+                                                       ctypes.byref(c)))
+        return {"prepare": a.value, "variance": b.value, "passes": list(passes), "finalize": c.value}
 
     def render_device(self, p, stats=None):
         """Whole session, image left on the (first) device: returns its device address (totalH x

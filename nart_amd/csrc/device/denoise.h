@@ -1,0 +1,296 @@
+// Edge-avoiding a-trous denoiser over the first-hit AOVs (include/nart_hip.h, nart_hip_denoise).
+//
+// Four kernels, one lane per cropped-image pixel, lanes along x, 32 x 8 pixel tiles (256 threads),
+// no atomics: every output is a pure function of its inputs, whatever the launch shape.
+//   k_dn_prepare   the three nart_pixel images -> guide {n.xyz, z}, cov, signal {s.rgb, v},
+//                  centre record {a_d.rgb, alpha} and depth slope
+//   k_dn_variance  7x7 guide-weighted luminance variance into signal.v
+//   k_dn_atrous    one 5x5 pass with holes (step 2^i), signal ping-pong
+//   k_dn_finalize  remodulate into the totalW x totalH nart_pixel output
+// The variance window and the passes of step 1 and 2 stage their tile plus halo in LDS (R = 3, 2, 4
+// pixels of halo: 36 B per staged pixel, at most 40 x 16 pixels = 22.5 KB); larger steps read global
+// memory (R = 0), where the 36 B per tap come out of the cache hierarchy.  Both ways run the same
+// arithmetic in the same order.
+//
+// The arithmetic is float32 + - * / sqrt and comparisons only, in the order the header fixes, built
+// without contraction: tests/denoise_py.py restates it in numpy and the images agree bit for bit.
+// min and max are written as comparisons (dn_min, dn_max) so that their NaN and signed-zero
+// behaviour is the restatement's np.where, not a library's.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace nd {
+
+struct DnArgs {
+    // inputs / output: nart_pixel images of totalW x totalH, 5 floats per pixel
+    const float* beauty;
+    const float* albedo;
+    const float* normal;
+    float* out;
+    // work buffers over the cropped W x H image
+    float4* guide;       // {n.xyz, z}; an empty pixel is all zeros (z == 0 marks it)
+    float* cov;
+    const float4* sig_in;  // {s.rgb, v}; v < 0 marks an invalid pixel (s = 0)
+    float4* sig_out;
+    float4* centre;      // {a_d.rgb, alpha}
+    float* slope;
+    uint32_t W, H, totalW, totalH, fb;
+    uint32_t step;
+    uint32_t normal_squarings;
+    float sigma_color, sigma_depth, depth_eps, sigma_coverage, albedo_floor;
+};
+
+constexpr int DN_TW = 32, DN_TH = 8;  // pixels per block: 256 lanes, lanes along x
+
+__device__ __forceinline__ float dn_max(float a, float b) { return a > b ? a : b; }
+__device__ __forceinline__ float dn_min(float a, float b) { return a < b ? a : b; }
+__device__ __forceinline__ float dn_abs(float a) { return __builtin_fabsf(a); }
+__device__ __forceinline__ bool dn_finite(float a) { return dn_abs(a) < __builtin_inff(); }
+__device__ __forceinline__ float dn_lum(const float4& s) { return (0.2126f * s.x + 0.7152f * s.y) + 0.0722f * s.z; }
+
+// Mean depth over hit samples of total-image pixel ti: normal.w / albedo.a, 0 for an empty pixel.
+__device__ __forceinline__ float dn_depth(const DnArgs& a, size_t ti) {
+    const float hs = a.albedo[ti * 5 + 3];
+    return hs > 0.f ? a.normal[ti * 5 + 3] / hs : 0.f;
+}
+
+__global__ void __launch_bounds__(256) k_dn_prepare(DnArgs a) {
+    const uint32_t x = blockIdx.x * DN_TW + (threadIdx.x & (DN_TW - 1));
+    const uint32_t y = blockIdx.y * DN_TH + threadIdx.x / DN_TW;
+    if (x >= a.W || y >= a.H) return;
+    const size_t ti = (size_t)(y + a.fb) * a.totalW + (x + a.fb);
+    const size_t i = (size_t)y * a.W + x;
+    const float* B = a.beauty + ti * 5;
+    const float* A = a.albedo + ti * 5;
+    const float* N = a.normal + ti * 5;
+    float c[4] = {0.f, 0.f, 0.f, 0.f};
+    if (B[4] > 0.f)
+        for (int k = 0; k < 4; ++k) c[k] = B[k] / B[4];
+    float al[3] = {0.f, 0.f, 0.f}, cov = 0.f;
+    if (A[4] > 0.f) {
+        for (int k = 0; k < 3; ++k) al[k] = A[k] / A[4];
+        cov = A[3] / A[4];
+    }
+    const float hs = A[3];
+    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (hs > 0.f) {
+        g.w = N[3] / hs;
+        if (g.w != 0.f) {
+            g.x = N[0] / hs;
+            g.y = N[1] / hs;
+            g.z = N[2] / hs;
+        } else {
+            g.w = 0.f;  // -0 -> +0
+        }
+    }
+    const float miss = 1.f - cov;
+    float4 ce;
+    ce.x = dn_max(al[0] + miss, a.albedo_floor);
+    ce.y = dn_max(al[1] + miss, a.albedo_floor);
+    ce.z = dn_max(al[2] + miss, a.albedo_floor);
+    ce.w = c[3];
+    const bool valid = dn_finite(c[0]) && dn_finite(c[1]) && dn_finite(c[2]);
+    float4 s = make_float4(0.f, 0.f, 0.f, -1.f);
+    if (valid) s = make_float4(c[0] / ce.x, c[1] / ce.y, c[2] / ce.z, 0.f);
+    // depth slope: per axis the smaller one-sided |dz| (the one available at a border, 0 on a
+    // single-pixel axis)
+    float sx = 0.f, sy = 0.f;
+    if (a.W > 1) {
+        const float dl = x > 0 ? dn_abs(g.w - dn_depth(a, ti - 1)) : 0.f;
+        const float dr = x + 1 < a.W ? dn_abs(dn_depth(a, ti + 1) - g.w) : 0.f;
+        sx = x == 0 ? dr : (x + 1 == a.W ? dl : dn_min(dl, dr));
+    }
+    if (a.H > 1) {
+        const float du = y > 0 ? dn_abs(g.w - dn_depth(a, ti - a.totalW)) : 0.f;
+        const float dd = y + 1 < a.H ? dn_abs(dn_depth(a, ti + a.totalW) - g.w) : 0.f;
+        sy = y == 0 ? dd : (y + 1 == a.H ? du : dn_min(du, dd));
+    }
+    a.guide[i] = g;
+    a.cov[i] = cov;
+    a.sig_out[i] = s;
+    a.centre[i] = ce;
+    a.slope[i] = sx + sy;
+}
+
+// A block's view of the per-tap records: its tile plus R pixels of halo in LDS (R > 0), or global
+// memory (R == 0).  at() is only called with coordinates inside the image.
+template <int R>
+struct DnView {
+    static constexpr int LW = DN_TW + 2 * R, LH = DN_TH + 2 * R;
+    float4* lg;
+    float4* ls;
+    float* lc;
+    const DnArgs& a;
+    int x0, y0;  // image coordinates of the staged region's first pixel
+
+    __device__ DnView(const DnArgs& args, float4* g, float4* s, float* c) : lg(g), ls(s), lc(c), a(args) {
+        x0 = (int)(blockIdx.x * DN_TW) - R;
+        y0 = (int)(blockIdx.y * DN_TH) - R;
+        if (R > 0) {
+            for (int k = threadIdx.x; k < LW * LH; k += 256) {
+                const int gx = x0 + k % LW, gy = y0 + k / LW;
+                float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f), s4 = make_float4(0.f, 0.f, 0.f, -1.f);
+                float c1 = 0.f;
+                if (gx >= 0 && gy >= 0 && gx < (int)a.W && gy < (int)a.H) {
+                    const size_t i = (size_t)gy * a.W + gx;
+                    g4 = a.guide[i];
+                    s4 = a.sig_in[i];
+                    c1 = a.cov[i];
+                }
+                lg[k] = g4;
+                ls[k] = s4;
+                lc[k] = c1;
+            }
+            __syncthreads();
+        }
+    }
+    __device__ __forceinline__ size_t idx(int x, int y) const {
+        return R > 0 ? (size_t)((y - y0) * LW + (x - x0)) : (size_t)y * a.W + x;
+    }
+    __device__ __forceinline__ float4 guide(int x, int y) const { return R > 0 ? lg[idx(x, y)] : a.guide[idx(x, y)]; }
+    __device__ __forceinline__ float4 sig(int x, int y) const { return R > 0 ? ls[idx(x, y)] : a.sig_in[idx(x, y)]; }
+    __device__ __forceinline__ float cov(int x, int y) const { return R > 0 ? lc[idx(x, y)] : a.cov[idx(x, y)]; }
+};
+
+// w_n * f(d_g + d_l) of a tap that is not the centre (include/nart_hip.h, "Guide terms").
+__device__ __forceinline__ float dn_tap_weight(const DnArgs& a, const float4& gp, float covp, float slope_p,
+                                               const float4& gq, float covq, float cheb, float d_l) {
+    float wn = 1.f;
+    if (!(gp.w == 0.f && gq.w == 0.f)) {
+        const float dot = (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z;
+        wn = dn_min(1.f, dn_max(0.f, dot));
+        for (uint32_t k = 0; k < a.normal_squarings; ++k) wn = wn * wn;
+    }
+    const float dz = dn_abs(gp.w - gq.w) / ((a.sigma_depth * (slope_p * cheb) + a.depth_eps * dn_max(gp.w, gq.w)) + 1e-30f);
+    const float dg = dz + dn_abs(covp - covq) / a.sigma_coverage;
+    const float t = dn_max(0.f, 1.f - (dg + d_l) * 0.125f);
+    const float t2 = t * t, t4 = t2 * t2;
+    return wn * (t4 * t4);
+}
+
+__global__ void __launch_bounds__(256) k_dn_variance(DnArgs a) {
+    constexpr int R = 3;
+    __shared__ float4 lg[DnView<R>::LW * DnView<R>::LH];
+    __shared__ float4 ls[DnView<R>::LW * DnView<R>::LH];
+    __shared__ float lc[DnView<R>::LW * DnView<R>::LH];
+    const DnView<R> v(a, lg, ls, lc);
+    const int x = blockIdx.x * DN_TW + (threadIdx.x & (DN_TW - 1));
+    const int y = blockIdx.y * DN_TH + threadIdx.x / DN_TW;
+    if (x >= (int)a.W || y >= (int)a.H) return;
+    const size_t i = (size_t)y * a.W + x;
+    float4 sp = v.sig(x, y);
+    if (sp.w < 0.f) {  // invalid: stays as it is
+        a.sig_out[i] = sp;
+        return;
+    }
+    const float4 gp = v.guide(x, y);
+    const float covp = v.cov(x, y), slope_p = a.slope[i];
+    float su = 0.f, sl = 0.f, sl2 = 0.f;
+    for (int dy = -R; dy <= R; ++dy) {
+        const int qy = y + dy;
+        if (qy < 0 || qy >= (int)a.H) continue;
+        for (int dx = -R; dx <= R; ++dx) {
+            const int qx = x + dx;
+            if (qx < 0 || qx >= (int)a.W) continue;
+            const float4 sq = v.sig(qx, qy);
+            if (sq.w < 0.f) continue;
+            float u = 1.f;
+            if (dx != 0 || dy != 0) {
+                const int cheb = max(abs(dx), abs(dy));
+                u = dn_tap_weight(a, gp, covp, slope_p, v.guide(qx, qy), v.cov(qx, qy), (float)cheb, 0.f);
+            }
+            const float l = dn_lum(sq);
+            su = su + u;
+            sl = sl + u * l;
+            sl2 = sl2 + u * (l * l);
+        }
+    }
+    const float m1 = sl / su, m2 = sl2 / su;
+    sp.w = dn_max(0.f, m2 - m1 * m1);
+    a.sig_out[i] = sp;
+}
+
+template <int R>
+__global__ void __launch_bounds__(256) k_dn_atrous(DnArgs a) {
+    constexpr int N = R > 0 ? DnView<R>::LW * DnView<R>::LH : 1;
+    __shared__ float4 lg[N];
+    __shared__ float4 ls[N];
+    __shared__ float lc[N];
+    const DnView<R> v(a, lg, ls, lc);
+    const int x = blockIdx.x * DN_TW + (threadIdx.x & (DN_TW - 1));
+    const int y = blockIdx.y * DN_TH + threadIdx.x / DN_TW;
+    const int W = (int)a.W, H = (int)a.H;
+    if (x >= W || y >= H) return;
+    const size_t i = (size_t)y * a.W + x;
+    const int step = (int)a.step;
+    const float4 sp = v.sig(x, y);
+    const float4 gp = v.guide(x, y);
+    const float covp = v.cov(x, y), slope_p = a.slope[i];
+    const bool valid_p = !(sp.w < 0.f);
+    // 3x3 blur of the variance, clamped coordinates; an invalid pixel counts as variance 0
+    float den = 0.f, lp = 0.f;
+    if (valid_p) {
+        float vb = 0.f;
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int qy = min(max(y + dy, 0), H - 1);
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int qx = min(max(x + dx, 0), W - 1);
+                const float k = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
+                vb = vb + k * dn_max(v.sig(qx, qy).w, 0.f);
+            }
+        }
+        den = a.sigma_color * sqrtf(vb) + 1e-6f;
+        lp = dn_lum(sp);
+    }
+    float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f;
+    for (int iy = -2; iy <= 2; ++iy) {
+        const int qy = y + iy * step;
+        if (qy < 0 || qy >= H) continue;
+        const float hy = iy == 0 ? 0.375f : (iy == 1 || iy == -1 ? 0.25f : 0.0625f);
+        for (int ix = -2; ix <= 2; ++ix) {
+            const int qx = x + ix * step;
+            if (qx < 0 || qx >= W) continue;
+            const float4 sq = v.sig(qx, qy);
+            if (sq.w < 0.f) continue;
+            const float hx = ix == 0 ? 0.375f : (ix == 1 || ix == -1 ? 0.25f : 0.0625f);
+            float w = hx * hy;
+            if (ix != 0 || iy != 0) {
+                const float d_l = valid_p ? dn_abs(lp - dn_lum(sq)) / den : 0.f;
+                const int cheb = step * max(abs(ix), abs(iy));
+                w = w * dn_tap_weight(a, gp, covp, slope_p, v.guide(qx, qy), v.cov(qx, qy), (float)cheb, d_l);
+            }
+            sw = sw + w;
+            sr = sr + w * sq.x;
+            sg = sg + w * sq.y;
+            sb = sb + w * sq.z;
+            sv = sv + (w * w) * sq.w;
+        }
+    }
+    float4 o = make_float4(0.f, 0.f, 0.f, -1.f);
+    if (sw > 0.f) o = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
+    a.sig_out[i] = o;
+}
+
+// Remodulate: cropped pixels {s * a_d, alpha, 1}, border pixels zero (sig_in: the last pass's output).
+__global__ void __launch_bounds__(256) k_dn_finalize(DnArgs a) {
+    const size_t n = (size_t)a.totalW * a.totalH;
+    const size_t ti = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (ti >= n) return;
+    const uint32_t tx = (uint32_t)(ti % a.totalW), ty = (uint32_t)(ti / a.totalW);
+    float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (tx >= a.fb && ty >= a.fb && tx - a.fb < a.W && ty - a.fb < a.H) {
+        const size_t i = (size_t)(ty - a.fb) * a.W + (tx - a.fb);
+        const float4 s = a.sig_in[i], ce = a.centre[i];
+        o[0] = s.x * ce.x;
+        o[1] = s.y * ce.y;
+        o[2] = s.z * ce.z;
+        o[3] = ce.w;
+        o[4] = 1.f;
+    }
+    for (int k = 0; k < 5; ++k) a.out[ti * 5 + k] = o[k];
+}
+
+}  // namespace nd

@@ -12,6 +12,9 @@
 //                   same EXR writer: <out>.albedo.exr (RGB albedo, A coverage) and <out>.normal.exr
 //                   (RGB shading normal, filtered and not renormalised; A depth), in half precision;
 //                   <out>_<n>.albedo.exr / <out>_<n>.normal.exr with several sessions
+//   --denoise       also write every session's denoised image (nart_hip_render_denoised, default
+//                   parameters; with --aovs nart_hip_denoise over the AOVs rendered anyway: the same
+//                   image) to <out>.denoised.exr, through the same writer
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -95,11 +98,11 @@ bool take_device_flags(std::vector<char*>& args, std::vector<int>& devices) {
     return true;
 }
 
-// Removes --aovs from argv; true if it was there.
-bool take_aov_flag(std::vector<char*>& args) {
+// Removes every `flag` (--aovs, --denoise) from argv; true if it was there.
+bool take_flag(std::vector<char*>& args, const char* flag) {
     std::vector<char*> kept;
     for (char* a : args)
-        if (std::strcmp(a, "--aovs")) kept.push_back(a);
+        if (std::strcmp(a, flag)) kept.push_back(a);
     const bool found = kept.size() != args.size();
     args = kept;
     return found;
@@ -110,7 +113,8 @@ bool take_aov_flag(std::vector<char*>& args) {
 int main(int argc, char* argv[]) {
     std::vector<char*> args(argv, argv + argc);
     std::vector<int> devices;
-    const bool aovs = take_aov_flag(args);
+    const bool aovs = take_flag(args, "--aovs");
+    const bool denoise = take_flag(args, "--denoise");
     if (!take_device_flags(args, devices)) return EXIT_FAILURE;
     if (args.size() < 3) {
         std::fprintf(stderr, "Too few arguments given.\nUsage example: %s <scene file> <output path>\n", argv[0]);
@@ -148,12 +152,18 @@ int main(int argc, char* argv[]) {
         nart_session_geometry g;
         nart_session_geometry_of(&p, &g);
         std::vector<nart_pixel> image((size_t)g.total_width * g.total_height);
-        std::vector<nart_pixel> albedo, normal;
+        std::vector<nart_pixel> albedo, normal, denoised;
+        if (denoise) denoised.resize(image.size());
         if (aovs) {
             albedo.resize(image.size());
             normal.resize(image.size());
             rc = nart_hip_render_aovs(ctx, &p, NART_AOV_ALBEDO | NART_AOV_NORMAL, image.data(), albedo.data(),
                                       normal.data(), nullptr, nullptr);
+            if (rc == NART_OK && denoise)
+                rc = nart_hip_denoise(ctx, &p, nullptr, image.data(), albedo.data(), normal.data(), denoised.data(),
+                                      nullptr);
+        } else if (denoise) {
+            rc = nart_hip_render_denoised(ctx, &p, nullptr, image.data(), denoised.data(), nullptr, nullptr);
         } else {
             rc = nart_hip_render(ctx, &p, image.data(), nullptr);
         }
@@ -169,16 +179,18 @@ int main(int argc, char* argv[]) {
             std::fprintf(stderr, "%s\n", nart_scene_last_error());
             return EXIT_FAILURE;
         }
+        std::vector<std::pair<const char*, const nart_pixel*>> extra;
         if (aovs) {
-            const std::pair<const char*, const nart_pixel*> extra[2] = {{".albedo.exr", albedo.data()},
-                                                                        {".normal.exr", normal.data()}};
-            for (const auto& e : extra) {
-                path = stem + e.first;
-                std::printf("Writing to %s...\n", path.c_str());
-                if (nart_write_exr(path.c_str(), &p, e.second, 3) != NART_OK) {
-                    std::fprintf(stderr, "%s\n", nart_scene_last_error());
-                    return EXIT_FAILURE;
-                }
+            extra.push_back({".albedo.exr", albedo.data()});
+            extra.push_back({".normal.exr", normal.data()});
+        }
+        if (denoise) extra.push_back({".denoised.exr", denoised.data()});
+        for (const auto& e : extra) {
+            path = stem + e.first;
+            std::printf("Writing to %s...\n", path.c_str());
+            if (nart_write_exr(path.c_str(), &p, e.second, 3) != NART_OK) {
+                std::fprintf(stderr, "%s\n", nart_scene_last_error());
+                return EXIT_FAILURE;
             }
         }
         std::chrono::duration<float> d = std::chrono::high_resolution_clock::now() - start;

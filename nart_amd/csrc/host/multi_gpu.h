@@ -146,9 +146,11 @@ int ensure_dev(nart_ctx* ctx, int dev, void*& buf, size_t& cap, size_t bytes, co
 // render) and each first-hit AOV requested through aov_images[k] (host images, null: not requested;
 // nart_hip_render_aovs).  Every device keeps its buffers' slabs back to back in sub_tiles[d], all are
 // gathered in the one RCCL group (or by device copies), and each buffer is then permuted and
-// combined on device 0 in turn.  aov_ms: the slowest device's AOV time.
+// combined on device 0 in turn.  aov_ms: the slowest device's AOV time.  dst_on_device: image and
+// aov_images are buffers on device 0 instead (nart_hip_render_denoised: nothing passes the host).
 int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, nart_render_stats* stats,
-                 nart_pixel* const* aov_images = nullptr, bool beauty = true, double* aov_ms = nullptr) {
+                 nart_pixel* const* aov_images = nullptr, bool beauty = true, double* aov_ms = nullptr,
+                 bool dst_on_device = false) {
     const uint32_t n = (uint32_t)ctx->subs.size();
     // the tile buffers of this render: -1 the beauty, k >= 0 AOV k; host destinations alongside
     std::vector<int> kinds;
@@ -302,7 +304,9 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, 
         if ((rc = nart_hip_combine_async(ctx->subs[0], p, static_cast<const nart_pixel*>(ctx->d_byid),
                                          static_cast<nart_pixel*>(ctx->d_image), s0)))
             return fail(ctx, rc, ctx->subs[0]->err);
-        if (dsts[i]) HIPCHK(hipMemcpyAsync(dsts[i], ctx->d_image, img_bytes, hipMemcpyDeviceToHost, s0));
+        if (dsts[i])
+            HIPCHK(hipMemcpyAsync(dsts[i], ctx->d_image, img_bytes,
+                                  dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s0));
     }
     HIPCHK(hipStreamSynchronize(s0));
     if (aov_ms)

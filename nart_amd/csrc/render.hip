@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/nart_hip.h"
+#include "device/denoise.h"
 #include "device/lbvh.h"
 #include "device/volume.h"
 #include "host/bvh_build.h"
@@ -76,6 +77,12 @@ struct nart_ctx {
     bool primary_ran = false;  // the last dispatch launched k_primary (ev[4] recorded)
     bool prim_valid = false;   // d_prim holds the current batch's camera-ray hits (first-hit AOVs)
     hipEvent_t ev_aov[2] = {nullptr, nullptr};  // around the AOV passes of a batch (render_buckets)
+    // denoiser (denoise_device): work buffers over the cropped image, the four device images of
+    // nart_hip_denoise / nart_hip_render_denoised, events between its kernels, the last run's times
+    void *d_dn = nullptr, *d_dn_img = nullptr;
+    size_t cap_dn = 0, cap_dn_img = 0;
+    hipEvent_t ev_dn[12] = {};
+    double dn_ms[11] = {};  // prepare, variance, passes 0..7, finalise
     uint32_t sched = 0;        // NART_SCHED_* bits of the current render (nart_render_stats::schedule)
     bool events = false;
     // megakernel work queue (launch_render)
@@ -1703,6 +1710,120 @@ int build_bvh_device(nart_ctx* ctx, const nart_scene_blob& blob, const std::vect
 
 #include "host/multi_gpu.h"
 
+namespace {
+
+// ---------------------------------------------------------------- denoiser (device/denoise.h)
+void denoise_defaults(nart_denoise_params* dp) {
+    dp->iterations = 5;
+    dp->normal_squarings = 5;
+    dp->sigma_color = 4.f;
+    dp->sigma_depth = 1.f;
+    dp->depth_eps = 1e-3f;
+    dp->sigma_coverage = 0.05f;
+    dp->albedo_floor = 0.01f;
+}
+
+// dp (null: the defaults) into out, or NART_E_INVALID.
+int check_denoise(nart_ctx* ctx, const nart_denoise_params* dp, nart_denoise_params& out) {
+    if (dp) out = *dp;
+    else denoise_defaults(&out);
+    if (out.iterations < 1 || out.iterations > 8) return fail(ctx, NART_E_INVALID, "denoise iterations must be 1..8");
+    if (out.normal_squarings > 16) return fail(ctx, NART_E_INVALID, "denoise normal_squarings must be <= 16");
+    if (!(out.sigma_color > 0.f) || !(out.sigma_depth > 0.f) || !(out.depth_eps > 0.f) || !(out.sigma_coverage > 0.f) ||
+        !(out.albedo_floor > 0.f))
+        return fail(ctx, NART_E_INVALID, "denoise sigmas, depth_eps and albedo_floor must be > 0");
+    return NART_OK;
+}
+
+// The four device images (beauty, albedo, normal, denoised) of a single-device context.
+int denoise_images(nart_ctx* ctx, const nart_session_geometry& g, float* img[4]) {
+    const size_t img_floats = (size_t)g.total_width * g.total_height * 5;
+    const size_t bytes = 4 * img_floats * sizeof(float);
+    if (int rc = ensure_dev(ctx, ctx->device, ctx->d_dn_img, ctx->cap_dn_img, bytes, "denoiser images")) return rc;
+    for (int k = 0; k < 4; ++k) img[k] = static_cast<float*>(ctx->d_dn_img) + (size_t)k * img_floats;
+    return NART_OK;
+}
+
+// Denoise device images on a single-device context: prepare, variance, the a-trous passes (LDS
+// tiles for steps 1 and 2, global reads beyond), finalise; synchronous.  ms: device time.
+int denoise_device(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params& dp, const float* d_beauty,
+                   const float* d_albedo, const float* d_normal, float* d_out, hipStream_t st, double* ms) {
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const size_t npx = (size_t)p->image_width * p->image_height;
+    // guide, signal x 2, centre (float4 each), then cov and slope
+    const size_t work_bytes = npx * (4 * sizeof(float4) + 2 * sizeof(float));
+    if (int rc = ensure_dev(ctx, ctx->device, ctx->d_dn, ctx->cap_dn, work_bytes, "denoiser work buffers")) return rc;
+    const uint32_t n_ev = dp.iterations + 4;
+    for (uint32_t k = 0; k < n_ev; ++k)
+        if (!ctx->ev_dn[k]) HIPCHK(hipEventCreate(&ctx->ev_dn[k]));
+    float4* f4 = static_cast<float4*>(ctx->d_dn);
+    float4* sig[2] = {f4 + npx, f4 + 2 * npx};
+    DnArgs a;
+    a.beauty = d_beauty;
+    a.albedo = d_albedo;
+    a.normal = d_normal;
+    a.out = d_out;
+    a.guide = f4;
+    a.centre = f4 + 3 * npx;
+    a.cov = reinterpret_cast<float*>(f4 + 4 * npx);
+    a.slope = a.cov + npx;
+    a.W = p->image_width;
+    a.H = p->image_height;
+    a.totalW = g.total_width;
+    a.totalH = g.total_height;
+    a.fb = g.filter_bounds;
+    a.step = 1;
+    a.normal_squarings = dp.normal_squarings;
+    a.sigma_color = dp.sigma_color;
+    a.sigma_depth = dp.sigma_depth;
+    a.depth_eps = dp.depth_eps;
+    a.sigma_coverage = dp.sigma_coverage;
+    a.albedo_floor = dp.albedo_floor;
+    const dim3 grid((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH), block(256);
+    uint32_t e = 0;
+    HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+    a.sig_in = nullptr;
+    a.sig_out = sig[0];
+    hipLaunchKernelGGL(k_dn_prepare, grid, block, 0, st, a);
+    HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+    a.sig_in = sig[0];
+    a.sig_out = sig[1];
+    hipLaunchKernelGGL(k_dn_variance, grid, block, 0, st, a);
+    HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+    int cur = 1;
+    for (uint32_t i = 0; i < dp.iterations; ++i) {
+        a.sig_in = sig[cur];
+        a.sig_out = sig[cur ^ 1];
+        a.step = 1u << i;
+        if (i == 0) hipLaunchKernelGGL(k_dn_atrous<2>, grid, block, 0, st, a);
+        else if (i == 1) hipLaunchKernelGGL(k_dn_atrous<4>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_dn_atrous<0>, grid, block, 0, st, a);
+        HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+        cur ^= 1;
+    }
+    a.sig_in = sig[cur];
+    const size_t n_total = (size_t)g.total_width * g.total_height;
+    hipLaunchKernelGGL(k_dn_finalize, dim3((uint32_t)((n_total + 255) / 256)), block, 0, st, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+    HIPCHK(hipEventSynchronize(ctx->ev_dn[e - 1]));
+    for (double& t : ctx->dn_ms) t = 0.0;
+    double total = 0.0;
+    for (uint32_t k = 0; k + 1 < e; ++k) {
+        float t = 0.f;
+        HIPCHK(hipEventElapsedTime(&t, ctx->ev_dn[k], ctx->ev_dn[k + 1]));
+        // events 0..2 bracket prepare and variance, the last pair the finalise kernel
+        ctx->dn_ms[k + 2 == e ? 10 : k] = t;
+        total += t;
+    }
+    if (ms) *ms = total;
+    return NART_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) {
@@ -1948,6 +2069,10 @@ void nart_hip_destroy(nart_ctx* ctx) {
         if (b) hipFree(b);
     for (void* b : {ctx->d_gather, ctx->d_image})  // nart_hip_render_device's tiles and image
         if (b) hipFree(b);
+    for (void* b : {ctx->d_dn, ctx->d_dn_img})
+        if (b) hipFree(b);
+    for (auto& e : ctx->ev_dn)
+        if (e) hipEventDestroy(e);
     for (void* b : ctx->env_bufs) hipFree(b);
     if (ctx->events)
         for (auto& e : ctx->ev) hipEventDestroy(e);
@@ -2192,6 +2317,95 @@ int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint
         for (size_t i = 0; i < ns; ++i) std::memcpy(out8 + i * 8 + 4 * k, rec.data() + i * 4, 4 * sizeof(float));
     }
     if (tri) HIPCHK(hipMemcpy(tri, ctx->d_prim, ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+void nart_hip_denoise_params_init(nart_denoise_params* dp) {
+    if (dp) denoise_defaults(dp);
+}
+
+int nart_hip_denoise(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, const nart_pixel* beauty,
+                     const nart_pixel* albedo, const nart_pixel* normal, nart_pixel* out, double* denoise_ms) {
+    if (!ctx || !p || !beauty || !albedo || !normal || !out) return NART_E_INVALID;
+    nart_denoise_params d;
+    int rc = check_denoise(ctx, dp, d);
+    if (rc) return rc;
+    if (!ctx->subs.empty()) {  // on the first device
+        rc = nart_hip_denoise(ctx->subs[0], p, &d, beauty, albedo, normal, out, denoise_ms);
+        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
+    }
+    if (!p->image_width || !p->image_height || !(p->filter_width > 0.f))
+        return fail(ctx, NART_E_INVALID, "imageWidth, imageHeight and filterWidth must be > 0");
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    float* img[4];
+    if ((rc = denoise_images(ctx, g, img))) return rc;
+    const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
+    const nart_pixel* src[3] = {beauty, albedo, normal};
+    for (int k = 0; k < 3; ++k) HIPCHK(hipMemcpy(img[k], src[k], img_bytes, hipMemcpyHostToDevice));
+    if ((rc = denoise_device(ctx, p, d, img[0], img[1], img[2], img[3], 0, denoise_ms))) return rc;
+    HIPCHK(hipMemcpy(out, img[3], img_bytes, hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+int nart_hip_render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, nart_pixel* image,
+                             nart_pixel* out, nart_render_stats* stats, double* denoise_ms) {
+    if (!ctx || !p || !out) return NART_E_INVALID;
+    nart_denoise_params d;
+    int rc = check_denoise(ctx, dp, d);
+    if (rc) return rc;
+    if (p->integrator == NART_INTEGRATOR_VOLUME)
+        return fail(ctx, NART_E_UNSUPPORTED, "the denoiser needs first-hit AOVs: the volume integrator has none");
+    auto t0 = std::chrono::steady_clock::now();
+    nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // the context that denoises
+    if ((rc = check_params(c0, p))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
+    float* img[4];
+    if ((rc = denoise_images(c0, g, img))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
+    if (c0 != ctx) {
+        nart_pixel* const aimg[2] = {reinterpret_cast<nart_pixel*>(img[1]), reinterpret_cast<nart_pixel*>(img[2])};
+        rc = render_multi(ctx, p, reinterpret_cast<nart_pixel*>(img[0]), stats, aimg, true, nullptr, true);
+    } else {
+        HIPCHK(hipSetDevice(ctx->device));
+        const uint32_t nb = g.n_buckets_x * g.n_buckets_y;
+        std::vector<uint32_t> ids(nb);
+        for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
+        // tile buffers back to back: the beauty, then the two AOVs
+        const size_t tile_floats = (size_t)nb * g.tile_size * g.tile_size * 5;
+        if ((rc = ensure_dev(ctx, ctx->device, ctx->d_gather, ctx->cap_gather, 3 * tile_floats * sizeof(float), "tiles")))
+            return rc;
+        float* tiles = static_cast<float*>(ctx->d_gather);
+        AovRequest rq;
+        rq.tiles[0] = tiles + tile_floats;
+        rq.tiles[1] = tiles + 2 * tile_floats;
+        rc = render_buckets(ctx, p, ids.data(), nb, tiles, 0, stats, &rq);
+        for (int k = 0; k < 3 && !rc; ++k)
+            rc = nart_hip_combine_async(ctx, p, reinterpret_cast<const nart_pixel*>(tiles + (size_t)k * tile_floats),
+                                        reinterpret_cast<nart_pixel*>(img[k]), 0);
+    }
+    if (!rc && (rc = denoise_device(c0, p, d, img[0], img[1], img[2], img[3], 0, denoise_ms)) && c0 != ctx)
+        fail(ctx, rc, c0->err);
+    if (!rc) {
+        HIPCHK(hipSetDevice(c0->device));
+        if (image) HIPCHK(hipMemcpy(image, img[0], img_bytes, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out, img[3], img_bytes, hipMemcpyDeviceToHost));
+    }
+    if (stats) stats->render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int nart_hip_denoise_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
+                             double* finalize_ms) {
+    if (!ctx) return NART_E_INVALID;
+    const nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];
+    if (prepare_ms) *prepare_ms = c0->dn_ms[0];
+    if (variance_ms) *variance_ms = c0->dn_ms[1];
+    if (pass_ms)
+        for (int k = 0; k < 8; ++k) pass_ms[k] = c0->dn_ms[2 + k];
+    if (finalize_ms) *finalize_ms = c0->dn_ms[10];
     return NART_OK;
 }
 
