@@ -108,27 +108,6 @@ __global__ void k_unshard(const float* slabs, float* by_id, const uint32_t* map,
     for (uint32_t k = threadIdx.x; k < tile_floats; k += blockDim.x) dst[k] = src[k];
 }
 
-// One render's device statistics: device times of the slowest device (the devices run
-// concurrently), work counts summed.  The caller adds the result to its own stats, as the
-// single-device path does (a stats struct reused over renders keeps accumulating).
-void merge_stats(nart_render_stats& out, const nart_render_stats& s) {
-    out.kernel_ms = std::max(out.kernel_ms, s.kernel_ms);
-    out.splat_ms = std::max(out.splat_ms, s.splat_ms);
-    out.latin_ms = std::max(out.latin_ms, s.latin_ms);
-    out.primary_ms = std::max(out.primary_ms, s.primary_ms);
-    out.kernel_launches = std::max(out.kernel_launches, s.kernel_launches);
-    out.schedule |= s.schedule;
-    out.samples += s.samples;
-    out.traced_samples += s.traced_samples;
-    out.rays_extend += s.rays_extend;
-    out.rays_shadow += s.rays_shadow;
-    out.node_visits += s.node_visits;
-    out.tri_tests += s.tri_tests;
-    out.bounces += s.bounces;
-    out.octree_checks += s.octree_checks;
-    out.octree_replays += s.octree_replays;
-}
-
 int ensure_dev(nart_ctx* ctx, int dev, void*& buf, size_t& cap, size_t bytes, const char* what) {
     if (bytes <= cap) return NART_OK;
     HIPCHK(hipSetDevice(dev));
@@ -140,38 +119,24 @@ int ensure_dev(nart_ctx* ctx, int dev, void*& buf, size_t& cap, size_t bytes, co
     return NART_OK;
 }
 
-// Render(), multi-device: shard, render concurrently, gather to device 0, combine, copy out (image
-// null: the combined image stays in ctx->d_image on device 0, nart_hip_render_device).
-// The gather runs over a list of tile buffers: the beauty (unless beauty is false: an AOV-only
-// render) and each first-hit AOV requested through aov_images[k] (host images, null: not requested;
-// nart_hip_render_aovs).  Every device keeps its buffers' slabs back to back in sub_tiles[d], all are
-// gathered in the one RCCL group (or by device copies), and each buffer is then permuted and
-// combined on device 0 in turn.  aov_ms: the slowest device's AOV time.  dst_on_device: image and
-// aov_images are buffers on device 0 instead (nart_hip_render_denoised: nothing passes the host).
-int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, nart_render_stats* stats,
-                 nart_pixel* const* aov_images = nullptr, bool beauty = true, double* aov_ms = nullptr,
-                 bool dst_on_device = false) {
+// The multi-device half of render_frame (which has validated p and sized a borrowed image buffer):
+// shard, render concurrently, gather to device 0, combine, deliver.
+// The gather runs over the request's list of tile buffers: the beauty (unless an AOV-only frame)
+// and each first-hit AOV requested.  Every device keeps its buffers' slabs back to back in
+// sub_tiles[d], all are gathered in the one RCCL group (or by device copies), and each buffer is
+// then permuted and combined into ctx->d_image on device 0 in turn, and copied from there to its
+// destination (none where the request borrows ctx->d_image itself: nart_hip_render_device).
+// aov_ms: the slowest device's AOV time.
+int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest& rq, nart_render_stats* stats,
+                 double* aov_ms) {
     const uint32_t n = (uint32_t)ctx->subs.size();
-    // the tile buffers of this render: -1 the beauty, k >= 0 AOV k; host destinations alongside
+    // the tile buffers of this render: -1 the beauty, k >= 0 AOV k
     std::vector<int> kinds;
-    std::vector<nart_pixel*> dsts;
-    if (beauty) {
-        kinds.push_back(-1);
-        dsts.push_back(image);
-    }
-    for (int k = 0; aov_images && k < 2; ++k)
-        if (aov_images[k]) {
-            kinds.push_back(k);
-            dsts.push_back(aov_images[k]);
-        }
+    for (int k = 0; k < 3; ++k)
+        if (rq.wants(k)) kinds.push_back(k - 1);
     const size_t K = kinds.size();
-    const bool want_aov = K > (beauty ? 1u : 0u);
-    if (want_aov && p && p->integrator == NART_INTEGRATOR_VOLUME)
-        return fail(ctx, NART_E_UNSUPPORTED, "first-hit AOVs need surfaces: the volume integrator has none");
-    if (ctx->rccl_broken)
-        return fail(ctx, NART_E_RCCL, "an earlier RCCL gather of this context failed; destroy it and create a new one");
-    int rc = check_params(ctx->subs[0], p);
-    if (rc) return fail(ctx, rc, ctx->subs[0]->err);
+    const bool want_aov = rq.wants_aovs();
+    int rc = NART_OK;
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
     const uint32_t nb = g.n_buckets_x * g.n_buckets_y;
@@ -203,7 +168,7 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, 
         }
         // buffer i of the list: slab i of sub_tiles[d]
         const size_t slab = ids[d].size() * tile_floats;
-        areq[d].beauty = beauty;
+        areq[d].beauty = rq.beauty;
         for (size_t i = 0; i < K; ++i)
             if (kinds[i] >= 0) areq[d].tiles[kinds[i]] = static_cast<float*>(ctx->sub_tiles[d]) + i * slab;
         rcs[d] = render_buckets(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(),
@@ -304,32 +269,23 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, 
         if ((rc = nart_hip_combine_async(ctx->subs[0], p, static_cast<const nart_pixel*>(ctx->d_byid),
                                          static_cast<nart_pixel*>(ctx->d_image), s0)))
             return fail(ctx, rc, ctx->subs[0]->err);
-        if (dsts[i])
-            HIPCHK(hipMemcpyAsync(dsts[i], ctx->d_image, img_bytes,
-                                  dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s0));
+        // the request's i-th buffer: to its host image, or to image i of the borrowed device buffer
+        void* dst = rq.on_device ? static_cast<char*>(*rq.image) + i * img_bytes
+                                 : static_cast<void*>(rq.dst[kinds[i] + 1]);
+        if (dst != ctx->d_image)
+            HIPCHK(hipMemcpyAsync(dst, ctx->d_image, img_bytes,
+                                  rq.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s0));
     }
     HIPCHK(hipStreamSynchronize(s0));
     if (aov_ms)
         for (uint32_t d = 0; d < n; ++d) *aov_ms = std::max(*aov_ms, areq[d].ms);
     if (stats) {
+        // one render: device times of the slowest device (they run concurrently), work counts
+        // summed; added to the caller's stats as the single-device path adds a render's
         nart_render_stats m;
         std::memset(&m, 0, sizeof(m));
-        for (uint32_t d = 0; d < n; ++d) merge_stats(m, st[d]);
-        stats->kernel_ms += m.kernel_ms;
-        stats->splat_ms += m.splat_ms;
-        stats->latin_ms += m.latin_ms;
-        stats->primary_ms += m.primary_ms;
-        stats->kernel_launches += m.kernel_launches;
-        stats->schedule |= m.schedule;
-        stats->samples += m.samples;
-        stats->traced_samples += m.traced_samples;
-        stats->rays_extend += m.rays_extend;
-        stats->rays_shadow += m.rays_shadow;
-        stats->node_visits += m.node_visits;
-        stats->tri_tests += m.tri_tests;
-        stats->bounces += m.bounces;
-        stats->octree_checks += m.octree_checks;
-        stats->octree_replays += m.octree_replays;
+        for (uint32_t d = 0; d < n; ++d) add_stats(m, st[d], Times::Max);
+        add_stats(*stats, m, Times::Sum);
     }
     return NART_OK;
 }

@@ -31,7 +31,7 @@ struct nart_ctx {
     uint32_t num_nodes = 0;
     int variant = 0;
     // 3 four pixels per lane (default), 2/1/0 one pixel per lane
-    int splat_mode = -1;  // -1: automatic (render_buckets)
+    int splat_mode = -1;  // -1: automatic (plan_splat)
     bool counters = false;
     bool has_env = false;  // scene has an environment light (selects the k_render build)
     uint32_t features = FT_ALL;  // scene feature mask (scene_features): selects the k_render_rq build
@@ -1328,22 +1328,83 @@ int launch_aov(nart_ctx* ctx, const RenderArgs& a, int rec, float4* out, hipStre
     return NART_OK;
 }
 
-// Render a bucket list into device tiles (list order).  Shared by all entry points.  With `aov`
-// each batch also splats the requested first-hit AOV records (k_aov into ctx->d_L, which the beauty
-// splat has consumed by then: no extra per-sample memory) into the request's tiles.
-int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n, float* d_tiles,
-                   hipStream_t st, nart_render_stats* stats, AovRequest* aov = nullptr) {
-    int rc = check_params(ctx, p);
-    if (rc) return rc;
-    const bool beauty = !aov || aov->beauty;
-    if (aov && p->integrator == NART_INTEGRATOR_VOLUME)
+int check_first_hit(nart_ctx* ctx, const nart_render_params* p) {
+    if (p->integrator == NART_INTEGRATOR_VOLUME)
         return fail(ctx, NART_E_UNSUPPORTED, "first-hit AOVs need surfaces: the volume integrator has none");
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const uint32_t nb_total = g.n_buckets_x * g.n_buckets_y;
-    for (uint32_t i = 0; i < n; ++i)
-        if (ids[i] >= nb_total) return fail(ctx, NART_E_INVALID, "bucket id out of range");
+    return NART_OK;
+}
+
+// s into `into`, field by field (render_ms is the caller's wall clock: RenderTimer).  Device times
+// and the launch count add up over the batches and renders of one device (Sum) and take the slowest
+// of devices that run concurrently (Max); work counts always add up.
+enum class Times { Sum, Max };
+void add_stats(nart_render_stats& into, const nart_render_stats& s, Times how) {
+    auto time = [how](auto& a, auto b) { a = how == Times::Max ? std::max(a, b) : a + b; };
+    time(into.kernel_ms, s.kernel_ms);
+    time(into.splat_ms, s.splat_ms);
+    time(into.latin_ms, s.latin_ms);
+    time(into.primary_ms, s.primary_ms);
+    time(into.kernel_launches, s.kernel_launches);
+    into.schedule |= s.schedule;
+    into.samples += s.samples;
+    into.traced_samples += s.traced_samples;
+    into.rays_extend += s.rays_extend;
+    into.rays_shadow += s.rays_shadow;
+    into.node_visits += s.node_visits;
+    into.tri_tests += s.tri_tests;
+    into.bounces += s.bounces;
+    into.octree_checks += s.octree_checks;
+    into.octree_replays += s.octree_replays;
+}
+
+// Wall time of a scope into stats->render_ms (a call that fails adds the time it took, too).
+struct RenderTimer {
+    nart_render_stats* stats;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    explicit RenderTimer(nart_render_stats* s) : stats(s) {}
+    RenderTimer(const RenderTimer&) = delete;
+    ~RenderTimer() {
+        using ms = std::chrono::duration<double, std::milli>;
+        if (stats) stats->render_ms += ms(std::chrono::steady_clock::now() - t0).count();
+    }
+};
+
+// Kernel arguments of n_slots slots laid out in the context's work buffers (ensure).
+RenderArgs make_render_args(const nart_ctx* ctx, const nart_render_params* p, const nart_session_geometry& g,
+                            uint32_t n_slots, unsigned long long* counters) {
+    RenderArgs ra;
+    ra.slot_xy = ctx->d_slot_xy;
+    ra.slot_so = ctx->d_slot_so;
+    ra.samples = ctx->d_samples;
+    ra.rng0 = ctx->d_rng;
+    ra.Lout = ctx->d_L;
+    ra.n_slots = n_slots;
+    ra.spp = p->spp;
+    ra.bounces = p->bounces;
+    ra.W = p->image_width;
+    ra.H = p->image_height;
+    ra.totalW = g.total_width;
+    ra.stack_depth = ctx->stack_depth;
+    ra.lds_nodes = 0;
+    ra.gamma = p->roughening_factor * p->roughening_factor;
+    ra.counters = counters;
+    return ra;
+}
+
+// How a render_buckets call splats: the kernel (all bit-identical) and its launch shape, and the
+// SplatArgs fields that hold for the whole call (the batch adds its buckets, samples and tiles).
+struct SplatPlan {
+    SplatArgs sa;
+    int mode = 0;         // 5 / 4 skewed time (rows / columns), 3 four tile pixels per lane, 1 / 0 one pixel per lane
+    bool skew = false;    // a pixel-major sample layout, for k_splat_skew (mode 4) or k_splat_rows (mode 5)
+    bool rows = false;    // k_splat_rows
+    uint32_t bands = 1;   // tile-row bands per bucket (k_splat_skew's NB)
+    size_t lut_bytes = 0;
+};
+
+// The splat of a call over n_buckets buckets; uploads the filter table, thresholds and LUT.
+int plan_splat(nart_ctx* ctx, const nart_render_params* p, const nart_session_geometry& g, uint32_t n_buckets,
+               SplatPlan& plan) {
     // filter table [64] + filter-index thresholds [65] (splat_thresholds)
     float table[64 + 65];
     nart_filter_table(table);
@@ -1362,7 +1423,7 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
     const double skew_min = 2.0;
     int n_cus = 0;
     HIPCHK(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    const double skew_waves = tile <= 64 ? (double)((n + 64 / tile - 1) / (64 / tile)) : 0.0;
+    const double skew_waves = tile <= 64 ? (double)((n_buckets + 64 / tile - 1) / (64 / tile)) : 0.0;
     // splat mode -1 (default): 4 where the launch is large enough, else 3; an explicit 4 forces it.
     // Launches of 1-2 waves per SIMD split each bucket's tile rows into two bands (twice the waves
     // for ~2/3 of the steps each): C5 1/2 shard 60 -> 49 ms (k_splat_col4: 62); a whole frame keeps
@@ -1390,6 +1451,93 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         if (!ctx->d_lut) HIPCHK(hipMalloc(&ctx->d_lut, SPLAT_LUT_MAX * sizeof(float4)));
         HIPCHK(hipMemcpy(ctx->d_lut, lut.data(), lut.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
+    plan.mode = splat_mode;
+    plan.skew = skew;
+    plan.rows = rows;
+    plan.bands = skew_bands;
+    plan.lut_bytes = lut.size() * sizeof(float4);
+    SplatArgs& sa = plan.sa;
+    sa.table = ctx->d_table;
+    sa.thr = thr_ok ? ctx->d_table + 64 : nullptr;
+    sa.idx_scale = 64.f / p->filter_width;
+    sa.spp = p->spp;
+    sa.B = p->bucket_size;
+    sa.fb = g.filter_bounds;
+    sa.tile = g.tile_size;
+    sa.nbx = g.n_buckets_x;
+    sa.totalW = g.total_width;
+    sa.totalH = g.total_height;
+    sa.fw = p->filter_width;
+    sa.invB = (B & (B - 1)) == 0 ? 1.f / (float)B : 0.f;
+    sa.lut = lut_ok ? static_cast<const float4*>(ctx->d_lut) : nullptr;
+    sa.lut_b0 = lut_b0;
+    sa.lut_n = (uint32_t)lut.size();
+    int ex = 0;
+    sa.invFw = std::frexp(p->filter_width, &ex) == 0.5f ? 1.f / p->filter_width : 0.f;
+    return NART_OK;
+}
+
+#ifndef NART_SPLAT_NP
+#define NART_SPLAT_NP 4
+#endif
+// sa.Lout into sa.tiles for the nbk buckets of a batch: the beauty, then each requested AOV's
+// records, by the same kernel.  Splat modes (all bit-identical): 5 / 4 skewed time, 3 four tile
+// pixels per lane (power-of-two buckets); 1 / 0 one tile pixel per lane with the threshold / direct
+// filter-index arithmetic (any bucket size; 2 selects 1 since the compare-only one-pixel kernel
+// was retired).
+int launch_splat(nart_ctx* ctx, const SplatPlan& plan, const SplatArgs& sa, uint32_t nbk, hipStream_t st) {
+    const dim3 block(256);
+    if (plan.rows) {
+        ctx->sched |= NART_SCHED_SPLAT_ROWS;
+        const uint32_t U = sa.tile * (2 * sa.fb + 1), ub = std::max(1u, 512u / U);
+        const uint32_t threads = (ub * U + 63) / 64 * 64, nblk = (nbk + ub - 1) / ub;
+        const size_t lds = plan.lut_bytes + 2u * ub * sizeof(uint32_t);
+        if (sa.fb == 1) hipLaunchKernelGGL((k_splat_rows<1>), dim3(nblk), dim3(threads), lds, st, sa);
+        else if (sa.fb == 2) hipLaunchKernelGGL((k_splat_rows<2>), dim3(nblk), dim3(threads), lds, st, sa);
+        else hipLaunchKernelGGL((k_splat_rows<3>), dim3(nblk), dim3(threads), lds, st, sa);
+    } else if (plan.skew) {
+        ctx->sched |= NART_SCHED_SPLAT_SKEW;
+        const uint32_t nb = plan.bands;
+        const uint32_t pb = 64u / sa.tile, nblk = (nbk * nb + 4 * pb - 1) / (4 * pb);
+        const size_t lds = plan.lut_bytes + 8u * pb * sizeof(uint32_t);
+        const int fbk = (int)sa.fb * 2 + (int)nb - 1;
+        if (fbk == 2) hipLaunchKernelGGL((k_splat_skew<1, 1>), dim3(nblk), block, lds, st, sa);
+        else if (fbk == 3) hipLaunchKernelGGL((k_splat_skew<1, 2>), dim3(nblk), block, lds, st, sa);
+        else if (fbk == 4) hipLaunchKernelGGL((k_splat_skew<2, 1>), dim3(nblk), block, lds, st, sa);
+        else if (fbk == 5) hipLaunchKernelGGL((k_splat_skew<2, 2>), dim3(nblk), block, lds, st, sa);
+        else if (fbk == 6) hipLaunchKernelGGL((k_splat_skew<3, 1>), dim3(nblk), block, lds, st, sa);
+        else hipLaunchKernelGGL((k_splat_skew<3, 2>), dim3(nblk), block, lds, st, sa);
+    } else if (sa.thr && sa.invB != 0.f && plan.mode >= 3) {
+        const uint64_t n4 = (uint64_t)nbk * sa.tile * ((sa.tile + NART_SPLAT_NP - 1) / NART_SPLAT_NP);
+        const dim3 grid((uint32_t)((n4 + 255) / 256));
+        if (sa.lut) hipLaunchKernelGGL((k_splat_col4<NART_SPLAT_NP, true>), grid, block, 0, st, sa);
+        else hipLaunchKernelGGL((k_splat_col4<NART_SPLAT_NP, false>), grid, block, 0, st, sa);
+    } else {
+        const uint64_t nthreads = (uint64_t)nbk * sa.tile * sa.tile;
+        const dim3 grid((uint32_t)((nthreads + 255) / 256));
+        if (sa.thr && plan.mode >= 1) hipLaunchKernelGGL(k_splat<1>, grid, block, 0, st, sa);
+        else hipLaunchKernelGGL(k_splat<0>, grid, block, 0, st, sa);
+    }
+    HIPCHK(hipGetLastError());
+    return NART_OK;
+}
+
+// Render a bucket list into device tiles (list order); p is validated by the caller (check_params).
+// Shared by all entry points.  With `aov` each batch also splats the requested first-hit AOV records
+// (k_aov into ctx->d_L, which the beauty splat has consumed by then: no extra per-sample memory)
+// into the request's tiles.
+int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n, float* d_tiles,
+                   hipStream_t st, nart_render_stats* stats, AovRequest* aov = nullptr) {
+    int rc = NART_OK;
+    const bool beauty = !aov || aov->beauty;
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const uint32_t nb_total = g.n_buckets_x * g.n_buckets_y;
+    for (uint32_t i = 0; i < n; ++i)
+        if (ids[i] >= nb_total) return fail(ctx, NART_E_INVALID, "bucket id out of range");
+    SplatPlan plan;
+    if ((rc = plan_splat(ctx, p, g, n, plan))) return rc;
     const size_t n_cnt = 24;
     if (!ctx->d_counters) HIPCHK(hipMalloc(&ctx->d_counters, n_cnt * sizeof(unsigned long long)));
     if (ctx->counters) HIPCHK(hipMemsetAsync(ctx->d_counters, 0, n_cnt * sizeof(unsigned long long), st));
@@ -1402,9 +1550,9 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             if (!e) HIPCHK(hipEventCreate(&e));
     const size_t limit = batch_slot_limit(ctx, p->spp);
     const uint32_t tpx = g.tile_size * g.tile_size;
-    double kernel_ms = 0.0, splat_ms = 0.0, latin_ms = 0.0, primary_ms = 0.0;
-    uint32_t launches = 0;
-    uint64_t traced = 0, counted = 0;
+    nart_render_stats acc;  // this call's share, added to *stats at the end
+    std::memset(&acc, 0, sizeof(acc));
+    uint64_t counted = 0;
     uint32_t b0 = 0;
     ctx->sched = 0;
     std::vector<uint32_t> xy, base;
@@ -1430,30 +1578,15 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             ++b1;
         }
         const uint32_t nslots = (uint32_t)xy.size(), nbk = b1 - b0;
-        traced += (uint64_t)nslots * p->spp;
+        acc.traced_samples += (uint64_t)nslots * p->spp;
         rc = ensure(ctx, nslots, p->spp, nbk);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(ctx->d_slot_xy, xy.data(), (size_t)nslots * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ctx->d_bucket_ids, ids + b0, (size_t)nbk * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ctx->d_bucket_base, base.data(), (size_t)nbk * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_slot_table, dim3(nbk), dim3(256), 0, st, ctx->d_bucket_base, nbk, nslots, p->spp,
-                           ctx->d_slot_so, skew);
-        RenderArgs ra;
-        ra.slot_xy = ctx->d_slot_xy;
-        ra.slot_so = ctx->d_slot_so;
-        ra.samples = ctx->d_samples;
-        ra.rng0 = ctx->d_rng;
-        ra.Lout = ctx->d_L;
-        ra.n_slots = nslots;
-        ra.spp = p->spp;
-        ra.bounces = p->bounces;
-        ra.W = p->image_width;
-        ra.H = p->image_height;
-        ra.totalW = g.total_width;
-        ra.stack_depth = ctx->stack_depth;
-        ra.lds_nodes = 0;
-        ra.gamma = p->roughening_factor * p->roughening_factor;
-        ra.counters = ctx->d_counters;
+                           ctx->d_slot_so, plan.skew);
+        const RenderArgs ra = make_render_args(ctx, p, g, nslots, ctx->d_counters);
         HIPCHK(hipEventRecord(ctx->ev[3], st));
         rc = launch_latin(ctx, ra, st);
         if (rc) return rc;
@@ -1465,79 +1598,14 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             if (rc) return rc;
         }
         HIPCHK(hipEventRecord(ctx->ev[1], st));
-        SplatArgs sa;
+        SplatArgs sa = plan.sa;
         sa.bucket_ids = ctx->d_bucket_ids;
         sa.bucket_base = ctx->d_bucket_base;
         sa.samples = ctx->d_samples;
         sa.Lout = ctx->d_L;
         sa.tiles = beauty ? d_tiles + (size_t)b0 * tpx * 5 : nullptr;
-        sa.table = ctx->d_table;
-        sa.thr = thr_ok ? ctx->d_table + 64 : nullptr;
-        sa.idx_scale = 64.f / p->filter_width;
         sa.n_buckets = nbk;
-        sa.spp = p->spp;
-        sa.B = p->bucket_size;
-        sa.fb = g.filter_bounds;
-        sa.tile = g.tile_size;
-        sa.nbx = g.n_buckets_x;
-        sa.totalW = g.total_width;
-        sa.totalH = g.total_height;
-        sa.fw = p->filter_width;
-        sa.invB = (p->bucket_size & (p->bucket_size - 1)) == 0 ? 1.f / (float)p->bucket_size : 0.f;
-        sa.lut = lut_ok ? static_cast<const float4*>(ctx->d_lut) : nullptr;
-        sa.lut_b0 = lut_b0;
-        sa.lut_n = (uint32_t)lut.size();
-        {
-            int ex = 0;
-            float m = std::frexp(p->filter_width, &ex);
-            sa.invFw = (m == 0.5f) ? 1.f / p->filter_width : 0.f;
-        }
-        uint64_t nthreads = (uint64_t)nbk * tpx;
-        const dim3 sg((uint32_t)((nthreads + 255) / 256));
-#ifndef NART_SPLAT_NP
-#define NART_SPLAT_NP 4
-#endif
-        const uint64_t n4 = (uint64_t)nbk * g.tile_size * ((g.tile_size + NART_SPLAT_NP - 1) / NART_SPLAT_NP);
-        // splat modes (all bit-identical): 4 skewed time, 3 four tile pixels per lane (power-of-two
-        // buckets); 1 / 0 one tile pixel per lane with the threshold / direct filter-index arithmetic
-        // (any bucket size; 2 selects 1 since the compare-only one-pixel kernel was retired)
-        // sa.Lout into sa.tiles: the beauty, then each requested AOV's records, by the same kernel
-        auto splat = [&]() -> int {
-        if (rows) {
-            ctx->sched |= NART_SCHED_SPLAT_ROWS;
-            const uint32_t U = g.tile_size * (2 * g.filter_bounds + 1), ub = std::max(1u, 512u / U);
-            const uint32_t threads = (ub * U + 63) / 64 * 64, nblk = (nbk + ub - 1) / ub;
-            const size_t lds = lut.size() * sizeof(float4) + 2u * ub * sizeof(uint32_t);
-            if (g.filter_bounds == 1) hipLaunchKernelGGL((k_splat_rows<1>), dim3(nblk), dim3(threads), lds, st, sa);
-            else if (g.filter_bounds == 2) hipLaunchKernelGGL((k_splat_rows<2>), dim3(nblk), dim3(threads), lds, st, sa);
-            else hipLaunchKernelGGL((k_splat_rows<3>), dim3(nblk), dim3(threads), lds, st, sa);
-        } else if (skew) {
-            ctx->sched |= NART_SCHED_SPLAT_SKEW;
-            const uint32_t nb = skew_bands;  // tile-row bands per bucket (k_splat_skew's NB)
-            const uint32_t pb = 64u / g.tile_size, nblk = (nbk * nb + 4 * pb - 1) / (4 * pb);
-            const size_t lds = lut.size() * sizeof(float4) + 8u * pb * sizeof(uint32_t);
-            const int fbk = (int)g.filter_bounds * 2 + (int)nb - 1;
-            if (fbk == 2) hipLaunchKernelGGL((k_splat_skew<1, 1>), dim3(nblk), dim3(256), lds, st, sa);
-            else if (fbk == 3) hipLaunchKernelGGL((k_splat_skew<1, 2>), dim3(nblk), dim3(256), lds, st, sa);
-            else if (fbk == 4) hipLaunchKernelGGL((k_splat_skew<2, 1>), dim3(nblk), dim3(256), lds, st, sa);
-            else if (fbk == 5) hipLaunchKernelGGL((k_splat_skew<2, 2>), dim3(nblk), dim3(256), lds, st, sa);
-            else if (fbk == 6) hipLaunchKernelGGL((k_splat_skew<3, 1>), dim3(nblk), dim3(256), lds, st, sa);
-            else hipLaunchKernelGGL((k_splat_skew<3, 2>), dim3(nblk), dim3(256), lds, st, sa);
-        } else if (sa.thr && sa.invB != 0.f && splat_mode >= 3)
-        {
-            if (sa.lut)
-                hipLaunchKernelGGL((k_splat_col4<NART_SPLAT_NP, true>), dim3((uint32_t)((n4 + 255) / 256)), dim3(256), 0,
-                                   st, sa);
-            else
-                hipLaunchKernelGGL((k_splat_col4<NART_SPLAT_NP, false>), dim3((uint32_t)((n4 + 255) / 256)), dim3(256),
-                                   0, st, sa);
-        }
-        else if (sa.thr && splat_mode >= 1) hipLaunchKernelGGL(k_splat<1>, sg, dim3(256), 0, st, sa);
-        else hipLaunchKernelGGL(k_splat<0>, sg, dim3(256), 0, st, sa);
-        HIPCHK(hipGetLastError());
-        return NART_OK;
-        };
-        if (beauty && (rc = splat())) return rc;
+        if (beauty && (rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
         HIPCHK(hipEventRecord(ctx->ev[2], st));
         if (aov) {
             // the dispatch's own camera-ray hits where it traced them first, else k_primary now
@@ -1547,7 +1615,7 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
                 if (!aov->tiles[k]) continue;
                 if ((rc = launch_aov(ctx, ra, k, ctx->d_L, st))) return rc;
                 sa.tiles = aov->tiles[k] + (size_t)b0 * tpx * 5;
-                if ((rc = splat())) return rc;
+                if ((rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
             }
             HIPCHK(hipEventRecord(ctx->ev_aov[1], st));
             HIPCHK(hipEventSynchronize(ctx->ev_aov[1]));
@@ -1559,38 +1627,33 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             aov->ms += ms;
         }
         HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        kernel_ms += ms;
+        acc.kernel_ms += ms;
         if (ctx->primary_ran) {
             HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
-            primary_ms += ms;
+            acc.primary_ms += ms;
         }
         HIPCHK(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
-        splat_ms += ms;
+        acc.splat_ms += ms;
         HIPCHK(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[0]));
-        latin_ms += ms;
-        if (beauty) ++launches;
+        acc.latin_ms += ms;
+        if (beauty) ++acc.kernel_launches;
         b0 = b1;
     }
     if (stats) {
-        stats->kernel_ms += kernel_ms;
-        stats->splat_ms += splat_ms;
-        stats->latin_ms += latin_ms;
-        stats->primary_ms += primary_ms;
-        stats->kernel_launches += launches;
-        stats->schedule |= ctx->sched;
-        stats->traced_samples += traced;
-        stats->samples += counted * p->spp;
+        acc.schedule = ctx->sched;
+        acc.samples = counted * p->spp;
         if (ctx->counters) {
             unsigned long long c[8];
             HIPCHK(hipMemcpy(c, ctx->d_counters, sizeof(c), hipMemcpyDeviceToHost));
-            stats->rays_extend += c[0];
-            stats->rays_shadow += c[1];
-            stats->node_visits += c[2];
-            stats->tri_tests += c[3];
-            stats->bounces += c[4];
-            stats->octree_checks += c[5];
-            stats->octree_replays += c[6];
+            acc.rays_extend = c[0];
+            acc.rays_shadow = c[1];
+            acc.node_visits = c[2];
+            acc.tri_tests = c[3];
+            acc.bounces = c[4];
+            acc.octree_checks = c[5];
+            acc.octree_replays = c[6];
         }
+        add_stats(*stats, acc, Times::Sum);
     }
     return NART_OK;
 }
@@ -1706,11 +1769,133 @@ int build_bvh_device(nart_ctx* ctx, const nart_scene_blob& blob, const std::vect
     return cleanup(NART_OK);
 }
 
+// ---------------------------------------------------------------- whole frames
+// What a whole-frame render produces, where it goes and whose buffers it uses (render_frame).
+// Buffer k: 0 the beauty, 1 + a first-hit AOV a (AOV_ALBEDO, AOV_NORMAL).
+struct FrameRequest {
+    bool beauty = true;            // false: an AOV-only frame, which launches no path kernel
+    bool aov[2] = {false, false};
+    // Delivery: the image of buffer k to the host at dst[k]; or on_device, the images of the
+    // requested buffers back to back, in buffer order, from the start of *image on device 0
+    // (ordered on its null stream: single-device frames do not wait for them).
+    nart_pixel* dst[3] = {nullptr, nullptr, nullptr};
+    bool on_device = false;
+    // The call's tile and image buffers.  image null: temporaries, allocated by the call and freed on
+    // every return path.  Else borrowed from a context, which keeps them for its next call (the
+    // memory a context holds between calls sets batch_slot_limit): the image buffer *image of
+    // capacity *image_cap on device 0, grown to max(images, buffers requested) images; tiles in
+    // d_gather.  A multi-device context always gathers and combines in its own cached buffers.
+    void** image = nullptr;
+    size_t* image_cap = nullptr;
+    uint32_t images = 0;
+
+    bool wants(int k) const { return k == 0 ? beauty : aov[k - 1]; }
+    bool wants_aovs() const { return aov[0] || aov[1]; }
+};
+
+// Temporaries of one call, freed when it returns.
+struct ScopedDeviceBufs {
+    void* p[2] = {nullptr, nullptr};
+    ScopedDeviceBufs() = default;
+    ScopedDeviceBufs(const ScopedDeviceBufs&) = delete;
+    ~ScopedDeviceBufs() {
+        for (void* b : p)
+            if (b) hipFree(b);
+    }
+};
+
+// The buffers a context keeps for whole frames (render_frame, render_multi) and the denoiser.
+void free_frame_buffers(nart_ctx* ctx) {
+    for (void* b : {ctx->d_gather, ctx->d_byid, ctx->d_image, ctx->d_slab_map, ctx->d_dn, ctx->d_dn_img})
+        if (b) hipFree(b);
+}
+
 }  // namespace
 
 #include "host/multi_gpu.h"
 
 namespace {
+
+// Render(): every bucket of the session, combined in bucket raster order, delivered as the request
+// says.  The one whole-frame path behind nart_hip_render, _render_aovs, _render_device and
+// _render_denoised.  Errors of a multi-device context's sub-contexts are re-raised on ctx.
+int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest& rq, nart_render_stats* stats,
+                 double* aov_ms) {
+    RenderTimer timer(stats);
+    if (aov_ms) *aov_ms = 0.0;
+    nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // device 0: combines, holds the images
+    int rc = NART_OK;
+    if (rq.wants_aovs() && (rc = check_first_hit(ctx, p))) return rc;
+    if (ctx->rccl_broken)
+        return fail(ctx, NART_E_RCCL, "an earlier RCCL gather of this context failed; destroy it and create a new one");
+    if ((rc = check_params(c0, p))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const uint32_t nb = g.n_buckets_x * g.n_buckets_y;
+    const size_t tile_floats = (size_t)nb * g.tile_size * g.tile_size * 5;
+    const size_t img_floats = (size_t)g.total_width * g.total_height * 5;
+    size_t K = 0;  // buffers requested
+    for (int k = 0; k < 3; ++k) K += rq.wants(k);
+    if (rq.image && (rc = ensure_dev(ctx, c0->device, *rq.image, *rq.image_cap,
+                                     std::max<size_t>(K, rq.images) * img_floats * sizeof(float), "image")))
+        return rc;
+    if (c0 != ctx) return render_multi(ctx, p, rq, stats, aov_ms);
+
+    HIPCHK(hipSetDevice(ctx->device));
+    // tile buffers back to back: the beauty (if any), then the requested AOVs; one image to combine
+    // into on the way to the host, or the borrowed images
+    ScopedDeviceBufs own;
+    void*& d_tiles = rq.image ? ctx->d_gather : own.p[0];
+    void*& d_img = rq.image ? *rq.image : own.p[1];
+    const size_t tile_bytes = K * tile_floats * sizeof(float);
+    if (rq.image) rc = ensure_dev(ctx, ctx->device, ctx->d_gather, ctx->cap_gather, tile_bytes, "tiles");
+    else if (!(rc = dmalloc(ctx, &d_tiles, tile_bytes, "tiles")))
+        rc = dmalloc(ctx, &d_img, img_floats * sizeof(float), "image");
+    if (rc) return rc;
+    float* tiles[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0, i = 0; k < 3; ++k)
+        if (rq.wants(k)) tiles[k] = static_cast<float*>(d_tiles) + (size_t)(i++) * tile_floats;
+    std::vector<uint32_t> ids(nb);
+    for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
+    AovRequest areq;
+    areq.beauty = rq.beauty;
+    areq.tiles[0] = tiles[1];
+    areq.tiles[1] = tiles[2];
+    rc = render_buckets(ctx, p, ids.data(), nb, tiles[0], 0, stats, rq.wants_aovs() ? &areq : nullptr);
+    if (aov_ms) *aov_ms = areq.ms;
+    for (int k = 0, i = 0; k < 3 && !rc; ++k) {
+        if (!rq.wants(k)) continue;
+        float* img = static_cast<float*>(d_img) + (rq.on_device ? (size_t)(i++) * img_floats : 0);
+        rc = nart_hip_combine_async(ctx, p, reinterpret_cast<const nart_pixel*>(tiles[k]),
+                                    reinterpret_cast<nart_pixel*>(img), 0);
+        if (rc || rq.on_device) continue;
+        if (hipMemcpy(rq.dst[k], img, img_floats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(ctx, NART_E_HIP, "copy image");
+    }
+    return rc;
+}
+
+// Slots of the per-sample entry points: one per pixel of a rect in total-image coordinates, row by
+// row, each pixel's samples a row of their own (k_slot_rows), on the null stream.  p is validated
+// by the caller.  An empty rect gives no slots: what then is the caller's to say.
+int rect_slots(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+               unsigned long long* counters, RenderArgs& ra) {
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    // in 64 bits: x0 + w may wrap in 32
+    if ((uint64_t)x0 + w > g.total_width || (uint64_t)y0 + h > g.total_height)
+        return fail(ctx, NART_E_INVALID, "rect out of range");
+    std::vector<uint32_t> xy;
+    for (uint32_t y = y0; y < y0 + h; ++y)
+        for (uint32_t x = x0; x < x0 + w; ++x) xy.push_back(x | (y << 16));
+    const uint32_t n = (uint32_t)xy.size();
+    if (int rc = ensure(ctx, n, p->spp, 1)) return rc;
+    HIPCHK(hipMemcpy(ctx->d_slot_xy, xy.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_slot_rows, dim3((n + 255) / 256), dim3(256), 0, 0, n, p->spp, ctx->d_slot_so);
+    ra = make_render_args(ctx, p, g, n, counters);
+    return NART_OK;
+}
 
 // ---------------------------------------------------------------- denoiser (device/denoise.h)
 void denoise_defaults(nart_denoise_params* dp) {
@@ -2052,8 +2237,7 @@ void nart_hip_destroy(nart_ctx* ctx) {
             if (d < ctx->streams.size() && ctx->streams[d]) hipStreamDestroy(ctx->streams[d]);
         }
         hipSetDevice(ctx->devs[0]);
-        for (void* b : {ctx->d_gather, ctx->d_byid, ctx->d_image, ctx->d_slab_map})
-            if (b) hipFree(b);
+        free_frame_buffers(ctx);
         for (nart_ctx* c : ctx->subs) nart_hip_destroy(c);
         delete ctx;
         return;
@@ -2067,10 +2251,7 @@ void nart_hip_destroy(nart_ctx* ctx) {
                     ctx->d_qhead, ctx->d_sort_tmp, ctx->d_ilist, ctx->d_gstack};
     for (void* b : bufs)
         if (b) hipFree(b);
-    for (void* b : {ctx->d_gather, ctx->d_image})  // nart_hip_render_device's tiles and image
-        if (b) hipFree(b);
-    for (void* b : {ctx->d_dn, ctx->d_dn_img})
-        if (b) hipFree(b);
+    free_frame_buffers(ctx);
     for (auto& e : ctx->ev_dn)
         if (e) hipEventDestroy(e);
     for (void* b : ctx->env_bufs) hipFree(b);
@@ -2144,10 +2325,9 @@ int nart_hip_render_buckets_async(nart_ctx* ctx, const nart_render_params* p, co
     if (!ctx || !bucket_ids || !d_tiles) return NART_E_INVALID;
     if (!ctx->subs.empty())
         return fail(ctx, NART_E_UNSUPPORTED, "render_buckets_async takes a single-device context (one per rank)");
-    auto t0 = std::chrono::steady_clock::now();
-    int rc = render_buckets(ctx, p, bucket_ids, n_buckets, reinterpret_cast<float*>(d_tiles), (hipStream_t)stream, stats);
-    if (stats) stats->render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    RenderTimer timer(stats);
+    if (int rc = check_params(ctx, p)) return rc;
+    return render_buckets(ctx, p, bucket_ids, n_buckets, reinterpret_cast<float*>(d_tiles), (hipStream_t)stream, stats);
 }
 
 int nart_hip_combine_async(nart_ctx* ctx, const nart_render_params* p, const nart_pixel* d_tiles, nart_pixel* d_image,
@@ -2177,36 +2357,9 @@ int nart_hip_combine_async(nart_ctx* ctx, const nart_render_params* p, const nar
 
 int nart_hip_render(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, nart_render_stats* stats) {
     if (!ctx || !p || !image) return NART_E_INVALID;
-    auto t0 = std::chrono::steady_clock::now();
-    if (!ctx->subs.empty()) {
-        const int rc = render_multi(ctx, p, image, stats);
-        if (stats) stats->render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return rc;
-    }
-    int rc = check_params(ctx, p);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const uint32_t nb = g.n_buckets_x * g.n_buckets_y;
-    std::vector<uint32_t> ids(nb);
-    for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
-    size_t tile_bytes = (size_t)nb * g.tile_size * g.tile_size * sizeof(nart_pixel);
-    size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
-    void *d_tiles = nullptr, *d_img = nullptr;
-    HIPCHK(hipMalloc(&d_tiles, tile_bytes));
-    if (hipMalloc(&d_img, img_bytes) != hipSuccess) {
-        hipFree(d_tiles);
-        return fail(ctx, NART_E_OOM, "hipMalloc image");
-    }
-    rc = render_buckets(ctx, p, ids.data(), nb, (float*)d_tiles, 0, stats);
-    if (!rc) rc = nart_hip_combine_async(ctx, p, (const nart_pixel*)d_tiles, (nart_pixel*)d_img, 0);
-    if (!rc && hipMemcpy(image, d_img, img_bytes, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(ctx, NART_E_HIP, "copy image");
-    hipFree(d_tiles);
-    hipFree(d_img);
-    if (stats) stats->render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    FrameRequest rq;
+    rq.dst[0] = image;
+    return render_frame(ctx, p, rq, stats, nullptr);
 }
 
 int nart_hip_render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_pixel* image,
@@ -2217,55 +2370,14 @@ int nart_hip_render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t ao
         return fail(ctx, NART_E_INVALID, "an AOV is requested without its image buffer");
     if (!aovs && !image) return fail(ctx, NART_E_INVALID, "neither the beauty nor an AOV is requested");
     if (!aovs) return nart_hip_render(ctx, p, image, stats);
-    if (p->integrator == NART_INTEGRATOR_VOLUME)
-        return fail(ctx, NART_E_UNSUPPORTED, "first-hit AOVs need surfaces: the volume integrator has none");
-    nart_pixel* const aimg[2] = {(aovs & NART_AOV_ALBEDO) ? albedo : nullptr, (aovs & NART_AOV_NORMAL) ? normal : nullptr};
-    if (aov_ms) *aov_ms = 0.0;
-    auto t0 = std::chrono::steady_clock::now();
-    auto done = [&](int rc) {
-        if (stats) stats->render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return rc;
-    };
-    if (!ctx->subs.empty()) return done(render_multi(ctx, p, image, stats, aimg, image != nullptr, aov_ms));
-    int rc = check_params(ctx, p);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const uint32_t nb = g.n_buckets_x * g.n_buckets_y;
-    std::vector<uint32_t> ids(nb);
-    for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
-    // tile buffers back to back: the beauty (if any), then the requested AOVs
-    const size_t tile_floats = (size_t)nb * g.tile_size * g.tile_size * 5;
-    const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
-    nart_pixel* dst[3] = {image, aimg[0], aimg[1]};
-    float* tiles[3] = {nullptr, nullptr, nullptr};
-    size_t nbuf = 0;
-    for (int k = 0; k < 3; ++k)
-        if (dst[k]) ++nbuf;
-    void *d_tiles = nullptr, *d_img = nullptr;
-    if ((rc = dmalloc(ctx, &d_tiles, nbuf * tile_floats * sizeof(float), "tiles"))) return rc;
-    if ((rc = dmalloc(ctx, &d_img, img_bytes, "image"))) {
-        hipFree(d_tiles);
-        return rc;
-    }
-    for (int k = 0, i = 0; k < 3; ++k)
-        if (dst[k]) tiles[k] = static_cast<float*>(d_tiles) + (size_t)(i++) * tile_floats;
-    AovRequest rq;
+    FrameRequest rq;
     rq.beauty = image != nullptr;
-    rq.tiles[0] = tiles[1];
-    rq.tiles[1] = tiles[2];
-    rc = render_buckets(ctx, p, ids.data(), nb, tiles[0], 0, stats, &rq);
-    for (int k = 0; k < 3 && !rc; ++k) {
-        if (!dst[k]) continue;
-        rc = nart_hip_combine_async(ctx, p, reinterpret_cast<const nart_pixel*>(tiles[k]), (nart_pixel*)d_img, 0);
-        if (!rc && hipMemcpy(dst[k], d_img, img_bytes, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(ctx, NART_E_HIP, "copy image");
-    }
-    hipFree(d_tiles);
-    hipFree(d_img);
-    if (aov_ms) *aov_ms = rq.ms;
-    return done(rc);
+    rq.aov[AOV_ALBEDO] = (aovs & NART_AOV_ALBEDO) != 0;
+    rq.aov[AOV_NORMAL] = (aovs & NART_AOV_NORMAL) != 0;
+    rq.dst[0] = image;
+    rq.dst[1 + AOV_ALBEDO] = albedo;
+    rq.dst[1 + AOV_NORMAL] = normal;
+    return render_frame(ctx, p, rq, stats, aov_ms);
 }
 
 int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w,
@@ -2276,40 +2388,13 @@ int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint
         return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
     }
     int rc = check_params(ctx, p);
-    if (rc) return rc;
-    if (p->integrator == NART_INTEGRATOR_VOLUME)
-        return fail(ctx, NART_E_UNSUPPORTED, "first-hit AOVs need surfaces: the volume integrator has none");
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    if ((uint64_t)x0 + w > g.total_width || (uint64_t)y0 + h > g.total_height || !w || !h)
-        return fail(ctx, NART_E_INVALID, "rect out of range");
-    std::vector<uint32_t> xy;
-    for (uint32_t y = y0; y < y0 + h; ++y)
-        for (uint32_t x = x0; x < x0 + w; ++x) xy.push_back(x | (y << 16));
-    const uint32_t n = (uint32_t)xy.size();
-    rc = ensure(ctx, n, p->spp, 1);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(ctx->d_slot_xy, xy.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_slot_rows, dim3((n + 255) / 256), dim3(256), 0, 0, n, p->spp, ctx->d_slot_so);
+    if (rc || (rc = check_first_hit(ctx, p))) return rc;
+    if (!w || !h) return fail(ctx, NART_E_INVALID, "empty rect");  // (nart_hip_render_samples launches over it)
     RenderArgs ra;
-    ra.slot_xy = ctx->d_slot_xy;
-    ra.slot_so = ctx->d_slot_so;
-    ra.samples = ctx->d_samples;
-    ra.rng0 = ctx->d_rng;
-    ra.Lout = ctx->d_L;
-    ra.n_slots = n;
-    ra.spp = p->spp;
-    ra.bounces = p->bounces;
-    ra.W = p->image_width;
-    ra.H = p->image_height;
-    ra.totalW = g.total_width;
-    ra.stack_depth = ctx->stack_depth;
-    ra.lds_nodes = 0;
-    ra.gamma = p->roughening_factor * p->roughening_factor;
-    ra.counters = nullptr;  // k_primary<false, ...> and k_aov count nothing
+    // k_primary<false, ...> and k_aov count nothing
+    if ((rc = rect_slots(ctx, p, x0, y0, w, h, nullptr, ra))) return rc;
     if ((rc = launch_latin(ctx, ra, 0)) || (rc = launch_aov_primary(ctx, ra, 0))) return rc;
-    const size_t ns = (size_t)n * p->spp;
+    const size_t ns = (size_t)ra.n_slots * p->spp;
     std::vector<float> rec(ns * 4);
     for (int k = 0; k < 2; ++k) {
         if ((rc = launch_aov(ctx, ra, k, ctx->d_L, 0))) return rc;
@@ -2355,46 +2440,27 @@ int nart_hip_render_denoised(nart_ctx* ctx, const nart_render_params* p, const n
     nart_denoise_params d;
     int rc = check_denoise(ctx, dp, d);
     if (rc) return rc;
-    if (p->integrator == NART_INTEGRATOR_VOLUME)
-        return fail(ctx, NART_E_UNSUPPORTED, "the denoiser needs first-hit AOVs: the volume integrator has none");
-    auto t0 = std::chrono::steady_clock::now();
     nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // the context that denoises
-    if ((rc = check_params(c0, p))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
+    // beauty and both AOVs into the first three of its four device images: nothing passes the host
+    FrameRequest rq;
+    rq.aov[AOV_ALBEDO] = rq.aov[AOV_NORMAL] = true;
+    rq.on_device = true;
+    rq.image = &c0->d_dn_img;
+    rq.image_cap = &c0->cap_dn_img;
+    rq.images = 4;
+    if ((rc = render_frame(ctx, p, rq, stats, nullptr))) return rc;
+    RenderTimer timer(stats);  // render_ms covers the whole call
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
     const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
     float* img[4];
-    if ((rc = denoise_images(c0, g, img))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
-    if (c0 != ctx) {
-        nart_pixel* const aimg[2] = {reinterpret_cast<nart_pixel*>(img[1]), reinterpret_cast<nart_pixel*>(img[2])};
-        rc = render_multi(ctx, p, reinterpret_cast<nart_pixel*>(img[0]), stats, aimg, true, nullptr, true);
-    } else {
-        HIPCHK(hipSetDevice(ctx->device));
-        const uint32_t nb = g.n_buckets_x * g.n_buckets_y;
-        std::vector<uint32_t> ids(nb);
-        for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
-        // tile buffers back to back: the beauty, then the two AOVs
-        const size_t tile_floats = (size_t)nb * g.tile_size * g.tile_size * 5;
-        if ((rc = ensure_dev(ctx, ctx->device, ctx->d_gather, ctx->cap_gather, 3 * tile_floats * sizeof(float), "tiles")))
-            return rc;
-        float* tiles = static_cast<float*>(ctx->d_gather);
-        AovRequest rq;
-        rq.tiles[0] = tiles + tile_floats;
-        rq.tiles[1] = tiles + 2 * tile_floats;
-        rc = render_buckets(ctx, p, ids.data(), nb, tiles, 0, stats, &rq);
-        for (int k = 0; k < 3 && !rc; ++k)
-            rc = nart_hip_combine_async(ctx, p, reinterpret_cast<const nart_pixel*>(tiles + (size_t)k * tile_floats),
-                                        reinterpret_cast<nart_pixel*>(img[k]), 0);
-    }
-    if (!rc && (rc = denoise_device(c0, p, d, img[0], img[1], img[2], img[3], 0, denoise_ms)) && c0 != ctx)
-        fail(ctx, rc, c0->err);
-    if (!rc) {
-        HIPCHK(hipSetDevice(c0->device));
-        if (image) HIPCHK(hipMemcpy(image, img[0], img_bytes, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out, img[3], img_bytes, hipMemcpyDeviceToHost));
-    }
-    if (stats) stats->render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    if ((rc = denoise_images(c0, g, img)) ||  // (sized by the frame: this lays them out)
+        (rc = denoise_device(c0, p, d, img[0], img[1], img[2], img[3], 0, denoise_ms)))
+        return c0 == ctx ? rc : fail(ctx, rc, c0->err);
+    HIPCHK(hipSetDevice(c0->device));
+    if (image) HIPCHK(hipMemcpy(image, img[0], img_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, img[3], img_bytes, hipMemcpyDeviceToHost));
+    return NART_OK;
 }
 
 int nart_hip_denoise_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
@@ -2412,32 +2478,18 @@ int nart_hip_denoise_timings(const nart_ctx* ctx, double* prepare_ms, double* va
 int nart_hip_render_device(nart_ctx* ctx, const nart_render_params* p, const nart_pixel** d_image,
                            nart_render_stats* stats) {
     if (!ctx || !p || !d_image) return NART_E_INVALID;
-    auto t0 = std::chrono::steady_clock::now();
-    int rc = NART_OK;
-    if (!ctx->subs.empty()) {
-        rc = render_multi(ctx, p, nullptr, stats);  // tiles gathered to device 0, combined there
-        if (!rc) *d_image = static_cast<const nart_pixel*>(ctx->d_image);
-    } else {
-        if ((rc = check_params(ctx, p))) return rc;
-        HIPCHK(hipSetDevice(ctx->device));
-        nart_session_geometry g;
-        nart_session_geometry_of(p, &g);
-        const uint32_t nb = g.n_buckets_x * g.n_buckets_y;
-        std::vector<uint32_t> ids(nb);
-        for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
-        const size_t tile_bytes = (size_t)nb * g.tile_size * g.tile_size * sizeof(nart_pixel);
-        const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
-        if ((rc = ensure_dev(ctx, ctx->device, ctx->d_gather, ctx->cap_gather, tile_bytes, "tiles")) ||
-            (rc = ensure_dev(ctx, ctx->device, ctx->d_image, ctx->cap_image, img_bytes, "image")))
-            return rc;
-        rc = render_buckets(ctx, p, ids.data(), nb, static_cast<float*>(ctx->d_gather), 0, stats);
-        if (!rc) rc = nart_hip_combine_async(ctx, p, static_cast<const nart_pixel*>(ctx->d_gather),
-                                            static_cast<nart_pixel*>(ctx->d_image), 0);
-        if (!rc && hipStreamSynchronize(0) != hipSuccess) rc = fail(ctx, NART_E_HIP, "render");
-        if (!rc) *d_image = static_cast<const nart_pixel*>(ctx->d_image);
+    // tiles gathered to device 0 and combined there (a multi-device context), into the context's image
+    FrameRequest rq;
+    rq.on_device = true;
+    rq.image = &ctx->d_image;
+    rq.image_cap = &ctx->cap_image;
+    if (int rc = render_frame(ctx, p, rq, stats, nullptr)) return rc;
+    if (ctx->subs.empty()) {  // (a multi-device frame has waited for its gather stream)
+        RenderTimer timer(stats);
+        if (hipStreamSynchronize(0) != hipSuccess) return fail(ctx, NART_E_HIP, "render");
     }
-    if (stats) stats->render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    *d_image = static_cast<const nart_pixel*>(ctx->d_image);
+    return NART_OK;
 }
 
 int nart_hip_render_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w,
@@ -2450,43 +2502,13 @@ int nart_hip_render_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t
     int rc = check_params(ctx, p);
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    if (x0 + w > g.total_width || y0 + h > g.total_height) return fail(ctx, NART_E_INVALID, "rect out of range");
-    std::vector<uint32_t> xy;
-    for (uint32_t y = y0; y < y0 + h; ++y)
-        for (uint32_t x = x0; x < x0 + w; ++x) xy.push_back(x | (y << 16));
-    uint32_t n = (uint32_t)xy.size();
-    rc = ensure(ctx, n, p->spp, 1);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(ctx->d_slot_xy, xy.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_slot_rows, dim3((n + 255) / 256), dim3(256), 0, 0, n, p->spp, ctx->d_slot_so);
     const size_t n_cnt = 24;
     if (!ctx->d_counters) HIPCHK(hipMalloc(&ctx->d_counters, n_cnt * sizeof(unsigned long long)));
     if (ctx->counters) HIPCHK(hipMemset(ctx->d_counters, 0, n_cnt * sizeof(unsigned long long)));
     RenderArgs ra;
-    ra.slot_xy = ctx->d_slot_xy;
-    ra.slot_so = ctx->d_slot_so;
-    ra.samples = ctx->d_samples;
-    ra.rng0 = ctx->d_rng;
-    ra.Lout = ctx->d_L;
-    ra.n_slots = n;
-    ra.spp = p->spp;
-    ra.bounces = p->bounces;
-    ra.W = p->image_width;
-    ra.H = p->image_height;
-    ra.totalW = g.total_width;
-    ra.stack_depth = ctx->stack_depth;
-    ra.lds_nodes = 0;
-    ra.gamma = p->roughening_factor * p->roughening_factor;
-    ra.counters = ctx->d_counters;
-    rc = launch_latin(ctx, ra, 0);
-    if (rc) return rc;
-    {
-        rc = dispatch_render(ctx, ra, p->integrator, 0);
-        if (rc) return rc;
-    }
-    HIPCHK(hipMemcpy(out, ctx->d_L, (size_t)n * p->spp * sizeof(float4), hipMemcpyDeviceToHost));
+    if ((rc = rect_slots(ctx, p, x0, y0, w, h, ctx->d_counters, ra))) return rc;
+    if ((rc = launch_latin(ctx, ra, 0)) || (rc = dispatch_render(ctx, ra, p->integrator, 0))) return rc;
+    HIPCHK(hipMemcpy(out, ctx->d_L, (size_t)ra.n_slots * p->spp * sizeof(float4), hipMemcpyDeviceToHost));
     return NART_OK;
 }
 
