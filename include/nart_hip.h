@@ -143,6 +143,35 @@ int nart_hip_render(nart_ctx* ctx, const nart_render_params* p, nart_pixel* imag
 int nart_hip_render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_pixel* image,
                          nart_pixel* albedo, nart_pixel* normal, nart_render_stats* stats, double* aov_ms);
 
+/* Second-moment image (no reference counterpart): how noisy each pixel is, from the renderer's own
+   samples.  A nart_pixel image of totalW*totalH.  For every tile pixel it accumulates, over the
+   samples AddSample (render.cpp:23-70) adds to that pixel and in AddSample's order (source pixel
+   raster, then sample index), with w the filter weight the beauty's splat uses for that (sample,
+   pixel) pair and (r, g, b, a) the sample's Li_alpha:
+       contribution      = { sum (r*r)*w, sum (g*g)*w, sum (b*b)*w, sum w*w }
+       filter_weight_sum =   sum w
+   every product and sum one float32 operation in the order written, nothing contracted; tiles are
+   combined in bucket raster order as every other image is.  filter_weight_sum therefore has the
+   beauty's bits, contribution.rgb / filter_weight_sum is the filtered second moment of the radiance,
+   and contribution.a / filter_weight_sum^2 is 1 / the effective sample count of the pixel.  It needs
+   no surfaces, so it also works for the volume integrator.
+
+   On the device the pass runs after the beauty's splat has consumed the batch's Li_alpha records:
+   k_moment squares their colour channels in place (no extra per-sample memory), and the beauty's
+   splat kernel runs once more, built with a flag that makes the fourth accumulator add w*w where
+   it otherwise adds a*w -- one more pass over the samples.  A render that does not ask for the
+   moment image launches exactly what it launched before.
+
+   nart_hip_render_moment: as nart_hip_render_aovs, with aovs allowed to be 0, plus the moment image
+   (required).  The moment image needs the path kernel: image may be null, and the path kernel and
+   the beauty's splat still run.  moment_ms, if non-null, receives the device time of k_moment plus
+   the moment splat.  The beauty and the AOVs have the bits nart_hip_render / nart_hip_render_aovs
+   give.  NART_E_INVALID: as nart_hip_render_aovs, or a null moment; NART_E_UNSUPPORTED: an AOV bit
+   with the volume integrator.  Multi-device contexts gather the moment tiles with the beauty's. */
+int nart_hip_render_moment(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_pixel* image,
+                           nart_pixel* albedo, nart_pixel* normal, nart_pixel* moment, nart_render_stats* stats,
+                           double* aov_ms, double* moment_ms);
+
 /* Debug / parity, as nart_hip_render_samples: the per-sample AOV records of pixels [x0,x0+w) x
    [y0,y0+h) in total-image coordinates (extra rows included) into host
    out8[((y-y0)*w + (x-x0))*spp + s][8] = albedo record then normal record; tri (optional) receives
@@ -187,6 +216,19 @@ int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint
    Variance (k_dn_variance), 7x7, dy outer and dx inner, both ascending:
        u = w_n * f(d_g);  su += u, sl += u * l_q, sl2 += u * (l_q * l_q)
        m1 = sl / su, m2 = sl2 / su, v = max(0, m2 - m1 * m1)
+   Sample variance (nart_hip_denoise_moment, nart_hip_render_denoised_moment; k_dn_prepare<true>): the
+   variance comes from the second-moment image instead, and k_dn_variance does not run.  Prepare
+   computes everything above, and for a valid pixel, with M the moment pixel (contribution rgba,
+   filter_weight_sum mw), c and a_d as above:
+       if mw > 0:  k = M.a / (mw * mw)                          (1 / the effective sample count)
+                   per channel ch: m2 = M.ch / mw, var = max(0, m2 - c.ch * c.ch), V.ch = var * k
+       else:       V = 0
+       sd = (0.2126 * (sqrt(V.r) / a_d.r) + 0.7152 * (sqrt(V.g) / a_d.g)) + 0.0722 * (sqrt(V.b) / a_d.b)
+       v  = sd * sd;  v = v < 1e30 ? v : 1e30                   (NaN and overflow become 1e30)
+   V is the variance of the filtered mean per channel; no Bessel correction is applied (it is low by
+   the factor 1 - k).  The channel sum takes the three channels' noise as fully correlated: the
+   conservative bound, and what one light path hitting or missing produces.  An invalid pixel keeps
+   v = -1 as above; the passes and finalise consume v as they do in the spatial mode.
    A-trous pass i = 0 .. iterations-1 (k_dn_atrous), step = 2^i, taps (dx, dy) = (ix, iy) * step for
    ix, iy in -2..2, iy outer, h = [1/16, 1/4, 3/8, 1/4, 1/16]:
        vb  = sum over dy, dx in -1..1 (dy outer, coordinates clamped to the image) of
@@ -222,6 +264,14 @@ int nart_hip_denoise(nart_ctx* ctx, const nart_render_params* p, const nart_deno
                      const nart_pixel* beauty, const nart_pixel* albedo, const nart_pixel* normal, nart_pixel* out,
                      double* denoise_ms);
 
+/* As nart_hip_denoise with the variance taken from moment, a second-moment image as
+   nart_hip_render_moment returns it ("Sample variance" above); nart_hip_denoise_timings then reports
+   variance_ms 0.  NART_E_INVALID additionally for a null moment or p->spp < 2 (one sample has no
+   variance). */
+int nart_hip_denoise_moment(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                            const nart_pixel* beauty, const nart_pixel* albedo, const nart_pixel* normal,
+                            const nart_pixel* moment, nart_pixel* out, double* denoise_ms);
+
 /* Render the beauty and both first-hit AOVs and denoise them on the device: the three images never
    pass through the host.  out receives the denoised image; image, if non-null, the noisy beauty,
    bit-identical to nart_hip_render's.  Multi-device contexts denoise on their first device after
@@ -230,6 +280,12 @@ int nart_hip_denoise(nart_ctx* ctx, const nart_render_params* p, const nart_deno
    before. */
 int nart_hip_render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
                              nart_pixel* image, nart_pixel* out, nart_render_stats* stats, double* denoise_ms);
+
+/* As nart_hip_render_denoised in the sample-variance mode: renders the beauty, both AOVs and the
+   second-moment image and denoises on the device, nothing passing through the host.  Errors as
+   nart_hip_render_denoised, plus NART_E_INVALID for p->spp < 2. */
+int nart_hip_render_denoised_moment(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                                    nart_pixel* image, nart_pixel* out, nart_render_stats* stats, double* denoise_ms);
 
 /* Device times (ms) of the last denoise of this context, kernel by kernel: prepare, variance, the
    a-trous passes (pass_ms[8], zero beyond the iterations run) and finalise.  Any pointer may be null. */

@@ -165,11 +165,18 @@ _HIP_SIGS = {
     "nart_hip_render": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), _P, ctypes.POINTER(RenderStats)]),
     "nart_hip_render_aovs": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, _P, _P, _P,
                                             ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_moment": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, _P, _P, _P, _P,
+                                              ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_aov_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, ctypes.c_uint32,
                                                    ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "nart_hip_denoise_params_init": (None, [ctypes.POINTER(DenoiseParams)]),
     "nart_hip_denoise": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams), _P, _P, _P, _P,
                                         ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_denoise_moment": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams), _P, _P, _P,
+                                               _P, _P, ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_denoised_moment": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams), _P,
+                                                       _P, ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_denoised": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams), _P, _P,
                                                 ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_denoise_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -515,24 +522,36 @@ class HipRenderer:
         self._check(self._lib.nart_hip_render(self._ctx, ctypes.byref(p), img.ctypes.data, ctypes.byref(st)))
         return img
 
-    def render_aovs(self, p, albedo=True, normal=True, beauty=True, stats=None):
+    def render_aovs(self, p, albedo=True, normal=True, beauty=True, stats=None, moment=False):
         """First-hit AOVs (nart_hip_render_aovs): a dict with (totalH, totalW, 5) float32 images under
         "albedo" ({albedo.rgb, coverage}), "normal" ({shading normal.xyz, depth}: a filtered average,
         not renormalised) and "beauty" (bit-identical to render()), each only if requested, plus
         "aov_ms", the device time of the AOV kernels.  finalize() of an image is the filtered AOV.
-        beauty=False renders the AOVs alone (no path kernel)."""
+        beauty=False renders the AOVs alone (no path kernel).
+        moment=True (nart_hip_render_moment) adds "moment", the second-moment image ({sum r^2 w,
+        sum g^2 w, sum b^2 w, sum w^2} and the beauty's filter weight sum; sample_variance() turns it
+        into a variance), and "moment_ms", the device time of its pass.  It needs the path kernel, so
+        with beauty=False it is NART_E_INVALID; albedo and normal may both be False."""
+        if moment and not beauty:
+            raise NartError(-1, "the moment image needs the path kernel: beauty=False cannot be combined with moment=True")
         g = session_geometry(p)
         shape = (g.total_height, g.total_width, PIXEL_FLOATS)
         out = {}
-        for name, want in (("beauty", beauty), ("albedo", albedo), ("normal", normal)):
+        for name, want in (("beauty", beauty), ("albedo", albedo), ("normal", normal), ("moment", moment)):
             if want:
                 out[name] = np.empty(shape, np.float32)
         ptr = lambda name: out[name].ctypes.data if name in out else None
         st = stats if stats is not None else RenderStats()
-        ms = ctypes.c_double()
+        ms, mms = ctypes.c_double(), ctypes.c_double()
         mask = (AOV_ALBEDO if albedo else 0) | (AOV_NORMAL if normal else 0)
-        self._check(self._lib.nart_hip_render_aovs(self._ctx, ctypes.byref(p), mask, ptr("beauty"), ptr("albedo"),
-                                                   ptr("normal"), ctypes.byref(st), ctypes.byref(ms)))
+        if moment:
+            self._check(self._lib.nart_hip_render_moment(self._ctx, ctypes.byref(p), mask, ptr("beauty"), ptr("albedo"),
+                                                         ptr("normal"), ptr("moment"), ctypes.byref(st),
+                                                         ctypes.byref(ms), ctypes.byref(mms)))
+            out["moment_ms"] = mms.value
+        else:
+            self._check(self._lib.nart_hip_render_aovs(self._ctx, ctypes.byref(p), mask, ptr("beauty"), ptr("albedo"),
+                                                       ptr("normal"), ctypes.byref(st), ctypes.byref(ms)))
         out["aov_ms"] = ms.value
         return out
 
@@ -546,27 +565,37 @@ class HipRenderer:
                                                           tri.ctypes.data))
         return out, tri
 
-    def denoise(self, p, beauty, albedo, normal, params=None):
+    def denoise(self, p, beauty, albedo, normal, params=None, moment=None):
         """Denoise host images (nart_hip_denoise): beauty, albedo and normal are (totalH, totalW, 5)
         float32 images as render_aovs() returns them; params a DenoiseParams (None: the defaults).
         Returns the denoised (totalH, totalW, 5) image: {rgb, alpha, 1} in the cropped window, zero
-        in the border, so finalize() and write_exr() take it as they take a render."""
+        in the border, so finalize() and write_exr() take it as they take a render.
+        moment: the second-moment image of render_aovs(moment=True); the filter then takes each
+        pixel's variance from it (nart_hip_denoise_moment; p.spp >= 2) instead of the spatial estimate."""
         g = session_geometry(p)
         shape = (g.total_height, g.total_width, PIXEL_FLOATS)
-        src = [np.ascontiguousarray(a, dtype=np.float32) for a in (beauty, albedo, normal)]
+        src = [np.ascontiguousarray(a, dtype=np.float32)
+               for a in (beauty, albedo, normal) + (() if moment is None else (moment,))]
         for a in src:
             if a.shape != shape:
                 raise ValueError("denoise: image of shape %s, expected %s" % (a.shape, shape))
         out = np.empty(shape, np.float32)
-        self._check(self._lib.nart_hip_denoise(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
-                                               src[0].ctypes.data, src[1].ctypes.data, src[2].ctypes.data,
-                                               out.ctypes.data, None))
+        dp = ctypes.byref(params) if params else None
+        if moment is None:
+            self._check(self._lib.nart_hip_denoise(self._ctx, ctypes.byref(p), dp, src[0].ctypes.data,
+                                                   src[1].ctypes.data, src[2].ctypes.data, out.ctypes.data, None))
+        else:
+            self._check(self._lib.nart_hip_denoise_moment(self._ctx, ctypes.byref(p), dp, src[0].ctypes.data,
+                                                          src[1].ctypes.data, src[2].ctypes.data, src[3].ctypes.data,
+                                                          out.ctypes.data, None))
         return out
 
-    def render_denoised(self, p, params=None, beauty=True, stats=None):
+    def render_denoised(self, p, params=None, beauty=True, stats=None, sample_variance=False):
         """Render the beauty and both first-hit AOVs and denoise them on the device
         (nart_hip_render_denoised): a dict with "denoised", "beauty" (the noisy image, bit-identical to
-        render(); only if requested) and "denoise_ms", the device time of the denoise kernels."""
+        render(); only if requested) and "denoise_ms", the device time of the denoise kernels.
+        sample_variance=True also renders the second-moment image and denoises with the variance
+        taken from it (nart_hip_render_denoised_moment; p.spp >= 2)."""
         g = session_geometry(p)
         shape = (g.total_height, g.total_width, PIXEL_FLOATS)
         out = {"denoised": np.empty(shape, np.float32)}
@@ -574,10 +603,10 @@ class HipRenderer:
             out["beauty"] = np.empty(shape, np.float32)
         st = stats if stats is not None else RenderStats()
         ms = ctypes.c_double()
-        self._check(self._lib.nart_hip_render_denoised(self._ctx, ctypes.byref(p),
-                                                       ctypes.byref(params) if params else None,
-                                                       out["beauty"].ctypes.data if beauty else None,
-                                                       out["denoised"].ctypes.data, ctypes.byref(st), ctypes.byref(ms)))
+        entry = self._lib.nart_hip_render_denoised_moment if sample_variance else self._lib.nart_hip_render_denoised
+        self._check(entry(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
+                          out["beauty"].ctypes.data if beauty else None, out["denoised"].ctypes.data, ctypes.byref(st),
+                          ctypes.byref(ms)))
         out["denoise_ms"] = ms.value
         return out
 
@@ -642,3 +671,30 @@ def finalize(p, image):
     crop = image[fb:fb + p.image_height, fb:fb + p.image_width]
     with np.errstate(divide="ignore", invalid="ignore"):
         return crop[..., :4] / crop[..., 4:5]
+
+
+def sample_variance(p, beauty, moment):
+    """The per-pixel variance image of a render, for users with their own denoiser or sampling loop:
+    the cropped (H, W, 4) float32 {V.rgb, 1/k} from the beauty and the second-moment image of
+    render_aovs(moment=True), by the header's formula (include/nart_hip.h, "Sample variance"), every
+    operation in float32 and in its order.  With M the moment pixel, mw its filter weight sum and
+    c = beauty.rgb / beauty.w (0 where beauty.w <= 0):
+        k = M.a / (mw * mw)         1 / k is the pixel's effective sample count
+        V.ch = max(0, M.ch / mw - c.ch * c.ch) * k      the variance of the filtered mean, no Bessel correction
+    and all four are 0 where mw <= 0."""
+    g = session_geometry(p)
+    fb, f32 = g.filter_bounds, np.float32
+    crop = lambda im: np.ascontiguousarray(im, f32)[fb:fb + p.image_height, fb:fb + p.image_width]
+    B, M = crop(beauty), crop(moment)
+    out = np.zeros(B.shape[:2] + (4,), f32)
+    with np.errstate(all="ignore"):
+        bw, mw = B[..., 4], M[..., 4]
+        c = np.where((bw > 0)[..., None], B[..., :3] / bw[..., None], f32(0)).astype(f32)
+        k = (M[..., 3] / (mw * mw)).astype(f32)
+        m2 = (M[..., :3] / mw[..., None]).astype(f32)
+        d = (m2 - c * c).astype(f32)
+        var = np.where(f32(0) > d, f32(0), d).astype(f32)  # max(0, d) = 0 > d ? 0 : d
+        ok = mw > 0
+        out[..., :3] = np.where(ok[..., None], var * k[..., None], f32(0))
+        out[..., 3] = np.where(ok, f32(1) / k, f32(0))
+    return out

@@ -5,6 +5,8 @@
 //   k_dn_prepare   the three nart_pixel images -> guide {n.xyz, z}, cov, signal {s.rgb, v},
 //                  centre record {a_d.rgb, alpha} and depth slope
 //   k_dn_variance  7x7 guide-weighted luminance variance into signal.v
+//                  (not launched in the sample-variance mode: k_dn_prepare<true> writes signal.v
+//                  from the renderer's second-moment image, see below)
 //   k_dn_atrous    one 5x5 pass with holes (step 2^i), signal ping-pong
 //   k_dn_finalize  remodulate into the totalW x totalH nart_pixel output
 // The variance window and the passes of step 1 and 2 stage their tile plus halo in LDS (R = 3, 2, 4
@@ -29,6 +31,7 @@ struct DnArgs {
     const float* beauty;
     const float* albedo;
     const float* normal;
+    const float* moment;  // second-moment image (k_dn_prepare<true> only), else null
     float* out;
     // work buffers over the cropped W x H image
     float4* guide;       // {n.xyz, z}; an empty pixel is all zeros (z == 0 marks it)
@@ -57,6 +60,32 @@ __device__ __forceinline__ float dn_depth(const DnArgs& a, size_t ti) {
     return hs > 0.f ? a.normal[ti * 5 + 3] / hs : 0.f;
 }
 
+// Sample variance of the demodulated luminance from the second-moment pixel M (include/nart_hip.h,
+// "Sample variance"): c the filtered beauty, ad the demodulation albedo.  k = sum w^2 / (sum w)^2 is
+// 1 / the effective sample count; per channel the weighted second moment minus the squared mean,
+// clamped at 0, times k is the variance of the filtered mean.  No Bessel correction is applied (the
+// estimate is the biased one, low by the factor 1 - k).  The channel standard deviations are summed
+// with the luminance weights, i.e. the channels' noise counts as fully correlated: the conservative
+// bound, and what one light path hitting or missing produces.  NaN and overflow become 1e30.
+__device__ __forceinline__ float dn_sample_variance(const float* M, const float* c, const float4& ad) {
+    float V[3] = {0.f, 0.f, 0.f};
+    const float mw = M[4];
+    if (mw > 0.f) {
+        const float k = M[3] / (mw * mw);
+        for (int ch = 0; ch < 3; ++ch) {
+            const float m2 = M[ch] / mw;
+            const float var = dn_max(0.f, m2 - c[ch] * c[ch]);
+            V[ch] = var * k;
+        }
+    }
+    const float sd = (0.2126f * (sqrtf(V[0]) / ad.x) + 0.7152f * (sqrtf(V[1]) / ad.y)) + 0.0722f * (sqrtf(V[2]) / ad.z);
+    const float v = sd * sd;
+    return v < 1e30f ? v : 1e30f;
+}
+
+// MOMENT: the sample-variance mode -- everything the spatial mode's prepare computes, and signal.v
+// from the moment image instead of 0 (k_dn_variance then does not run).
+template <bool MOMENT>
 __global__ void __launch_bounds__(256) k_dn_prepare(DnArgs a) {
     const uint32_t x = blockIdx.x * DN_TW + (threadIdx.x & (DN_TW - 1));
     const uint32_t y = blockIdx.y * DN_TH + threadIdx.x / DN_TW;
@@ -94,7 +123,7 @@ __global__ void __launch_bounds__(256) k_dn_prepare(DnArgs a) {
     ce.w = c[3];
     const bool valid = dn_finite(c[0]) && dn_finite(c[1]) && dn_finite(c[2]);
     float4 s = make_float4(0.f, 0.f, 0.f, -1.f);
-    if (valid) s = make_float4(c[0] / ce.x, c[1] / ce.y, c[2] / ce.z, 0.f);
+    if (valid) s = make_float4(c[0] / ce.x, c[1] / ce.y, c[2] / ce.z, MOMENT ? dn_sample_variance(a.moment + ti * 5, c, ce) : 0.f);
     // depth slope: per axis the smaller one-sided |dz| (the one available at a border, 0 on a
     // single-pixel axis)
     float sx = 0.f, sy = 0.f;

@@ -2,6 +2,7 @@
 //   k_latin    per traced pixel: RNG seed + LatinSquare            (render.cpp:81-85, sampling.cpp:72-86)
 //   k_render   per traced pixel: all spp samples of Li_alpha       (render.cpp:87-107, pathintegrator.cpp)
 //   k_splat    per bucket tile pixel: ordered Gaussian splat      (render.cpp:23-70)
+//   k_moment   per sample record: squared colour channels, for the second-moment image's splat pass
 //   k_combine  per image pixel: tiles summed in bucket raster order (render.cpp:183-203)
 #pragma once
 
@@ -1871,9 +1872,33 @@ ND bool splat_hits_thr(const SplatArgs& A, const float* table, const float* thr,
 //    a = RN(sc - fw) and b = RN(sc + fw) as the reference rounds them;
 //  * dist and the filter index as in splat_hits_thr.
 
+// ---------------------------------------------------------------- second-moment image
+// The moment image (include/nart_hip.h, nart_hip_render_moment) accumulates per tile pixel
+//   contribution = {sum (r*r)*w, sum (g*g)*w, sum (b*b)*w, sum w*w}, filter_weight_sum = sum w
+// over the (sample, pixel) pairs of the beauty's splat, in its order.  k_moment squares the colour
+// channels of the batch's Li_alpha records in place once the beauty splat has consumed them (lane =
+// record, along the sample layout, which is dense in either order; no LDS, no atomics); the splat
+// kernels then run once more with MOM = true, which makes the fourth accumulator add w * w where
+// the beauty adds L.w * w.  Every other operation, and so filter_weight_sum, is the beauty's.
+__global__ __launch_bounds__(256) void k_moment(float4* L, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 v = L[i];
+    v.x = v.x * v.x;
+    v.y = v.y * v.y;
+    v.z = v.z * v.z;
+    L[i] = v;
+}
+// the factor the fourth accumulator multiplies by w: the record's alpha, or with MOM the weight
+template <bool MOM>
+ND float splat_a(float Lw, float w) {
+    return MOM ? w : Lw;
+}
+
 // MODE 0: direct AddSample arithmetic (splat_hits); 1: filter index from thresholds
 // (splat_hits_thr).  The fallbacks of the splat: any bucket size and filter width.
-template <int MODE>
+// MOM (every splat kernel): the moment image's pass, see k_moment.
+template <int MODE, bool MOM = false>
 __global__ __launch_bounds__(256) void k_splat(SplatArgs A) {
     __shared__ float s_table[64];
     __shared__ float s_thr[65];
@@ -1949,10 +1974,10 @@ __global__ __launch_bounds__(256) void k_splat(SplatArgs A) {
                 bool h1 = NART_SPLAT_HITS(fx + uv1.x, fy + uv1.y, w1);
                 bool h2 = NART_SPLAT_HITS(fx + uv2.x, fy + uv2.y, w2);
                 bool h3 = NART_SPLAT_HITS(fx + uv3.x, fy + uv3.y, w3);
-                if (h0) { c0 += L0.x * w0; c1 += L0.y * w0; c2 += L0.z * w0; c3 += L0.w * w0; ws += w0; }
-                if (h1) { c0 += L1.x * w1; c1 += L1.y * w1; c2 += L1.z * w1; c3 += L1.w * w1; ws += w1; }
-                if (h2) { c0 += L2.x * w2; c1 += L2.y * w2; c2 += L2.z * w2; c3 += L2.w * w2; ws += w2; }
-                if (h3) { c0 += L3.x * w3; c1 += L3.y * w3; c2 += L3.z * w3; c3 += L3.w * w3; ws += w3; }
+                if (h0) { c0 += L0.x * w0; c1 += L0.y * w0; c2 += L0.z * w0; c3 += splat_a<MOM>(L0.w, w0) * w0; ws += w0; }
+                if (h1) { c0 += L1.x * w1; c1 += L1.y * w1; c2 += L1.z * w1; c3 += splat_a<MOM>(L1.w, w1) * w1; ws += w1; }
+                if (h2) { c0 += L2.x * w2; c1 += L2.y * w2; c2 += L2.z * w2; c3 += splat_a<MOM>(L2.w, w2) * w2; ws += w2; }
+                if (h3) { c0 += L3.x * w3; c1 += L3.y * w3; c2 += L3.z * w3; c3 += splat_a<MOM>(L3.w, w3) * w3; ws += w3; }
             }
             for (; i < A.spp; ++i) {
                 float2 uv = sp[(size_t)i * npx];
@@ -1962,7 +1987,7 @@ __global__ __launch_bounds__(256) void k_splat(SplatArgs A) {
                     c0 += Lv.x * w;
                     c1 += Lv.y * w;
                     c2 += Lv.z * w;
-                    c3 += Lv.w * w;
+                    c3 += splat_a<MOM>(Lv.w, w) * w;
                     ws += w;
                 }
             }
@@ -1996,7 +2021,7 @@ ND int lut_cell(float d2, int b0, int last) {
     return r;
 }
 typedef float nd_f2v __attribute__((ext_vector_type(2)));  // packed-math pairs (v_pk_mul/add_f32)
-template <int NP, bool LUT>
+template <int NP, bool LUT, bool MOM = false>
 __global__ __launch_bounds__(256) void k_splat_col4(SplatArgs A) {
     __shared__ float s_table[64];
     __shared__ float s_thr[65];
@@ -2099,7 +2124,7 @@ __global__ __launch_bounds__(256) void k_splat_col4(SplatArgs A) {
                     if (hit) {
                         const nd_f2v w2 = nd_f2v{w, w};
                         cxy[j] += nd_f2v{L.x, L.y} * w2;
-                        czw[j] += nd_f2v{L.z, L.w} * w2;
+                        czw[j] += nd_f2v{L.z, splat_a<MOM>(L.w, w)} * w2;
                         cws[j] += w;
                     }
                 }
@@ -2201,21 +2226,21 @@ template <int W>
 ND bool skew_all_rows(const SkewPrep<W>& p) {
     return p.xhit && p.loy < p.ys[1] && p.ys[W - 1] < p.hiy;
 }
-template <int W>
+template <int W, bool MOM>
 ND void skew_add_all(const SkewPrep<W>& p, float4 L, nd_f2v (&cxy)[W], nd_f2v (&czw)[W], float (&cws)[W]) {
 #pragma unroll
     for (int k = 0; k < W; ++k) {
         const float w = p.d2[k] >= p.ev[k].x ? p.ev[k].z : p.ev[k].y;
         const nd_f2v w2 = nd_f2v{w, w};
         cxy[k] += nd_f2v{L.x, L.y} * w2;
-        czw[k] += nd_f2v{L.z, L.w} * w2;
+        czw[k] += nd_f2v{L.z, splat_a<MOM>(L.w, w)} * w2;
         cws[k] += w;
     }
 }
-template <int W>
+template <int W, bool MOM>
 ND void skew_add_rows(const SkewPrep<W>& p, float4 L, nd_f2v (&cxy)[W], nd_f2v (&czw)[W], float (&cws)[W]) {
     if (skew_all_rows(p)) {
-        skew_add_all(p, L, cxy, czw, cws);
+        skew_add_all<W, MOM>(p, L, cxy, czw, cws);
         return;
     }
 #pragma unroll
@@ -2224,7 +2249,7 @@ ND void skew_add_rows(const SkewPrep<W>& p, float4 L, nd_f2v (&cxy)[W], nd_f2v (
             const float w = p.d2[k] >= p.ev[k].x ? p.ev[k].z : p.ev[k].y;
             const nd_f2v w2 = nd_f2v{w, w};
             cxy[k] += nd_f2v{L.x, L.y} * w2;
-            czw[k] += nd_f2v{L.z, L.w} * w2;
+            czw[k] += nd_f2v{L.z, splat_a<MOM>(L.w, w)} * w2;
             cws[k] += w;
         }
     }
@@ -2255,7 +2280,7 @@ ND void skew_add_rows(const SkewPrep<W>& p, float4 L, nd_f2v (&cxy)[W], nd_f2v (
 // lanes with its own source rows [band start - 2R, band end - 1] (the 2R rows before a band are
 // read by both neighbours): NB times the waves for ~1/NB of the steps each, for launches whose
 // time is otherwise the waves' latency (VALU ~30 % busy at 2.7 waves per SIMD).
-template <int R, int NB>
+template <int R, int NB, bool MOM = false>
 __global__ __launch_bounds__(256, 2) void k_splat_skew(SplatArgs A) {
     constexpr int W = 2 * R + 1, NWR = 2 * R + 2;
     extern __shared__ __attribute__((aligned(16))) float4 s_dyn4[];
@@ -2344,7 +2369,7 @@ __global__ __launch_bounds__(256, 2) void k_splat_skew(SplatArgs A) {
     auto splat_w = [&](float2 uv, float4 L) {
         SkewPrep<W> p;
         skew_prep(p, uv, fx, fy, edgeX, edgeY, xsA, xsB, ybA, ybB, fw, s_lut, lut_b0, lut_last);
-        skew_add_rows(p, L, cxy, czw, cws);
+        skew_add_rows<W, MOM>(p, L, cxy, czw, cws);
     };
     // a group of PF samples: every sample's distance terms and cell reads first (one basic block,
     // so one sample's LDS round trip overlaps the next one's arithmetic; per-sample branches had
@@ -2364,10 +2389,10 @@ __global__ __launch_bounds__(256, 2) void k_splat_skew(SplatArgs A) {
         }
         if (all) {
 #pragma unroll
-            for (uint32_t u = 0; u < G; ++u) skew_add_all(p[u], L[u], cxy, czw, cws);
+            for (uint32_t u = 0; u < G; ++u) skew_add_all<W, MOM>(p[u], L[u], cxy, czw, cws);
         } else {
 #pragma unroll
-            for (uint32_t u = 0; u < G; ++u) skew_add_rows(p[u], L[u], cxy, czw, cws);
+            for (uint32_t u = 0; u < G; ++u) skew_add_rows<W, MOM>(p[u], L[u], cxy, czw, cws);
         }
     };
     auto source_pass = [&](int sy, int sx) {  // every sample of bucket-local pixel (sx, sy)
@@ -2444,7 +2469,7 @@ __global__ __launch_bounds__(256, 2) void k_splat_skew(SplatArgs A) {
                     acc[k][0] += L.x * w;
                     acc[k][1] += L.y * w;
                     acc[k][2] += L.z * w;
-                    acc[k][3] += L.w * w;
+                    acc[k][3] += splat_a<MOM>(L.w, w) * w;
                     acc[k][4] += w;
                 }
             }
@@ -2495,7 +2520,7 @@ __global__ __launch_bounds__(256, 2) void k_splat_skew(SplatArgs A) {
 #ifndef NART_ROWS_PF
 #define NART_ROWS_PF 4  // samples per group; the next group is in flight (few waves: latency-bound)
 #endif
-template <int R>
+template <int R, bool MOM = false>
 __global__ __launch_bounds__(512) void k_splat_rows(SplatArgs A) {
     constexpr int W = 2 * R + 1, NWR = 2 * R + 2;
     extern __shared__ __attribute__((aligned(16))) float4 s_dyn4[];
@@ -2581,7 +2606,7 @@ __global__ __launch_bounds__(512) void k_splat_rows(SplatArgs A) {
         if (xhit && (scy - fw) < ys + 1.f && ys < (scy + fw)) {
             const nd_f2v w2 = nd_f2v{w, w};
             cxy += nd_f2v{L.x, L.y} * w2;
-            czw += nd_f2v{L.z, L.w} * w2;
+            czw += nd_f2v{L.z, splat_a<MOM>(L.w, w)} * w2;
             cws += w;
         }
     };
@@ -2673,7 +2698,7 @@ __global__ __launch_bounds__(512) void k_splat_rows(SplatArgs A) {
                         acc[0] += L.x * w;
                         acc[1] += L.y * w;
                         acc[2] += L.z * w;
-                        acc[3] += L.w * w;
+                        acc[3] += splat_a<MOM>(L.w, w) * w;
                         acc[4] += w;
                     }
                 }

@@ -15,6 +15,10 @@
 //   --denoise       also write every session's denoised image (nart_hip_render_denoised, default
 //                   parameters; with --aovs nart_hip_denoise over the AOVs rendered anyway: the same
 //                   image) to <out>.denoised.exr, through the same writer
+//   --sample-variance  with --denoise: the denoiser takes each pixel's variance from the renderer's
+//                   second-moment image (nart_hip_render_denoised_moment; with --aovs
+//                   nart_hip_render_moment + nart_hip_denoise_moment: the same image) instead of the
+//                   spatial estimate; without --denoise it is an error
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -98,7 +102,7 @@ bool take_device_flags(std::vector<char*>& args, std::vector<int>& devices) {
     return true;
 }
 
-// Removes every `flag` (--aovs, --denoise) from argv; true if it was there.
+// Removes every `flag` (--aovs, --denoise, --sample-variance) from argv; true if it was there.
 bool take_flag(std::vector<char*>& args, const char* flag) {
     std::vector<char*> kept;
     for (char* a : args)
@@ -115,6 +119,11 @@ int main(int argc, char* argv[]) {
     std::vector<int> devices;
     const bool aovs = take_flag(args, "--aovs");
     const bool denoise = take_flag(args, "--denoise");
+    const bool sample_variance = take_flag(args, "--sample-variance");
+    if (sample_variance && !denoise) {
+        std::fprintf(stderr, "Error: --sample-variance selects the denoiser's variance input and needs --denoise\n");
+        return EXIT_FAILURE;
+    }
     if (!take_device_flags(args, devices)) return EXIT_FAILURE;
     if (args.size() < 3) {
         std::fprintf(stderr, "Too few arguments given.\nUsage example: %s <scene file> <output path>\n", argv[0]);
@@ -152,9 +161,18 @@ int main(int argc, char* argv[]) {
         nart_session_geometry g;
         nart_session_geometry_of(&p, &g);
         std::vector<nart_pixel> image((size_t)g.total_width * g.total_height);
-        std::vector<nart_pixel> albedo, normal, denoised;
+        std::vector<nart_pixel> albedo, normal, denoised, moment;
         if (denoise) denoised.resize(image.size());
-        if (aovs) {
+        if (aovs && sample_variance) {
+            albedo.resize(image.size());
+            normal.resize(image.size());
+            moment.resize(image.size());
+            rc = nart_hip_render_moment(ctx, &p, NART_AOV_ALBEDO | NART_AOV_NORMAL, image.data(), albedo.data(),
+                                        normal.data(), moment.data(), nullptr, nullptr, nullptr);
+            if (rc == NART_OK)
+                rc = nart_hip_denoise_moment(ctx, &p, nullptr, image.data(), albedo.data(), normal.data(), moment.data(),
+                                             denoised.data(), nullptr);
+        } else if (aovs) {
             albedo.resize(image.size());
             normal.resize(image.size());
             rc = nart_hip_render_aovs(ctx, &p, NART_AOV_ALBEDO | NART_AOV_NORMAL, image.data(), albedo.data(),
@@ -162,6 +180,8 @@ int main(int argc, char* argv[]) {
             if (rc == NART_OK && denoise)
                 rc = nart_hip_denoise(ctx, &p, nullptr, image.data(), albedo.data(), normal.data(), denoised.data(),
                                       nullptr);
+        } else if (sample_variance) {
+            rc = nart_hip_render_denoised_moment(ctx, &p, nullptr, image.data(), denoised.data(), nullptr, nullptr);
         } else if (denoise) {
             rc = nart_hip_render_denoised(ctx, &p, nullptr, image.data(), denoised.data(), nullptr, nullptr);
         } else {

@@ -122,20 +122,20 @@ int ensure_dev(nart_ctx* ctx, int dev, void*& buf, size_t& cap, size_t bytes, co
 // The multi-device half of render_frame (which has validated p and sized a borrowed image buffer):
 // shard, render concurrently, gather to device 0, combine, deliver.
 // The gather runs over the request's list of tile buffers: the beauty (unless an AOV-only frame)
-// and each first-hit AOV requested.  Every device keeps its buffers' slabs back to back in
+// and each first-hit AOV requested, and the second-moment image.  Every device keeps its buffers' slabs back to back in
 // sub_tiles[d], all are gathered in the one RCCL group (or by device copies), and each buffer is
 // then permuted and combined into ctx->d_image on device 0 in turn, and copied from there to its
 // destination (none where the request borrows ctx->d_image itself: nart_hip_render_device).
-// aov_ms: the slowest device's AOV time.
+// aov_ms, moment_ms: the slowest device's AOV and moment-pass times.
 int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest& rq, nart_render_stats* stats,
-                 double* aov_ms) {
+                 double* aov_ms, double* moment_ms) {
     const uint32_t n = (uint32_t)ctx->subs.size();
-    // the tile buffers of this render: -1 the beauty, k >= 0 AOV k
+    // the tile buffers of this render: -1 the beauty, 0 and 1 AOV k, 2 the moment image
     std::vector<int> kinds;
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; k < FRAME_BUFS; ++k)
         if (rq.wants(k)) kinds.push_back(k - 1);
     const size_t K = kinds.size();
-    const bool want_aov = rq.wants_aovs();
+    const bool want_aov = rq.wants_aovs() || rq.moment;
     int rc = NART_OK;
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
@@ -170,7 +170,8 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
         const size_t slab = ids[d].size() * tile_floats;
         areq[d].beauty = rq.beauty;
         for (size_t i = 0; i < K; ++i)
-            if (kinds[i] >= 0) areq[d].tiles[kinds[i]] = static_cast<float*>(ctx->sub_tiles[d]) + i * slab;
+            if (kinds[i] >= 0)
+                (kinds[i] == 2 ? areq[d].moment : areq[d].tiles[kinds[i]]) = static_cast<float*>(ctx->sub_tiles[d]) + i * slab;
         rcs[d] = render_buckets(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(),
                                 static_cast<float*>(ctx->sub_tiles[d]), ctx->streams[d], &st[d],
                                 want_aov ? &areq[d] : nullptr);
@@ -262,6 +263,7 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     HIPCHK(hipMemcpyAsync(ctx->d_slab_map, map.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s0));
     // (stream order lets the buffers share d_byid and d_image)
     for (size_t i = 0; i < K; ++i) {
+        if (!rq.on_device && !rq.dst[kinds[i] + 1]) continue;  // rendered for another buffer's sake, not delivered
         hipLaunchKernelGGL(k_unshard, dim3(nb), dim3(256), 0, s0, slabs + i * nb * tile_floats,
                            static_cast<float*>(ctx->d_byid), static_cast<const uint32_t*>(ctx->d_slab_map), nb,
                            (uint32_t)tile_floats);
@@ -279,6 +281,8 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     HIPCHK(hipStreamSynchronize(s0));
     if (aov_ms)
         for (uint32_t d = 0; d < n; ++d) *aov_ms = std::max(*aov_ms, areq[d].ms);
+    if (moment_ms)
+        for (uint32_t d = 0; d < n; ++d) *moment_ms = std::max(*moment_ms, areq[d].moment_ms);
     if (stats) {
         // one render: device times of the slowest device (they run concurrently), work counts
         // summed; added to the caller's stats as the single-device path adds a render's

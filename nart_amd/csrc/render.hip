@@ -76,9 +76,11 @@ struct nart_ctx {
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ev[4]: after k_primary
     bool primary_ran = false;  // the last dispatch launched k_primary (ev[4] recorded)
     bool prim_valid = false;   // d_prim holds the current batch's camera-ray hits (first-hit AOVs)
-    hipEvent_t ev_aov[2] = {nullptr, nullptr};  // around the AOV passes of a batch (render_buckets)
+    // around the AOV passes ([0], [1]) and the moment pass ([2], [3]) of a batch (render_buckets)
+    hipEvent_t ev_aov[4] = {nullptr, nullptr, nullptr, nullptr};
     // denoiser (denoise_device): work buffers over the cropped image, the four device images of
-    // nart_hip_denoise / nart_hip_render_denoised, events between its kernels, the last run's times
+    // nart_hip_denoise / nart_hip_render_denoised (five with the moment image), events between its
+    // kernels, the last run's times
     void *d_dn = nullptr, *d_dn_img = nullptr;
     size_t cap_dn = 0, cap_dn_img = 0;
     hipEvent_t ev_dn[12] = {};
@@ -1296,10 +1298,15 @@ int launch_latin(nart_ctx* ctx, const RenderArgs& ra, hipStream_t st) {
 // A render's AOV request (nart_hip_render_aovs): tiles[k] receives the splatted records of AOV k
 // (AOV_ALBEDO, AOV_NORMAL; null: not requested), laid out like the beauty tiles.  beauty false: an
 // AOV-only render, which launches no path kernel.  ms: device time of the k_aov + AOV splat launches.
+// moment: tiles of the second-moment image (k_moment + the MOM splat over the batch's Li_alpha, so it
+// needs the beauty's path kernel), moment_ms their device time.
 struct AovRequest {
     float* tiles[2] = {nullptr, nullptr};
+    float* moment = nullptr;
     bool beauty = true;
-    double ms = 0.0;
+    double ms = 0.0, moment_ms = 0.0;
+
+    bool first_hit() const { return tiles[0] || tiles[1]; }
 };
 
 // Camera-ray hits of the batch in `a` into ctx->d_prim, for AOVs of a dispatch that did not run
@@ -1485,51 +1492,60 @@ int plan_splat(nart_ctx* ctx, const nart_render_params* p, const nart_session_ge
 // pixels per lane (power-of-two buckets); 1 / 0 one tile pixel per lane with the threshold / direct
 // filter-index arithmetic (any bucket size; 2 selects 1 since the compare-only one-pixel kernel
 // was retired).
-int launch_splat(nart_ctx* ctx, const SplatPlan& plan, const SplatArgs& sa, uint32_t nbk, hipStream_t st) {
+// MOM: the moment image's pass (kernels.h k_moment): the same kernel and launch shape.
+template <bool MOM>
+int launch_splat_as(nart_ctx* ctx, const SplatPlan& plan, const SplatArgs& sa, uint32_t nbk, hipStream_t st) {
     const dim3 block(256);
     if (plan.rows) {
         ctx->sched |= NART_SCHED_SPLAT_ROWS;
         const uint32_t U = sa.tile * (2 * sa.fb + 1), ub = std::max(1u, 512u / U);
         const uint32_t threads = (ub * U + 63) / 64 * 64, nblk = (nbk + ub - 1) / ub;
         const size_t lds = plan.lut_bytes + 2u * ub * sizeof(uint32_t);
-        if (sa.fb == 1) hipLaunchKernelGGL((k_splat_rows<1>), dim3(nblk), dim3(threads), lds, st, sa);
-        else if (sa.fb == 2) hipLaunchKernelGGL((k_splat_rows<2>), dim3(nblk), dim3(threads), lds, st, sa);
-        else hipLaunchKernelGGL((k_splat_rows<3>), dim3(nblk), dim3(threads), lds, st, sa);
+        if (sa.fb == 1) hipLaunchKernelGGL((k_splat_rows<1, MOM>), dim3(nblk), dim3(threads), lds, st, sa);
+        else if (sa.fb == 2) hipLaunchKernelGGL((k_splat_rows<2, MOM>), dim3(nblk), dim3(threads), lds, st, sa);
+        else hipLaunchKernelGGL((k_splat_rows<3, MOM>), dim3(nblk), dim3(threads), lds, st, sa);
     } else if (plan.skew) {
         ctx->sched |= NART_SCHED_SPLAT_SKEW;
         const uint32_t nb = plan.bands;
         const uint32_t pb = 64u / sa.tile, nblk = (nbk * nb + 4 * pb - 1) / (4 * pb);
         const size_t lds = plan.lut_bytes + 8u * pb * sizeof(uint32_t);
         const int fbk = (int)sa.fb * 2 + (int)nb - 1;
-        if (fbk == 2) hipLaunchKernelGGL((k_splat_skew<1, 1>), dim3(nblk), block, lds, st, sa);
-        else if (fbk == 3) hipLaunchKernelGGL((k_splat_skew<1, 2>), dim3(nblk), block, lds, st, sa);
-        else if (fbk == 4) hipLaunchKernelGGL((k_splat_skew<2, 1>), dim3(nblk), block, lds, st, sa);
-        else if (fbk == 5) hipLaunchKernelGGL((k_splat_skew<2, 2>), dim3(nblk), block, lds, st, sa);
-        else if (fbk == 6) hipLaunchKernelGGL((k_splat_skew<3, 1>), dim3(nblk), block, lds, st, sa);
-        else hipLaunchKernelGGL((k_splat_skew<3, 2>), dim3(nblk), block, lds, st, sa);
+        if (fbk == 2) hipLaunchKernelGGL((k_splat_skew<1, 1, MOM>), dim3(nblk), block, lds, st, sa);
+        else if (fbk == 3) hipLaunchKernelGGL((k_splat_skew<1, 2, MOM>), dim3(nblk), block, lds, st, sa);
+        else if (fbk == 4) hipLaunchKernelGGL((k_splat_skew<2, 1, MOM>), dim3(nblk), block, lds, st, sa);
+        else if (fbk == 5) hipLaunchKernelGGL((k_splat_skew<2, 2, MOM>), dim3(nblk), block, lds, st, sa);
+        else if (fbk == 6) hipLaunchKernelGGL((k_splat_skew<3, 1, MOM>), dim3(nblk), block, lds, st, sa);
+        else hipLaunchKernelGGL((k_splat_skew<3, 2, MOM>), dim3(nblk), block, lds, st, sa);
     } else if (sa.thr && sa.invB != 0.f && plan.mode >= 3) {
         const uint64_t n4 = (uint64_t)nbk * sa.tile * ((sa.tile + NART_SPLAT_NP - 1) / NART_SPLAT_NP);
         const dim3 grid((uint32_t)((n4 + 255) / 256));
-        if (sa.lut) hipLaunchKernelGGL((k_splat_col4<NART_SPLAT_NP, true>), grid, block, 0, st, sa);
-        else hipLaunchKernelGGL((k_splat_col4<NART_SPLAT_NP, false>), grid, block, 0, st, sa);
+        if (sa.lut) hipLaunchKernelGGL((k_splat_col4<NART_SPLAT_NP, true, MOM>), grid, block, 0, st, sa);
+        else hipLaunchKernelGGL((k_splat_col4<NART_SPLAT_NP, false, MOM>), grid, block, 0, st, sa);
     } else {
         const uint64_t nthreads = (uint64_t)nbk * sa.tile * sa.tile;
         const dim3 grid((uint32_t)((nthreads + 255) / 256));
-        if (sa.thr && plan.mode >= 1) hipLaunchKernelGGL(k_splat<1>, grid, block, 0, st, sa);
-        else hipLaunchKernelGGL(k_splat<0>, grid, block, 0, st, sa);
+        if (sa.thr && plan.mode >= 1) hipLaunchKernelGGL((k_splat<1, MOM>), grid, block, 0, st, sa);
+        else hipLaunchKernelGGL((k_splat<0, MOM>), grid, block, 0, st, sa);
     }
     HIPCHK(hipGetLastError());
     return NART_OK;
+}
+int launch_splat(nart_ctx* ctx, const SplatPlan& plan, const SplatArgs& sa, uint32_t nbk, hipStream_t st,
+                 bool moment = false) {
+    return moment ? launch_splat_as<true>(ctx, plan, sa, nbk, st) : launch_splat_as<false>(ctx, plan, sa, nbk, st);
 }
 
 // Render a bucket list into device tiles (list order); p is validated by the caller (check_params).
 // Shared by all entry points.  With `aov` each batch also splats the requested first-hit AOV records
 // (k_aov into ctx->d_L, which the beauty splat has consumed by then: no extra per-sample memory)
-// into the request's tiles.
+// into the request's tiles; with aov->moment, between the two, the second-moment image (k_moment
+// squares the Li_alpha records in place, one more splat pass with MOM).
 int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n, float* d_tiles,
                    hipStream_t st, nart_render_stats* stats, AovRequest* aov = nullptr) {
     int rc = NART_OK;
     const bool beauty = !aov || aov->beauty;
+    const bool first_hit = aov && aov->first_hit(), moment = aov && aov->moment;
+    if (moment && !beauty) return fail(ctx, NART_E_INVALID, "the moment image needs the path kernel (the beauty)");
     HIPCHK(hipSetDevice(ctx->device));
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
@@ -1607,7 +1623,16 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         sa.n_buckets = nbk;
         if (beauty && (rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
         HIPCHK(hipEventRecord(ctx->ev[2], st));
-        if (aov) {
+        if (moment) {
+            HIPCHK(hipEventRecord(ctx->ev_aov[2], st));
+            const uint64_t ns = (uint64_t)nslots * p->spp;
+            hipLaunchKernelGGL(k_moment, dim3((uint32_t)((ns + 255) / 256)), dim3(256), 0, st, ctx->d_L, ns);
+            HIPCHK(hipGetLastError());
+            sa.tiles = aov->moment + (size_t)b0 * tpx * 5;
+            if ((rc = launch_splat(ctx, plan, sa, nbk, st, true))) return rc;
+            HIPCHK(hipEventRecord(ctx->ev_aov[3], st));
+        }
+        if (first_hit) {
             // the dispatch's own camera-ray hits where it traced them first, else k_primary now
             if (!ctx->prim_valid && (rc = launch_aov_primary(ctx, ra, st))) return rc;
             HIPCHK(hipEventRecord(ctx->ev_aov[0], st));
@@ -1620,11 +1645,16 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             HIPCHK(hipEventRecord(ctx->ev_aov[1], st));
             HIPCHK(hipEventSynchronize(ctx->ev_aov[1]));
         }
+        if (moment) HIPCHK(hipEventSynchronize(ctx->ev_aov[3]));
         HIPCHK(hipEventSynchronize(ctx->ev[2]));
         float ms = 0.f;
-        if (aov) {
+        if (first_hit) {
             HIPCHK(hipEventElapsedTime(&ms, ctx->ev_aov[0], ctx->ev_aov[1]));
             aov->ms += ms;
+        }
+        if (moment) {
+            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_aov[2], ctx->ev_aov[3]));
+            aov->moment_ms += ms;
         }
         HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
         acc.kernel_ms += ms;
@@ -1771,14 +1801,16 @@ int build_bvh_device(nart_ctx* ctx, const nart_scene_blob& blob, const std::vect
 
 // ---------------------------------------------------------------- whole frames
 // What a whole-frame render produces, where it goes and whose buffers it uses (render_frame).
-// Buffer k: 0 the beauty, 1 + a first-hit AOV a (AOV_ALBEDO, AOV_NORMAL).
+// Buffer k: 0 the beauty, 1 + a first-hit AOV a (AOV_ALBEDO, AOV_NORMAL), 3 the second-moment image.
+constexpr int FRAME_BUFS = 4;
 struct FrameRequest {
     bool beauty = true;            // false: an AOV-only frame, which launches no path kernel
     bool aov[2] = {false, false};
-    // Delivery: the image of buffer k to the host at dst[k]; or on_device, the images of the
-    // requested buffers back to back, in buffer order, from the start of *image on device 0
-    // (ordered on its null stream: single-device frames do not wait for them).
-    nart_pixel* dst[3] = {nullptr, nullptr, nullptr};
+    bool moment = false;           // needs the path kernel: NART_E_INVALID without the beauty
+    // Delivery: the image of buffer k to the host at dst[k] (null: rendered, not delivered); or
+    // on_device, the images of the requested buffers back to back, in buffer order, from the start of
+    // *image on device 0 (ordered on its null stream: single-device frames do not wait for them).
+    nart_pixel* dst[FRAME_BUFS] = {nullptr, nullptr, nullptr, nullptr};
     bool on_device = false;
     // The call's tile and image buffers.  image null: temporaries, allocated by the call and freed on
     // every return path.  Else borrowed from a context, which keeps them for its next call (the
@@ -1789,7 +1821,7 @@ struct FrameRequest {
     size_t* image_cap = nullptr;
     uint32_t images = 0;
 
-    bool wants(int k) const { return k == 0 ? beauty : aov[k - 1]; }
+    bool wants(int k) const { return k == 0 ? beauty : (k == 3 ? moment : aov[k - 1]); }
     bool wants_aovs() const { return aov[0] || aov[1]; }
 };
 
@@ -1817,12 +1849,16 @@ void free_frame_buffers(nart_ctx* ctx) {
 namespace {
 
 // Render(): every bucket of the session, combined in bucket raster order, delivered as the request
-// says.  The one whole-frame path behind nart_hip_render, _render_aovs, _render_device and
-// _render_denoised.  Errors of a multi-device context's sub-contexts are re-raised on ctx.
+// says.  The one whole-frame path behind nart_hip_render, _render_aovs, _render_moment,
+// _render_device, _render_denoised and _render_denoised_moment.  Errors of a multi-device context's
+// sub-contexts are re-raised on ctx.
 int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest& rq, nart_render_stats* stats,
-                 double* aov_ms) {
+                 double* aov_ms, double* moment_ms = nullptr) {
     RenderTimer timer(stats);
     if (aov_ms) *aov_ms = 0.0;
+    if (moment_ms) *moment_ms = 0.0;
+    if (rq.moment && !rq.beauty)
+        return fail(ctx, NART_E_INVALID, "the moment image needs the path kernel: it cannot be rendered without the beauty");
     nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // device 0: combines, holds the images
     int rc = NART_OK;
     if (rq.wants_aovs() && (rc = check_first_hit(ctx, p))) return rc;
@@ -1835,15 +1871,15 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     const size_t tile_floats = (size_t)nb * g.tile_size * g.tile_size * 5;
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5;
     size_t K = 0;  // buffers requested
-    for (int k = 0; k < 3; ++k) K += rq.wants(k);
+    for (int k = 0; k < FRAME_BUFS; ++k) K += rq.wants(k);
     if (rq.image && (rc = ensure_dev(ctx, c0->device, *rq.image, *rq.image_cap,
                                      std::max<size_t>(K, rq.images) * img_floats * sizeof(float), "image")))
         return rc;
-    if (c0 != ctx) return render_multi(ctx, p, rq, stats, aov_ms);
+    if (c0 != ctx) return render_multi(ctx, p, rq, stats, aov_ms, moment_ms);
 
     HIPCHK(hipSetDevice(ctx->device));
-    // tile buffers back to back: the beauty (if any), then the requested AOVs; one image to combine
-    // into on the way to the host, or the borrowed images
+    // tile buffers back to back: the beauty (if any), then the requested AOVs and the moment image;
+    // one image to combine into on the way to the host, or the borrowed images
     ScopedDeviceBufs own;
     void*& d_tiles = rq.image ? ctx->d_gather : own.p[0];
     void*& d_img = rq.image ? *rq.image : own.p[1];
@@ -1852,8 +1888,8 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     else if (!(rc = dmalloc(ctx, &d_tiles, tile_bytes, "tiles")))
         rc = dmalloc(ctx, &d_img, img_floats * sizeof(float), "image");
     if (rc) return rc;
-    float* tiles[3] = {nullptr, nullptr, nullptr};
-    for (int k = 0, i = 0; k < 3; ++k)
+    float* tiles[FRAME_BUFS] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0, i = 0; k < FRAME_BUFS; ++k)
         if (rq.wants(k)) tiles[k] = static_cast<float*>(d_tiles) + (size_t)(i++) * tile_floats;
     std::vector<uint32_t> ids(nb);
     for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
@@ -1861,10 +1897,12 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     areq.beauty = rq.beauty;
     areq.tiles[0] = tiles[1];
     areq.tiles[1] = tiles[2];
-    rc = render_buckets(ctx, p, ids.data(), nb, tiles[0], 0, stats, rq.wants_aovs() ? &areq : nullptr);
+    areq.moment = tiles[3];
+    rc = render_buckets(ctx, p, ids.data(), nb, tiles[0], 0, stats, rq.wants_aovs() || rq.moment ? &areq : nullptr);
     if (aov_ms) *aov_ms = areq.ms;
-    for (int k = 0, i = 0; k < 3 && !rc; ++k) {
-        if (!rq.wants(k)) continue;
+    if (moment_ms) *moment_ms = areq.moment_ms;
+    for (int k = 0, i = 0; k < FRAME_BUFS && !rc; ++k) {
+        if (!rq.wants(k) || (!rq.on_device && !rq.dst[k])) continue;
         float* img = static_cast<float*>(d_img) + (rq.on_device ? (size_t)(i++) * img_floats : 0);
         rc = nart_hip_combine_async(ctx, p, reinterpret_cast<const nart_pixel*>(tiles[k]),
                                     reinterpret_cast<nart_pixel*>(img), 0);
@@ -1920,19 +1958,23 @@ int check_denoise(nart_ctx* ctx, const nart_denoise_params* dp, nart_denoise_par
     return NART_OK;
 }
 
-// The four device images (beauty, albedo, normal, denoised) of a single-device context.
-int denoise_images(nart_ctx* ctx, const nart_session_geometry& g, float* img[4]) {
+// The n device images of a single-device context: 4 (beauty, albedo, normal, denoised), or 5 in the
+// sample-variance mode (beauty, albedo, normal, moment, denoised).
+int denoise_images(nart_ctx* ctx, const nart_session_geometry& g, float* img[5], int n = 4) {
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5;
-    const size_t bytes = 4 * img_floats * sizeof(float);
+    const size_t bytes = (size_t)n * img_floats * sizeof(float);
     if (int rc = ensure_dev(ctx, ctx->device, ctx->d_dn_img, ctx->cap_dn_img, bytes, "denoiser images")) return rc;
-    for (int k = 0; k < 4; ++k) img[k] = static_cast<float*>(ctx->d_dn_img) + (size_t)k * img_floats;
+    for (int k = 0; k < n; ++k) img[k] = static_cast<float*>(ctx->d_dn_img) + (size_t)k * img_floats;
     return NART_OK;
 }
 
 // Denoise device images on a single-device context: prepare, variance, the a-trous passes (LDS
 // tiles for steps 1 and 2, global reads beyond), finalise; synchronous.  ms: device time.
+// d_moment non-null: the sample-variance mode -- k_dn_prepare<true> takes the variance from the
+// second-moment image and k_dn_variance is not launched (its time reads 0).
 int denoise_device(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params& dp, const float* d_beauty,
-                   const float* d_albedo, const float* d_normal, float* d_out, hipStream_t st, double* ms) {
+                   const float* d_albedo, const float* d_normal, const float* d_moment, float* d_out, hipStream_t st,
+                   double* ms) {
     HIPCHK(hipSetDevice(ctx->device));
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
@@ -1949,6 +1991,7 @@ int denoise_device(nart_ctx* ctx, const nart_render_params* p, const nart_denois
     a.beauty = d_beauty;
     a.albedo = d_albedo;
     a.normal = d_normal;
+    a.moment = d_moment;
     a.out = d_out;
     a.guide = f4;
     a.centre = f4 + 3 * npx;
@@ -1970,12 +2013,18 @@ int denoise_device(nart_ctx* ctx, const nart_render_params* p, const nart_denois
     uint32_t e = 0;
     HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
     a.sig_in = nullptr;
-    a.sig_out = sig[0];
-    hipLaunchKernelGGL(k_dn_prepare, grid, block, 0, st, a);
-    HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
-    a.sig_in = sig[0];
-    a.sig_out = sig[1];
-    hipLaunchKernelGGL(k_dn_variance, grid, block, 0, st, a);
+    if (d_moment) {  // signal and variance at once, where the variance pass would have left them
+        a.sig_out = sig[1];
+        hipLaunchKernelGGL(k_dn_prepare<true>, grid, block, 0, st, a);
+        HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+    } else {
+        a.sig_out = sig[0];
+        hipLaunchKernelGGL(k_dn_prepare<false>, grid, block, 0, st, a);
+        HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+        a.sig_in = sig[0];
+        a.sig_out = sig[1];
+        hipLaunchKernelGGL(k_dn_variance, grid, block, 0, st, a);
+    }
     HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
     int cur = 1;
     for (uint32_t i = 0; i < dp.iterations; ++i) {
@@ -1997,6 +2046,7 @@ int denoise_device(nart_ctx* ctx, const nart_render_params* p, const nart_denois
     for (double& t : ctx->dn_ms) t = 0.0;
     double total = 0.0;
     for (uint32_t k = 0; k + 1 < e; ++k) {
+        if (d_moment && k == 1) continue;  // no variance kernel ran between these two events
         float t = 0.f;
         HIPCHK(hipEventElapsedTime(&t, ctx->ev_dn[k], ctx->ev_dn[k + 1]));
         // events 0..2 bracket prepare and variance, the last pair the finalise kernel
@@ -2005,6 +2055,91 @@ int denoise_device(nart_ctx* ctx, const nart_render_params* p, const nart_denois
     }
     if (ms) *ms = total;
     return NART_OK;
+}
+
+int check_sample_variance(nart_ctx* ctx, const nart_render_params* p) {
+    if (p->spp < 2) return fail(ctx, NART_E_INVALID, "sample variance needs spp >= 2");
+    return NART_OK;
+}
+
+// nart_hip_denoise (moment null) and nart_hip_denoise_moment: host images through the device.
+int denoise_host(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, const nart_pixel* beauty,
+                 const nart_pixel* albedo, const nart_pixel* normal, const nart_pixel* moment, nart_pixel* out,
+                 double* denoise_ms) {
+    nart_denoise_params d;
+    int rc = check_denoise(ctx, dp, d);
+    if (rc || (moment && (rc = check_sample_variance(ctx, p)))) return rc;
+    if (!ctx->subs.empty()) {  // on the first device
+        rc = denoise_host(ctx->subs[0], p, &d, beauty, albedo, normal, moment, out, denoise_ms);
+        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
+    }
+    if (!p->image_width || !p->image_height || !(p->filter_width > 0.f))
+        return fail(ctx, NART_E_INVALID, "imageWidth, imageHeight and filterWidth must be > 0");
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const int n = moment ? 5 : 4;  // the inputs, then the denoised image
+    float* img[5];
+    if ((rc = denoise_images(ctx, g, img, n))) return rc;
+    const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
+    const nart_pixel* src[4] = {beauty, albedo, normal, moment};
+    for (int k = 0; k + 1 < n; ++k) HIPCHK(hipMemcpy(img[k], src[k], img_bytes, hipMemcpyHostToDevice));
+    if ((rc = denoise_device(ctx, p, d, img[0], img[1], img[2], moment ? img[3] : nullptr, img[n - 1], 0, denoise_ms)))
+        return rc;
+    HIPCHK(hipMemcpy(out, img[n - 1], img_bytes, hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+// nart_hip_render_denoised and, with sample_variance, nart_hip_render_denoised_moment.
+int render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, bool sample_variance,
+                    nart_pixel* image, nart_pixel* out, nart_render_stats* stats, double* denoise_ms) {
+    nart_denoise_params d;
+    int rc = check_denoise(ctx, dp, d);
+    if (rc || (sample_variance && (rc = check_sample_variance(ctx, p)))) return rc;
+    nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // the context that denoises
+    // beauty, both AOVs (and the moment image) into the first of its device images, the denoised image
+    // after them: nothing passes the host
+    const int n = sample_variance ? 5 : 4;
+    FrameRequest rq;
+    rq.aov[AOV_ALBEDO] = rq.aov[AOV_NORMAL] = true;
+    rq.moment = sample_variance;
+    rq.on_device = true;
+    rq.image = &c0->d_dn_img;
+    rq.image_cap = &c0->cap_dn_img;
+    rq.images = (uint32_t)n;
+    if ((rc = render_frame(ctx, p, rq, stats, nullptr))) return rc;
+    RenderTimer timer(stats);  // render_ms covers the whole call
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
+    float* img[5];
+    if ((rc = denoise_images(c0, g, img, n)) ||  // (sized by the frame: this lays them out)
+        (rc = denoise_device(c0, p, d, img[0], img[1], img[2], sample_variance ? img[3] : nullptr, img[n - 1], 0,
+                             denoise_ms)))
+        return c0 == ctx ? rc : fail(ctx, rc, c0->err);
+    HIPCHK(hipSetDevice(c0->device));
+    if (image) HIPCHK(hipMemcpy(image, img[0], img_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, img[n - 1], img_bytes, hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+// nart_hip_render_aovs (moment null) and nart_hip_render_moment.
+int render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_pixel* image, nart_pixel* albedo,
+                nart_pixel* normal, nart_pixel* moment, nart_render_stats* stats, double* aov_ms, double* moment_ms) {
+    if (aovs & ~(NART_AOV_ALBEDO | NART_AOV_NORMAL)) return fail(ctx, NART_E_INVALID, "unknown AOV bit");
+    if (((aovs & NART_AOV_ALBEDO) && !albedo) || ((aovs & NART_AOV_NORMAL) && !normal))
+        return fail(ctx, NART_E_INVALID, "an AOV is requested without its image buffer");
+    FrameRequest rq;
+    // the moment image needs the path kernel: with it the beauty is rendered even where it is not asked for
+    rq.beauty = image != nullptr || moment != nullptr;
+    rq.moment = moment != nullptr;
+    rq.aov[AOV_ALBEDO] = (aovs & NART_AOV_ALBEDO) != 0;
+    rq.aov[AOV_NORMAL] = (aovs & NART_AOV_NORMAL) != 0;
+    rq.dst[0] = image;
+    rq.dst[1 + AOV_ALBEDO] = albedo;
+    rq.dst[1 + AOV_NORMAL] = normal;
+    rq.dst[3] = moment;
+    return render_frame(ctx, p, rq, stats, aov_ms, moment_ms);
 }
 
 }  // namespace
@@ -2370,14 +2505,15 @@ int nart_hip_render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t ao
         return fail(ctx, NART_E_INVALID, "an AOV is requested without its image buffer");
     if (!aovs && !image) return fail(ctx, NART_E_INVALID, "neither the beauty nor an AOV is requested");
     if (!aovs) return nart_hip_render(ctx, p, image, stats);
-    FrameRequest rq;
-    rq.beauty = image != nullptr;
-    rq.aov[AOV_ALBEDO] = (aovs & NART_AOV_ALBEDO) != 0;
-    rq.aov[AOV_NORMAL] = (aovs & NART_AOV_NORMAL) != 0;
-    rq.dst[0] = image;
-    rq.dst[1 + AOV_ALBEDO] = albedo;
-    rq.dst[1 + AOV_NORMAL] = normal;
-    return render_frame(ctx, p, rq, stats, aov_ms);
+    return render_aovs(ctx, p, aovs, image, albedo, normal, nullptr, stats, aov_ms, nullptr);
+}
+
+int nart_hip_render_moment(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_pixel* image,
+                           nart_pixel* albedo, nart_pixel* normal, nart_pixel* moment, nart_render_stats* stats,
+                           double* aov_ms, double* moment_ms) {
+    if (!ctx || !p) return NART_E_INVALID;
+    if (!moment) return fail(ctx, NART_E_INVALID, "the moment image buffer is required");
+    return render_aovs(ctx, p, aovs, image, albedo, normal, moment, stats, aov_ms, moment_ms);
 }
 
 int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w,
@@ -2412,55 +2548,26 @@ void nart_hip_denoise_params_init(nart_denoise_params* dp) {
 int nart_hip_denoise(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, const nart_pixel* beauty,
                      const nart_pixel* albedo, const nart_pixel* normal, nart_pixel* out, double* denoise_ms) {
     if (!ctx || !p || !beauty || !albedo || !normal || !out) return NART_E_INVALID;
-    nart_denoise_params d;
-    int rc = check_denoise(ctx, dp, d);
-    if (rc) return rc;
-    if (!ctx->subs.empty()) {  // on the first device
-        rc = nart_hip_denoise(ctx->subs[0], p, &d, beauty, albedo, normal, out, denoise_ms);
-        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
-    }
-    if (!p->image_width || !p->image_height || !(p->filter_width > 0.f))
-        return fail(ctx, NART_E_INVALID, "imageWidth, imageHeight and filterWidth must be > 0");
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    float* img[4];
-    if ((rc = denoise_images(ctx, g, img))) return rc;
-    const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
-    const nart_pixel* src[3] = {beauty, albedo, normal};
-    for (int k = 0; k < 3; ++k) HIPCHK(hipMemcpy(img[k], src[k], img_bytes, hipMemcpyHostToDevice));
-    if ((rc = denoise_device(ctx, p, d, img[0], img[1], img[2], img[3], 0, denoise_ms))) return rc;
-    HIPCHK(hipMemcpy(out, img[3], img_bytes, hipMemcpyDeviceToHost));
-    return NART_OK;
+    return denoise_host(ctx, p, dp, beauty, albedo, normal, nullptr, out, denoise_ms);
+}
+
+int nart_hip_denoise_moment(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                            const nart_pixel* beauty, const nart_pixel* albedo, const nart_pixel* normal,
+                            const nart_pixel* moment, nart_pixel* out, double* denoise_ms) {
+    if (!ctx || !p || !beauty || !albedo || !normal || !moment || !out) return NART_E_INVALID;
+    return denoise_host(ctx, p, dp, beauty, albedo, normal, moment, out, denoise_ms);
 }
 
 int nart_hip_render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, nart_pixel* image,
                              nart_pixel* out, nart_render_stats* stats, double* denoise_ms) {
     if (!ctx || !p || !out) return NART_E_INVALID;
-    nart_denoise_params d;
-    int rc = check_denoise(ctx, dp, d);
-    if (rc) return rc;
-    nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // the context that denoises
-    // beauty and both AOVs into the first three of its four device images: nothing passes the host
-    FrameRequest rq;
-    rq.aov[AOV_ALBEDO] = rq.aov[AOV_NORMAL] = true;
-    rq.on_device = true;
-    rq.image = &c0->d_dn_img;
-    rq.image_cap = &c0->cap_dn_img;
-    rq.images = 4;
-    if ((rc = render_frame(ctx, p, rq, stats, nullptr))) return rc;
-    RenderTimer timer(stats);  // render_ms covers the whole call
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
-    float* img[4];
-    if ((rc = denoise_images(c0, g, img)) ||  // (sized by the frame: this lays them out)
-        (rc = denoise_device(c0, p, d, img[0], img[1], img[2], img[3], 0, denoise_ms)))
-        return c0 == ctx ? rc : fail(ctx, rc, c0->err);
-    HIPCHK(hipSetDevice(c0->device));
-    if (image) HIPCHK(hipMemcpy(image, img[0], img_bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out, img[3], img_bytes, hipMemcpyDeviceToHost));
-    return NART_OK;
+    return render_denoised(ctx, p, dp, false, image, out, stats, denoise_ms);
+}
+
+int nart_hip_render_denoised_moment(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                                    nart_pixel* image, nart_pixel* out, nart_render_stats* stats, double* denoise_ms) {
+    if (!ctx || !p || !out) return NART_E_INVALID;
+    return render_denoised(ctx, p, dp, true, image, out, stats, denoise_ms);
 }
 
 int nart_hip_denoise_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
