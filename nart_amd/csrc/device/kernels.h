@@ -7,6 +7,7 @@
 #pragma once
 
 #include "path.h"
+#include "queue_layout.h"  // RQ_*_BIT: the flag bits of queue entries
 
 namespace nd {
 
@@ -182,9 +183,6 @@ struct RenderArgs {
     uint32_t stack_lds = 0;
     int2* gstack = nullptr;
 };
-#define RQ_PRIO_BIT 0x80000000u
-#define RQ_PAIR_BIT 0x40000000u
-#define RQ_QUAD_BIT 0x20000000u  // with RQ_PAIR_BIT: the pixel's group has four lanes, not rq_pairs
 
 // xorshift32 state after n draws (rng.h:38-40 applied n times)
 ND uint32_t rng_jump(uint32_t y, uint32_t n) {

@@ -20,6 +20,7 @@
 #include "device/lbvh.h"
 #include "device/volume.h"
 #include "host/bvh_build.h"
+#include "host/path_schedule.h"
 
 using namespace nd;
 
@@ -87,7 +88,7 @@ struct nart_ctx {
     double dn_ms[11] = {};  // prepare, variance, passes 0..7, finalise
     uint32_t sched = 0;        // NART_SCHED_* bits of the current render (nart_render_stats::schedule)
     bool events = false;
-    // megakernel work queue (launch_render)
+    // path-kernel scheduling buffers (ensure_queue, ensure_ilist, ensure_gstack; launch_render, dispatch_volume)
     uint32_t* d_queue = nullptr;
     uint32_t* d_cost = nullptr;
     void* d_ilist = nullptr;   // dielectric-list columns beyond ILIST_REG (bounces > ILIST_REG)
@@ -517,6 +518,34 @@ int ensure_queue(nart_ctx* ctx, uint32_t n) {
     return NART_OK;
 }
 
+// Grow-only per-thread columns of the path kernels (capacity reset before the free, as in ensure).
+int grow(nart_ctx* ctx, void*& p, size_t& cap, size_t bytes, const char* what) {
+    if (bytes <= cap) return NART_OK;
+    cap = 0;
+    if (p) HIPCHK(hipFree(p));
+    p = nullptr;
+    const int rc = dmalloc(ctx, &p, bytes, what);
+    if (!rc) cap = bytes;
+    return rc;
+}
+
+// The dielectric list's entries beyond ILIST_REG (bounces > ILIST_REG): one column per thread of
+// the largest launch (whole 512-thread blocks over every slot).
+int ensure_ilist(nart_ctx* ctx, RenderArgs& a) {
+    const size_t lanes = ((size_t)a.n_slots + 511) / 512 * 512;
+    a.ilist_stride = (uint32_t)lanes;
+    const int rc = grow(ctx, ctx->d_ilist, ctx->cap_ilist, lanes * (ILIST_MAX - ILIST_REG) * sizeof(uint2), "dielectric lists");
+    a.ilist_ext = static_cast<uint2*>(ctx->d_ilist);
+    return rc;
+}
+
+// The lean build's traversal-stack levels beyond the LDS: `levels` entries per launched thread.
+int ensure_gstack(nart_ctx* ctx, size_t threads, uint32_t levels, RenderArgs& a) {
+    const int rc = grow(ctx, ctx->d_gstack, ctx->cap_gstack, threads * levels * sizeof(int2), "traversal stack columns");
+    a.gstack = static_cast<int2*>(ctx->d_gstack);
+    return rc;
+}
+
 // LDS of one k_render block: traversal stack + as many top BVH nodes as fit while
 // NART_RENDER_WAVES blocks share a CU's 160 KiB (NART_LDS_NODES overrides the node count).
 uint32_t render_lds_nodes(const nart_ctx* ctx, size_t fixed = 0, uint32_t blocks_of_256 = 1) {
@@ -535,16 +564,8 @@ bool rq_fits(const nart_ctx* ctx) {
 }
 
 // ---------------------------------------------------------------- megakernel scheduling
-// A pixel's samples are one serial chain (its RNG stream), so a frame can finish no earlier
-// than its costliest pixels, and a wave of 64 costly pixels runs several times longer than one
-// such pixel alone (the wave executes the union of its lanes' work).  With the work queue the
-// grid is persistent: lanes take pixels from a queue ordered by a cost probe (one sample per
-// pixel), the costliest pixels spread over all waves so that each holds only a few of them,
-// and a lane whose pixel is done takes the next one instead of idling until its wave ends.
-// The image is unchanged (each pixel's samples stay on its own RNG stream).
-//   NART_QUEUE=0  one lane per pixel, no queue (the launch order is the slot order)
-//   NART_QUEUE=1  persistent lanes, queue in slot order
-//   NART_QUEUE=2  persistent lanes, queue ordered by the cost probe (default)
+// host/path_schedule.h decides a launch's schedule (plan_path: the policy, its measurements and the
+// knobs); the kernels below prepare what it asks for and launch_render executes it.
 
 // Group (wave-sized run of 64 consecutive slots: a 16x4 strip of a bucket) costs, as keys of an
 // ascending sort that puts the costliest group first; a partial last group always sorts last.
@@ -590,48 +611,15 @@ __global__ void k_flag_top(const uint32_t* sorted, uint32_t n, uint32_t E, uint3
     flag[sorted[r]] = r < E ? 1u : 0u;
 }
 
-// Queue: in the first round of W waves, lanes j < k of wave w take the costly pixel of rank
-// j*W + w (each wave holds k of them); every other position takes the remaining pixels in
-// slot order (spatially coherent waves).
-// With prio set (k_render_rq) the costly entries carry RQ_PRIO_BIT; with pairs = Q (2 or 4) each
-// costly pixel goes to Q adjacent lanes (Qj .. Qj + Q - 1) with RQ_PAIR_BIT too, and the queue is
-// n + (Q - 1)*k*W long.
+// The probe-ordered pixel queue (device/queue_layout.h queue_entry): top = the pixels by cost class,
+// rest = the others in slot order.
 __global__ void k_build_queue(const uint32_t* top, const uint32_t* rest, uint32_t n, uint32_t W, uint32_t k,
                               uint32_t prio, uint32_t pairs, uint32_t half, uint32_t quad, uint32_t* queue) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t per = pairs ? pairs : 1u, kk = per * k;  // first-round lanes of the costly pixels
-    if (p >= n + (per - 1u) * k * W + (quad ? 2u * W : 0u)) return;
-    const uint32_t g = 64u * W;
-    if (p < g && quad) {
-        // quad: each first-round wave's costliest pixel (ranks 0..W-1) on four lanes, its other k-1
-        // costly pixels on pairs
-        const uint32_t w = p / 64u, j = p % 64u, kq = kk + 2u;
-        if (j < 4u) queue[p] = top[w] | prio | RQ_PAIR_BIT | RQ_QUAD_BIT;
-        else if (j < kq) queue[p] = top[((j - 4u) / per + 1u) * W + w] | prio | RQ_PAIR_BIT;
-        else queue[p] = rest[w * (64u - kq) + (j - kq)];
-    } else if (p >= g && quad) {
-        queue[p] = rest[(64u - kk - 2u) * W + (p - g)];
-    } else if (p < g && half) {
-        // half = BW, the waves of a ray-queue block (8 or 12: PB = 2 or 3 per SIMD): only its first 4
-        // waves hold costly pixels (PB k each), so each SIMD has one priority wave
-        const uint32_t BW = half, PB = BW / 4u;
-        const uint32_t w = p / 64u, j = p % 64u, b = w / BW, i = w % BW, k2 = PB * kk;
-        const uint32_t pw = b * 4u + i;  // priority wave index
-        const uint32_t roff = b * BW * (64u - kk) + (i < 4u ? i * (64u - k2) : 4u * (64u - k2) + (i - 4u) * 64u);
-        if (i < 4u && j < k2) queue[p] = top[(j / per) * (W / PB) + pw] | prio | (pairs ? RQ_PAIR_BIT : 0u);
-        else queue[p] = rest[roff + (i < 4u ? j - k2 : j)];
-    } else if (p < g) {
-        const uint32_t w = p / 64u, j = p % 64u;
-        queue[p] = j < kk ? (top[(j / per) * W + w] | prio | (pairs ? RQ_PAIR_BIT : 0u))
-                          : rest[w * (64u - kk) + (j - kk)];
-    } else {
-        queue[p] = rest[(64u - kk) * W + (p - g)];
-    }
+    if (p >= queue_length(n, W, k, pairs, quad)) return;
+    const QueueEntry e = queue_entry(p, n, W, k, prio, pairs, half, quad);
+    queue[p] = (e.top ? top : rest)[e.index] | e.flags;
 }
-
-// Pixel list (into `out`) of the wave-sized slot groups ordered by the probe costs in
-// ctx->d_cost, costliest group first (ties keep slot order).
-int sort_groups_by_cost(nart_ctx* ctx, uint32_t n, uint32_t* out, hipStream_t st);
 
 // Sample-major bucket layout: slot `base + p` of a bucket of `cnt` traced pixels keeps sample s
 // at base*spp + s*cnt + p (k_splat_col4's lanes then read neighbouring pixels' sample s from one
@@ -673,54 +661,141 @@ __global__ void k_iota(uint32_t* v, uint32_t n) {
     if (i < n) v[i] = i;
 }
 
-#ifndef NART_RQ_GROUP_LANES
-#define NART_RQ_GROUP_LANES 2
-#endif
-// pixel work queue: 2 = cost probe + priority queue / wave-group refill (the schedule; 0, no
-// queue, and 1, refill in slot order, were A/B forms)
-constexpr int queue_mode() { return 2; }
-
-int sort_groups_by_cost(nart_ctx* ctx, uint32_t n, uint32_t* out, hipStream_t st) {
+// The wave-sized slot groups ordered by the probe costs in ctx->d_cost (`per` entries per group),
+// costliest group first (ties keep slot order): group ids into ctx->d_vals[1], keys into d_keys[1];
+// with `out`, their pixel list too.
+int sort_groups_by_cost(nart_ctx* ctx, uint32_t n, uint32_t per, uint32_t* out, hipStream_t st) {
     const uint32_t ng = (n + 63) / 64;
     hipLaunchKernelGGL(k_group_keys, dim3((ng + 255) / 256), dim3(256), 0, st, ctx->d_cost, n, ctx->d_keys[0],
-                       ctx->d_vals[0]);
+                       ctx->d_vals[0], per);
     size_t tmp = ctx->cap_sort_tmp;
     HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->d_sort_tmp, tmp, ctx->d_keys[0], ctx->d_keys[1], ctx->d_vals[0],
                                               ctx->d_vals[1], (int)ng, 0, 32, st));
-    hipLaunchKernelGGL(k_expand_groups, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_vals[1], n, out);
+    if (out) hipLaunchKernelGGL(k_expand_groups, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_vals[1], n, out);
     HIPCHK(hipGetLastError());
     return NART_OK;
 }
 
-uint32_t lean_stack(const nart_ctx* ctx);
-// traversal-phase quorum of throughput-bound ray-queue launches: the phase ends once the wave's
-// queue is empty and at most this many lanes still trace (0/4/16/32: 134.7/123.5/123.0/129.9 vs
-// 121.6 ms at 8 in round 2)
-#ifndef NART_RQ_QUORUM
-#define NART_RQ_QUORUM 8u
-#endif
+// Resident blocks of a kernel on the context's device (CUs x blocks per CU, at least one).  One
+// query per dispatch and kernel: the callers pass the figure down.
+int resident_blocks(nart_ctx* ctx, const void* kernel, int block, size_t lds, uint32_t* out) {
+    int cus = 0, per_cu = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds));
+    *out = (uint32_t)std::max(1, cus * std::max(per_cu, 1));
+    return NART_OK;
+}
 
+// LDS of a k_render block: the traversal stack and the staged BVH nodes.
+size_t k_render_lds(const nart_ctx* ctx) {
+    return (size_t)ctx->stack_depth * 256 * 8 + node_lds_bytes(render_lds_nodes(ctx));
+}
+
+// The path schedule's knobs, each read once per launch.
+SchedKnobs read_sched_knobs() {
+    SchedKnobs k;
+    const std::pair<const char*, Knob*> all[] = {
+        {"NART_PRIMARY_PACKET", &k.primary_packet}, {"NART_RQ_PRIO", &k.rq_prio}, {"NART_RQ_PAIRS", &k.rq_pairs},
+        {"NART_RQ_HALF", &k.rq_half}, {"NART_RQ_QUAD", &k.rq_quad}, {"NART_RQ_SETPRIO", &k.rq_setprio},
+        {"NART_RQ_ORDER", &k.rq_order}, {"NART_RQ_TOPF", &k.rq_topf}, {"NART_PROBE_SUB", &k.probe_sub},
+        {"NART_QUEUE_K", &k.queue_k}};
+    for (const auto& [name, knob] : all) {
+        const char* e = env_opt(name);
+        *knob = Knob{e != nullptr, e && *e, e && *e ? std::atof(e) : 0.0};
+    }
+    return k;
+}
+
+// What the scheduling steps of one launch_render share.
+using PathKernel = void (*)(DScene, RenderArgs);
+struct PathLaunch {
+    nart_ctx* ctx;
+    hipStream_t st;
+    const PathSchedule& plan;
+    PathKernel probe;  // k_render with the cost counters, its LDS and its arguments
+    size_t lds;
+    RenderArgs args;
+};
+
+// Cost probe: the first sample of the plan's pixels, work estimates into ctx->d_cost.
+int run_probe(const PathLaunch& L) {
+    nart_ctx* ctx = L.ctx;
+    RenderArgs pb = L.args;
+    pb.spp = 1;
+    pb.cost = ctx->d_cost;
+    pb.probe_sub = L.plan.probe == PathProbe::Sampled ? L.plan.probe_sub : 0u;
+    hipLaunchKernelGGL(L.probe, dim3(L.plan.probe_blocks), dim3(256), L.lds, L.st, ctx->scene, pb);
+    HIPCHK(hipGetLastError());
+    return NART_OK;
+}
+
+// Groups: the persistent grid's waves take 64-slot groups from b.ghead, in slot order or in b.gorder.
+int schedule_groups(const PathLaunch& L, RenderArgs& b) {
+    nart_ctx* ctx = L.ctx;
+    const PathSchedule& plan = L.plan;
+    HIPCHK(hipMemsetAsync(ctx->d_qhead, 0, sizeof(uint32_t), L.st));
+    b.ghead = ctx->d_qhead;
+    if (plan.probe == PathProbe::None) return NART_OK;
+    const uint32_t ng = (b.n_slots + 63) / 64;
+    int rc = run_probe(L);
+    if (!rc) rc = sort_groups_by_cost(ctx, b.n_slots, plan.probe_sub, nullptr, L.st);
+    if (rc) return rc;
+    b.gorder = ctx->d_vals[1];
+    if (plan.order == 2) {  // the E costliest groups first, each class in slot order
+        hipLaunchKernelGGL(k_group_class, dim3((ng + 255) / 256), dim3(256), 0, L.st, ctx->d_vals[1], ng, plan.E,
+                           ctx->d_keys[0], ctx->d_vals[0]);
+        size_t tmp = ctx->cap_sort_tmp;
+        HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->d_sort_tmp, tmp, ctx->d_keys[0], ctx->d_keys[1], ctx->d_vals[0],
+                                                  ctx->d_queue, (int)ng, 0, 1, L.st));
+        b.gorder = ctx->d_queue;
+    }
+    return NART_OK;
+}
+
+// PixelQueue: the probe-ordered queue (queue_entry) and the refill head of the persistent grid.
+// WholeGroupsByCost: one lane per pixel, the groups launched costliest first.
+int schedule_pixel_queue(const PathLaunch& L, RenderArgs& b) {
+    nart_ctx* ctx = L.ctx;
+    const PathSchedule& plan = L.plan;
+    const uint32_t n = b.n_slots;
+    const bool whole = plan.shape == PathShape::WholeGroupsByCost;
+    const dim3 eg((n + 255) / 256), block(256);
+    int rc = run_probe(L);
+    if (!rc) rc = sort_groups_by_cost(ctx, n, 64, whole ? ctx->d_queue : ctx->d_cost, L.st);
+    b.queue = ctx->d_queue;
+    if (rc || whole) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_vals[1], ctx->d_cost, (size_t)n * 4, hipMemcpyDeviceToDevice, L.st));
+    // d_vals[1] = pixels by cost class; partition the rest (slot order) from the top k*W
+    hipLaunchKernelGGL(k_flag_top, eg, block, 0, L.st, ctx->d_vals[1], n, plan.k * plan.W, ctx->d_keys[0]);
+    hipLaunchKernelGGL(k_iota, eg, block, 0, L.st, ctx->d_cost, n);
+    size_t tmp = ctx->cap_sort_tmp;
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->d_sort_tmp, tmp, ctx->d_keys[0], ctx->d_keys[1], ctx->d_cost,
+                                              ctx->d_vals[0], (int)n, 0, 1, L.st));
+    hipLaunchKernelGGL(k_build_queue, dim3((plan.qlen + 255) / 256), block, 0, L.st, ctx->d_vals[1], ctx->d_vals[0], n,
+                       plan.W, plan.k, plan.rq_prio ? RQ_PRIO_BIT : 0u, plan.pairs, plan.half, plan.quad, ctx->d_queue);
+    b.rq_setprio = plan.rq_setprio;
+    b.rq_prio = plan.rq_prio;
+    b.rq_pairs = plan.pairs;
+    b.qlen = plan.qlen;
+    HIPCHK(hipMemsetAsync(ctx->d_qhead, 0, sizeof(uint32_t), L.st));
+    b.qhead = ctx->d_qhead;
+    b.qbase = plan.qbase;
+    return NART_OK;
+}
+
+uint32_t lean_stack(const nart_ctx* ctx);
+
+// One batch of the path integrator: k_primary, what the plan's shape prepares, the path kernel.
+// The template parameters select kernel builds; host/path_schedule.h plan_path decides the rest.
+// resident_k: resident blocks of k_render (dispatch_megakernel's occupancy query).
 template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true>
-int launch_render(nart_ctx* ctx, const RenderArgs& a_in, hipStream_t st) {
+int launch_render(nart_ctx* ctx, const RenderArgs& a_in, uint32_t resident_k, hipStream_t st) {
     auto kern = k_render<EXT, COUNT, ENV>;
     auto kern_rq = k_render_rq<EXT, COUNT, ENV, FM, WV, PR>;
     constexpr uint32_t RQB = RQ_BLOCK_OF(COUNT, WV);  // ray-queue block (kernels.h)
     RenderArgs a = a_in;
-    if (EXT) {
-        // the dielectric list's entries beyond ILIST_REG: one column per thread of the largest
-        // launch below (whole 512-thread blocks over every slot)
-        const size_t lanes = ((size_t)a.n_slots + 511) / 512 * 512;
-        const size_t bytes = lanes * (ILIST_MAX - ILIST_REG) * sizeof(uint2);
-        if (bytes > ctx->cap_ilist) {
-            if (ctx->d_ilist) HIPCHK(hipFree(ctx->d_ilist));
-            ctx->d_ilist = nullptr;
-            ctx->cap_ilist = 0;
-            if (hipMalloc(&ctx->d_ilist, bytes) != hipSuccess) return fail(ctx, NART_E_OOM, "hipMalloc dielectric lists");
-            ctx->cap_ilist = bytes;
-        }
-        a.ilist_ext = static_cast<uint2*>(ctx->d_ilist);
-        a.ilist_stride = (uint32_t)lanes;
-    }
+    int rc = EXT ? ensure_ilist(ctx, a) : NART_OK;
+    if (rc) return rc;
     static std::atomic<uint64_t> attr{0};  // dynamic LDS above the 64 KiB default, set once per device
     const uint64_t dbit = 1ull << (ctx->device & 63);
     if (!(attr.load() & dbit)) {
@@ -735,26 +810,30 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, hipStream_t st) {
     // run k_render (256-lane blocks, stack_depth * 2 KiB) instead -- same image.
     const bool rq = ctx->variant == 0 && rq_fits(ctx);
     ctx->fm_used = rq ? FM : FT_ALL;
-    if (rq && FM != FT_ALL) ctx->sched |= NART_SCHED_SPECIALIZED;
-    if (rq && WV == 3 && !PR) ctx->sched |= NART_SCHED_LEAN;
-    // camera rays first, coherently (k_primary; leaving them to the path kernel measured C3 470 vs
-    // 407 ms per frame, profiles/r02h_env_ab.log)
-    const bool primary = true;
-
-    // rounds of resident waves from which a launch counts as throughput-bound: ray-queue quorum 8
-    // (else 0), no priority lanes or speculative pairs
-    const double q_rounds = 3.0;
+    // k_render (the cost probe, the fallback): top BVH nodes staged in LDS.  The ray-queue kernel,
+    // one block per CU (2 or 3 waves per SIMD): outbox, results and id lists take part of the LDS;
+    // the lean build keeps lean_stack(ctx) stack levels there and the rest in a global column per
+    // thread.  (Staging the top BVH nodes in LDS for k_primary too measured slower: a wave's
+    // coherent rays read the same node, which the L1 broadcasts: 9.7 vs 8.2 ms at 64 spp)
     RenderArgs b = a;
     b.lds_nodes = render_lds_nodes(ctx);
-    const size_t lds = (size_t)ctx->stack_depth * 256 * 8 + node_lds_bytes(b.lds_nodes);
-    RenderArgs brq = a;  // ray-queue kernel: outbox, results and id lists take part of the LDS
-    if (rq && primary && ctx->d_prim && a.cost == nullptr) {
-        // (staging the top BVH nodes in LDS, as the path kernel does, measured slower here: a
-        // wave's coherent rays read the same node, which the L1 broadcasts: 9.7 vs 8.2 ms at 64 spp)
-        // camera rays as wave packets (path.h traverse_packet; C3 -1.7 ms, C4 -31 ms per frame,
-        // profiles/r04_primary_packet_ab.log); NART_PRIMARY_PACKET=0 (read per call): one ray per lane
+    const size_t lds = k_render_lds(ctx);
+    const uint32_t skd = WV == 3 ? lean_stack(ctx) : ctx->stack_depth;
+    const uint32_t rq_nodes = render_lds_nodes(ctx, rq_lds_bytes(skd, RQB), NART_RENDER_WAVES);
+    const size_t lds_rq = rq_lds_bytes(skd, RQB) + node_lds_bytes(rq_nodes);
+    uint32_t resident_rq = 1;
+    if (rq && (rc = resident_blocks(ctx, (const void*)kern_rq, RQB, lds_rq, &resident_rq))) return rc;
+
+    const PathLaunchIn in{a.n_slots, resident_k, resident_rq * (RQB / 256), RQB, WV, PR, ENV, rq, FM != FT_ALL,
+                          ctx->d_prim && a.cost == nullptr};
+    const PathSchedule plan = plan_path(in, read_sched_knobs());
+    if (plan.error) return fail(ctx, NART_E_INVALID, plan.error);
+    ctx->sched |= plan.sched;
+
+    const uint32_t* prim = a.prim;
+    if (plan.primary) {
         RenderArgs pa = a;
-        pa.packet = env_num("NART_PRIMARY_PACKET", 1.0) != 0.0 ? 1u : 0u;
+        pa.packet = plan.packet;
         hipLaunchKernelGGL((k_primary<COUNT, ENV, FM>), dim3((a.n_slots + 255) / 256), dim3(256),
                            (size_t)ctx->stack_depth * 256 * 8, st, ctx->scene, pa, ctx->d_prim);
         HIPCHK(hipGetLastError());
@@ -762,246 +841,50 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, hipStream_t st) {
             HIPCHK(hipEventRecord(ctx->ev[4], st));
             ctx->primary_ran = true;
         }
-        ctx->sched |= NART_SCHED_PRIMARY;
         ctx->prim_valid = true;
-        brq.prim = ctx->d_prim;
+        prim = ctx->d_prim;
     }
-    // one ray-queue block per CU (2 or 3 waves per SIMD); the lean build keeps lean_stack(ctx)
-    // stack levels in LDS and the rest in a global column per thread
-    const uint32_t skd = WV == 3 ? lean_stack(ctx) : ctx->stack_depth;
-    brq.lds_nodes = render_lds_nodes(ctx, rq_lds_bytes(skd, RQB), NART_RENDER_WAVES);
-    const size_t lds_rq = rq_lds_bytes(skd, RQB) + node_lds_bytes(brq.lds_nodes);
-    const dim3 block(256);
-    uint32_t blocks = (a.n_slots + 255) / 256;
-    const int mode = queue_mode();
-    int cus = 0, per_cu = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, 256, lds));
-    const uint32_t resident_k = (uint32_t)std::max(1, cus * std::max(per_cu, 1));
-    // rounds of resident waves (of k_render: the same figure for every build, so that the lean
-    // build's choice, lean_fits, and this launch's thresholds agree)
-    const double R = (double)a.n_slots / (64.0 * 4.0 * resident_k);
-    // resident blocks of 256 lanes of the kernel this launch runs: the ray-queue kernel holds one
-    // 512- or 768-lane block per CU, so its persistent grid and the waves the queue deals its
-    // first round over are its own (the lean build has 1.5x k_render's resident lanes)
-    int per_cu_rq = 0;
-    if (rq) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_rq, (const void*)kern_rq, RQB, lds_rq));
-    const uint32_t resident = rq ? (uint32_t)std::max(1, cus * std::max(per_cu_rq, 1)) * (RQB / 256) : resident_k;
-    const uint32_t W = resident * 4;  // resident (persistent) waves
-    // the ray-queue kernel takes kern's place (its own LDS layout); the cost probe keeps k_render
-    auto launch = [&](uint32_t nblocks, const RenderArgs& args) -> int {
-        if (rq) {
-            // traversal-phase quorum: 8 on throughput-bound launches; 0 (every queued ray resolved
-            // before the path phase) on small shards, whose costliest pixels' chains set the time
-            // (1/8 C3 shard: 100.5 -> 96.0 ms)
-            RenderArgs r2 = args;
-            r2.lds_nodes = brq.lds_nodes;
-            r2.prim = brq.prim;
-            r2.stack_lds = skd;
-            r2.rq_quorum = R >= q_rounds ? NART_RQ_QUORUM : 0u;
-            const uint32_t per = RQB / 256;  // launches are counted in blocks of 256
-            const uint32_t grid = (nblocks + per - 1) / per;
-            const size_t threads = (size_t)grid * RQB;
-            if (r2.stack_lds < 1 || r2.stack_lds > ctx->stack_depth || lds_rq > (size_t)160 * 1024)
-                return fail(ctx, NART_E_INVALID, "ray-queue LDS layout out of range");
-            // per-thread global columns, indexed by the global thread id: sized from this grid
-            if (EXT && threads > r2.ilist_stride)
-                return fail(ctx, NART_E_INVALID, "dielectric-list columns smaller than the launch");
-            if (skd < ctx->stack_depth) {
-                const size_t bytes = threads * (ctx->stack_depth - skd) * sizeof(int2);
-                if (bytes > ctx->cap_gstack) {
-                    if (ctx->d_gstack) HIPCHK(hipFree(ctx->d_gstack));
-                    ctx->d_gstack = nullptr;
-                    ctx->cap_gstack = 0;
-                    if (hipMalloc(&ctx->d_gstack, bytes) != hipSuccess)
-                        return fail(ctx, NART_E_OOM, "hipMalloc traversal stack columns");
-                    ctx->cap_gstack = bytes;
-                }
-                r2.gstack = static_cast<int2*>(ctx->d_gstack);
-            }
-            hipLaunchKernelGGL(kern_rq, dim3(grid), dim3(RQB), lds_rq, st, ctx->scene, r2);
-        } else {
-            hipLaunchKernelGGL(kern, dim3(nblocks), block, lds, st, ctx->scene, args);
-        }
+    if (plan.queue_room && (rc = ensure_queue(ctx, plan.queue_room))) return rc;
+    const PathLaunch L{ctx, st, plan, k_render<EXT, true, ENV>, lds, b};
+    switch (plan.shape) {
+        case PathShape::Direct: break;
+        case PathShape::Groups: rc = schedule_groups(L, b); break;
+        case PathShape::WholeGroupsByCost:
+        case PathShape::PixelQueue: rc = schedule_pixel_queue(L, b); break;
+    }
+    if (rc) return rc;
+
+    if (!rq) {
+        hipLaunchKernelGGL(kern, dim3(plan.blocks), dim3(256), lds, st, ctx->scene, b);
         HIPCHK(hipGetLastError());
         return NART_OK;
-    };
-    if (mode > 0) {
-        if (blocks > resident) {  // more pixels than resident lanes: persistent grid + queue
-            const uint32_t n = a.n_slots;
-            // room for the speculative groups' duplicates: qlen = n + (Q - 1) * k * W with Q * k <= 64
-            int rc = ensure_queue(ctx, n + 63u * W);
-            if (rc) return rc;
-            const dim3 eg((n + 255) / 256);
-            // costly pixels per first-round wave: few when the shard is small (their serial chains
-            // bound the frame), all 64 (packed, launched first) when there are many rounds
-            // Priority lanes for the costly pixels in the ray-queue kernel (NART_RQ_PRIO=0: off, 2:
-            // also on launches of >= 3 rounds), run as speculative lane groups of Q lanes
-            // (NART_RQ_PAIRS: 0 one lane per pixel, 1 or 2 pairs, 4 groups of four).  Only small
-            // shards (< 3 rounds of resident waves), whose time is their costliest pixels' chains: on
-            // throughput-bound launches the priority breaks and the speculative duplicates cost
-            // throughput (1/2 C3 shard 238 -> 249 ms, C4 batches 3175 -> 3381 ms with them on)
-            const int prio_env = (int)env_num("NART_RQ_PRIO", 1.0);
-            const bool prio_on = prio_env == 2 || (prio_env == 1 && R < q_rounds);
-            const int pe = (int)env_num("NART_RQ_PAIRS", NART_RQ_GROUP_LANES);
-            const uint32_t Q = pe <= 0 ? 0u : (pe >= 4 ? 4u : 2u);
-            // (the lean build has no priority lanes: it runs only where prio_on is false anyway)
-            const uint32_t pbit = (rq && prio_on && PR) ? RQ_PRIO_BIT : 0u;
-            // Half waves (default): the costly pixels only on the first 4 waves of each ray-queue
-            // block (8 or 12 waves), PB = 2 or 3 shares each -- one such wave per SIMD -- and those
-            // waves at a raised issue priority (s_setprio 2, NART_RQ_SETPRIO) while they hold priority
-            // work, so the SIMD's other waves fill their stalls instead of sharing issue with them.
-            // C3 1/8 shard, every rank: mean 84.2 -> 80.9 ms, worst 87-92 -> 86.0 ms
-            // (profiles/r05h_chain_schedule_ab.log).  NART_RQ_HALF=0: dealt over every wave.
-            const uint32_t BW = RQB / 64u, PB = BW / 4u;
-            // costly pixels per first-round wave: few when the shard is small (their serial chains
-            // bound the frame), all 64 (packed, launched first) when there are many rounds.  C3 1/8
-            // shard, mean of the 8 ranks with half waves at k = 4/6/8/12/14/16 per two-wave block
-            // share: 95.2/88.8/81.4/80.9/81.3/81.6 ms; three-wave blocks keep the same number of
-            // costly pixels (k W constant: 8 per share).  The half layout is settled first, so a
-            // configuration it does not fit falls back to k = 8 dealt over every wave.
-            const uint32_t k_half = PB == 2u ? 12u : 8u;
-            const bool half = pbit && rq && env_num("NART_RQ_HALF", 1.0) != 0.0 && (W % BW) == 0u && R < 3.0 &&
-                              PB * ((Q && Q * k_half <= 64u) ? Q : 1u) * k_half <= 64u;
-            uint32_t k = R >= 3.0 ? 32u : (half ? k_half : 8u);
-            // ray-queue kernel: wave-group refill from 6 rounds of resident waves (C3 1/2 shard, 8
-            // rounds: 241 -> 235 ms; C4 batches, ~9 rounds: 1385 -> 1566 Msamples/s).  Below that a
-            // wave of costly groups outlasts the rest (1/4 shard, 4 rounds: 146 -> 211 ms; with the
-            // groups cost-ordered still 156 vs 114 ms), and the probe-ordered pixel queue with
-            // priority lanes stays.  The lean build (from 3 rounds where it runs: scenes without
-            // glass) takes groups from there: C2 1/4 shard 32.2 -> 27.9 ms
-            // (profiles/r06x_mid_shards.log)
-            const double g_rounds = WV == 3 ? 3.0 : 6.0;
-            if (R >= (rq ? g_rounds : 12.0) && mode == 2 && !env_opt("NART_QUEUE_K")) {
-                // many rounds: the slot order (costly waves interleaved with cheap ones in time)
-                // measured faster than any reordering; no probe.  The ray-queue kernel runs it on
-                // a persistent grid whose waves take wave-sized slot groups in that order
-                // (one wave per group, blocks retiring as a whole: 422 vs 407 ms, profiles/r02h_env_ab.log)
-                const bool groups = rq;
-                if (groups) {
-                    HIPCHK(hipMemsetAsync(ctx->d_qhead, 0, sizeof(uint32_t), st));
-                    b.ghead = ctx->d_qhead;
-                    // group order (NART_RQ_ORDER): 0 slot order; 1 costliest group first (cost
-                    // probe); 2 (default) the NART_RQ_TOPF % (default 10) costliest groups first,
-                    // each class in slot order.  In slot order the costly groups (behind the
-                    // glass) taken last left a tail: at 90 % of the C3 launch only 25 of 2,048
-                    // waves were still running (WAVEPROF timeline).  C3 frame 445 -> 407 ms
-                    // (probe included; order 1: 408, top 20 / 35 %: 408 / 408 ms)
-                    // the lean build's slower waves leave a longer tail behind the costly groups taken
-                    // late: fully cost-ordered groups (1) measured C3 227.5 vs 235-247 ms for the
-                    // costliest 10 % first (2), 250 / 245 / 260 ms for 5 / 20 / 35 %, slot order 299
-                    // (profiles/r06r_group_order_ab.log), C2 75 vs 77 ms; C4's environment-light
-                    // frame keeps 2 (4K/128: 609 vs 624 ms, r06s_group_order_c4_c2.log).  The two-wave
-                    // build's launches of 6-12 rounds (C3 1/2 shard, chain-bound) also take 1: worst
-                    // rank 183-184 -> 167-169 ms (profiles/r06x_mid_shards.log)
-                    const int order = (int)env_num("NART_RQ_ORDER", !ENV ? 1.0 : 2.0);
-                    ctx->sched |= NART_SCHED_WAVE_GROUPS;
-                    if (order == 1 || order == 2) {
-                        // cost probe: the first sample of NART_PROBE_SUB (default 8) evenly spaced
-                        // pixels of every 64-slot group (64: every pixel).  Only the group order
-                        // depends on it (costliest NART_RQ_TOPF % first), and that order is not
-                        // sensitive to the estimate (TOPF 10 / 20 / 35 %: 407 / 408 / 408 ms)
-                        // Launches of fewer than NART_PROBE_SUB_ROUNDS (12) rounds of resident waves
-                        // probe every pixel: there a costly group the sample missed and took late
-                        // sets the tail (C4 1/8 shards, 8 rounds: worst rank 488-496 ms probing every
-                        // pixel, 552-556 ms sampled; profiles/r05ah_c4_probe_ab.log)
-                        const uint32_t ng = (n + 63) / 64;
-                        const double sub_rounds = 12.0;
-                        uint32_t sub = (uint32_t)env_num("NART_PROBE_SUB", R >= sub_rounds ? 8.0 : 64.0);
-                        if (sub != 1u && sub != 2u && sub != 4u && sub != 8u && sub != 16u && sub != 32u) sub = 64u;
-                        RenderArgs pb = b;
-                        pb.spp = 1;
-                        pb.cost = ctx->d_cost;
-                        pb.ghead = nullptr;
-                        pb.probe_sub = sub < 64u ? sub : 0u;
-                        const uint32_t pblocks = sub < 64u ? (ng * sub + 255u) / 256u : blocks;
-                        hipLaunchKernelGGL((k_render<EXT, true, ENV>), dim3(pblocks), block, lds, st, ctx->scene, pb);
-                        const dim3 gg((ng + 255) / 256);
-                        hipLaunchKernelGGL(k_group_keys, gg, block, 0, st, ctx->d_cost, n, ctx->d_keys[0], ctx->d_vals[0],
-                                           sub);
-                        size_t tmp = ctx->cap_sort_tmp;
-                        HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->d_sort_tmp, tmp, ctx->d_keys[0], ctx->d_keys[1],
-                                                                  ctx->d_vals[0], ctx->d_vals[1], (int)ng, 0, 32, st));
-                        if (order == 1) {
-                            b.gorder = ctx->d_vals[1];
-                        } else {
-                            const double f = env_num("NART_RQ_TOPF", 10.0);
-                            const uint32_t E = (uint32_t)std::min<double>(ng, std::max(0.0, f) * 0.01 * ng);
-                            hipLaunchKernelGGL(k_group_class, gg, block, 0, st, ctx->d_vals[1], ng, E, ctx->d_keys[0],
-                                               ctx->d_vals[0]);
-                            tmp = ctx->cap_sort_tmp;
-                            HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->d_sort_tmp, tmp, ctx->d_keys[0], ctx->d_keys[1],
-                                                                      ctx->d_vals[0], ctx->d_queue, (int)ng, 0, 1, st));
-                            b.gorder = ctx->d_queue;
-                        }
-                    }
-                    // launches are counted in blocks of 256 threads
-                    blocks = std::min(blocks, resident);
-                }
-                return launch(blocks, b);
-            }
-            if (env_opt("NART_QUEUE_K")) k = (uint32_t)std::max(1.0, std::min(64.0, env_num("NART_QUEUE_K", 8.0)));
-            const bool refill = k < 64u || mode == 1;
-            if (mode == 1) {
-                hipLaunchKernelGGL(k_iota, eg, block, 0, st, ctx->d_queue, n);
-            } else {
-                RenderArgs pb = b;  // cost probe: the first sample of every pixel
-                pb.spp = 1;
-                pb.cost = ctx->d_cost;
-                hipLaunchKernelGGL((k_render<EXT, true, ENV>), dim3(blocks), block, lds, st, ctx->scene, pb);
-                int rc2 = sort_groups_by_cost(ctx, n, k == 64u ? ctx->d_queue : ctx->d_cost, st);
-                if (rc2) return rc2;
-                size_t tmp = 0;
-                if (k == 64u) {  // whole groups, costliest first (coherent waves, longest chains first)
-                    b.queue = ctx->d_queue;
-                    return launch(blocks, b);
-                }
-                HIPCHK(hipMemcpyAsync(ctx->d_vals[1], ctx->d_cost, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-                // d_vals[1] = pixels by cost class; partition the rest (slot order) from the top k*W
-                hipLaunchKernelGGL(k_flag_top, eg, block, 0, st, ctx->d_vals[1], n, k * W, ctx->d_keys[0]);
-                hipLaunchKernelGGL(k_iota, eg, block, 0, st, ctx->d_cost, n);
-                tmp = ctx->cap_sort_tmp;
-                HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->d_sort_tmp, tmp, ctx->d_keys[0], ctx->d_keys[1],
-                                                          ctx->d_cost, ctx->d_vals[0], (int)n, 0, 1, st));
-                const uint32_t pairs = (pbit && Q && Q * k <= 64u) ? Q : 0u;
-                // (re-checked: NART_QUEUE_K may have changed k)
-                const bool hw = half && PB * (pairs ? pairs : 1u) * k <= 64u;
-                // NART_RQ_QUAD (A/B): each first-round wave's costliest pixel gets four lanes
-                const bool quad = pbit && pairs == 2u && 2u * k + 2u <= 64u && env_num("NART_RQ_QUAD", 0.0) != 0.0;
-                const uint32_t qlen = n + (pairs ? (pairs - 1u) * k * W : 0u) + (quad ? 2u * W : 0u);
-                hipLaunchKernelGGL(k_build_queue, dim3((qlen + 255) / 256), block, 0, st, ctx->d_vals[1], ctx->d_vals[0],
-                                   n, W, k, pbit, pairs, hw && !quad ? BW : 0u, quad ? 1u : 0u, ctx->d_queue);
-                b.rq_setprio = pbit ? (uint32_t)std::max(0.0, env_num("NART_RQ_SETPRIO", hw ? 1.0 : 0.0)) : 0u;
-                if (hw && !quad) ctx->sched |= NART_SCHED_HALF_WAVES;
-                b.rq_prio = pbit ? 1u : 0u;
-                b.rq_pairs = pairs;
-                b.qlen = qlen;
-                if (pbit) ctx->sched |= NART_SCHED_PRIORITY;
-                if (pairs) ctx->sched |= NART_SCHED_SPEC_PAIRS;
-            }
-            b.queue = ctx->d_queue;
-            if (refill) {
-                HIPCHK(hipMemsetAsync(ctx->d_qhead, 0, sizeof(uint32_t), st));
-                b.qhead = ctx->d_qhead;
-                ctx->sched |= NART_SCHED_PROBE_QUEUE;
-                // whole ray-queue blocks, so that every first-round lane's entry lies below qbase
-                const uint32_t per = rq ? RQB / 256 : 1u;
-                blocks = (resident + per - 1u) / per * per;
-                b.qbase = blocks * 256;
-            }
-        }
     }
-    return launch(blocks, b);
+    // the ray-queue kernel takes k_render's place, with its own LDS layout
+    b.lds_nodes = rq_nodes;
+    b.prim = prim;
+    b.stack_lds = skd;
+    b.rq_quorum = plan.rq_quorum;
+    const uint32_t per = RQB / 256;  // the plan counts launches in blocks of 256
+    const uint32_t grid = (plan.blocks + per - 1) / per;
+    const size_t threads = (size_t)grid * RQB;
+    if (b.stack_lds < 1 || b.stack_lds > ctx->stack_depth || lds_rq > (size_t)160 * 1024)
+        return fail(ctx, NART_E_INVALID, "ray-queue LDS layout out of range");
+    // per-thread global columns, indexed by the global thread id: sized from this grid
+    if (EXT && threads > b.ilist_stride) return fail(ctx, NART_E_INVALID, "dielectric-list columns smaller than the launch");
+    if (skd < ctx->stack_depth && (rc = ensure_gstack(ctx, threads, ctx->stack_depth - skd, b))) return rc;
+    hipLaunchKernelGGL(kern_rq, dim3(grid), dim3(RQB), lds_rq, st, ctx->scene, b);
+    HIPCHK(hipGetLastError());
+    return NART_OK;
 }
 
 template <bool ENV>
-int launch_render_maxl(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
+int launch_render_maxl(nart_ctx* ctx, const RenderArgs& a, uint32_t res, hipStream_t st) {
     // a path grows the dielectric list by at most one entry per bounce: the register list alone
     // serves bounces <= ILIST_REG; deeper ones (up to 32) spill it to the per-lane columns
     const bool c = ctx->counters;
     if (a.bounces <= ILIST_REG)
-        return c ? launch_render<false, true, ENV>(ctx, a, st) : launch_render<false, false, ENV>(ctx, a, st);
-    return c ? launch_render<true, true, ENV>(ctx, a, st) : launch_render<true, false, ENV>(ctx, a, st);
+        return c ? launch_render<false, true, ENV>(ctx, a, res, st) : launch_render<false, false, ENV>(ctx, a, res, st);
+    return c ? launch_render<true, true, ENV>(ctx, a, res, st) : launch_render<true, false, ENV>(ctx, a, res, st);
 }
 
 // Scene-specialised builds of the path kernels (k_render_rq, k_primary): glassSphere's (C3:
@@ -1028,19 +911,6 @@ uint32_t lean_stack(const nart_ctx* ctx) {
     return k;
 }
 
-// Rounds of resident waves a launch of n slots spans (launch_render's R): from 3 on the launch is
-// throughput-bound and runs without priority lanes or speculative pairs.
-double launch_rounds(nart_ctx* ctx, uint32_t n) {
-    int cus = 0, per_cu = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) return 0.0;
-    const size_t lds = (size_t)ctx->stack_depth * 256 * 8 + node_lds_bytes(render_lds_nodes(ctx));
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_render<false, false, false>, 256, lds) !=
-        hipSuccess)
-        return 0.0;
-    const double W = (double)std::max(1, cus * std::max(per_cu, 1)) * 4.0;
-    return (double)n / (64.0 * W);
-}
-
 // The lean three-waves-per-SIMD build (kernels.h WV = 3) for throughput-bound launches.  It raises
 // throughput (C3 whole frame, 16 rounds of resident waves: path kernels 276.6 -> ~241 ms; C4 4K
 // frame and its 1/8 shards, 8 rounds: 492 -> 456 ms) but each of its waves runs slower, which
@@ -1048,37 +918,43 @@ double launch_rounds(nart_ctx* ctx, uint32_t n) {
 // paths behind the dielectric) set the time of their smaller launches, where the two-wave build
 // stays faster (C3 1/2 and 1/4 shards, 8 and 4 rounds: 172-185 / 114 ms vs 202-206 / 131 ms lean;
 // profiles/r06k_lean_rounds_ab.log), so they take it from 12 rounds on, other scenes from 3.
-bool lean_fits(nart_ctx* ctx, const RenderArgs& a) {
+bool lean_fits(const nart_ctx* ctx, const RenderArgs& a, uint32_t resident_k) {
     if (ctx->variant != 0 || !ctx->lean || !rq_fits(ctx)) return false;
     // glass scenes' small launches are bound by their costly pixels' chains, which the priority
     // lanes of the two-wave build shorten (C3 1/2, 1/4 shards: 183 / 115 ms two-wave vs 194 / 130
     // lean); scenes without glass or an environment light take the lean build from 1.5 rounds
     // (C2 1/8 shards, 2 rounds: mean 22.1 vs 23.9 ms, profiles/r06zg_c2_shard8.log)
     const double from = (ctx->features & FT_GLASS) ? 12.0 : (ctx->has_env ? 3.0 : 1.5);
-    return launch_rounds(ctx, a.n_slots) >= env_num("NART_LEAN_ROUNDS", from);
+    return rounds_of(a.n_slots, resident_k) >= env_num("NART_LEAN_ROUNDS", from);
 }
 
 int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
+    // resident blocks of k_render, the figure every threshold in rounds of resident waves refers to
+    // (lean_fits, plan_path).  Every k_render build is compiled for two waves per SIMD and has the
+    // same LDS, so one build's occupancy stands for all of them.
+    uint32_t res = 0;
+    int rc = resident_blocks(ctx, (const void*)k_render<false, false, false>, 256, k_render_lds(ctx), &res);
+    if (rc) return rc;
     const uint32_t f = ctx->features;
     auto covers = [f](uint32_t m) { return (f & ~m) == 0u; };
     if (ctx->specialize && !ctx->counters && a.bounces <= ILIST_REG) {
         if (!ctx->has_env && covers(FM_DIFFUSE)) {
-            if (lean_fits(ctx, a)) return launch_render<false, false, false, FM_DIFFUSE, 3, false>(ctx, a, st);
-            return launch_render<false, false, false, FM_DIFFUSE>(ctx, a, st);
+            if (lean_fits(ctx, a, res)) return launch_render<false, false, false, FM_DIFFUSE, 3, false>(ctx, a, res, st);
+            return launch_render<false, false, false, FM_DIFFUSE>(ctx, a, res, st);
         }
         if (!ctx->has_env && covers(FM_GLASS)) {
-            if (lean_fits(ctx, a)) return launch_render<false, false, false, FM_GLASS, 3, false>(ctx, a, st);
+            if (lean_fits(ctx, a, res)) return launch_render<false, false, false, FM_GLASS, 3, false>(ctx, a, res, st);
             // (small shards keep two waves per SIMD: the priority-lane build at three, 168 VGPRs with
             // 14 spilled, measured C3 1/8 shards worst 83-85 vs 79-81 ms, mean 79.5-79.8 vs 75.9-76.0;
             // profiles/r06l_three_wave_prio_ab.log)
-            return launch_render<false, false, false, FM_GLASS>(ctx, a, st);
+            return launch_render<false, false, false, FM_GLASS>(ctx, a, res, st);
         }
         if (ctx->has_env && covers(FM_ENVTEX)) {
-            if (lean_fits(ctx, a)) return launch_render<false, false, true, FM_ENVTEX, 3, false>(ctx, a, st);
-            return launch_render<false, false, true, FM_ENVTEX>(ctx, a, st);
+            if (lean_fits(ctx, a, res)) return launch_render<false, false, true, FM_ENVTEX, 3, false>(ctx, a, res, st);
+            return launch_render<false, false, true, FM_ENVTEX>(ctx, a, res, st);
         }
     }
-    return ctx->has_env ? launch_render_maxl<true>(ctx, a, st) : launch_render_maxl<false>(ctx, a, st);
+    return ctx->has_env ? launch_render_maxl<true>(ctx, a, res, st) : launch_render_maxl<false>(ctx, a, res, st);
 }
 
 // Volume integrator: k_render_volume_sm (lanes advance one tentative collision per iteration and
@@ -1097,62 +973,58 @@ int dispatch_volume(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
     // 10.5 rounds: 134 -> 122 ms); smaller ones keep the unconstrained build, whose lanes' serial
     // chains are shorter (C5 1/2, 1/4, 1/8 shards: 79 / 74 / 71 ms vs 83 / 80 / 76 with 4 waves;
     // profiles/r03h_vol_w4_ab.log)
-    int cus = 0, per_cu = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_render_volume_sm<false, 1>, 256, dl));
-    const uint32_t resident = (uint32_t)std::max(1, cus * std::max(per_cu, 1));
+    uint32_t resident = 0;
+    int rc = resident_blocks(ctx, (const void*)k_render_volume_sm<false, 1>, 256, dl, &resident);
+    if (rc) return rc;
     const double w4_rounds = 8.0;
     const bool w4 = (double)blocks / (double)resident >= w4_rounds;
     uint32_t grid = blocks;
-    if (queue_mode() == 2) {
-        const uint32_t n = a.n_slots;
-        if (blocks > resident && (double)n / (256.0 * resident) < 12.0 && a.spp > 4) {
-            const uint32_t W = resident * 4;  // resident waves
-            int rc = ensure_queue(ctx, n + 63u * W);
-            if (rc) return rc;
-            RenderArgs pb = b;
-            pb.spp = 4;
-            pb.cost = ctx->d_cost;
-            hipLaunchKernelGGL((k_render_volume_sm<false, 1>), dim3(blocks), block, dl, st, ctx->scene, pb);
-            rc = sort_groups_by_cost(ctx, n, ctx->d_queue, st);
-            if (rc) return rc;
-            b.queue = ctx->d_queue;
-            ctx->sched |= NART_SCHED_VOL_QUEUE;
-            // Sparse waves on shards of < NART_VOL_SPARSE_ROUNDS (default 2) rounds of resident
-            // waves: the costliest groups (probe cost >= NART_VOL_SPARSE_F (4) x the median group's)
-            // spread NART_VOL_SPARSE (16) pixels per wave, the other lanes idle.  A wave executes
-            // the union of its lanes' divergent chains, and a frame's costliest volume pixels
-            // cluster: C5's centre pixels take 30 ms alone at 1,024 spp, 69 ms as a wave of 64.
-            // C5 1/8 shard 73.7 -> 65.3 ms; on larger shards (2+ rounds) the mostly idle sparse
-            // waves hold slots the other groups need (1/2 shard 78 -> 127 ms), and 1-8 pixels per
-            // wave measured worse (profiles/r04h_c5_sparse.log).  Only the order of work changes.
-            const uint32_t S = (uint32_t)std::max(1.0, std::min(64.0, env_num("NART_VOL_SPARSE", 16.0)));
-            const double f = env_num("NART_VOL_SPARSE_F", 4.0), max_rounds = env_num("NART_VOL_SPARSE_ROUNDS", 2.0);
-            if (S < 64u && (64u % S) == 0u && (double)blocks / (double)resident < max_rounds) {
-                const uint32_t ng = (n + 63) / 64;
-                std::vector<uint32_t> keys(ng);
-                HIPCHK(hipMemcpyAsync(keys.data(), ctx->d_keys[1], (size_t)ng * 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                std::vector<uint32_t> costs;  // sorted descending (partial last group excluded)
-                for (uint32_t g = 0; g < ng; ++g)
-                    if (keys[g] != 0xFFFFFFFFu) costs.push_back(0xFFFFFFFEu - keys[g]);
-                uint32_t H = 0;
-                if (!costs.empty()) {
-                    const double med = costs[costs.size() / 2];
-                    while (H < costs.size() && (double)costs[H] >= f * med) ++H;
-                }
-                H = std::min<uint32_t>(H, 63u * W / (64u / S * 64u));  // queue room (ensure_queue)
-                if (H) {
-                    const uint32_t qlen = H * (64u / S) * 64u + (n - 64u * H);
-                    hipLaunchKernelGGL(k_sparse_groups, dim3((qlen + 255) / 256), block, 0, st, ctx->d_vals[1], n, H, S,
-                                       qlen, ctx->d_queue);
-                    b.qlen = qlen;
-                    grid = (qlen + 255) / 256;
-                    ctx->sched |= NART_SCHED_VOL_SPARSE;
-                }
+    const uint32_t n = a.n_slots;
+    if (blocks > resident && rounds_of(n, resident) < 12.0 && a.spp > 4) {
+        const uint32_t W = resident * 4;  // resident waves
+        if ((rc = ensure_queue(ctx, n + 63u * W))) return rc;
+        RenderArgs pb = b;
+        pb.spp = 4;
+        pb.cost = ctx->d_cost;
+        hipLaunchKernelGGL((k_render_volume_sm<false, 1>), dim3(blocks), block, dl, st, ctx->scene, pb);
+        rc = sort_groups_by_cost(ctx, n, 64, ctx->d_queue, st);
+        if (rc) return rc;
+        b.queue = ctx->d_queue;
+        ctx->sched |= NART_SCHED_VOL_QUEUE;
+        // Sparse waves on shards of < NART_VOL_SPARSE_ROUNDS (default 2) rounds of resident
+        // waves: the costliest groups (probe cost >= NART_VOL_SPARSE_F (4) x the median group's)
+        // spread NART_VOL_SPARSE (16) pixels per wave, the other lanes idle.  A wave executes
+        // the union of its lanes' divergent chains, and a frame's costliest volume pixels
+        // cluster: C5's centre pixels take 30 ms alone at 1,024 spp, 69 ms as a wave of 64.
+        // C5 1/8 shard 73.7 -> 65.3 ms; on larger shards (2+ rounds) the mostly idle sparse
+        // waves hold slots the other groups need (1/2 shard 78 -> 127 ms), and 1-8 pixels per
+        // wave measured worse (profiles/r04h_c5_sparse.log).  Only the order of work changes.
+        const uint32_t S = (uint32_t)std::max(1.0, std::min(64.0, env_num("NART_VOL_SPARSE", 16.0)));
+        const double f = env_num("NART_VOL_SPARSE_F", 4.0), max_rounds = env_num("NART_VOL_SPARSE_ROUNDS", 2.0);
+        if (S < 64u && (64u % S) == 0u && (double)blocks / (double)resident < max_rounds) {
+            const uint32_t ng = (n + 63) / 64;
+            std::vector<uint32_t> keys(ng);
+            HIPCHK(hipMemcpyAsync(keys.data(), ctx->d_keys[1], (size_t)ng * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            std::vector<uint32_t> costs;  // sorted descending (partial last group excluded)
+            for (uint32_t g = 0; g < ng; ++g)
+                if (keys[g] != 0xFFFFFFFFu) costs.push_back(0xFFFFFFFEu - keys[g]);
+            uint32_t H = 0;
+            if (!costs.empty()) {
+                const double med = costs[costs.size() / 2];
+                while (H < costs.size() && (double)costs[H] >= f * med) ++H;
             }
-            HIPCHK(hipGetLastError());
+            H = std::min<uint32_t>(H, 63u * W / (64u / S * 64u));  // queue room (ensure_queue)
+            if (H) {
+                const uint32_t qlen = H * (64u / S) * 64u + (n - 64u * H);
+                hipLaunchKernelGGL(k_sparse_groups, dim3((qlen + 255) / 256), block, 0, st, ctx->d_vals[1], n, H, S,
+                                   qlen, ctx->d_queue);
+                b.qlen = qlen;
+                grid = (qlen + 255) / 256;
+                ctx->sched |= NART_SCHED_VOL_SPARSE;
+            }
         }
+        HIPCHK(hipGetLastError());
     }
     if (ctx->counters) hipLaunchKernelGGL((k_render_volume_sm<true, 1>), dim3(grid), block, dl, st, ctx->scene, b);
     else if (w4) hipLaunchKernelGGL((k_render_volume_sm<false, NART_VOL_WV>), dim3(grid), block, dl, st, ctx->scene, b);

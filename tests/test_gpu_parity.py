@@ -91,9 +91,17 @@ def test_framebuffer_glass_sphere_c1(glass_gpu, glass_oracle, glass_scene):
     assert np.isfinite(res).all()
 
 
-@pytest.mark.parametrize("w,h,spp,prio", [(1024, 576, 2, "1"), (1024, 576, 2, "2"), (512, 400, 2, "1"), (512, 400, 6, "1")],
+# schedule_names() of the scheduler cases below on an MI355X (256 CUs)
+_QUEUE = ["primary", "probe_queue", "specialized", "splat_rows"]
+_PRIO = sorted(_QUEUE + ["priority"])
+_PAIRS = sorted(_PRIO + ["spec_pairs"])
+_HALF = sorted(_PAIRS + ["half_waves"])
+
+
+@pytest.mark.parametrize("w,h,spp,prio,sched", [(1024, 576, 2, "1", _QUEUE), (1024, 576, 2, "2", _PAIRS),
+                                                (512, 400, 2, "1", _HALF), (512, 400, 6, "1", _HALF)],
                          ids=["k32", "k32-prio", "k8", "k8-6spp"])
-def test_queue_scheduler_frames(gpu, glass_scene, monkeypatch, w, h, spp, prio):
+def test_queue_scheduler_frames(gpu, glass_scene, monkeypatch, w, h, spp, prio, sched):
     """More traced pixels than resident lanes: the megakernel runs the cost probe, the costly
     pixels are spread over the persistent waves and finished lanes refill from the queue
     (render.hip launch_render); in the ray-queue kernel they are priority lanes whose rays are
@@ -102,16 +110,20 @@ def test_queue_scheduler_frames(gpu, glass_scene, monkeypatch, w, h, spp, prio):
     changes; the frame must not."""
     monkeypatch.setenv("NART_RQ_PRIO", prio)
     p = _params(glass_scene, w, h, spp)
-    g = nart_amd.HipRenderer(glass_scene, variant=0).render(p)
+    st = nart_amd.RenderStats()
+    g = nart_amd.HipRenderer(glass_scene, variant=0).render(p, st)
+    assert st.schedule_names() == sched
     r = oracle.Oracle(glass_scene).render(p)
     assert _bits_equal(g, r), _report(g, r)
 
 
-@pytest.mark.parametrize("pairs,extra", [("2", ""), ("4", ""), ("0", ""), ("2", "NART_RQ_QUAD=1"), ("2", "NART_RQ_HALF=0"),
-                                         ("2", "NART_RQ_SETPRIO=0")],
+@pytest.mark.parametrize("pairs,extra,sched", [("2", "", _HALF), ("4", "", _PAIRS),
+                                               ("0", "", sorted(_PRIO + ["half_waves"])),
+                                               ("2", "NART_RQ_QUAD=1", _PAIRS), ("2", "NART_RQ_HALF=0", _PAIRS),
+                                               ("2", "NART_RQ_SETPRIO=0", _HALF)],
                          ids=["speculative-pairs", "speculative-quads", "single-lanes", "quad-top", "all-waves",
                               "no-setprio"])
-def test_queue_speculative_pairs(gpu, glass_scene, monkeypatch, pairs, extra):
+def test_queue_speculative_pairs(gpu, glass_scene, monkeypatch, pairs, extra, sched):
     """A shard of ~1.2 rounds of resident waves at 24 spp: the costliest pixels run as speculative
     lane pairs (one lane on the chain's frontier sample, the other on the next sample from a
     predicted RNG state; kept only when the prediction was exact).  Long enough chains for both
@@ -123,7 +135,9 @@ def test_queue_speculative_pairs(gpu, glass_scene, monkeypatch, pairs, extra):
     if extra:
         monkeypatch.setenv(*extra.split("="))
     p = _params(glass_scene, 512, 300, 24)
-    g = nart_amd.HipRenderer(glass_scene, variant=0).render(p)
+    st = nart_amd.RenderStats()
+    g = nart_amd.HipRenderer(glass_scene, variant=0).render(p, st)
+    assert st.schedule_names() == sched
     r = oracle.Oracle(glass_scene).render(p)
     assert _bits_equal(g, r), _report(g, r)
 
@@ -163,7 +177,9 @@ def test_group_probe_sampling(gpu, glass_scene, full_frame_1spp, monkeypatch, su
 
 def test_queue_scheduler_environment(gpu, env_scene):
     p = _params(env_scene, 480, 300, 2)
-    g = nart_amd.HipRenderer(env_scene, variant=0).render(p)
+    st = nart_amd.RenderStats()
+    g = nart_amd.HipRenderer(env_scene, variant=0).render(p, st)
+    assert st.schedule_names() == ["half_waves", "primary", "priority", "probe_queue", "spec_pairs", "splat_rows"]
     r = oracle.Oracle(env_scene).render(p)
     assert _bits_equal(g, r), _report(g, r)
 

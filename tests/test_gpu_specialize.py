@@ -84,6 +84,7 @@ def test_glass_sphere_lean_build(gpu, glass_scene, monkeypatch, lds_levels):
     # a whole 1080p frame: 16 rounds of resident waves (glass scenes go lean from 12, render.hip lean_fits)
     a, b, feats, build, sched = _both(glass_scene, _params(glass_scene, 1920, 1080, 1))
     assert build == FM_GLASS and "lean" in sched, (hex(build), sched)
+    assert sched == ["lean", "primary", "specialized", "splat_skew", "wave_groups"]
     assert _same_bits(a, b)
 
 
@@ -92,6 +93,7 @@ def test_cornell_lean_build(gpu, cornell_scene):
     priority lanes or speculative pairs, 768-lane blocks at three waves per SIMD (kernels.h WV)."""
     a, b, feats, build, sched = _both(cornell_scene, _params(cornell_scene, 1280, 720, 2))
     assert build == FM_DIFFUSE and "lean" in sched, (hex(build), sched)
+    assert sched == ["lean", "primary", "specialized", "splat_rows", "wave_groups"]
     assert _same_bits(a, b)
 
 
@@ -101,6 +103,7 @@ def test_cornell_lean_probe_queue(gpu, cornell_scene):
     queue (no wave groups below 3 rounds).  Same bits as the generic build."""
     a, b, feats, build, sched = _both(cornell_scene, _params(cornell_scene, 640, 480, 2))
     assert build == FM_DIFFUSE and "lean" in sched and "wave_groups" not in sched, (hex(build), sched)
+    assert sched == ["lean", "primary", "probe_queue", "specialized", "splat_rows"]
     assert _same_bits(a, b)
 
 
