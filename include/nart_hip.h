@@ -172,6 +172,74 @@ int nart_hip_render_moment(nart_ctx* ctx, const nart_render_params* p, uint32_t 
                            nart_pixel* albedo, nart_pixel* normal, nart_pixel* moment, nart_render_stats* stats,
                            double* aov_ms, double* moment_ms);
 
+/* Adaptive sampling (no reference counterpart): a pilot pass at few samples, a noise estimate per
+   bucket from the bucket's own samples, and more samples only for the buckets that need them.
+
+   Levels: L_0 = min_spp, L_{i+1} = min(L_i * growth, spp), ending on spp = p->spp, the maximum; the
+   single level spp if min_spp >= spp; at most 32 levels (the 32nd is spp).  If every bucket refines
+   to the top the extra work is at most 1 / (growth - 1) of a uniform render.
+
+   The loop, per device over the buckets the device owns (a multi-device context shards as ever and
+   each device refines its own share; the estimate below needs the bucket's own tiles only):
+     1. render the listed buckets at L_i: the beauty, the second-moment tiles and the requested AOVs;
+     2. k_bucket_error: one float E per listed bucket (below);
+     3. the bucket's tiles REPLACE its tiles of the earlier level.  They are not accumulated: a
+        pixel's RNG stream is seeded by its coordinates (render.cpp:78-108), so a second pass replays
+        the first pass's numbers and the two would be correlated;
+     4. a bucket stops iff E <= threshold (a NaN or infinite E refines), or if L_i is the last level;
+     5. the buckets that did not stop, in ascending id order, are the next list; an empty list ends
+        the loop;
+     6. the tiles are combined in bucket raster order and delivered as every other image is.
+   Every bucket's tile is therefore, bit for bit, that bucket's tile of a uniform render at the sample
+   count the bucket ended on (a bucket's tile never depends on the buckets rendered with it), and the
+   second-moment image carries each pixel's effective sample count (sum w^2 / (sum w)^2), so
+   nart_hip_denoise_moment works on an adaptive frame unchanged.
+
+   Bucket error E: the relative standard error of the bucket's mean luminance.  All arithmetic is
+   float32 + - * / sqrt and comparisons, one operation each, in the order written (nothing
+   contracted, divide and sqrt correctly rounded); max(a, b) means a > b ? a : b.  The own pixels of
+   bucket (bx, by) are its tile pixels (fb + dx, fb + dy), dx in [0, nx), nx = min(B, total_width -
+   B * bx), dy in [0, ny), ny likewise, fb = filter_bounds, B = bucket_size: the splat centres of the
+   pixels the bucket traces, extra rows included.  Per own pixel, T the beauty tile pixel and M the
+   moment tile pixel (contribution rgba, filter_weight_sum w):
+       if T.w > 0:  c  = T.rgb / T.w
+                    k  = M.a / (M.w * M.w)
+                    per channel ch: m2 = M.ch / M.w, var = max(0, m2 - c.ch * c.ch), V.ch = var * k
+                    sd = (0.2126 * sqrt(V.r) + 0.7152 * sqrt(V.g)) + 0.0722 * sqrt(V.b)
+                    l  = max((0.2126 * c.r + 0.7152 * c.g) + 0.0722 * c.b, 0)
+       else:        sd = 0, l = 0
+   Sums start from 0: per row rs[dy] = sum over dx ascending of sd, rl[dy] likewise of l; then
+   S = sum over dy ascending of rs[dy], Ls likewise of rl[dy];
+       E = S / (Ls + floor * float(nx * ny))
+   floor keeps dark buckets from dividing by nothing; a black bucket has E = 0.  E is a pure function
+   of the two tiles: no atomics, any launch shape, any place in the list.
+
+   nart_hip_adaptive_levels (host only, no device): the level list for a maximum spp into levels
+   (room for 32; null to query *n).  ap null: the defaults.
+   nart_hip_render_adaptive: ap null means the defaults.  aovs, image, albedo, normal and moment as in
+   nart_hip_render_moment, except that moment may be null (the moment tiles are rendered regardless)
+   and that nothing but the per-bucket outputs need be requested.  bucket_spp (uint32[nBucketsX *
+   nBucketsY], bucket-id order) receives the sample count each bucket ended on, bucket_error
+   (float[same]) the E of that final level (so E is computed at the last level too); both optional.
+   stats add up over the levels: samples is the number of samples taken, replaced ones included.
+   adaptive_ms, if non-null, receives the device time of the error and scatter kernels over all
+   levels (the slowest device's).  No other entry point changes what it launches.
+   NART_E_INVALID: as nart_hip_render_aovs, or min_spp < 2, p->spp < 2 (one sample has no variance),
+   growth outside 2..16, a threshold that is NaN or < 0 (+inf is allowed: nothing refines), a floor
+   that is not finite and > 0.  NART_E_UNSUPPORTED: an AOV bit with the volume integrator (without
+   AOV bits the volume integrator works). */
+typedef struct nart_adaptive_params {
+    uint32_t min_spp;   /* samples of the pilot pass, >= 2                         default 16   */
+    uint32_t growth;    /* factor between levels, 2..16                            default 4    */
+    float threshold;    /* a bucket stops when its E <= threshold                  default 0.1  */
+    float floor;        /* luminance added per pixel to the denominator of E       default 0.01 */
+} nart_adaptive_params;
+void nart_hip_adaptive_params_init(nart_adaptive_params* ap);
+int nart_hip_adaptive_levels(const nart_adaptive_params* ap, uint32_t spp, uint32_t* levels, uint32_t* n);
+int nart_hip_render_adaptive(nart_ctx* ctx, const nart_render_params* p, const nart_adaptive_params* ap, uint32_t aovs,
+                             nart_pixel* image, nart_pixel* albedo, nart_pixel* normal, nart_pixel* moment,
+                             uint32_t* bucket_spp, float* bucket_error, nart_render_stats* stats, double* adaptive_ms);
+
 /* Debug / parity, as nart_hip_render_samples: the per-sample AOV records of pixels [x0,x0+w) x
    [y0,y0+h) in total-image coordinates (extra rows included) into host
    out8[((y-y0)*w + (x-x0))*spp + s][8] = albedo record then normal record; tri (optional) receives

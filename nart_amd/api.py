@@ -108,6 +108,24 @@ class DenoiseParams(ctypes.Structure):
         return "DenoiseParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
 
 
+class AdaptiveParams(ctypes.Structure):
+    """nart_adaptive_params (include/nart_hip.h, "Adaptive sampling"); AdaptiveParams.defaults() is
+    nart_hip_adaptive_params_init, keyword arguments override single fields."""
+    _fields_ = [("min_spp", ctypes.c_uint32), ("growth", ctypes.c_uint32), ("threshold", ctypes.c_float),
+                ("floor", ctypes.c_float)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        ap = cls()
+        hip_lib().nart_hip_adaptive_params_init(ctypes.byref(ap))
+        for k, v in kw.items():
+            setattr(ap, k, v)
+        return ap
+
+    def __repr__(self):
+        return "AdaptiveParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
 class _Texture(ctypes.Structure):
     """nart_texture (include/nart_scene.h)."""
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("rgba", _P)]
@@ -168,6 +186,12 @@ _HIP_SIGS = {
     "nart_hip_render_moment": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, _P, _P, _P, _P,
                                               ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double),
                                               ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_adaptive_params_init": (None, [ctypes.POINTER(AdaptiveParams)]),
+    "nart_hip_adaptive_levels": (ctypes.c_int, [ctypes.POINTER(AdaptiveParams), ctypes.c_uint32,
+                                                ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    "nart_hip_render_adaptive": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(AdaptiveParams),
+                                                ctypes.c_uint32, _P, _P, _P, _P, _P, _P, ctypes.POINTER(RenderStats),
+                                                ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_aov_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, ctypes.c_uint32,
                                                    ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "nart_hip_denoise_params_init": (None, [ctypes.POINTER(DenoiseParams)]),
@@ -555,6 +579,36 @@ class HipRenderer:
         out["aov_ms"] = ms.value
         return out
 
+    def render_adaptive(self, p, params=None, albedo=False, normal=False, moment=False, stats=None):
+        """Adaptive sampling (nart_hip_render_adaptive; include/nart_hip.h has the algorithm): a pilot
+        pass at params.min_spp, then only the buckets whose error exceeds params.threshold again at
+        growth times the samples, up to p.spp.  params an AdaptiveParams (None: the defaults).
+        Returns a dict with "beauty", the requested "albedo" / "normal" / "moment" images (as
+        render_aovs() returns them; every bucket's share has the bits of a uniform render at the
+        sample count the bucket ended on), "bucket_spp" (uint32) and "bucket_error" (float32, the
+        error of the bucket's final level), both of shape (n_buckets_y, n_buckets_x), "levels" (the
+        sample counts of the levels) and "adaptive_ms", the device time of the error and scatter
+        kernels.  stats.samples is the number of samples taken over all levels."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        out = {}
+        for name, want in (("beauty", True), ("albedo", albedo), ("normal", normal), ("moment", moment)):
+            if want:
+                out[name] = np.empty(shape, np.float32)
+        ptr = lambda name: out[name].ctypes.data if name in out else None
+        out["bucket_spp"] = np.zeros((g.n_buckets_y, g.n_buckets_x), np.uint32)
+        out["bucket_error"] = np.zeros((g.n_buckets_y, g.n_buckets_x), np.float32)
+        st = stats if stats is not None else RenderStats()
+        ms = ctypes.c_double()
+        mask = (AOV_ALBEDO if albedo else 0) | (AOV_NORMAL if normal else 0)
+        self._check(self._lib.nart_hip_render_adaptive(
+            self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None, mask, ptr("beauty"), ptr("albedo"),
+            ptr("normal"), ptr("moment"), out["bucket_spp"].ctypes.data, out["bucket_error"].ctypes.data,
+            ctypes.byref(st), ctypes.byref(ms)))
+        out["levels"] = adaptive_levels(params, p.spp)
+        out["adaptive_ms"] = ms.value
+        return out
+
     def render_aov_samples(self, p, x0, y0, w, h):
         """Per-sample AOV records of a rect in total-image coordinates (nart_hip_render_aov_samples):
         (h, w, spp, 8) float32 = {albedo.rgb, hit, normal.xyz, depth} and (h, w, spp) uint32 first-hit
@@ -671,6 +725,27 @@ def finalize(p, image):
     crop = image[fb:fb + p.image_height, fb:fb + p.image_width]
     with np.errstate(divide="ignore", invalid="ignore"):
         return crop[..., :4] / crop[..., 4:5]
+
+
+def adaptive_levels(params, spp):
+    """Host only: the sample counts of the adaptive levels for a maximum of spp samples
+    (nart_hip_adaptive_levels): min_spp, times growth per level, ending on spp.  params an
+    AdaptiveParams (None: the defaults)."""
+    lib = hip_lib()
+    levels, n = (ctypes.c_uint32 * 32)(), ctypes.c_uint32()
+    rc = lib.nart_hip_adaptive_levels(ctypes.byref(params) if params else None, spp, levels, ctypes.byref(n))
+    if rc != NART_OK:
+        raise NartError(rc, "nart_hip_adaptive_levels: invalid parameters or spp < 2")
+    return [int(levels[i]) for i in range(n.value)]
+
+
+def spp_image(p, bucket_spp):
+    """The per-pixel sample count of an adaptive render: the cropped (H, W) uint32 map in which every
+    pixel holds the sample count of the bucket that traced it (render_adaptive()'s "bucket_spp")."""
+    g = session_geometry(p)
+    b = np.ascontiguousarray(bucket_spp, np.uint32).reshape(g.n_buckets_y, g.n_buckets_x)
+    B = p.bucket_size
+    return np.repeat(np.repeat(b, B, axis=0), B, axis=1)[:p.image_height, :p.image_width].copy()
 
 
 def sample_variance(p, beauty, moment):

@@ -19,6 +19,14 @@
 //                   second-moment image (nart_hip_render_denoised_moment; with --aovs
 //                   nart_hip_render_moment + nart_hip_denoise_moment: the same image) instead of the
 //                   spatial estimate; without --denoise it is an error
+//   --adaptive T    render every session adaptively (nart_hip_render_adaptive) with threshold T: a pilot
+//                   pass, then more samples only for the buckets whose error exceeds T; -s is the
+//                   maximum.  Also writes <out>.spp.exr (RGB = the sample count of the pixel's bucket,
+//                   A = 1) and prints the levels, the buckets rendered per level and the samples
+//                   taken.  With --aovs the AOVs are the adaptive call's; with --denoise the adaptive
+//                   images go through nart_hip_denoise, with --sample-variance too through
+//                   nart_hip_denoise_moment
+//   --min-spp N     with --adaptive: the samples of the pilot pass (default 16); without it an error
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -112,6 +120,25 @@ bool take_flag(std::vector<char*>& args, const char* flag) {
     return found;
 }
 
+// Removes every `flag <value>` pair from argv; the last value into `value`.  False (after a
+// message) if a flag lacks its value.
+bool take_value_flag(std::vector<char*>& args, const char* flag, const char*& value) {
+    std::vector<char*> kept;
+    for (size_t i = 0; i < args.size(); ++i) {
+        if (std::strcmp(args[i], flag)) {
+            kept.push_back(args[i]);
+            continue;
+        }
+        if (i + 1 >= args.size()) {
+            std::fprintf(stderr, "Error: %s needs a value\n", flag);
+            return false;
+        }
+        value = args[++i];
+    }
+    args = kept;
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[]) {
@@ -123,6 +150,30 @@ int main(int argc, char* argv[]) {
     if (sample_variance && !denoise) {
         std::fprintf(stderr, "Error: --sample-variance selects the denoiser's variance input and needs --denoise\n");
         return EXIT_FAILURE;
+    }
+    const char *adaptive_arg = nullptr, *min_spp_arg = nullptr;
+    if (!take_value_flag(args, "--adaptive", adaptive_arg) || !take_value_flag(args, "--min-spp", min_spp_arg))
+        return EXIT_FAILURE;
+    if (min_spp_arg && !adaptive_arg) {
+        std::fprintf(stderr, "Error: --min-spp sets the pilot pass of adaptive sampling and needs --adaptive\n");
+        return EXIT_FAILURE;
+    }
+    const bool adaptive = adaptive_arg != nullptr;
+    nart_adaptive_params ap;
+    nart_hip_adaptive_params_init(&ap);
+    if (adaptive) {
+        char* end = nullptr;
+        ap.threshold = std::strtof(adaptive_arg, &end);
+        if (!adaptive_arg[0] || *end) {
+            std::fprintf(stderr, "Error: --adaptive %s\n", adaptive_arg);
+            return EXIT_FAILURE;
+        }
+        int v = 0;
+        if (min_spp_arg && (!parse_int(min_spp_arg, v) || v < 0)) {
+            std::fprintf(stderr, "Error: --min-spp %s\n", min_spp_arg);
+            return EXIT_FAILURE;
+        }
+        if (min_spp_arg) ap.min_spp = (uint32_t)v;
     }
     if (!take_device_flags(args, devices)) return EXIT_FAILURE;
     if (args.size() < 3) {
@@ -163,7 +214,41 @@ int main(int argc, char* argv[]) {
         std::vector<nart_pixel> image((size_t)g.total_width * g.total_height);
         std::vector<nart_pixel> albedo, normal, denoised, moment;
         if (denoise) denoised.resize(image.size());
-        if (aovs && sample_variance) {
+        std::vector<uint32_t> bucket_spp;
+        if (adaptive) {
+            // the adaptive call renders what the flags need; the denoiser then runs over its images
+            const bool guides = aovs || denoise;
+            if (guides) {
+                albedo.resize(image.size());
+                normal.resize(image.size());
+            }
+            if (sample_variance) moment.resize(image.size());
+            bucket_spp.resize((size_t)g.n_buckets_x * g.n_buckets_y);
+            nart_render_stats st;
+            std::memset(&st, 0, sizeof(st));
+            rc = nart_hip_render_adaptive(ctx, &p, &ap, guides ? NART_AOV_ALBEDO | NART_AOV_NORMAL : 0u, image.data(),
+                                          guides ? albedo.data() : nullptr, guides ? normal.data() : nullptr,
+                                          sample_variance ? moment.data() : nullptr, bucket_spp.data(), nullptr, &st,
+                                          nullptr);
+            if (rc == NART_OK && sample_variance)
+                rc = nart_hip_denoise_moment(ctx, &p, nullptr, image.data(), albedo.data(), normal.data(), moment.data(),
+                                             denoised.data(), nullptr);
+            else if (rc == NART_OK && denoise)
+                rc = nart_hip_denoise(ctx, &p, nullptr, image.data(), albedo.data(), normal.data(), denoised.data(),
+                                      nullptr);
+            uint32_t levels[32], nl = 0;
+            if (rc == NART_OK && nart_hip_adaptive_levels(&ap, p.spp, levels, &nl) == NART_OK) {
+                // a bucket was rendered at every level up to the one it ended on
+                std::printf("Adaptive: levels");
+                for (uint32_t l = 0; l < nl; ++l) {
+                    size_t cnt = 0;
+                    for (uint32_t s : bucket_spp) cnt += s >= levels[l];
+                    std::printf(" %u spp x %zu buckets%s", levels[l], cnt, l + 1 < nl ? "," : ";");
+                }
+                std::printf(" %llu of %llu samples\n", (unsigned long long)st.samples,
+                            (unsigned long long)p.image_width * p.image_height * p.spp);
+            }
+        } else if (aovs && sample_variance) {
             albedo.resize(image.size());
             normal.resize(image.size());
             moment.resize(image.size());
@@ -205,6 +290,18 @@ int main(int argc, char* argv[]) {
             extra.push_back({".normal.exr", normal.data()});
         }
         if (denoise) extra.push_back({".denoised.exr", denoised.data()});
+        std::vector<nart_pixel> spp_img;
+        if (adaptive) {
+            // pixel (x, y) of the cropped image was traced by bucket (x / B, y / B)
+            spp_img.assign(image.size(), nart_pixel{{0.f, 0.f, 0.f, 0.f}, 0.f});
+            for (uint32_t y = 0; y < p.image_height; ++y)
+                for (uint32_t x = 0; x < p.image_width; ++x) {
+                    const float s = (float)bucket_spp[(size_t)(y / p.bucket_size) * g.n_buckets_x + x / p.bucket_size];
+                    spp_img[(size_t)(y + g.filter_bounds) * g.total_width + x + g.filter_bounds] =
+                        nart_pixel{{s, s, s, 1.f}, 1.f};
+                }
+            extra.push_back({".spp.exr", spp_img.data()});
+        }
         for (const auto& e : extra) {
             path = stem + e.first;
             std::printf("Writing to %s...\n", path.c_str());

@@ -11,6 +11,8 @@
 //     (library-owned communicator, ncclCommInitAll over the device list), permuted into bucket-id
 //     order and combined in bucket raster order on device 0 (k_combine) -- so the image is
 //     bit-identical for any N.
+// An adaptive frame (FrameRequest::adaptive) differs in the third step only: each thread refines its
+// device's share (render_buckets_adaptive) into the same slabs; gather and combine follow unchanged.
 // RCCL is loaded at run time (dlopen), so single-device use never needs it.  A device list with
 // repeated ordinals (a rehearsal of N ranks on fewer GPUs) gathers with device copies instead,
 // since an RCCL communicator needs distinct GPUs.  NART_GATHER=rccl|copy overrides the choice
@@ -159,6 +161,14 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     std::vector<int> rcs(n, NART_OK);
     std::vector<nart_render_stats> st(n);
     std::vector<AovRequest> areq(n);
+    std::vector<AdaptiveRun> runs;  // adaptive: one per device, parameters and levels copied in
+    if (rq.adaptive) {
+        runs.resize(n);
+        for (AdaptiveRun& r : runs) {
+            r.ap = rq.adaptive->ap;
+            r.levels = rq.adaptive->levels;
+        }
+    }
     std::vector<std::thread> th;
     auto work = [&](uint32_t d) {
         if (ids[d].empty()) return;
@@ -172,9 +182,19 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
         for (size_t i = 0; i < K; ++i)
             if (kinds[i] >= 0)
                 (kinds[i] == 2 ? areq[d].moment : areq[d].tiles[kinds[i]]) = static_cast<float*>(ctx->sub_tiles[d]) + i * slab;
-        rcs[d] = render_buckets(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(),
-                                static_cast<float*>(ctx->sub_tiles[d]), ctx->streams[d], &st[d],
-                                want_aov ? &areq[d] : nullptr);
+        if (rq.adaptive) {
+            // the device refines its own shard: a bucket's error needs its own tiles only
+            float* frame[FRAME_BUFS] = {nullptr, nullptr, nullptr, nullptr};
+            for (size_t i = 0; i < K; ++i) frame[kinds[i] + 1] = static_cast<float*>(ctx->sub_tiles[d]) + i * slab;
+            rcs[d] = render_buckets_adaptive(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(), frame,
+                                             ctx->streams[d], &st[d], runs[d]);
+            areq[d].ms = runs[d].aov_ms;
+            areq[d].moment_ms = runs[d].moment_ms;
+        } else {
+            rcs[d] = render_buckets(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(),
+                                    static_cast<float*>(ctx->sub_tiles[d]), ctx->streams[d], &st[d],
+                                    want_aov ? &areq[d] : nullptr);
+        }
         if (rcs[d] == NART_OK && hipStreamSynchronize(ctx->streams[d]) != hipSuccess) rcs[d] = NART_E_HIP;
     };
     for (uint32_t d = 0; d < n; ++d) std::memset(&st[d], 0, sizeof(st[d]));
@@ -190,6 +210,22 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     for (uint32_t d = 0; d < n; ++d)
         if (rcs[d] != NART_OK)
             return fail(ctx, rcs[d], "device " + std::to_string(ctx->devs[d]) + ": " + ctx->subs[d]->err);
+    if (rq.adaptive) {
+        // the shards' results in bucket-id order; buckets per level added up, the slowest device's time
+        AdaptiveRun& out = *rq.adaptive;
+        out.spp.assign(nb, 0);
+        out.err.assign(nb, 0.f);
+        out.rendered.assign(out.levels.size(), 0);
+        for (uint32_t d = 0; d < n; ++d) {
+            if (ids[d].empty()) continue;
+            for (size_t i = 0; i < ids[d].size(); ++i) {
+                out.spp[ids[d][i]] = runs[d].spp[i];
+                out.err[ids[d][i]] = runs[d].err[i];
+            }
+            for (size_t l = 0; l < out.rendered.size(); ++l) out.rendered[l] += runs[d].rendered[l];
+            out.ms = std::max(out.ms, runs[d].ms);
+        }
+    }
 
     // 2. gather the slabs to device 0 (rank order), RCCL over xGMI or device copies
     std::vector<size_t> first_b(n, 0);

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/nart_hip.h"
+#include "device/adaptive.h"
 #include "device/denoise.h"
 #include "device/lbvh.h"
 #include "device/volume.h"
@@ -79,6 +80,8 @@ struct nart_ctx {
     bool prim_valid = false;   // d_prim holds the current batch's camera-ray hits (first-hit AOVs)
     // around the AOV passes ([0], [1]) and the moment pass ([2], [3]) of a batch (render_buckets)
     hipEvent_t ev_aov[4] = {nullptr, nullptr, nullptr, nullptr};
+    // around the error and scatter kernels of an adaptive level (render_buckets_adaptive)
+    hipEvent_t ev_ad[2] = {nullptr, nullptr};
     // denoiser (denoise_device): work buffers over the cropped image, the four device images of
     // nart_hip_denoise / nart_hip_render_denoised (five with the moment image), events between its
     // kernels, the last run's times
@@ -1675,6 +1678,20 @@ int build_bvh_device(nart_ctx* ctx, const nart_scene_blob& blob, const std::vect
 // What a whole-frame render produces, where it goes and whose buffers it uses (render_frame).
 // Buffer k: 0 the beauty, 1 + a first-hit AOV a (AOV_ALBEDO, AOV_NORMAL), 3 the second-moment image.
 constexpr int FRAME_BUFS = 4;
+
+// One adaptive render (include/nart_hip.h, "Adaptive sampling"): the validated parameters and the
+// level list going in; coming out, per bucket (in the order of the list rendered: bucket-id order for
+// a whole frame) the sample count it ended on and the error of that level, the buckets rendered per
+// level, and the device times of the error and scatter kernels, the AOV passes and the moment passes.
+struct AdaptiveRun {
+    nart_adaptive_params ap;
+    std::vector<uint32_t> levels;
+    std::vector<uint32_t> spp;
+    std::vector<float> err;
+    std::vector<uint32_t> rendered;
+    double ms = 0.0, aov_ms = 0.0, moment_ms = 0.0;
+};
+
 struct FrameRequest {
     bool beauty = true;            // false: an AOV-only frame, which launches no path kernel
     bool aov[2] = {false, false};
@@ -1692,6 +1709,9 @@ struct FrameRequest {
     void** image = nullptr;
     size_t* image_cap = nullptr;
     uint32_t images = 0;
+    // Adaptive sampling: every device refines its own buckets (render_buckets_adaptive) instead of
+    // rendering them once at p->spp; needs the beauty.  Null: the uniform render.
+    AdaptiveRun* adaptive = nullptr;
 
     bool wants(int k) const { return k == 0 ? beauty : (k == 3 ? moment : aov[k - 1]); }
     bool wants_aovs() const { return aov[0] || aov[1]; }
@@ -1712,6 +1732,153 @@ struct ScopedDeviceBufs {
 void free_frame_buffers(nart_ctx* ctx) {
     for (void* b : {ctx->d_gather, ctx->d_byid, ctx->d_image, ctx->d_slab_map, ctx->d_dn, ctx->d_dn_img})
         if (b) hipFree(b);
+}
+
+// ---------------------------------------------------------------- adaptive sampling (device/adaptive.h)
+void adaptive_defaults(nart_adaptive_params* ap) {
+    ap->min_spp = 16;
+    ap->growth = 4;
+    ap->threshold = 0.1f;
+    ap->floor = 0.01f;
+}
+
+// The message of what is wrong with the parameters, or null.
+const char* adaptive_params_error(const nart_adaptive_params& ap, uint32_t spp) {
+    if (ap.min_spp < 2) return "adaptive min_spp must be >= 2 (one sample has no variance)";
+    if (spp < 2) return "adaptive sampling needs spp >= 2 (one sample has no variance)";
+    if (ap.growth < 2 || ap.growth > 16) return "adaptive growth must be in 2..16";
+    if (!(ap.threshold >= 0.f)) return "adaptive threshold must be >= 0 (+inf: nothing refines)";
+    if (!(ap.floor > 0.f) || !std::isfinite(ap.floor)) return "adaptive floor must be finite and > 0";
+    return nullptr;
+}
+
+// L_0 = min_spp, L_{i+1} = min(L_i * growth, spp), ending on spp; the one level spp if min_spp >= spp.
+constexpr uint32_t ADAPTIVE_MAX_LEVELS = 32;
+std::vector<uint32_t> adaptive_levels(const nart_adaptive_params& ap, uint32_t spp) {
+    std::vector<uint32_t> levels;
+    uint64_t L = ap.min_spp;
+    while (L < spp && levels.size() + 1 < ADAPTIVE_MAX_LEVELS) {
+        levels.push_back((uint32_t)L);
+        L = std::min<uint64_t>(L * ap.growth, spp);
+    }
+    levels.push_back(spp);
+    return levels;
+}
+
+// The adaptive counterpart of render_buckets: the listed buckets, refined level by level, into the
+// frame's tile buffers frame[k] (FrameRequest's buffer k, list order: slot i is ids[i]; null: not
+// wanted).  Every level renders its list at that level's sample count into list-ordered scratch
+// tiles -- the beauty and the second-moment tiles always, an AOV where frame[] asks for it --
+// k_bucket_error reduces each bucket's two tiles to its error, k_scatter_tiles moves the wanted
+// buffers' tiles to their slots (replacing the earlier level's: a pixel's RNG stream is seeded by
+// its coordinates, so a second pass would replay the first one's numbers and must not be
+// accumulated), and the buckets whose error is not <= threshold form the next list.  A bucket's tiles
+// are therefore those of a uniform render at the sample count it ended on.  The scratch is a
+// temporary of the call.  p and run.ap are validated by the caller; run.levels is set.
+int render_buckets_adaptive(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n,
+                            float* const frame[FRAME_BUFS], hipStream_t st, nart_render_stats* stats, AdaptiveRun& run) {
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const size_t tile_floats = (size_t)g.tile_size * g.tile_size * 5;
+    run.spp.assign(n, 0);
+    run.err.assign(n, 0.f);
+    run.rendered.assign(run.levels.size(), 0);
+    if (!n) return NART_OK;
+    for (auto& e : ctx->ev_ad)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    // scratch buffer k: FrameRequest's numbering (0 the beauty, 1 + AOV, 3 the moment tiles)
+    bool use[FRAME_BUFS] = {true, frame[1] != nullptr, frame[2] != nullptr, true};
+    ScopedDeviceBufs own;
+    size_t nS = 0;
+    for (bool u : use) nS += u;
+    const size_t slab = (size_t)n * tile_floats;
+    int rc = dmalloc(ctx, &own.p[0], nS * slab * sizeof(float), "adaptive scratch tiles");
+    if (!rc) rc = dmalloc(ctx, &own.p[1], (size_t)n * 12, "adaptive bucket lists");
+    if (rc) return rc;
+    float* scratch[FRAME_BUFS] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0, i = 0; k < FRAME_BUFS; ++k)
+        if (use[k]) scratch[k] = static_cast<float*>(own.p[0]) + (size_t)(i++) * slab;
+    uint32_t* d_ids = static_cast<uint32_t*>(own.p[1]);
+    uint32_t* d_slot = d_ids + n;
+    float* d_err = reinterpret_cast<float*>(d_slot + n);
+
+    std::vector<uint32_t> cur(n), cur_ids, next;  // slots of the current list, ascending
+    for (uint32_t i = 0; i < n; ++i) cur[i] = i;
+    std::vector<float> E;
+    const size_t stage_lds = (2 * (size_t)p->bucket_size * (p->bucket_size + 1) + 2 * (size_t)p->bucket_size) * sizeof(float);
+    const bool stage = stage_lds <= 64 * 1024;
+    if ((size_t)p->bucket_size * 2 * sizeof(float) > 64 * 1024)
+        return fail(ctx, NART_E_UNSUPPORTED, "adaptive sampling: bucket rows do not fit the LDS");
+    for (size_t li = 0; li < run.levels.size() && !cur.empty(); ++li) {
+        const uint32_t m = (uint32_t)cur.size();
+        const bool last = li + 1 == run.levels.size();
+        nart_render_params pl = *p;
+        pl.spp = run.levels[li];
+        cur_ids.resize(m);
+        for (uint32_t i = 0; i < m; ++i) cur_ids[i] = ids[cur[i]];
+        AovRequest areq;
+        areq.tiles[0] = scratch[1];
+        areq.tiles[1] = scratch[2];
+        areq.moment = scratch[3];
+        rc = render_buckets(ctx, &pl, cur_ids.data(), m, scratch[0], st, stats, &areq);
+        run.aov_ms += areq.ms;
+        run.moment_ms += areq.moment_ms;
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(d_ids, cur_ids.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_slot, cur.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(ctx->ev_ad[0], st));
+        BucketErrorArgs ea;
+        ea.beauty = scratch[0];
+        ea.moment = scratch[3];
+        ea.ids = d_ids;
+        ea.err = d_err;
+        ea.n = m;
+        ea.B = p->bucket_size;
+        ea.fb = g.filter_bounds;
+        ea.tile = g.tile_size;
+        ea.nbx = g.n_buckets_x;
+        ea.totalW = g.total_width;
+        ea.totalH = g.total_height;
+        ea.floor = run.ap.floor;
+        if (stage) hipLaunchKernelGGL((k_bucket_error<true>), dim3(m), dim3(64), stage_lds, st, ea);
+        else hipLaunchKernelGGL((k_bucket_error<false>), dim3(m), dim3(64), 2 * (size_t)p->bucket_size * sizeof(float), st, ea);
+        HIPCHK(hipGetLastError());
+        ScatterArgs sc;
+        uint32_t nsc = 0;
+        for (int k = 0; k < FRAME_BUFS; ++k)
+            if (frame[k] && scratch[k]) {
+                sc.src[nsc] = scratch[k];
+                sc.dst[nsc++] = frame[k];
+            }
+        for (uint32_t k = nsc; k < (uint32_t)SCATTER_BUFS; ++k) {
+            sc.src[k] = nullptr;
+            sc.dst[k] = nullptr;
+        }
+        sc.slot = d_slot;
+        sc.n = m;
+        sc.tile_floats = (uint32_t)tile_floats;
+        if (nsc) {
+            hipLaunchKernelGGL(k_scatter_tiles, dim3(m, nsc), dim3(256), 0, st, sc);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(ctx->ev_ad[1], st));
+        E.resize(m);
+        HIPCHK(hipMemcpyAsync(E.data(), d_err, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_ad[0], ctx->ev_ad[1]));
+        run.ms += ms;
+        run.rendered[li] = m;
+        next.clear();
+        for (uint32_t i = 0; i < m; ++i) {
+            run.spp[cur[i]] = run.levels[li];
+            run.err[cur[i]] = E[i];
+            if (!last && !(E[i] <= run.ap.threshold)) next.push_back(cur[i]);  // a NaN error refines
+        }
+        cur.swap(next);
+    }
+    return NART_OK;
 }
 
 }  // namespace
@@ -1770,7 +1937,13 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     areq.tiles[0] = tiles[1];
     areq.tiles[1] = tiles[2];
     areq.moment = tiles[3];
-    rc = render_buckets(ctx, p, ids.data(), nb, tiles[0], 0, stats, rq.wants_aovs() || rq.moment ? &areq : nullptr);
+    if (rq.adaptive) {
+        rc = render_buckets_adaptive(ctx, p, ids.data(), nb, tiles, 0, stats, *rq.adaptive);
+        areq.ms = rq.adaptive->aov_ms;
+        areq.moment_ms = rq.adaptive->moment_ms;
+    } else {
+        rc = render_buckets(ctx, p, ids.data(), nb, tiles[0], 0, stats, rq.wants_aovs() || rq.moment ? &areq : nullptr);
+    }
     if (aov_ms) *aov_ms = areq.ms;
     if (moment_ms) *moment_ms = areq.moment_ms;
     for (int k = 0, i = 0; k < FRAME_BUFS && !rc; ++k) {
@@ -2266,6 +2439,8 @@ void nart_hip_destroy(nart_ctx* ctx) {
         for (auto& e : ctx->ev) hipEventDestroy(e);
     for (auto& e : ctx->ev_aov)
         if (e) hipEventDestroy(e);
+    for (auto& e : ctx->ev_ad)
+        if (e) hipEventDestroy(e);
     delete ctx;
 }
 
@@ -2386,6 +2561,51 @@ int nart_hip_render_moment(nart_ctx* ctx, const nart_render_params* p, uint32_t 
     if (!ctx || !p) return NART_E_INVALID;
     if (!moment) return fail(ctx, NART_E_INVALID, "the moment image buffer is required");
     return render_aovs(ctx, p, aovs, image, albedo, normal, moment, stats, aov_ms, moment_ms);
+}
+
+void nart_hip_adaptive_params_init(nart_adaptive_params* ap) {
+    if (ap) adaptive_defaults(ap);
+}
+
+int nart_hip_adaptive_levels(const nart_adaptive_params* ap, uint32_t spp, uint32_t* levels, uint32_t* n) {
+    if (!n) return NART_E_INVALID;
+    nart_adaptive_params a;
+    if (ap) a = *ap;
+    else adaptive_defaults(&a);
+    if (adaptive_params_error(a, spp)) return NART_E_INVALID;
+    const std::vector<uint32_t> l = adaptive_levels(a, spp);
+    *n = (uint32_t)l.size();
+    if (levels) std::copy(l.begin(), l.end(), levels);
+    return NART_OK;
+}
+
+int nart_hip_render_adaptive(nart_ctx* ctx, const nart_render_params* p, const nart_adaptive_params* ap, uint32_t aovs,
+                             nart_pixel* image, nart_pixel* albedo, nart_pixel* normal, nart_pixel* moment,
+                             uint32_t* bucket_spp, float* bucket_error, nart_render_stats* stats, double* adaptive_ms) {
+    if (!ctx || !p) return NART_E_INVALID;
+    if (adaptive_ms) *adaptive_ms = 0.0;
+    if (aovs & ~(NART_AOV_ALBEDO | NART_AOV_NORMAL)) return fail(ctx, NART_E_INVALID, "unknown AOV bit");
+    if (((aovs & NART_AOV_ALBEDO) && !albedo) || ((aovs & NART_AOV_NORMAL) && !normal))
+        return fail(ctx, NART_E_INVALID, "an AOV is requested without its image buffer");
+    AdaptiveRun run;
+    if (ap) run.ap = *ap;
+    else adaptive_defaults(&run.ap);
+    if (const char* why = adaptive_params_error(run.ap, p->spp)) return fail(ctx, NART_E_INVALID, why);
+    run.levels = adaptive_levels(run.ap, p->spp);
+    FrameRequest rq;
+    rq.adaptive = &run;
+    rq.moment = moment != nullptr;
+    rq.aov[AOV_ALBEDO] = (aovs & NART_AOV_ALBEDO) != 0;
+    rq.aov[AOV_NORMAL] = (aovs & NART_AOV_NORMAL) != 0;
+    rq.dst[0] = image;
+    rq.dst[1 + AOV_ALBEDO] = albedo;
+    rq.dst[1 + AOV_NORMAL] = normal;
+    rq.dst[3] = moment;
+    if (int rc = render_frame(ctx, p, rq, stats, nullptr, nullptr)) return rc;
+    if (bucket_spp) std::copy(run.spp.begin(), run.spp.end(), bucket_spp);
+    if (bucket_error) std::copy(run.err.begin(), run.err.end(), bucket_error);
+    if (adaptive_ms) *adaptive_ms = run.ms;
+    return NART_OK;
 }
 
 int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w,
