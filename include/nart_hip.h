@@ -415,6 +415,35 @@ typedef struct nart_bvh_info {
 } nart_bvh_info;
 int nart_hip_bvh_info(const nart_scene_blob* scene, nart_bvh_info* out);
 
+/* Test hooks (read only): the acceleration structure itself, copied to the host.
+       nodes      num_nodes BVHNode records of 64 B (device/dscene.h: lo0[3] hi0[3] lo1[3] hi1[3]
+                  child[2] pad[2]; child >= 0 an inner node, < 0 a leaf ~(first << 5 | (count - 1)))
+       tri_isect  num_leaf_tris triangle test records of 16 floats, leaf order
+       tri_perm   3 * num_leaf_tris permuted records of 16 floats (axis-major; the trailing padding
+                  records of the device buffer are not copied)
+   and in info the counts, root_code (the traversal's root: 0, or a leaf code when the tree is one
+   leaf, -1 when it is empty), pad (what every child box was grown by) and stack_depth.
+   Capacities are in nodes (nodes_cap) and floats (isect_cap, perm_cap).  info is always filled; with
+   all three buffers null the call is a size query.  NART_E_INVALID: a null ctx / scene or info, only
+   some buffers null, or a capacity that is too small (nothing is copied then).
+   nart_hip_bvh_dump (host only, no device): the binned-SAH tree nart_hip_create builds by default,
+   with the padding and the octree words it would have there.
+   nart_hip_context_bvh_dump: the tree the context built, host SAH or device LBVH (on_device = 1).
+   A multi-device context dumps its first device's tree (every device builds its own from the same
+   scene). */
+typedef struct nart_bvh_dump_info {
+    uint32_t num_nodes;
+    uint32_t num_leaf_tris;
+    uint32_t stack_depth;
+    int32_t root_code;
+    float pad;
+    uint32_t on_device;
+} nart_bvh_dump_info;
+int nart_hip_bvh_dump(const nart_scene_blob* scene, nart_bvh_dump_info* info, void* nodes, size_t nodes_cap,
+                      float* tri_isect, size_t isect_cap, float* tri_perm, size_t perm_cap);
+int nart_hip_context_bvh_dump(const nart_ctx* ctx, nart_bvh_dump_info* info, void* nodes, size_t nodes_cap,
+                              float* tri_isect, size_t isect_cap, float* tri_perm, size_t perm_cap);
+
 /* The acceleration structure a context built: nodes, stack depth, leaf triangles; reserved = 1
    when it was built on the device (NART_BVH_BUILD=device: a linear BVH, device/lbvh.h; default
    the host's binned SAH), and the build time in ms (host wall clock, uploads included). */

@@ -59,6 +59,18 @@ class BvhInfo(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+class BvhDumpInfo(ctypes.Structure):
+    """nart_bvh_dump_info (include/nart_hip.h)."""
+    _fields_ = [("num_nodes", ctypes.c_uint32), ("num_leaf_tris", ctypes.c_uint32), ("stack_depth", ctypes.c_uint32),
+                ("root_code", ctypes.c_int32), ("pad", ctypes.c_float), ("on_device", ctypes.c_uint32)]
+
+
+# BVHNode (csrc/device/dscene.h), 64 B: two child boxes, two child codes (>= 0 an inner node, < 0 a
+# leaf ~(first << 5 | (count - 1)))
+BVH_NODE_DTYPE = np.dtype([("lo0", np.float32, 3), ("hi0", np.float32, 3), ("lo1", np.float32, 3),
+                           ("hi1", np.float32, 3), ("child", np.int32, 2), ("pad", np.int32, 2)])
+
+
 # nart_render_stats.schedule bits (include/nart_hip.h NART_SCHED_*)
 SCHED = {"probe_queue": 0x1, "priority": 0x2, "spec_pairs": 0x4, "wave_groups": 0x8, "vol_queue": 0x10,
          "vol_sparse": 0x20, "splat_skew": 0x40, "primary": 0x80, "splat_rows": 0x100,
@@ -224,6 +236,10 @@ _HIP_SIGS = {
     "nart_hip_splat_lut": (ctypes.c_int, [ctypes.c_float, _P, ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(ctypes.c_uint32)]),
     "nart_hip_bvh_info": (ctypes.c_int, [_P, ctypes.POINTER(BvhInfo)]),
+    "nart_hip_bvh_dump": (ctypes.c_int, [_P, ctypes.POINTER(BvhDumpInfo), _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P,
+                                         ctypes.c_size_t]),
+    "nart_hip_context_bvh_dump": (ctypes.c_int, [_P, ctypes.POINTER(BvhDumpInfo), _P, ctypes.c_size_t, _P,
+                                                 ctypes.c_size_t, _P, ctypes.c_size_t]),
     "nart_hip_create_multi": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(_P)]),
     "nart_hip_context_devices": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "nart_hip_debug_fault": (ctypes.c_int, [_P, ctypes.c_int]),
@@ -360,6 +376,34 @@ def bvh_info(scene):
     if rc != NART_OK:
         raise NartError(rc, "nart_hip_bvh_info")
     return {"num_nodes": info.num_nodes, "stack_depth": info.stack_depth, "num_leaf_tris": info.num_leaf_tris}
+
+
+def _bvh_dump(entry, handle):
+    """The two-call protocol of nart_hip_bvh_dump / nart_hip_context_bvh_dump: sizes, then the copy."""
+    info = BvhDumpInfo()
+    rc = entry(handle, ctypes.byref(info), None, 0, None, 0, None, 0)
+    if rc != NART_OK:
+        raise NartError(rc, "BVH dump (size query)")
+    nn, nt = info.num_nodes, info.num_leaf_tris
+    nodes = np.zeros(max(nn, 1), BVH_NODE_DTYPE)
+    isect = np.zeros((max(nt, 1), 16), np.float32)
+    perm = np.zeros((3, max(nt, 1), 16), np.float32)
+    rc = entry(handle, ctypes.byref(info), nodes.ctypes.data, nn, isect.ctypes.data, nt * 16, perm.ctypes.data,
+               nt * 48)
+    if rc != NART_OK:
+        raise NartError(rc, "BVH dump")
+    return {"nodes": nodes[:nn], "tri_isect": isect[:nt], "tri_perm": perm[:, :nt], "root_code": int(info.root_code),
+            "pad": np.float32(info.pad), "stack_depth": int(info.stack_depth), "num_nodes": int(nn),
+            "num_leaf_tris": int(nt), "on_device": bool(info.on_device)}
+
+
+def bvh_dump(scene):
+    """Host only (test hook, nart_hip_bvh_dump): the binned-SAH tree a render context builds for `scene`
+    by default, as a dict of numpy arrays: "nodes" (a structured array lo0, hi0, lo1, hi1, child, pad),
+    "tri_isect" (num_leaf_tris, 16) float32 records in leaf order, "tri_perm" (3, num_leaf_tris, 16) the
+    records permuted per ray major axis, and "root_code", "pad" (float32: what the child boxes were
+    grown by), "stack_depth", "num_nodes", "num_leaf_tris", "on_device"."""
+    return _bvh_dump(hip_lib().nart_hip_bvh_dump, _P(scene.blob))
 
 
 class Scene:
@@ -518,6 +562,11 @@ class HipRenderer:
         self._check(self._lib.nart_hip_context_bvh(self._ctx, ctypes.byref(info), ctypes.byref(ms)))
         return {"num_nodes": info.num_nodes, "stack_depth": info.stack_depth, "num_leaf_tris": info.num_leaf_tris,
                 "on_device": bool(info.reserved), "build_ms": ms.value}
+
+    def bvh_dump(self):
+        """Test hook (nart_hip_context_bvh_dump): the tree this context built (host SAH or device
+        LBVH; a multi-device context's first device), copied to the host, as bvh_dump(scene) returns it."""
+        return _bvh_dump(self._lib.nart_hip_context_bvh_dump, self._ctx)
 
     def devices(self):
         """(number of devices, gather over RCCL) of this context."""

@@ -124,6 +124,8 @@ struct nart_ctx {
     bool bvh_on_device = false;
     double bvh_ms = 0.0;
     uint32_t num_leaf_tris = 0;
+    int32_t root_code = -1;  // the traversal's root (DScene::root), kept for nart_hip_context_bvh_dump
+    float bvh_pad = 0.f;     // what the child boxes were grown by
     void *d_gather = nullptr, *d_byid = nullptr, *d_image = nullptr, *d_slab_map = nullptr;
     size_t cap_gather = 0, cap_byid = 0, cap_image = 0, cap_slab_map = 0;
 };
@@ -2187,6 +2189,56 @@ int render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_
     return render_frame(ctx, p, rq, stats, aov_ms, moment_ms);
 }
 
+// Largest coordinate magnitude of the scene (triangles and camera position; at least 1): the scale
+// of the BVH box padding and of the octree margins (nart_hip_create, nart_hip_bvh_dump).
+float scene_maxabs(const nart_scene_blob& blob) {
+    float maxabs = 1.f;
+    for (uint32_t g = 0; g < blob.num_triangles; ++g) {
+        const nart_triangle& T = blob.triangles[g];
+        for (int k = 0; k < 3; ++k)
+            maxabs = std::max(maxabs, std::max(std::fabs(T.v0[k]), std::max(std::fabs(T.v1[k]), std::fabs(T.v2[k]))));
+    }
+    for (int k = 12; k < 15; ++k) maxabs = std::max(maxabs, std::fabs(blob.camera.m[k]));
+    for (int k = 3; k < 16; k += 4) maxabs = std::max(maxabs, std::fabs(blob.camera.m[k]));
+    return maxabs;
+}
+
+// vertex block of every triangle test record, permuted for each ray major axis, followed
+// by the plane {n, dot(v0, n)}: one 64-B record, so a test issues its four loads at once
+void permute_tri_records(const std::vector<float>& tri_isect, std::vector<float>& perm) {
+    const size_t nt = tri_isect.size() / 16;
+    perm.assign((3 * nt + NART_TRI_PAD) * 16, 0.f);  // + padding records (trav_step's record groups)
+    for (int m = 0; m < 3; ++m) {
+        const int kx = (m + 1) % 3, ky = (m + 2) % 3, kz = m;
+        for (size_t i = 0; i < nt; ++i) {
+            const float* r = &tri_isect[i * 16];
+            const float* v[3] = {r + 4, r + 7, r + 10};  // v0, v1, v2 (words 4-12)
+            float* o = &perm[((size_t)m * nt + i) * 16];
+            for (int k = 0; k < 3; ++k) {
+                o[3 * k + 0] = v[k][kx];
+                o[3 * k + 1] = v[k][ky];
+                o[3 * k + 2] = v[k][kz];
+            }
+            o[9] = r[13];   // global index
+            o[10] = r[14];  // octree leaf | inside bit
+            o[11] = r[15];  // grazing threshold
+            for (int k = 0; k < 4; ++k) o[12 + k] = r[k];  // plane (words 0-3)
+        }
+    }
+}
+
+// nart_hip_bvh_dump / nart_hip_context_bvh_dump: the sizes, and whether the caller's buffers hold them
+// (all three null: a size query)
+int bvh_dump_check(const nart_bvh_dump_info& info, const void* nodes, size_t nodes_cap, const float* tri_isect,
+                   size_t isect_cap, const float* tri_perm, size_t perm_cap) {
+    if (!nodes && !tri_isect && !tri_perm) return 1;
+    if (!nodes || !tri_isect || !tri_perm) return NART_E_INVALID;
+    if (nodes_cap < info.num_nodes || isect_cap < (size_t)info.num_leaf_tris * 16 ||
+        perm_cap < (size_t)info.num_leaf_tris * 48)
+        return NART_E_INVALID;
+    return NART_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2233,14 +2285,7 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
     uint32_t n_chunks = 0;
     nart::RefOctree oct;
     nart::reference_visibility(*blob, mask, root_leaf, n_chunks, &oct);
-    float maxabs = 1.f;
-    for (uint32_t g = 0; g < blob->num_triangles; ++g) {
-        const nart_triangle& T = blob->triangles[g];
-        for (int k = 0; k < 3; ++k)
-            maxabs = std::max(maxabs, std::max(std::fabs(T.v0[k]), std::max(std::fabs(T.v1[k]), std::fabs(T.v2[k]))));
-    }
-    for (int k = 12; k < 15; ++k) maxabs = std::max(maxabs, std::fabs(blob->camera.m[k]));
-    for (int k = 3; k < 16; k += 4) maxabs = std::max(maxabs, std::fabs(blob->camera.m[k]));
+    const float maxabs = scene_maxabs(*blob);
     // hit points deviate from the reference's slab arithmetic by far less than 2^-14 * scene
     // scale (|o| + |t d| <= 3 * maxabs, errors of a few ulps): octree.h oc_clear
     const float pad = maxabs * 6.103515625e-05f + 1e-6f, margin = maxabs * 6.103515625e-05f;
@@ -2263,27 +2308,8 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
         lb.num_leaf_tris = (uint32_t)(bvh.tri_isect.size() / 16);
         if ((rc = upload(ctx, ctx->d_nodes, bvh.nodes.data(), bvh.nodes.size()))) return bail(rc);
         if ((rc = upload(ctx, ctx->d_tri_isect, bvh.tri_isect.data(), bvh.tri_isect.size()))) return bail(rc);
-        // vertex block of every triangle test record, permuted for each ray major axis, followed
-        // by the plane {n, dot(v0, n)}: one 64-B record, so a test issues its four loads at once
-        const size_t nt = bvh.tri_isect.size() / 16;
-        std::vector<float> perm((3 * nt + NART_TRI_PAD) * 16);  // + padding records (trav_step's record groups)
-        for (int m = 0; m < 3; ++m) {
-            const int kx = (m + 1) % 3, ky = (m + 2) % 3, kz = m;
-            for (size_t i = 0; i < nt; ++i) {
-                const float* r = &bvh.tri_isect[i * 16];
-                const float* v[3] = {r + 4, r + 7, r + 10};  // v0, v1, v2 (words 4-12)
-                float* o = &perm[((size_t)m * nt + i) * 16];
-                for (int k = 0; k < 3; ++k) {
-                    o[3 * k + 0] = v[k][kx];
-                    o[3 * k + 1] = v[k][ky];
-                    o[3 * k + 2] = v[k][kz];
-                }
-                o[9] = r[13];   // global index
-                o[10] = r[14];  // octree leaf | inside bit
-                o[11] = r[15];  // grazing threshold
-                for (int k = 0; k < 4; ++k) o[12 + k] = r[k];  // plane (words 0-3)
-            }
-        }
+        std::vector<float> perm;
+        permute_tri_records(bvh.tri_isect, perm);
         if ((rc = upload(ctx, ctx->d_tri_perm, perm.data(), perm.size()))) return bail(rc);
     }
     ctx->bvh_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
@@ -2291,6 +2317,8 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
     if ((size_t)ctx->stack_depth * 256 * 8 > (size_t)160 * 1024) return bail(NART_E_UNSUPPORTED);  // LDS stack
     ctx->num_nodes = lb.num_nodes;
     ctx->num_leaf_tris = lb.num_leaf_tris;
+    ctx->root_code = lb.root_code;
+    ctx->bvh_pad = pad;
     std::vector<uint32_t> tri_mesh(blob->num_triangles);
     std::vector<DMesh> meshes(blob->num_meshes);
     for (uint32_t m = 0; m < blob->num_meshes; ++m) {
@@ -2723,6 +2751,62 @@ int nart_hip_bvh_info(const nart_scene_blob* blob, nart_bvh_info* out) {
     out->stack_depth = std::max<uint32_t>(bvh.max_stack + 1, 2);  // as nart_hip_create
     out->num_leaf_tris = bvh.num_leaf_tris;
     out->reserved = 0;
+    return NART_OK;
+}
+
+int nart_hip_bvh_dump(const nart_scene_blob* blob, nart_bvh_dump_info* info, void* nodes, size_t nodes_cap,
+                      float* tri_isect, size_t isect_cap, float* tri_perm, size_t perm_cap) {
+    if (!blob || !info) return NART_E_INVALID;
+    // as nart_hip_create's host build
+    std::vector<uint8_t> mask;
+    bool root_leaf = false;
+    uint32_t n_chunks = 0;
+    nart::RefOctree oct;
+    nart::reference_visibility(*blob, mask, root_leaf, n_chunks, &oct);
+    const float maxabs = scene_maxabs(*blob);
+    const float pad = maxabs * 6.103515625e-05f + 1e-6f, margin = maxabs * 6.103515625e-05f;
+    nart::BuiltBVH bvh;
+    nart::build_bvh(*blob, mask, pad, bvh);
+    nart::annotate_octree_leaves(*blob, oct, margin, bvh);
+    info->num_nodes = (uint32_t)bvh.nodes.size();
+    info->num_leaf_tris = (uint32_t)(bvh.tri_isect.size() / 16);
+    info->stack_depth = std::max<uint32_t>(bvh.max_stack + 1, 2);
+    info->root_code = bvh.root_code;
+    info->pad = pad;
+    info->on_device = 0;
+    const int rc = bvh_dump_check(*info, nodes, nodes_cap, tri_isect, isect_cap, tri_perm, perm_cap);
+    if (rc) return rc < 0 ? rc : NART_OK;
+    std::vector<float> perm;
+    permute_tri_records(bvh.tri_isect, perm);
+    if (info->num_nodes) std::memcpy(nodes, bvh.nodes.data(), (size_t)info->num_nodes * sizeof(BVHNode));
+    if (info->num_leaf_tris) {
+        std::memcpy(tri_isect, bvh.tri_isect.data(), (size_t)info->num_leaf_tris * 64);
+        std::memcpy(tri_perm, perm.data(), (size_t)info->num_leaf_tris * 3 * 64);
+    }
+    return NART_OK;
+}
+
+int nart_hip_context_bvh_dump(const nart_ctx* ctx, nart_bvh_dump_info* info, void* nodes, size_t nodes_cap,
+                              float* tri_isect, size_t isect_cap, float* tri_perm, size_t perm_cap) {
+    if (!ctx || !info) return NART_E_INVALID;
+    const nart_ctx* c = ctx->subs.empty() ? ctx : ctx->subs[0];
+    info->num_nodes = c->num_nodes;
+    info->num_leaf_tris = c->num_leaf_tris;
+    info->stack_depth = c->stack_depth;
+    info->root_code = c->root_code;
+    info->pad = c->bvh_pad;
+    info->on_device = c->bvh_on_device ? 1u : 0u;
+    const int rc = bvh_dump_check(*info, nodes, nodes_cap, tri_isect, isect_cap, tri_perm, perm_cap);
+    if (rc) return rc < 0 ? rc : NART_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return NART_E_HIP;
+    const size_t nt = info->num_leaf_tris;
+    if ((info->num_nodes &&
+         hipMemcpy(nodes, c->d_nodes, (size_t)info->num_nodes * sizeof(BVHNode), hipMemcpyDeviceToHost) != hipSuccess) ||
+        (nt && (hipMemcpy(tri_isect, c->d_tri_isect, nt * 64, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(tri_perm, c->d_tri_perm, nt * 3 * 64, hipMemcpyDeviceToHost) != hipSuccess))) {
+        (void)hipGetLastError();
+        return NART_E_HIP;
+    }
     return NART_OK;
 }
 
