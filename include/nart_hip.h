@@ -240,6 +240,97 @@ int nart_hip_render_adaptive(nart_ctx* ctx, const nart_render_params* p, const n
                              nart_pixel* image, nart_pixel* albedo, nart_pixel* normal, nart_pixel* moment,
                              uint32_t* bucket_spp, float* bucket_error, nart_render_stats* stats, double* adaptive_ms);
 
+/* Firefly cascade (no reference counterpart): a robust image next to the beauty, after Zirr, Hanika
+   and Dachsbacher, "Re-weighting Firefly Samples for Improved Finite-Sample Monte Carlo Estimates"
+   (2018).  Every sample is split by luminance between two neighbouring brightness layers, each layer
+   is splatted and combined like any other image, and a layer's contribution to a pixel is trusted
+   only as far as the pixel's 3x3 neighbourhood holds enough samples of about that brightness: a real
+   highlight or caustic has many, a firefly has one.  Opt-in: no other entry point changes its bits,
+   its launches or the memory it finds.
+
+   All arithmetic is float32 + - * / and comparisons, one operation each, in the order written
+   (nothing contracted, divide correctly rounded); tests/cascade_py.py restates it in numpy.
+   lum(r, g, b) = (0.2126 * r + 0.7152 * g) + 0.0722 * b.
+
+   Levels: b_0 = start, b_{j+1} = b_j * base, j < K = layers, formed on the host in float32.  A level
+   that is not finite, or not above the level before it (a denormal start), is NART_E_INVALID.
+
+   Split, per sample record L = {r, g, b, a}, l = lum(r, g, b):
+       if !(l - l == 0) (not finite) or l <= b_0:   layer 0 takes the record whole
+       else if l > b_{K-1}:                         layer K-1 takes it whole
+       else, j the index with b_j < l <= b_{j+1}:
+           w_lo = (b_{j+1} / l - 1) / (base - 1),  w_hi = 1 - w_lo
+           layer j   gets {r * w_lo, g * w_lo, b * w_lo, a * w_lo}
+           layer j+1 gets {r * w_hi, g * w_hi, b * w_hi, a * w_hi}
+   and every other layer's record for the sample is exactly {+0, +0, +0, +0}.  In exact arithmetic the
+   layers sum to the sample and sum_j w_j * l / b_j = 1, which is what lets a layer's brightness be
+   read as a sample count.  (With levels that are powers of two, the defaults among them, both
+   weights lie in [0, 1]; another base can round w_lo an ulp beyond 1 right above a level.)
+
+   Layer images: each layer's record stream goes through the beauty's splat plan and the tile combine
+   as if it were Li_alpha (the plain splat kernels, unchanged), so every layer image's
+   filter_weight_sum has the beauty's bits.  On the device k_cascade_split writes layer j's records
+   into a second per-sample record buffer (16 B per sample, held only while the call runs:
+   batches are sized for 44 instead of 28 B per sample in such a call) right after the beauty's
+   splat, once per layer per batch, each time followed by the plan's splat into that layer's tiles.
+
+   Reweighting (k_cascade_reweight), over the cropped image_width x image_height image (pixel (x, y) is
+   total-image pixel (x + fb, y + fb)), per pixel p; C_j layer j's pixel, W = beauty.filter_weight_sum,
+   N = float(spp):
+       m_j      = C_j.rgb / W per channel                       (0 where W <= 0)
+       lambda_j = lum(m_j) > 0 ? lum(m_j) : 0                   (so a NaN counts as no samples)
+       omega_0  = 1;  for j >= 1:
+           acc = 0, cnt = 0
+           over the taps q = p + (dx, dy), dy = -1, 0, 1 outer, dx = -1, 0, 1 inner, those inside
+           the cropped image only:
+               s = (lambda_{j-1}(q) + lambda_j(q)) + lambda_{j+1}(q)     (last term omitted for j = K-1)
+               acc = acc + s,  cnt = cnt + 1
+           g = ((acc * N) / b_j) / cnt      the mean expected number of samples of about this
+                                            brightness per neighbourhood pixel
+           t = g / kappa,  omega_j = t < 1 ? t : 1              (a NaN gives 1)
+       rgb   = ((m_0 + omega_1 * m_1) + omega_2 * m_2) + ...    per channel
+       alpha = beauty.a / W
+   The output is a nart_pixel image of totalW x totalH: cropped pixels {rgb, alpha, 1}, border pixels
+   all zero, as the denoiser's; where W <= 0 the pixel is all zeros, weight included.  A non-finite
+   layer pixel stays non-finite (omega * NaN), as in the beauty, and reaches no further than its own
+   3x3 neighbourhood.  The image is a pure function of the inputs: no atomics, any launch shape.
+
+   nart_hip_cascade_defaults: layers 6, start 1, base 8, kappa 2.
+   nart_hip_cascade_levels (host only, no device): the K levels into levels (room for 8; null to
+   query *n).  cp null: the defaults.
+   nart_hip_render_cascade: renders the beauty and the K layers and reweights on the device (a
+   multi-device context renders each shard's layer tiles next to its beauty tiles, gathers them with
+   the beauty's gather and reweights on its first device).  image (required) receives the robust
+   image; beauty, if non-null, the beauty with nart_hip_render's bits; layers, if non-null, the K layer
+   images back to back (K * totalW * totalH nart_pixel), for users with their own reweighting.  cp
+   null: the defaults.  The volume integrator is supported (the cascade needs no surfaces).
+   nart_hip_cascade_reweight: the filter alone over host images, as nart_hip_denoise is for the
+   denoiser; multi-device contexts run it on their first device.  p gives the image geometry and spp.
+   nart_hip_cascade_timings: device times (ms, HIP events) of the last cascade call of the context:
+   cascade_ms the split and layer splats (the slowest device's; 0 after nart_hip_cascade_reweight),
+   reweight_ms the reweighting.  Either pointer may be null.
+   NART_E_INVALID: layers outside 2..8, a start, base or kappa that is not finite, start <= 0,
+   base <= 1, kappa <= 0, a bad level (above), a null ctx, p, image (or beauty or layers of
+   nart_hip_cascade_reweight), spp < 1.  NART_E_OOM: a failed allocation; the context is then as it
+   was.  Not offered: the cascade together with adaptive sampling, with the first-hit AOVs or the
+   moment image, or with the denoiser in one call (there is no entry point that combines them, and
+   the CLI refuses --robust with --adaptive, --aovs and --denoise); whether the robust image should
+   feed the denoiser is a later decision. */
+typedef struct nart_cascade_params {
+    uint32_t layers;  /* K, 2..8                                                    default 6 */
+    float start;      /* b_0, the first level: finite and > 0                       default 1 */
+    float base;       /* the ratio between levels: finite and > 1                   default 8 */
+    float kappa;      /* the neighbourhood's expected sample count at which a layer
+                         is fully trusted: finite and > 0                           default 2 */
+} nart_cascade_params;
+void nart_hip_cascade_defaults(nart_cascade_params* cp);
+int nart_hip_cascade_levels(const nart_cascade_params* cp, float* levels, uint32_t* n);
+int nart_hip_render_cascade(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params* cp, nart_pixel* image,
+                            nart_pixel* beauty, nart_pixel* layers, nart_render_stats* stats);
+int nart_hip_cascade_reweight(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params* cp,
+                              const nart_pixel* beauty, const nart_pixel* layers, nart_pixel* image);
+int nart_hip_cascade_timings(const nart_ctx* ctx, double* cascade_ms, double* reweight_ms);
+
 /* Debug / parity, as nart_hip_render_samples: the per-sample AOV records of pixels [x0,x0+w) x
    [y0,y0+h) in total-image coordinates (extra rows included) into host
    out8[((y-y0)*w + (x-x0))*spp + s][8] = albedo record then normal record; tri (optional) receives

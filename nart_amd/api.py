@@ -138,6 +138,24 @@ class AdaptiveParams(ctypes.Structure):
         return "AdaptiveParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
 
 
+class CascadeParams(ctypes.Structure):
+    """nart_cascade_params (include/nart_hip.h, "Firefly cascade"); CascadeParams.defaults() is
+    nart_hip_cascade_defaults, keyword arguments override single fields."""
+    _fields_ = [("layers", ctypes.c_uint32), ("start", ctypes.c_float), ("base", ctypes.c_float),
+                ("kappa", ctypes.c_float)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        cp = cls()
+        hip_lib().nart_hip_cascade_defaults(ctypes.byref(cp))
+        for k, v in kw.items():
+            setattr(cp, k, v)
+        return cp
+
+    def __repr__(self):
+        return "CascadeParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
 class _Texture(ctypes.Structure):
     """nart_texture (include/nart_scene.h)."""
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("rgba", _P)]
@@ -204,6 +222,14 @@ _HIP_SIGS = {
     "nart_hip_render_adaptive": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(AdaptiveParams),
                                                 ctypes.c_uint32, _P, _P, _P, _P, _P, _P, ctypes.POINTER(RenderStats),
                                                 ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_cascade_defaults": (None, [ctypes.POINTER(CascadeParams)]),
+    "nart_hip_cascade_levels": (ctypes.c_int, [ctypes.POINTER(CascadeParams), ctypes.POINTER(ctypes.c_float),
+                                               ctypes.POINTER(ctypes.c_uint32)]),
+    "nart_hip_render_cascade": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(CascadeParams), _P, _P, _P,
+                                               ctypes.POINTER(RenderStats)]),
+    "nart_hip_cascade_reweight": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(CascadeParams), _P, _P,
+                                                 _P]),
+    "nart_hip_cascade_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_aov_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, ctypes.c_uint32,
                                                    ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "nart_hip_denoise_params_init": (None, [ctypes.POINTER(DenoiseParams)]),
@@ -658,6 +684,54 @@ class HipRenderer:
         out["adaptive_ms"] = ms.value
         return out
 
+    def _cascade_timings(self, out):
+        c, w = ctypes.c_double(), ctypes.c_double()
+        self._check(self._lib.nart_hip_cascade_timings(self._ctx, ctypes.byref(c), ctypes.byref(w)))
+        out["cascade_ms"], out["reweight_ms"] = c.value, w.value
+        return out
+
+    def render_robust(self, p, params=None, with_beauty=False, with_layers=False, stats=None):
+        """Firefly cascade (nart_hip_render_cascade; include/nart_hip.h has the definition): every
+        sample is split by luminance between two neighbouring brightness layers, and a layer counts
+        in a pixel only as far as the pixel's 3x3 neighbourhood holds enough samples of about that
+        brightness.  params a CascadeParams (None: the defaults).  Returns a dict with "robust", the
+        (totalH, totalW, 5) float32 image {rgb, alpha, 1} in the cropped window and zero in the border
+        (finalize() and write_exr() take it as they take a render); "beauty" (bit-identical to
+        render()) and "layers" ((K, totalH, totalW, 5): the layer images, each with the beauty's filter
+        weight sum) if requested; "levels" (float32 b_0 .. b_{K-1}); "cascade_ms", the device time of
+        the split and layer splats, and "reweight_ms", that of the reweighting."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        levels = cascade_levels(params)
+        out = {"robust": np.empty(shape, np.float32), "levels": levels}
+        if with_beauty:
+            out["beauty"] = np.empty(shape, np.float32)
+        if with_layers:
+            out["layers"] = np.empty((len(levels),) + shape, np.float32)
+        ptr = lambda name: out[name].ctypes.data if name in out else None
+        st = stats if stats is not None else RenderStats()
+        self._check(self._lib.nart_hip_render_cascade(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
+                                                      ptr("robust"), ptr("beauty"), ptr("layers"), ctypes.byref(st)))
+        return self._cascade_timings(out)
+
+    def cascade_reweight(self, p, beauty, layers, params=None):
+        """The cascade's reweighting alone over host images (nart_hip_cascade_reweight): beauty a
+        (totalH, totalW, 5) float32 image and layers the (K, totalH, totalW, 5) layer images as
+        render_robust(with_beauty=True, with_layers=True) returns them, K = params.layers; p gives
+        the geometry and spp.  Returns a dict with "robust" and "reweight_ms"."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        K = len(cascade_levels(params))
+        b = np.ascontiguousarray(beauty, dtype=np.float32)
+        l = np.ascontiguousarray(layers, dtype=np.float32)
+        if b.shape != shape or l.shape != (K,) + shape:
+            raise ValueError("cascade_reweight: images of shape %s and %s, expected %s and %s"
+                             % (b.shape, l.shape, shape, (K,) + shape))
+        out = {"robust": np.empty(shape, np.float32)}
+        self._check(self._lib.nart_hip_cascade_reweight(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
+                                                        b.ctypes.data, l.ctypes.data, out["robust"].ctypes.data))
+        return self._cascade_timings(out)
+
     def render_aov_samples(self, p, x0, y0, w, h):
         """Per-sample AOV records of a rect in total-image coordinates (nart_hip_render_aov_samples):
         (h, w, spp, 8) float32 = {albedo.rgb, hit, normal.xyz, depth} and (h, w, spp) uint32 first-hit
@@ -786,6 +860,17 @@ def adaptive_levels(params, spp):
     if rc != NART_OK:
         raise NartError(rc, "nart_hip_adaptive_levels: invalid parameters or spp < 2")
     return [int(levels[i]) for i in range(n.value)]
+
+
+def cascade_levels(params=None):
+    """Host only: the brightness levels b_0 .. b_{K-1} of the firefly cascade as float32
+    (nart_hip_cascade_levels).  params a CascadeParams (None: the defaults); invalid ones raise."""
+    lib = hip_lib()
+    levels, n = (ctypes.c_float * 8)(), ctypes.c_uint32()
+    rc = lib.nart_hip_cascade_levels(ctypes.byref(params) if params else None, levels, ctypes.byref(n))
+    if rc != NART_OK:
+        raise NartError(rc, "nart_hip_cascade_levels: invalid cascade parameters")
+    return np.array([levels[i] for i in range(n.value)], np.float32)
 
 
 def spp_image(p, bucket_spp):

@@ -27,6 +27,10 @@
 //                   images go through nart_hip_denoise, with --sample-variance too through
 //                   nart_hip_denoise_moment
 //   --min-spp N     with --adaptive: the samples of the pilot pass (default 16); without it an error
+//   --robust [KAPPA]  also write every session's firefly-robust image (nart_hip_render_cascade, default
+//                   parameters; KAPPA, if the next argument is a number, replaces kappa) to
+//                   <out>.robust.exr; <out>.exr is the same call's beauty.  Not offered together with
+//                   --adaptive, --aovs or --denoise: an error
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -139,6 +143,30 @@ bool take_value_flag(std::vector<char*>& args, const char* flag, const char*& va
     return true;
 }
 
+// Removes every `flag [number]` from argv; true if it was there.  The argument after the flag is
+// its value only if all of it parses as a number (the last value into `value`).
+bool take_optional_value_flag(std::vector<char*>& args, const char* flag, float& value) {
+    std::vector<char*> kept;
+    bool found = false;
+    for (size_t i = 0; i < args.size(); ++i) {
+        if (std::strcmp(args[i], flag)) {
+            kept.push_back(args[i]);
+            continue;
+        }
+        found = true;
+        if (i + 1 < args.size() && args[i + 1][0]) {
+            char* end = nullptr;
+            const float v = std::strtof(args[i + 1], &end);
+            if (!*end) {
+                value = v;
+                ++i;
+            }
+        }
+    }
+    args = kept;
+    return found;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[]) {
@@ -159,6 +187,18 @@ int main(int argc, char* argv[]) {
         return EXIT_FAILURE;
     }
     const bool adaptive = adaptive_arg != nullptr;
+    nart_cascade_params cp;
+    nart_hip_cascade_defaults(&cp);
+    const bool robust = take_optional_value_flag(args, "--robust", cp.kappa);
+    if (robust && (adaptive || aovs || denoise)) {
+        std::fprintf(stderr, "Error: --robust is not offered together with --adaptive, --aovs or --denoise\n");
+        return EXIT_FAILURE;
+    }
+    uint32_t n_levels = 0;
+    if (robust && nart_hip_cascade_levels(&cp, nullptr, &n_levels) != NART_OK) {
+        std::fprintf(stderr, "Error: --robust %g: kappa must be finite and > 0\n", cp.kappa);
+        return EXIT_FAILURE;
+    }
     nart_adaptive_params ap;
     nart_hip_adaptive_params_init(&ap);
     if (adaptive) {
@@ -212,10 +252,13 @@ int main(int argc, char* argv[]) {
         nart_session_geometry g;
         nart_session_geometry_of(&p, &g);
         std::vector<nart_pixel> image((size_t)g.total_width * g.total_height);
-        std::vector<nart_pixel> albedo, normal, denoised, moment;
+        std::vector<nart_pixel> albedo, normal, denoised, moment, robust_img;
         if (denoise) denoised.resize(image.size());
         std::vector<uint32_t> bucket_spp;
-        if (adaptive) {
+        if (robust) {
+            robust_img.resize(image.size());
+            rc = nart_hip_render_cascade(ctx, &p, &cp, robust_img.data(), image.data(), nullptr, nullptr);
+        } else if (adaptive) {
             // the adaptive call renders what the flags need; the denoiser then runs over its images
             const bool guides = aovs || denoise;
             if (guides) {
@@ -290,6 +333,7 @@ int main(int argc, char* argv[]) {
             extra.push_back({".normal.exr", normal.data()});
         }
         if (denoise) extra.push_back({".denoised.exr", denoised.data()});
+        if (robust) extra.push_back({".robust.exr", robust_img.data()});
         std::vector<nart_pixel> spp_img;
         if (adaptive) {
             // pixel (x, y) of the cropped image was traced by bucket (x / B, y / B)

@@ -17,6 +17,7 @@
 
 #include "../../include/nart_hip.h"
 #include "device/adaptive.h"
+#include "device/cascade.h"
 #include "device/denoise.h"
 #include "device/lbvh.h"
 #include "device/volume.h"
@@ -82,6 +83,10 @@ struct nart_ctx {
     hipEvent_t ev_aov[4] = {nullptr, nullptr, nullptr, nullptr};
     // around the error and scatter kernels of an adaptive level (render_buckets_adaptive)
     hipEvent_t ev_ad[2] = {nullptr, nullptr};
+    // firefly cascade: around the split + layer splats of a batch ([0], [1]: render_buckets) and
+    // around the reweighting ([2], [3]: cascade_device); the last cascade call's times
+    hipEvent_t ev_cas[4] = {nullptr, nullptr, nullptr, nullptr};
+    double cas_ms[2] = {0.0, 0.0};  // split + layer splats, reweighting
     // denoiser (denoise_device): work buffers over the cropped image, the four device images of
     // nart_hip_denoise / nart_hip_render_denoised (five with the moment image), events between its
     // kernels, the last run's times
@@ -423,8 +428,9 @@ int check_params(nart_ctx* ctx, const nart_render_params* p) {
 // (plus what this context already holds for it), at least 16 GiB: whole frames up to 4K x 512 spp
 // (119 GB) render in one batch -- fewer launch tails than the former fixed 16 GiB (C5 469 -> 413
 // ms, C4 5.27 -> 4.43 s per frame; profiles/r03a_bb_c4.log, r03a_bb_c5_s*.log).  NART_BATCH_BYTES
-// overrides.
-size_t batch_slot_limit(const nart_ctx* ctx, uint32_t spp) {
+// overrides.  A cascade call (nart_hip_render_cascade) holds a second record buffer while it runs:
+// extra_per_sample = 16, 44 B per sample; every other call passes 0 and sees what it saw before.
+size_t batch_slot_limit(const nart_ctx* ctx, uint32_t spp, size_t extra_per_sample = 0) {
     size_t budget = (size_t)16 << 30;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
@@ -437,7 +443,7 @@ size_t batch_slot_limit(const nart_ctx* ctx, uint32_t spp) {
         (void)hipGetLastError();
     }
     if (const char* e = env_opt("NART_BATCH_BYTES")) budget = (size_t)std::strtoull(e, nullptr, 10);
-    size_t per = 8 + (size_t)spp * (sizeof(float2) + sizeof(float4) + sizeof(uint32_t));
+    size_t per = 8 + (size_t)spp * (sizeof(float2) + sizeof(float4) + sizeof(uint32_t) + extra_per_sample);
     size_t n = budget / per;
     return n < 256 ? 256 : n;
 }
@@ -1177,11 +1183,22 @@ int launch_latin(nart_ctx* ctx, const RenderArgs& ra, hipStream_t st) {
 // AOV-only render, which launches no path kernel.  ms: device time of the k_aov + AOV splat launches.
 // moment: tiles of the second-moment image (k_moment + the MOM splat over the batch's Li_alpha, so it
 // needs the beauty's path kernel), moment_ms their device time.
+// cascade: the firefly cascade's layer tiles (include/nart_hip.h, "Firefly cascade"): layers[j]
+// receives layer j's share of every Li_alpha record (k_cascade_split into a second record buffer of
+// the call, then the plain splat), cascade_ms their device time.  Needs the beauty as well.
+struct CascadeLevels {
+    uint32_t K = 0;
+    float base = 0.f;
+    float b[CASCADE_MAX_LAYERS] = {};
+};
 struct AovRequest {
     float* tiles[2] = {nullptr, nullptr};
     float* moment = nullptr;
     bool beauty = true;
     double ms = 0.0, moment_ms = 0.0;
+    const CascadeLevels* cascade = nullptr;
+    float* layers[CASCADE_MAX_LAYERS] = {};
+    double cascade_ms = 0.0;
 
     bool first_hit() const { return tiles[0] || tiles[1]; }
 };
@@ -1250,6 +1267,17 @@ struct RenderTimer {
     ~RenderTimer() {
         using ms = std::chrono::duration<double, std::milli>;
         if (stats) stats->render_ms += ms(std::chrono::steady_clock::now() - t0).count();
+    }
+};
+
+// Temporaries of one call, freed when it returns.
+struct ScopedDeviceBufs {
+    void* p[2] = {nullptr, nullptr};
+    ScopedDeviceBufs() = default;
+    ScopedDeviceBufs(const ScopedDeviceBufs&) = delete;
+    ~ScopedDeviceBufs() {
+        for (void* b : p)
+            if (b) hipFree(b);
     }
 };
 
@@ -1416,13 +1444,17 @@ int launch_splat(nart_ctx* ctx, const SplatPlan& plan, const SplatArgs& sa, uint
 // Shared by all entry points.  With `aov` each batch also splats the requested first-hit AOV records
 // (k_aov into ctx->d_L, which the beauty splat has consumed by then: no extra per-sample memory)
 // into the request's tiles; with aov->moment, between the two, the second-moment image (k_moment
-// squares the Li_alpha records in place, one more splat pass with MOM).
+// squares the Li_alpha records in place, one more splat pass with MOM).  With aov->cascade, right
+// after the beauty's splat and before anything overwrites d_L, one k_cascade_split + plain splat per
+// layer; the second record buffer they go through is a temporary of this call.
 int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n, float* d_tiles,
                    hipStream_t st, nart_render_stats* stats, AovRequest* aov = nullptr) {
     int rc = NART_OK;
     const bool beauty = !aov || aov->beauty;
     const bool first_hit = aov && aov->first_hit(), moment = aov && aov->moment;
     if (moment && !beauty) return fail(ctx, NART_E_INVALID, "the moment image needs the path kernel (the beauty)");
+    const CascadeLevels* cascade = aov ? aov->cascade : nullptr;
+    if (cascade && !beauty) return fail(ctx, NART_E_INVALID, "the cascade layers need the path kernel (the beauty)");
     HIPCHK(hipSetDevice(ctx->device));
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
@@ -1441,7 +1473,12 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
     if (aov)
         for (auto& e : ctx->ev_aov)
             if (!e) HIPCHK(hipEventCreate(&e));
-    const size_t limit = batch_slot_limit(ctx, p->spp);
+    if (cascade)
+        for (int k = 0; k < 2; ++k)
+            if (!ctx->ev_cas[k]) HIPCHK(hipEventCreate(&ctx->ev_cas[k]));
+    const size_t limit = batch_slot_limit(ctx, p->spp, cascade ? sizeof(float4) : 0);
+    ScopedDeviceBufs layer_records;  // cascade: the second per-sample record buffer, 16 B per sample
+    size_t layer_records_cap = 0;
     const uint32_t tpx = g.tile_size * g.tile_size;
     nart_render_stats acc;  // this call's share, added to *stats at the end
     std::memset(&acc, 0, sizeof(acc));
@@ -1500,6 +1537,39 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         sa.n_buckets = nbk;
         if (beauty && (rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
         HIPCHK(hipEventRecord(ctx->ev[2], st));
+        if (cascade) {
+            const uint64_t ns = (uint64_t)nslots * p->spp;
+            if (ns > layer_records_cap) {
+                void* smaller = layer_records.p[0];
+                layer_records.p[0] = nullptr;
+                layer_records_cap = 0;
+                if (smaller) HIPCHK(hipFree(smaller));
+                if ((rc = dmalloc(ctx, &layer_records.p[0], ns * sizeof(float4), "cascade layer records"))) return rc;
+                layer_records_cap = ns;
+            }
+            HIPCHK(hipEventRecord(ctx->ev_cas[0], st));
+            CascadeSplitArgs ca;
+            ca.L = ctx->d_L;
+            ca.out = static_cast<float4*>(layer_records.p[0]);
+            ca.n = ns;
+            ca.K = cascade->K;
+            ca.b_first = cascade->b[0];
+            ca.b_top = cascade->b[cascade->K - 1];
+            ca.base_m1 = cascade->base - 1.f;
+            sa.Lout = ca.out;
+            for (uint32_t j = 0; j < cascade->K; ++j) {
+                ca.j = j;
+                ca.b_prev = j > 0 ? cascade->b[j - 1] : 0.f;
+                ca.b_cur = cascade->b[j];
+                ca.b_next = j + 1 < cascade->K ? cascade->b[j + 1] : 0.f;
+                hipLaunchKernelGGL(k_cascade_split, dim3((uint32_t)((ns + 255) / 256)), dim3(256), 0, st, ca);
+                HIPCHK(hipGetLastError());
+                sa.tiles = aov->layers[j] + (size_t)b0 * tpx * 5;
+                if ((rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
+            }
+            sa.Lout = ctx->d_L;
+            HIPCHK(hipEventRecord(ctx->ev_cas[1], st));
+        }
         if (moment) {
             HIPCHK(hipEventRecord(ctx->ev_aov[2], st));
             const uint64_t ns = (uint64_t)nslots * p->spp;
@@ -1523,8 +1593,13 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             HIPCHK(hipEventSynchronize(ctx->ev_aov[1]));
         }
         if (moment) HIPCHK(hipEventSynchronize(ctx->ev_aov[3]));
+        if (cascade) HIPCHK(hipEventSynchronize(ctx->ev_cas[1]));
         HIPCHK(hipEventSynchronize(ctx->ev[2]));
         float ms = 0.f;
+        if (cascade) {
+            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_cas[0], ctx->ev_cas[1]));
+            aov->cascade_ms += ms;
+        }
         if (first_hit) {
             HIPCHK(hipEventElapsedTime(&ms, ctx->ev_aov[0], ctx->ev_aov[1]));
             aov->ms += ms;
@@ -1679,7 +1754,9 @@ int build_bvh_device(nart_ctx* ctx, const nart_scene_blob& blob, const std::vect
 // ---------------------------------------------------------------- whole frames
 // What a whole-frame render produces, where it goes and whose buffers it uses (render_frame).
 // Buffer k: 0 the beauty, 1 + a first-hit AOV a (AOV_ALBEDO, AOV_NORMAL), 3 the second-moment image.
+// With the firefly cascade (FrameRequest::cascade) buffer FRAME_BUFS + j is layer j's image.
 constexpr int FRAME_BUFS = 4;
+constexpr int FRAME_BUFS_ALL = FRAME_BUFS + (int)CASCADE_MAX_LAYERS;
 
 // One adaptive render (include/nart_hip.h, "Adaptive sampling"): the validated parameters and the
 // level list going in; coming out, per bucket (in the order of the list rendered: bucket-id order for
@@ -1701,7 +1778,7 @@ struct FrameRequest {
     // Delivery: the image of buffer k to the host at dst[k] (null: rendered, not delivered); or
     // on_device, the images of the requested buffers back to back, in buffer order, from the start of
     // *image on device 0 (ordered on its null stream: single-device frames do not wait for them).
-    nart_pixel* dst[FRAME_BUFS] = {nullptr, nullptr, nullptr, nullptr};
+    nart_pixel* dst[FRAME_BUFS_ALL] = {};
     bool on_device = false;
     // The call's tile and image buffers.  image null: temporaries, allocated by the call and freed on
     // every return path.  Else borrowed from a context, which keeps them for its next call (the
@@ -1714,20 +1791,16 @@ struct FrameRequest {
     // Adaptive sampling: every device refines its own buckets (render_buckets_adaptive) instead of
     // rendering them once at p->spp; needs the beauty.  Null: the uniform render.
     AdaptiveRun* adaptive = nullptr;
+    // Firefly cascade: the K layer images next to the beauty (needs it; not with adaptive);
+    // *cascade_ms receives the device time of the split and layer splats (the slowest device's).
+    const CascadeLevels* cascade = nullptr;
+    double* cascade_ms = nullptr;
 
-    bool wants(int k) const { return k == 0 ? beauty : (k == 3 ? moment : aov[k - 1]); }
-    bool wants_aovs() const { return aov[0] || aov[1]; }
-};
-
-// Temporaries of one call, freed when it returns.
-struct ScopedDeviceBufs {
-    void* p[2] = {nullptr, nullptr};
-    ScopedDeviceBufs() = default;
-    ScopedDeviceBufs(const ScopedDeviceBufs&) = delete;
-    ~ScopedDeviceBufs() {
-        for (void* b : p)
-            if (b) hipFree(b);
+    bool wants(int k) const {
+        if (k >= FRAME_BUFS) return cascade && (uint32_t)(k - FRAME_BUFS) < cascade->K;
+        return k == 0 ? beauty : (k == 3 ? moment : aov[k - 1]);
     }
+    bool wants_aovs() const { return aov[0] || aov[1]; }
 };
 
 // The buffers a context keeps for whole frames (render_frame, render_multi) and the denoiser.
@@ -1900,6 +1973,9 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     if (moment_ms) *moment_ms = 0.0;
     if (rq.moment && !rq.beauty)
         return fail(ctx, NART_E_INVALID, "the moment image needs the path kernel: it cannot be rendered without the beauty");
+    if (rq.cascade && (!rq.beauty || rq.adaptive))
+        return fail(ctx, NART_E_UNSUPPORTED, "the cascade layers need the beauty and a uniform render");
+    if (rq.cascade_ms) *rq.cascade_ms = 0.0;
     nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // device 0: combines, holds the images
     int rc = NART_OK;
     if (rq.wants_aovs() && (rc = check_first_hit(ctx, p))) return rc;
@@ -1912,7 +1988,7 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     const size_t tile_floats = (size_t)nb * g.tile_size * g.tile_size * 5;
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5;
     size_t K = 0;  // buffers requested
-    for (int k = 0; k < FRAME_BUFS; ++k) K += rq.wants(k);
+    for (int k = 0; k < FRAME_BUFS_ALL; ++k) K += rq.wants(k);
     if (rq.image && (rc = ensure_dev(ctx, c0->device, *rq.image, *rq.image_cap,
                                      std::max<size_t>(K, rq.images) * img_floats * sizeof(float), "image")))
         return rc;
@@ -1929,8 +2005,8 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     else if (!(rc = dmalloc(ctx, &d_tiles, tile_bytes, "tiles")))
         rc = dmalloc(ctx, &d_img, img_floats * sizeof(float), "image");
     if (rc) return rc;
-    float* tiles[FRAME_BUFS] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0, i = 0; k < FRAME_BUFS; ++k)
+    float* tiles[FRAME_BUFS_ALL] = {};
+    for (int k = 0, i = 0; k < FRAME_BUFS_ALL; ++k)
         if (rq.wants(k)) tiles[k] = static_cast<float*>(d_tiles) + (size_t)(i++) * tile_floats;
     std::vector<uint32_t> ids(nb);
     for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
@@ -1939,16 +2015,20 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     areq.tiles[0] = tiles[1];
     areq.tiles[1] = tiles[2];
     areq.moment = tiles[3];
+    areq.cascade = rq.cascade;
+    for (uint32_t j = 0; j < CASCADE_MAX_LAYERS; ++j) areq.layers[j] = tiles[FRAME_BUFS + j];
     if (rq.adaptive) {
         rc = render_buckets_adaptive(ctx, p, ids.data(), nb, tiles, 0, stats, *rq.adaptive);
         areq.ms = rq.adaptive->aov_ms;
         areq.moment_ms = rq.adaptive->moment_ms;
     } else {
-        rc = render_buckets(ctx, p, ids.data(), nb, tiles[0], 0, stats, rq.wants_aovs() || rq.moment ? &areq : nullptr);
+        rc = render_buckets(ctx, p, ids.data(), nb, tiles[0], 0, stats,
+                            rq.wants_aovs() || rq.moment || rq.cascade ? &areq : nullptr);
     }
     if (aov_ms) *aov_ms = areq.ms;
     if (moment_ms) *moment_ms = areq.moment_ms;
-    for (int k = 0, i = 0; k < FRAME_BUFS && !rc; ++k) {
+    if (rq.cascade_ms) *rq.cascade_ms = areq.cascade_ms;
+    for (int k = 0, i = 0; k < FRAME_BUFS_ALL && !rc; ++k) {
         if (!rq.wants(k) || (!rq.on_device && !rq.dst[k])) continue;
         float* img = static_cast<float*>(d_img) + (rq.on_device ? (size_t)(i++) * img_floats : 0);
         rc = nart_hip_combine_async(ctx, p, reinterpret_cast<const nart_pixel*>(tiles[k]),
@@ -2187,6 +2267,162 @@ int render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_
     rq.dst[1 + AOV_NORMAL] = normal;
     rq.dst[3] = moment;
     return render_frame(ctx, p, rq, stats, aov_ms, moment_ms);
+}
+
+// ---------------------------------------------------------------- firefly cascade (device/cascade.h)
+void cascade_defaults(nart_cascade_params* cp) {
+    cp->layers = 6;
+    cp->start = 1.f;
+    cp->base = 8.f;
+    cp->kappa = 2.f;
+}
+
+// cp (null: the defaults) into out and its levels into lv; the message of what is wrong, or null.
+const char* cascade_params_error(const nart_cascade_params* cp, nart_cascade_params& out, CascadeLevels& lv) {
+    if (cp) out = *cp;
+    else cascade_defaults(&out);
+    if (out.layers < 2 || out.layers > CASCADE_MAX_LAYERS) return "cascade layers must be in 2..8";
+    if (!std::isfinite(out.start) || !(out.start > 0.f)) return "cascade start must be finite and > 0";
+    if (!std::isfinite(out.base) || !(out.base > 1.f)) return "cascade base must be finite and > 1";
+    if (!std::isfinite(out.kappa) || !(out.kappa > 0.f)) return "cascade kappa must be finite and > 0";
+    lv.K = out.layers;
+    lv.base = out.base;
+    float b = out.start;
+    for (uint32_t j = 0; j < lv.K; ++j) {
+        if (!std::isfinite(b)) return "a cascade level is not finite";
+        if (j > 0 && !(b > lv.b[j - 1])) return "the cascade levels do not increase (start too small for base)";
+        lv.b[j] = b;
+        b = b * out.base;
+    }
+    return nullptr;
+}
+
+// The reweighting over device images on a single-device context: beauty, the K layer images back to
+// back, the robust image out; synchronous.  The time goes to ctx->cas_ms[1].
+int cascade_device(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params& cp, const CascadeLevels& lv,
+                   const float* d_beauty, const float* d_layers, float* d_out, hipStream_t st) {
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    for (int k = 2; k < 4; ++k)
+        if (!ctx->ev_cas[k]) HIPCHK(hipEventCreate(&ctx->ev_cas[k]));
+    CascadeReweightArgs a;
+    a.beauty = d_beauty;
+    a.layers = d_layers;
+    a.out = d_out;
+    a.W = p->image_width;
+    a.H = p->image_height;
+    a.totalW = g.total_width;
+    a.totalH = g.total_height;
+    a.fb = g.filter_bounds;
+    a.K = lv.K;
+    a.N = (float)p->spp;
+    a.kappa = cp.kappa;
+    for (uint32_t j = 0; j < CASCADE_MAX_LAYERS; ++j) a.b[j] = j < lv.K ? lv.b[j] : 0.f;
+    HIPCHK(hipEventRecord(ctx->ev_cas[2], st));
+    // the border stays zero: the kernel writes the cropped pixels only
+    HIPCHK(hipMemsetAsync(d_out, 0, (size_t)g.total_width * g.total_height * sizeof(nart_pixel), st));
+    const dim3 grid((a.W + CS_TW - 1) / CS_TW, (a.H + CS_TH - 1) / CS_TH), block(CS_TW * CS_TH);
+    hipLaunchKernelGGL(k_cascade_reweight, grid, block, (size_t)lv.K * CS_PLANE * sizeof(float), st, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev_cas[3], st));
+    HIPCHK(hipEventSynchronize(ctx->ev_cas[3]));
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, ctx->ev_cas[2], ctx->ev_cas[3]));
+    ctx->cas_ms[1] = t;
+    return NART_OK;
+}
+
+// The tile buffers a context keeps between whole frames grow with the number of buffers a frame
+// asks for.  A cascade frame asks for up to nine: what it made them grow by is given back when the
+// call returns, so that a later render finds the free memory (batch_slot_limit) it found before.
+struct CascadeTileGuard {
+    nart_ctx* ctx;
+    size_t gather_cap;
+    std::vector<size_t> sub_cap;
+    explicit CascadeTileGuard(nart_ctx* c) : ctx(c), gather_cap(c->cap_gather), sub_cap(c->sub_cap) {}
+    CascadeTileGuard(const CascadeTileGuard&) = delete;
+    ~CascadeTileGuard() {
+        const int dev0 = ctx->subs.empty() ? ctx->device : ctx->devs[0];
+        if (ctx->cap_gather > gather_cap && hipSetDevice(dev0) == hipSuccess) {
+            hipFree(ctx->d_gather);
+            ctx->d_gather = nullptr;
+            ctx->cap_gather = 0;
+        }
+        for (size_t d = 0; d < sub_cap.size(); ++d)
+            if (ctx->sub_cap[d] > sub_cap[d] && hipSetDevice(ctx->devs[d]) == hipSuccess) {
+                hipFree(ctx->sub_tiles[d]);
+                ctx->sub_tiles[d] = nullptr;
+                ctx->sub_cap[d] = 0;
+            }
+    }
+};
+
+int check_cascade_frame(nart_ctx* ctx, const nart_render_params* p) {
+    if (!p->image_width || !p->image_height || !(p->filter_width > 0.f))
+        return fail(ctx, NART_E_INVALID, "imageWidth, imageHeight and filterWidth must be > 0");
+    if (p->spp < 1) return fail(ctx, NART_E_INVALID, "the cascade needs spp >= 1");
+    return NART_OK;
+}
+
+// nart_hip_render_cascade: the beauty and the K layers through render_frame into device images of
+// the call, the reweighting on device 0 after them, then what the caller asked for to the host.
+int render_cascade(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params& cp, const CascadeLevels& lv,
+                   nart_pixel* image, nart_pixel* beauty, nart_pixel* layers, nart_render_stats* stats) {
+    nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];
+    ctx->cas_ms[0] = ctx->cas_ms[1] = 0.0;
+    CascadeTileGuard guard(ctx);
+    ScopedDeviceBufs imgs;  // the device images of the call, on device 0
+    size_t imgs_cap = 0;
+    const uint32_t K = lv.K;
+    FrameRequest rq;
+    rq.cascade = &lv;
+    rq.cascade_ms = &ctx->cas_ms[0];
+    rq.on_device = true;
+    rq.image = &imgs.p[0];
+    rq.image_cap = &imgs_cap;
+    rq.images = K + 2;  // the beauty, the layers, the robust image
+    int rc = render_frame(ctx, p, rq, stats, nullptr);
+    if (rc) return rc;
+    RenderTimer timer(stats);  // render_ms covers the whole call
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
+    float* d = static_cast<float*>(imgs.p[0]);
+    float* d_out = d + (size_t)(K + 1) * img_floats;
+    if ((rc = cascade_device(c0, p, cp, lv, d, d + img_floats, d_out, 0))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
+    ctx->cas_ms[1] = c0->cas_ms[1];
+    HIPCHK(hipSetDevice(c0->device));
+    HIPCHK(hipMemcpy(image, d_out, img_bytes, hipMemcpyDeviceToHost));
+    if (beauty) HIPCHK(hipMemcpy(beauty, d, img_bytes, hipMemcpyDeviceToHost));
+    if (layers) HIPCHK(hipMemcpy(layers, d + img_floats, (size_t)K * img_bytes, hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+// nart_hip_cascade_reweight: host images through the (first) device.
+int cascade_host(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params& cp, const CascadeLevels& lv,
+                 const nart_pixel* beauty, const nart_pixel* layers, nart_pixel* image) {
+    if (!ctx->subs.empty()) {
+        const int rc = cascade_host(ctx->subs[0], p, cp, lv, beauty, layers, image);
+        ctx->cas_ms[0] = 0.0;
+        ctx->cas_ms[1] = ctx->subs[0]->cas_ms[1];
+        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
+    }
+    ctx->cas_ms[0] = ctx->cas_ms[1] = 0.0;
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const uint32_t K = lv.K;
+    const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
+    ScopedDeviceBufs imgs;  // the beauty, the layers, the robust image
+    if (int rc = dmalloc(ctx, &imgs.p[0], (size_t)(K + 2) * img_bytes, "cascade images")) return rc;
+    float* d = static_cast<float*>(imgs.p[0]);
+    float* d_out = d + (size_t)(K + 1) * img_floats;
+    HIPCHK(hipMemcpy(d, beauty, img_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + img_floats, layers, (size_t)K * img_bytes, hipMemcpyHostToDevice));
+    if (int rc = cascade_device(ctx, p, cp, lv, d, d + img_floats, d_out, 0)) return rc;
+    HIPCHK(hipMemcpy(image, d_out, img_bytes, hipMemcpyDeviceToHost));
+    return NART_OK;
 }
 
 // Largest coordinate magnitude of the scene (triangles and camera position; at least 1): the scale
@@ -2469,6 +2705,8 @@ void nart_hip_destroy(nart_ctx* ctx) {
         if (e) hipEventDestroy(e);
     for (auto& e : ctx->ev_ad)
         if (e) hipEventDestroy(e);
+    for (auto& e : ctx->ev_cas)
+        if (e) hipEventDestroy(e);
     delete ctx;
 }
 
@@ -2633,6 +2871,47 @@ int nart_hip_render_adaptive(nart_ctx* ctx, const nart_render_params* p, const n
     if (bucket_spp) std::copy(run.spp.begin(), run.spp.end(), bucket_spp);
     if (bucket_error) std::copy(run.err.begin(), run.err.end(), bucket_error);
     if (adaptive_ms) *adaptive_ms = run.ms;
+    return NART_OK;
+}
+
+void nart_hip_cascade_defaults(nart_cascade_params* cp) {
+    if (cp) cascade_defaults(cp);
+}
+
+int nart_hip_cascade_levels(const nart_cascade_params* cp, float* levels, uint32_t* n) {
+    if (!n) return NART_E_INVALID;
+    nart_cascade_params c;
+    CascadeLevels lv;
+    if (cascade_params_error(cp, c, lv)) return NART_E_INVALID;
+    *n = lv.K;
+    if (levels) std::copy(lv.b, lv.b + lv.K, levels);
+    return NART_OK;
+}
+
+int nart_hip_render_cascade(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params* cp, nart_pixel* image,
+                            nart_pixel* beauty, nart_pixel* layers, nart_render_stats* stats) {
+    nart_cascade_params c;
+    CascadeLevels lv;
+    if (const char* why = cascade_params_error(cp, c, lv)) return fail(ctx, NART_E_INVALID, why);
+    if (!ctx || !p || !image) return NART_E_INVALID;
+    if (int rc = check_cascade_frame(ctx, p)) return rc;
+    return render_cascade(ctx, p, c, lv, image, beauty, layers, stats);
+}
+
+int nart_hip_cascade_reweight(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params* cp,
+                              const nart_pixel* beauty, const nart_pixel* layers, nart_pixel* image) {
+    nart_cascade_params c;
+    CascadeLevels lv;
+    if (const char* why = cascade_params_error(cp, c, lv)) return fail(ctx, NART_E_INVALID, why);
+    if (!ctx || !p || !beauty || !layers || !image) return NART_E_INVALID;
+    if (int rc = check_cascade_frame(ctx, p)) return rc;
+    return cascade_host(ctx, p, c, lv, beauty, layers, image);
+}
+
+int nart_hip_cascade_timings(const nart_ctx* ctx, double* cascade_ms, double* reweight_ms) {
+    if (!ctx) return NART_E_INVALID;
+    if (cascade_ms) *cascade_ms = ctx->cas_ms[0];
+    if (reweight_ms) *reweight_ms = ctx->cas_ms[1];
     return NART_OK;
 }
 
