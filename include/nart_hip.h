@@ -37,8 +37,21 @@ typedef struct nart_render_stats {
                                its launches; observability for tests and benches)         */
     uint64_t samples;       /* camera samples counted in the metric (W*H*spp share)     */
     uint64_t traced_samples;/* samples actually traced (incl. extra rows, render.cpp:164) */
-    /* Counter pass only (nart_hip_set_counters(ctx,1)); zero otherwise.  bounces = extension
-     * hits shaded (BSDF + EstimateDirect + continuation). */
+    /* Counter pass only (nart_hip_set_counters(ctx,1)); zero otherwise.
+     * rays_extend, bounces and rays_shadow are path counts: each accepted sample's, whichever lane
+     * or schedule ran it (a speculative lane's sample counts once it is verified, a dropped one
+     * never), so they depend only on the scene and the session.
+     *   rays_extend  closest-hit queries: the camera ray of every traced sample with a bounce limit
+     *                above zero, plus one per continued bounce (pathintegrator.cpp:184)
+     *   bounces      "shaded" hits: extension queries that found a surface, i.e. every hit the
+     *                integrator processes -- a BSDF is built for it; where the nested-dielectric
+     *                list admits it, EstimateDirect and the continuation sample follow, otherwise
+     *                (a lower-priority interface) the path only steps through it
+     *   rays_shadow  occlusion queries of EstimateDirect actually traced: the device skips a query
+     *                whose term is exactly zero, so this is at most the reference's two per valid hit
+     * node_visits, tri_tests (and octree_checks, octree_replays below) are traversal work, added by
+     * whichever lane traces a ray: they include the speculative lanes' dropped samples and the
+     * packet traversal of the camera rays, so they do depend on the schedule. */
     uint64_t rays_extend, rays_shadow, node_visits, tri_tests, bounces;
     double latin_ms;        /* device time of the LatinSquare kernel                    */
     /* Counter pass only: hits whose octree reachability needed the exact ancestor-chain check,

@@ -1095,7 +1095,8 @@ NHD size_t rq_lds_bytes(uint32_t stack_depth, uint32_t block) {
 #ifndef NART_RQ_BLOCK
 #define NART_RQ_BLOCK 512
 #endif
-// The counter pass (COUNT: untimed, its counts are per ray and do not depend on the schedule) runs
+// The counter pass (COUNT: untimed; its path counts are per accepted sample and do not depend on the
+// schedule, its traversal counts include the speculative lanes' dropped work) runs
 // 256-lane blocks at one wave per SIMD, so its counters do not push the kernel past 256 VGPRs.
 //
 // WV = 3: the lean throughput build for launches of >= 3 rounds of resident waves (whole frames),
@@ -1200,6 +1201,16 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
 
     TraceCounters cnt = {0u, 0u, 0u, 0u};
     uint32_t n_ext = 0, n_sh = 0, n_bounce = 0;
+    // COUNT: the path counts of the lane's current sample, added to the totals where the sample's result
+    // is written -- a speculative job's only once it is verified, a dropped job's never -- so that the
+    // totals are per accepted sample and do not depend on the schedule (cnt, the traversal work, is
+    // added by whichever lane traces a ray and does include dropped speculation)
+    uint32_t j_ext = 0, j_sh = 0, j_bounce = 0;
+    auto count_sample = [&]() {
+        n_ext += j_ext;
+        n_sh += j_sh;
+        n_bounce += j_bounce;
+    };
     f3 L = F3(0.f, 0.f, 0.f), beta = F3(0.f, 0.f, 0.f);
     f3 c1 = F3(0.f, 0.f, 0.f), c2 = F3(0.f, 0.f, 0.f), betak = F3(0.f, 0.f, 0.f);
     float alpha = 0.f, eta_sampled = 1.f, eta_outer = 1.f, alphaTweak = 1.f;
@@ -1268,13 +1279,14 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
             jfl |= J_FIN;
         } else {
             A.Lout[soff + (uint64_t)s * sstr] = v;
+            if (COUNT) count_sample();
             ++s;
         }
     };
     auto queue_ext = [&](f3 o, f3 d) {
         put_ray(0, o, d, light_loop(o, d));
         ext_pending = true;
-        if (COUNT) ++n_ext;
+        if (COUNT) ++j_ext;
     };
 
     bool raised = false;  // this wave runs at a raised issue priority (A.rq_setprio)
@@ -1357,7 +1369,10 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
                     for (uint32_t k = 0; k < 4; ++k)
                         if (gs[k] == pF && (gfl[k] & J_VER) && (gfl[k] & J_FIN)) kc = k;
                     if (kc == 4u) break;
-                    if (kc == mi) A.Lout[soff + (uint64_t)pF * sstr] = jres;
+                    if (kc == mi) {
+                        A.Lout[soff + (uint64_t)pF * sstr] = jres;
+                        if (COUNT) count_sample();
+                    }
                     // majority vote over the committed samples' draw counts
                     uint32_t n = 0u, e = 0u;
 #pragma unroll
@@ -1487,6 +1502,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
         //    a hit is to be shaded, a ray is queued or the pixel is done.
         while (active) {
             nd = 0;
+            if (COUNT) j_ext = j_sh = j_bounce = 0;
             // pixel-major rows (stride 1): samples and camera hits are read in pairs, the odd one
             // kept for the lane's next sample -- each read of a line the lane's neighbours do not
             // share then serves two samples
@@ -1555,7 +1571,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
         }
         // 3. shade the hits (pathintegrator.cpp:185-246)
         if (need_shade) {
-            if (COUNT) ++n_bounce;
+            if (COUNT) ++j_bounce;  // shaded hit (nart_hip.h nart_render_stats::bounces)
             const float4 ro = my_out[lane * 2], rd = my_out[lane * 2 + 1];
             const Ray cur = make_ray(F3(ro.x, ro.y, ro.z), F3(rd.x, rd.y, rd.z));
             Isect is;
@@ -1664,7 +1680,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
                 }
             }
             ++bounce;
-            if (COUNT) n_sh += (use1 ? 1u : 0u) + (use2 ? 1u : 0u);
+            if (COUNT) j_sh += (use1 ? 1u : 0u) + (use2 ? 1u : 0u);
             ext_pending = false;
             if (cont && bounce < A.bounces) queue_ext(no, nd);
             if (newk) {

@@ -1078,7 +1078,8 @@ static v3 light_sample_li(const oracle_scene* s, int li_idx, lisect_t* li, v3 p,
 typedef struct { uint32_t meshID; uint32_t priority; float eta; } iinfo_t;
 #define SHADOW_BIAS 0.001f
 
-typedef struct { heap_t heap; } worker_t;
+/* cnt: this worker's path counts (ORACLE_N_* in nart_oracle.h), summed over the workers after a render */
+typedef struct { heap_t heap; uint64_t cnt[ORACLE_N_COUNTS]; } worker_t;
 
 static int isect_is_valid(const isect_t* is, const iinfo_t* list, uint32_t n, float* eta_outer) { /* pathintegrator.cpp:7-36 */
     *eta_outer = 1.f;
@@ -1128,6 +1129,7 @@ static v3 estimate_direct(const oracle_scene* s, worker_t* w, v3 wo, const bsdf_
         isect_t sh;
         isect_init(&sh);
         sh.tMax = li.tMax;
+        ++w->cnt[ORACLE_N_VISIBILITY]; /* pathintegrator.cpp:72 */
         if (!bvh_intersect(s, &shadow, &sh, &w->heap)) {
             float weight = 1.f;
             if (!(*flags & F_SPECULAR)) {
@@ -1153,6 +1155,7 @@ static v3 estimate_direct(const oracle_scene* s, worker_t* w, v3 wo, const bsdf_
     isect_t sh;
     isect_init(&sh);
     sh.tMax = li.tMax;
+    ++w->cnt[ORACLE_N_VISIBILITY]; /* pathintegrator.cpp:105 */
     if (!bvh_intersect(s, &shadow, &sh, &w->heap) && lightingPdf > 0.f) {
         float weight = 1.f;
         scatteringPdf = bsdf_pdf(bsdf, wo, wi, 1, eta_outer);
@@ -1202,7 +1205,9 @@ static v4 li_alpha(const oracle_scene* s, worker_t* w, rng_t* rng, ray_t ray, co
                 alpha = 1.f;
             }
         }
+        ++w->cnt[ORACLE_N_EXTENSION]; /* pathintegrator.cpp:184 */
         if (bvh_intersect(s, &ray, &is, &w->heap)) {
+            ++w->cnt[ORACLE_N_SHADED];
             bsdf_t bsdf;
             create_bsdf(s, &is, alphaTweak, &bsdf);
             if (isect_is_valid(&is, list, nlist, &eta_outer)) {
@@ -1546,6 +1551,7 @@ static void render_tile(const oracle_scene* s, worker_t* w, const nart_render_pa
             latin_square(&rng, p->spp, smp);
             for (uint32_t i = 0; i < p->spp; ++i) {
                 ray_t ray = cast_ray(s, smp[i], p->image_width, p->image_height, x, y);
+                ++w->cnt[ORACLE_N_SAMPLES];
                 v4 L = p->integrator == NART_INTEGRATOR_VOLUME ? li_volume(s, &rng, ray, p) : li_alpha(s, w, &rng, ray, p);
                 v2 sc = V2((float)(x + ss->fb) + smp[i].x, (float)(y + ss->fb) + smp[i].y);
                 add_sample(ss, p, sc, L, tile);
@@ -1562,6 +1568,7 @@ typedef struct {
     uint32_t n;
     nart_pixel* tiles;
     atomic_uint next;
+    atomic_ullong cnt[ORACLE_N_COUNTS]; /* the workers' path counts, each added once when the worker ends */
 } job_t;
 
 static void* worker_main(void* arg) {
@@ -1576,6 +1583,7 @@ static void* worker_main(void* arg) {
         uint32_t id = j->ids[k];
         render_tile(j->s, &w, j->p, j->ss, id % j->ss->nbx, id / j->ss->nbx, j->tiles + tpx * k, smp);
     }
+    for (int c = 0; c < ORACLE_N_COUNTS; ++c) atomic_fetch_add(&j->cnt[c], (unsigned long long)w.cnt[c]);
     free(smp);
     free(w.heap.e);
     return NULL;
@@ -1591,8 +1599,8 @@ static int check_params(const oracle_scene* s, const nart_render_params* p) {
     return NART_OK;
 }
 
-int oracle_render_buckets(oracle_scene* s, const nart_render_params* p, const uint32_t* ids, uint32_t n,
-                          nart_pixel* tiles, int threads) {
+static int render_buckets_counted(oracle_scene* s, const nart_render_params* p, const uint32_t* ids, uint32_t n,
+                                  nart_pixel* tiles, int threads, uint64_t* counts) {
     int rc = check_params(s, p);
     if (rc) return rc;
     sess_t ss;
@@ -1605,15 +1613,28 @@ int oracle_render_buckets(oracle_scene* s, const nart_render_params* p, const ui
     j.n = n;
     j.tiles = tiles;
     atomic_init(&j.next, 0u);
+    for (int c = 0; c < ORACLE_N_COUNTS; ++c) atomic_init(&j.cnt[c], 0ull);
     if (threads < 1) threads = 1;
     pthread_t* th = (pthread_t*)malloc(sizeof(pthread_t) * (size_t)threads);
     for (int t = 0; t < threads; ++t) pthread_create(&th[t], NULL, worker_main, &j);
     for (int t = 0; t < threads; ++t) pthread_join(th[t], NULL);
     free(th);
+    if (counts)
+        for (int c = 0; c < ORACLE_N_COUNTS; ++c) counts[c] = (uint64_t)atomic_load(&j.cnt[c]);
     return NART_OK;
 }
 
+int oracle_render_buckets(oracle_scene* s, const nart_render_params* p, const uint32_t* ids, uint32_t n,
+                          nart_pixel* tiles, int threads) {
+    return render_buckets_counted(s, p, ids, n, tiles, threads, NULL);
+}
+
 int oracle_render(oracle_scene* s, const nart_render_params* p, nart_pixel* image, int threads) {
+    return oracle_render_counted(s, p, image, threads, NULL);
+}
+
+int oracle_render_counted(oracle_scene* s, const nart_render_params* p, nart_pixel* image, int threads,
+                          uint64_t* counts) {
     int rc = check_params(s, p);
     if (rc) return rc;
     sess_t ss;
@@ -1624,7 +1645,7 @@ int oracle_render(oracle_scene* s, const nart_render_params* p, nart_pixel* imag
     uint32_t* ids = (uint32_t*)malloc(sizeof(uint32_t) * nb);
     if (!tiles || !ids) { free(tiles); free(ids); return NART_E_OOM; }
     for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
-    rc = oracle_render_buckets(s, p, ids, nb, tiles, threads);
+    rc = render_buckets_counted(s, p, ids, nb, tiles, threads, counts);
     if (!rc) {
         /* combine in bucket raster order (render.cpp:183-203) */
         memset(image, 0, sizeof(nart_pixel) * ss.totalW * ss.totalH);

@@ -34,6 +34,20 @@ void oracle_destroy(oracle_scene* s);
    queue (tbb::task_group stand-in).  image: totalW*totalH Pixels. */
 int oracle_render(oracle_scene* s, const nart_render_params* p, nart_pixel* image, int threads);
 
+/* Path counts of one render, summed over the worker threads (each worker counts privately and adds
+   its totals once, so concurrent renders do not mix and counting changes no rendered bit):
+     EXTENSION   closest-hit queries of Li_alpha: the camera ray plus one per continued bounce
+                 (pathintegrator.cpp:184)
+     SHADED      those queries that found a surface -- every hit the integrator goes on to process,
+                 the lower-priority interfaces it only steps through included
+     VISIBILITY  occlusion queries of EstimateDirect (pathintegrator.cpp:72 and :105)
+     SAMPLES     camera samples traced (extra rows and columns included) */
+enum { ORACLE_N_EXTENSION = 0, ORACLE_N_SHADED = 1, ORACLE_N_VISIBILITY = 2, ORACLE_N_SAMPLES = 3, ORACLE_N_COUNTS = 4 };
+
+/* oracle_render that also reports the render's path counts: counts[ORACLE_N_COUNTS] (or NULL). */
+int oracle_render_counted(oracle_scene* s, const nart_render_params* p, nart_pixel* image, int threads,
+                          uint64_t* counts);
+
 /* RenderTile for a list of bucket ids into tiles[i] (tile_size^2 Pixels each). */
 int oracle_render_buckets(oracle_scene* s, const nart_render_params* p, const uint32_t* ids,
                           uint32_t n, nart_pixel* tiles, int threads);

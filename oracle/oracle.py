@@ -68,6 +68,7 @@ def lib():
         _lib.oracle_create.argtypes = [P, ctypes.POINTER(P)]
         _lib.oracle_destroy.argtypes = [P]
         _lib.oracle_render.argtypes = [P, P, P, ctypes.c_int]
+        _lib.oracle_render_counted.argtypes = [P, P, P, ctypes.c_int, P]
         _lib.oracle_render_buckets.argtypes = [P, P, P, ctypes.c_uint32, P, ctypes.c_int]
         _lib.oracle_render_samples.argtypes = [P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                ctypes.c_uint32, P, P]
@@ -86,6 +87,10 @@ def lib():
     return _lib
 
 
+# order of oracle_render_counted's counts (nart_oracle.h ORACLE_N_*)
+PATH_COUNTS = ("extension_queries", "shaded_hits", "visibility_queries", "traced_samples")
+
+
 class Oracle:
     def __init__(self, scene):
         self.scene = scene  # keeps the blob alive
@@ -94,13 +99,18 @@ class Oracle:
         if rc:
             raise RuntimeError("oracle_create failed: %d" % rc)
 
-    def render(self, p, threads=None):
+    def render(self, p, threads=None, counts=None):
+        """The whole frame.  counts: a dict that receives this render's path counts (PATH_COUNTS:
+        nart_oracle.h ORACLE_N_*), summed over the worker threads."""
         from nart_amd import session_geometry
         g = session_geometry(p)
         img = np.zeros((g.total_height, g.total_width, 5), np.float32)
-        rc = lib().oracle_render(self._h, ctypes.byref(p), img.ctypes.data, threads or default_threads())
+        c = (ctypes.c_uint64 * len(PATH_COUNTS))()
+        rc = lib().oracle_render_counted(self._h, ctypes.byref(p), img.ctypes.data, threads or default_threads(), c)
         if rc:
             raise RuntimeError("oracle_render failed: %d" % rc)
+        if counts is not None:
+            counts.update(zip(PATH_COUNTS, (int(v) for v in c)))
         return img
 
     def render_buckets(self, p, ids, threads=None):

@@ -148,6 +148,49 @@ def test_oracle_render_properties(glass_scene):
     assert np.isfinite(s).all()
 
 
+def test_oracle_path_counts(glass_scene, materials_scene):
+    """Oracle.render(counts=...): per-render path counts (nart_oracle.h ORACLE_N_*), the reference the
+    counter pass's rays_extend / bounces / rays_shadow are checked against.  Counting changes no
+    bit of the image, the sums do not depend on the number of workers, two renders running at the
+    same time do not mix, and the counts obey the integrator's structure (pathintegrator.cpp:165-246)."""
+    import threading
+    frames = []
+    for sc, w, h, spp in ((glass_scene, 40, 24, 3), (materials_scene, 33, 21, 2)):
+        p = nart_amd.load_sessions(sc.path)[0]
+        p.image_width, p.image_height, p.spp = w, h, spp
+        o = oracle.Oracle(sc)
+        c1, c4 = {}, {}
+        a = o.render(p, threads=1, counts=c1)
+        b = o.render(p, threads=4, counts=c4)
+        plain = o.render(p, threads=4)
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.array_equal(a.view(np.uint32), plain.view(np.uint32))
+        assert c1 == c4 and set(c1) == set(oracle.PATH_COUNTS)
+        g = nart_amd.session_geometry(p)
+        n = g.total_width * g.total_height * spp
+        assert c1["traced_samples"] == n
+        # one camera query per sample, then at most one more per shaded hit; a shaded hit makes at most
+        # the two occlusion queries of EstimateDirect
+        assert n <= c1["extension_queries"] <= n + c1["shaded_hits"]
+        assert 0 < c1["shaded_hits"] < c1["extension_queries"]
+        assert 0 < c1["visibility_queries"] <= 2 * c1["shaded_hits"]
+        frames.append((o, p, c1))
+        for bounces, ext in ((0, 0), (1, n)):
+            q = p.copy()
+            q.bounces = bounces
+            c = {}
+            o.render(q, counts=c)
+            assert c["extension_queries"] == ext and c["traced_samples"] == n
+            assert c["shaded_hits"] <= ext and (bounces or c["visibility_queries"] == 0)
+    got = [{}, {}]
+    th = [threading.Thread(target=lambda i=i: frames[i][0].render(frames[i][1], threads=3, counts=got[i]))
+          for i in range(2)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    assert got[0] == frames[0][2] and got[1] == frames[1][2]
+
+
 def test_oracle_tiles_combine_equals_render(glass_scene):
     """Render() == bucket tiles combined in raster order by the product's host combine."""
     p = nart_amd.load_sessions(glass_scene.path)[0]
