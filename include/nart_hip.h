@@ -344,6 +344,89 @@ int nart_hip_cascade_reweight(nart_ctx* ctx, const nart_render_params* p, const 
                               const nart_pixel* beauty, const nart_pixel* layers, nart_pixel* image);
 int nart_hip_cascade_timings(const nart_ctx* ctx, double* cascade_ms, double* reweight_ms);
 
+/* First-hit ID mattes (no reference counterpart): which mesh or material a pixel shows, and how much
+   of the pixel it covers.  A filtered average of ids means nothing at a silhouette, so an id image is
+   a set of (id, coverage) pairs per pixel, ranked by coverage (the Cryptomatte idea).  Opt-in: no
+   other entry point changes its bits, its launches or the memory it finds; the path kernels are not
+   touched.
+
+   Id kinds.  NART_MATTE_MESH: a sample's id is the mesh index of its first-hit triangle, in scene
+   order; N = num_meshes.  NART_MATTE_MATERIAL: that mesh's material index; N = num_materials.
+
+   The first hit is exactly the first-hit AOVs' hit: the reference octree's answer at bounce 0, bounded
+   by the nearest analytic light; IsectIsValid is not applied.  A miss has no id.  The feature needs
+   surfaces: the volume integrator returns NART_E_UNSUPPORTED.
+
+   Id limit.  N <= 32, because the 8 coverage planes are the extra images the frame path already
+   carries; more ids return NART_E_UNSUPPORTED.  N = 0 (a scene without meshes) is allowed and gives
+   empty ranks.
+
+   Coverage planes.  There are P = ceil(N / 4) planes.  The per-sample record of plane q is
+       {[id == 4q], [id == 4q+1], [id == 4q+2], [id == 4q+3]}   as 1.0f or +0.0f;
+   a miss or an id >= N gives all +0.  Each plane's record stream goes through the call's splat plan and
+   the tile combine exactly as Li_alpha does (the plain splat kernels, unchanged), so
+   plane[q].contribution[c] is the sum of the filter weights w over the samples of id 4q+c in
+   AddSample's order, and filter_weight_sum has the beauty's bits.  On the device k_matte_ids writes
+   plane q's records into the per-sample record buffer once the beauty's splat (if any) has consumed
+   it, once per plane per batch, each time followed by the plan's splat into that plane's tiles: no
+   extra per-sample memory, as for the first-hit AOVs.
+
+   Ranking (k_matte_rank), per pixel of the cropped image_width x image_height image (pixel (x, y) is
+   total-image pixel (x + fb, y + fb)); W = plane[0].filter_weight_sum:
+       c_m = plane[m / 4].contribution[m % 4] / W     one float32 divide, m < N
+       only ids with c_m > 0 are candidates (zero, negative and NaN values are never ranked)
+       rank r = 0 .. R-1 takes the candidate not yet taken with the greatest c_m; among equal values
+       the least m wins; a rank without a candidate is {-1.0f, 0.0f}
+   R = ranks: even, 2..8.
+   Rank output: R / 2 nart_pixel images of totalW x totalH.  Image k holds
+       {float(id_2k), c_2k, float(id_2k+1), c_2k+1, 1}
+   in cropped pixels; border pixels are all zero; where W <= 0 (or with N = 0) the pixel is
+   {-1, 0, -1, 0, 1}.  nart_write_exr works on these images unchanged; ids <= 31 are exact in half.
+
+   Extraction (k_matte_extract) takes an id set as a bit mask (bit m: id m).  Per cropped pixel
+       m = sum over r ascending, from 0, of c_r for the ranks whose id is in the set, in float32
+   (an id is in the set when 0 <= id < 64 and bit uint(id) of the mask is set); the output is a
+   nart_pixel image with cropped pixels {m, m, m, m, 1} and a zero border.
+
+   Every output is a pure function of its inputs: no atomics, any launch shape; tests/matte_py.py
+   restates planes, ranking and extraction in numpy.
+
+   nart_hip_matte_defaults: kind mesh, ranks 6.
+   nart_hip_matte_ids (host only, no device): N of a scene and kind into *n_ids; NART_E_UNSUPPORTED
+   above 32 (*n_ids is still set).
+   nart_hip_render_mattes: renders the P planes and ranks them on the device (a multi-device context
+   renders each shard's plane tiles, gathers them with the beauty's gather and ranks on its first
+   device).  ranks (required) receives the R / 2 rank images back to back; image, if non-null, the
+   beauty with nart_hip_render's bits (null: a matte-only call, which launches LatinSquare, the camera
+   rays and the plane passes, and no path kernel); planes, if non-null, the P plane images back to
+   back.  mp null: the defaults.
+   nart_hip_matte_rank: the ranking alone over P = ceil(n_ids / 4) host plane images (planes may be
+   null with n_ids = 0), as nart_hip_cascade_reweight is for the cascade; nart_hip_matte_extract: the
+   extraction over the R / 2 host rank images of mp.  Multi-device contexts run both on their first
+   device.  p gives the image geometry.
+   nart_hip_matte_timings: device times (ms, HIP events) of the last matte call of the context:
+   matte_ms the plane passes (the slowest device's; 0 after nart_hip_matte_rank), rank_ms the ranking.
+   Either pointer may be null.
+   NART_E_INVALID: a null ctx, p, ranks or required image; an unknown kind; ranks odd or outside
+   2..8; n_ids > 32 (nart_hip_matte_rank).  NART_E_UNSUPPORTED: the volume integrator, or more than 32
+   ids.  An error leaves the context usable.  Not offered: the mattes together with adaptive sampling
+   or the cascade in one call. */
+#define NART_MATTE_MESH 0u
+#define NART_MATTE_MATERIAL 1u
+typedef struct nart_matte_params {
+    uint32_t kind;   /* NART_MATTE_MESH or NART_MATTE_MATERIAL                      default mesh */
+    uint32_t ranks;  /* R, the (id, coverage) pairs kept per pixel: even, 2..8     default 6 */
+} nart_matte_params;
+void nart_hip_matte_defaults(nart_matte_params* mp);
+int nart_hip_matte_ids(const nart_scene_blob* scene, uint32_t kind, uint32_t* n_ids);
+int nart_hip_render_mattes(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params* mp, nart_pixel* ranks,
+                           nart_pixel* image, nart_pixel* planes, nart_render_stats* stats);
+int nart_hip_matte_rank(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params* mp, uint32_t n_ids,
+                        const nart_pixel* planes, nart_pixel* ranks);
+int nart_hip_matte_extract(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params* mp,
+                           const nart_pixel* ranks, uint64_t id_mask, nart_pixel* out);
+int nart_hip_matte_timings(const nart_ctx* ctx, double* matte_ms, double* rank_ms);
+
 /* Debug / parity, as nart_hip_render_samples: the per-sample AOV records of pixels [x0,x0+w) x
    [y0,y0+h) in total-image coordinates (extra rows included) into host
    out8[((y-y0)*w + (x-x0))*spp + s][8] = albedo record then normal record; tri (optional) receives

@@ -156,6 +156,26 @@ class CascadeParams(ctypes.Structure):
         return "CascadeParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
 
 
+class MatteParams(ctypes.Structure):
+    """nart_matte_params (include/nart_hip.h, "First-hit ID mattes"); MatteParams.defaults() is
+    nart_hip_matte_defaults, keyword arguments override single fields."""
+    _fields_ = [("kind", ctypes.c_uint32), ("ranks", ctypes.c_uint32)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        mp = cls()
+        hip_lib().nart_hip_matte_defaults(ctypes.byref(mp))
+        for k, v in kw.items():
+            setattr(mp, k, v)
+        return mp
+
+    def __repr__(self):
+        return "MatteParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
+MATTE_MESH, MATTE_MATERIAL = 0, 1  # NART_MATTE_* (include/nart_hip.h)
+
+
 class _Texture(ctypes.Structure):
     """nart_texture (include/nart_scene.h)."""
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("rgba", _P)]
@@ -230,6 +250,15 @@ _HIP_SIGS = {
     "nart_hip_cascade_reweight": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(CascadeParams), _P, _P,
                                                  _P]),
     "nart_hip_cascade_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_matte_defaults": (None, [ctypes.POINTER(MatteParams)]),
+    "nart_hip_matte_ids": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "nart_hip_render_mattes": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(MatteParams), _P, _P, _P,
+                                              ctypes.POINTER(RenderStats)]),
+    "nart_hip_matte_rank": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(MatteParams), ctypes.c_uint32,
+                                           _P, _P]),
+    "nart_hip_matte_extract": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(MatteParams), _P,
+                                              ctypes.c_uint64, _P]),
+    "nart_hip_matte_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_aov_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, ctypes.c_uint32,
                                                    ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "nart_hip_denoise_params_init": (None, [ctypes.POINTER(DenoiseParams)]),
@@ -732,6 +761,73 @@ class HipRenderer:
                                                         b.ctypes.data, l.ctypes.data, out["robust"].ctypes.data))
         return self._cascade_timings(out)
 
+    def _matte_timings(self, out):
+        m, r = ctypes.c_double(), ctypes.c_double()
+        self._check(self._lib.nart_hip_matte_timings(self._ctx, ctypes.byref(m), ctypes.byref(r)))
+        out["matte_ms"], out["rank_ms"] = m.value, r.value
+        return out
+
+    def render_mattes(self, p, params=None, with_beauty=False, with_planes=False, stats=None):
+        """First-hit ID mattes (nart_hip_render_mattes; include/nart_hip.h has the definition): per
+        pixel the R = params.ranks greatest (id, coverage) pairs of the meshes or materials its camera
+        samples hit first.  params a MatteParams (None: the defaults).  Returns a dict with "ranks", an
+        (R/2, totalH, totalW, 5) float32 array (image k: {id_2k, c_2k, id_2k+1, c_2k+1, 1} in the
+        cropped window, an empty rank is {-1, 0}; zero in the border; write_exr() takes each image as
+        it takes a render); "n_ids"; "beauty" (bit-identical to render()) and "planes" ((P, totalH,
+        totalW, 5): the coverage planes, four ids each, with the beauty's filter weight sum) if
+        requested; "matte_ms", the device time of the plane passes, and "rank_ms", that of the ranking.
+        Without with_beauty no path kernel is launched."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        mp = params if params is not None else MatteParams.defaults()
+        n = ctypes.c_uint32()
+        self._lib.nart_hip_matte_ids(self.scene.blob, mp.kind, ctypes.byref(n))  # the call below reports errors
+        out = {"ranks": np.empty((max(1, mp.ranks // 2),) + shape, np.float32), "n_ids": n.value}
+        if with_beauty:
+            out["beauty"] = np.empty(shape, np.float32)
+        if with_planes:
+            out["planes"] = np.empty(((n.value + 3) // 4,) + shape, np.float32)
+        ptr = lambda name: out[name].ctypes.data if name in out else None
+        st = stats if stats is not None else RenderStats()
+        self._check(self._lib.nart_hip_render_mattes(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
+                                                     ptr("ranks"), ptr("beauty"), ptr("planes"), ctypes.byref(st)))
+        out["ranks"] = out["ranks"][:mp.ranks // 2]
+        return self._matte_timings(out)
+
+    def matte_rank(self, p, planes, n_ids, params=None):
+        """The ranking alone over host planes (nart_hip_matte_rank): planes the (ceil(n_ids / 4), totalH,
+        totalW, 5) float32 coverage planes as render_mattes(with_planes=True) returns them; p gives the
+        geometry.  Returns a dict with "ranks" and "rank_ms"."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        mp = params if params is not None else MatteParams.defaults()
+        P = (int(n_ids) + 3) // 4
+        pl = np.ascontiguousarray(planes, dtype=np.float32).reshape((-1,) + shape)
+        if pl.shape[0] != P:
+            raise ValueError("matte_rank: %d planes, expected %d for %d ids" % (pl.shape[0], P, n_ids))
+        out = {"ranks": np.empty((max(1, mp.ranks // 2),) + shape, np.float32)}
+        self._check(self._lib.nart_hip_matte_rank(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
+                                                  int(n_ids), pl.ctypes.data if P else None, out["ranks"].ctypes.data))
+        out["ranks"] = out["ranks"][:mp.ranks // 2]
+        return self._matte_timings(out)
+
+    def matte_extract(self, p, ranks, ids, params=None):
+        """The coverage of an id set (nart_hip_matte_extract): ranks the (R/2, totalH, totalW, 5) rank
+        images of render_mattes() or matte_rank() with the same params; ids an iterable of ids or an
+        integer bit mask (bit m: id m).  Returns the (totalH, totalW, 5) float32 matte {m, m, m, m, 1}
+        (zero in the border)."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        mp = params if params is not None else MatteParams.defaults()
+        rk = np.ascontiguousarray(ranks, dtype=np.float32)
+        if rk.shape != (mp.ranks // 2,) + shape:
+            raise ValueError("matte_extract: rank images of shape %s, expected %s" % (rk.shape, (mp.ranks // 2,) + shape))
+        mask = ids if isinstance(ids, int) else sum(1 << int(i) for i in set(ids))
+        out = np.empty(shape, np.float32)
+        self._check(self._lib.nart_hip_matte_extract(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
+                                                     rk.ctypes.data, mask & (2 ** 64 - 1), out.ctypes.data))
+        return out
+
     def render_aov_samples(self, p, x0, y0, w, h):
         """Per-sample AOV records of a rect in total-image coordinates (nart_hip_render_aov_samples):
         (h, w, spp, 8) float32 = {albedo.rgb, hit, normal.xyz, depth} and (h, w, spp) uint32 first-hit
@@ -860,6 +956,17 @@ def adaptive_levels(params, spp):
     if rc != NART_OK:
         raise NartError(rc, "nart_hip_adaptive_levels: invalid parameters or spp < 2")
     return [int(levels[i]) for i in range(n.value)]
+
+
+def matte_ids(scene, kind=MATTE_MESH):
+    """Host only: the number of matte ids N of a scene for an id kind (nart_hip_matte_ids): its meshes
+    (MATTE_MESH) or its materials (MATTE_MATERIAL).  More than 32 raise NART_E_UNSUPPORTED."""
+    n = ctypes.c_uint32()
+    rc = hip_lib().nart_hip_matte_ids(scene.blob, int(kind), ctypes.byref(n))
+    if rc != NART_OK:
+        raise NartError(rc, "nart_hip_matte_ids: %s" % ("an unknown id kind" if rc == -1
+                                                        else "%d ids; at most 32 are supported" % n.value))
+    return n.value
 
 
 def cascade_levels(params=None):

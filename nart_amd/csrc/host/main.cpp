@@ -31,6 +31,13 @@
 //                   parameters; KAPPA, if the next argument is a number, replaces kappa) to
 //                   <out>.robust.exr; <out>.exr is the same call's beauty.  Not offered together with
 //                   --adaptive, --aovs or --denoise: an error
+//   --mattes [mesh|material]  also write every session's first-hit ID mattes (nart_hip_render_mattes;
+//                   ids are mesh indices by default) to <out>.matte.00.exr ... <out>.matte.0{R/2-1}.exr:
+//                   image k holds (id, coverage) of ranks 2k and 2k+1 in RG and BA; <out>.exr is the
+//                   same call's beauty.  With --aovs or --denoise the mattes are a matte-only call
+//                   after the main one.  Not offered together with --adaptive or --robust: an error
+//   --matte-ranks N with --mattes: the ranks kept per pixel, even and in 2..8 (default 6)
+//   --matte-ids a,b,..  with --mattes: also write <out>.matte.exr, the summed coverage of that id set
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -167,6 +174,30 @@ bool take_optional_value_flag(std::vector<char*>& args, const char* flag, float&
     return found;
 }
 
+// Removes every `flag [word]` from argv, where word is one of `words`; true if the flag was there
+// (the last word into `value`).
+bool take_optional_word_flag(std::vector<char*>& args, const char* flag, const std::vector<const char*>& words,
+                             const char*& value) {
+    std::vector<char*> kept;
+    bool found = false;
+    for (size_t i = 0; i < args.size(); ++i) {
+        if (std::strcmp(args[i], flag)) {
+            kept.push_back(args[i]);
+            continue;
+        }
+        found = true;
+        if (i + 1 < args.size())
+            for (const char* w : words)
+                if (!std::strcmp(args[i + 1], w)) {
+                    value = w;
+                    ++i;
+                    break;
+                }
+    }
+    args = kept;
+    return found;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[]) {
@@ -198,6 +229,45 @@ int main(int argc, char* argv[]) {
     if (robust && nart_hip_cascade_levels(&cp, nullptr, &n_levels) != NART_OK) {
         std::fprintf(stderr, "Error: --robust %g: kappa must be finite and > 0\n", cp.kappa);
         return EXIT_FAILURE;
+    }
+    nart_matte_params mp;
+    nart_hip_matte_defaults(&mp);
+    const char *matte_kind = nullptr, *matte_ranks_arg = nullptr, *matte_ids_arg = nullptr;
+    const bool mattes = take_optional_word_flag(args, "--mattes", {"mesh", "material"}, matte_kind);
+    if (!take_value_flag(args, "--matte-ranks", matte_ranks_arg) || !take_value_flag(args, "--matte-ids", matte_ids_arg))
+        return EXIT_FAILURE;
+    if ((matte_ranks_arg || matte_ids_arg) && !mattes) {
+        std::fprintf(stderr, "Error: --matte-ranks and --matte-ids belong to the ID mattes and need --mattes\n");
+        return EXIT_FAILURE;
+    }
+    if (mattes && (adaptive || robust)) {
+        std::fprintf(stderr, "Error: --mattes is not offered together with --adaptive or --robust\n");
+        return EXIT_FAILURE;
+    }
+    uint64_t matte_mask = 0;
+    if (mattes) {
+        if (matte_kind && !std::strcmp(matte_kind, "material")) mp.kind = NART_MATTE_MATERIAL;
+        int v = 0;
+        if (matte_ranks_arg && (!parse_int(matte_ranks_arg, v) || v < 2 || v > 8 || (v & 1))) {
+            std::fprintf(stderr, "Error: --matte-ranks %s: the ranks must be even and in 2..8\n", matte_ranks_arg);
+            return EXIT_FAILURE;
+        }
+        if (matte_ranks_arg) mp.ranks = (uint32_t)v;
+        if (matte_ids_arg) {
+            const std::string s(matte_ids_arg);
+            size_t pos = 0;
+            while (pos <= s.size()) {
+                size_t c = s.find(',', pos);
+                if (c == std::string::npos) c = s.size();
+                int id = 0;
+                if (!parse_int(s.substr(pos, c - pos).c_str(), id) || id < 0 || id > 31) {
+                    std::fprintf(stderr, "Error: --matte-ids %s: a comma-separated list of ids in 0..31\n", matte_ids_arg);
+                    return EXIT_FAILURE;
+                }
+                matte_mask |= 1ull << id;
+                pos = c + 1;
+            }
+        }
     }
     nart_adaptive_params ap;
     nart_hip_adaptive_params_init(&ap);
@@ -252,12 +322,17 @@ int main(int argc, char* argv[]) {
         nart_session_geometry g;
         nart_session_geometry_of(&p, &g);
         std::vector<nart_pixel> image((size_t)g.total_width * g.total_height);
-        std::vector<nart_pixel> albedo, normal, denoised, moment, robust_img;
+        std::vector<nart_pixel> albedo, normal, denoised, moment, robust_img, matte_ranks, matte_img;
+        if (mattes) matte_ranks.resize((size_t)(mp.ranks / 2) * image.size());
+        // alone, the matte call renders the beauty too; next to AOVs or the denoiser it follows their call
+        const bool mattes_after = mattes && (aovs || denoise);
         if (denoise) denoised.resize(image.size());
         std::vector<uint32_t> bucket_spp;
         if (robust) {
             robust_img.resize(image.size());
             rc = nart_hip_render_cascade(ctx, &p, &cp, robust_img.data(), image.data(), nullptr, nullptr);
+        } else if (mattes && !mattes_after) {
+            rc = nart_hip_render_mattes(ctx, &p, &mp, matte_ranks.data(), image.data(), nullptr, nullptr);
         } else if (adaptive) {
             // the adaptive call renders what the flags need; the denoiser then runs over its images
             const bool guides = aovs || denoise;
@@ -315,6 +390,12 @@ int main(int argc, char* argv[]) {
         } else {
             rc = nart_hip_render(ctx, &p, image.data(), nullptr);
         }
+        if (rc == NART_OK && mattes_after)
+            rc = nart_hip_render_mattes(ctx, &p, &mp, matte_ranks.data(), nullptr, nullptr, nullptr);
+        if (rc == NART_OK && mattes && matte_ids_arg) {
+            matte_img.resize(image.size());
+            rc = nart_hip_matte_extract(ctx, &p, &mp, matte_ranks.data(), matte_mask, matte_img.data());
+        }
         if (rc != NART_OK) {
             std::fprintf(stderr, "Error: render failed (%d): %s\n", rc, nart_hip_last_error(ctx));
             return EXIT_FAILURE;
@@ -327,13 +408,16 @@ int main(int argc, char* argv[]) {
             std::fprintf(stderr, "%s\n", nart_scene_last_error());
             return EXIT_FAILURE;
         }
-        std::vector<std::pair<const char*, const nart_pixel*>> extra;
+        std::vector<std::pair<std::string, const nart_pixel*>> extra;
         if (aovs) {
             extra.push_back({".albedo.exr", albedo.data()});
             extra.push_back({".normal.exr", normal.data()});
         }
         if (denoise) extra.push_back({".denoised.exr", denoised.data()});
         if (robust) extra.push_back({".robust.exr", robust_img.data()});
+        for (uint32_t i = 0; mattes && i < mp.ranks / 2; ++i)
+            extra.push_back({".matte.0" + std::to_string(i) + ".exr", matte_ranks.data() + (size_t)i * image.size()});
+        if (mattes && matte_ids_arg) extra.push_back({".matte.exr", matte_img.data()});
         std::vector<nart_pixel> spp_img;
         if (adaptive) {
             // pixel (x, y) of the cropped image was traced by bucket (x / B, y / B)

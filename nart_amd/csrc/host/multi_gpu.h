@@ -124,7 +124,8 @@ int ensure_dev(nart_ctx* ctx, int dev, void*& buf, size_t& cap, size_t bytes, co
 // The multi-device half of render_frame (which has validated p and sized a borrowed image buffer):
 // shard, render concurrently, gather to device 0, combine, deliver.
 // The gather runs over the request's list of tile buffers: the beauty (unless an AOV-only frame)
-// and each first-hit AOV requested, the second-moment image and the cascade's layers.  Every device keeps its buffers' slabs back to back in
+// and each first-hit AOV requested, the second-moment image and the cascade's layers or the ID
+// mattes' coverage planes.  Every device keeps its buffers' slabs back to back in
 // sub_tiles[d], all are gathered in the one RCCL group (or by device copies), and each buffer is
 // then permuted and combined into ctx->d_image on device 0 in turn, and copied from there to its
 // destination (none where the request borrows ctx->d_image itself: nart_hip_render_device).
@@ -133,12 +134,12 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
                  double* aov_ms, double* moment_ms) {
     const uint32_t n = (uint32_t)ctx->subs.size();
     // the tile buffers of this render: -1 the beauty, 0 and 1 AOV k, 2 the moment image, 3 + j
-    // cascade layer j
+    // cascade layer j or matte plane j
     std::vector<int> kinds;
     for (int k = 0; k < FRAME_BUFS_ALL; ++k)
         if (rq.wants(k)) kinds.push_back(k - 1);
     const size_t K = kinds.size();
-    const bool want_aov = rq.wants_aovs() || rq.moment || rq.cascade;
+    const bool want_aov = rq.wants_aovs() || rq.moment || rq.cascade || rq.matte.on;
     int rc = NART_OK;
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
@@ -181,9 +182,10 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
         const size_t slab = ids[d].size() * tile_floats;
         areq[d].beauty = rq.beauty;
         areq[d].cascade = rq.cascade;
+        areq[d].matte = rq.matte;
         for (size_t i = 0; i < K; ++i) {
             float* buf = static_cast<float*>(ctx->sub_tiles[d]) + i * slab;
-            if (kinds[i] >= 3) areq[d].layers[kinds[i] - 3] = buf;
+            if (kinds[i] >= 3) (rq.matte.on ? areq[d].planes : areq[d].layers)[kinds[i] - 3] = buf;
             else if (kinds[i] >= 0) (kinds[i] == 2 ? areq[d].moment : areq[d].tiles[kinds[i]]) = buf;
         }
         if (rq.adaptive) {
@@ -325,6 +327,8 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
         for (uint32_t d = 0; d < n; ++d) *moment_ms = std::max(*moment_ms, areq[d].moment_ms);
     if (rq.cascade_ms)
         for (uint32_t d = 0; d < n; ++d) *rq.cascade_ms = std::max(*rq.cascade_ms, areq[d].cascade_ms);
+    if (rq.matte_ms)
+        for (uint32_t d = 0; d < n; ++d) *rq.matte_ms = std::max(*rq.matte_ms, areq[d].matte_ms);
     if (stats) {
         // one render: device times of the slowest device (they run concurrently), work counts
         // summed; added to the caller's stats as the single-device path adds a render's

@@ -20,6 +20,7 @@
 #include "device/cascade.h"
 #include "device/denoise.h"
 #include "device/lbvh.h"
+#include "device/matte.h"
 #include "device/volume.h"
 #include "host/bvh_build.h"
 #include "host/path_schedule.h"
@@ -87,6 +88,11 @@ struct nart_ctx {
     // around the reweighting ([2], [3]: cascade_device); the last cascade call's times
     hipEvent_t ev_cas[4] = {nullptr, nullptr, nullptr, nullptr};
     double cas_ms[2] = {0.0, 0.0};  // split + layer splats, reweighting
+    // first-hit ID mattes: around the plane passes of a batch ([0], [1]: render_buckets) and around
+    // the ranking ([2], [3]: matte_rank_device); the last matte call's times
+    hipEvent_t ev_mat[4] = {nullptr, nullptr, nullptr, nullptr};
+    double mat_ms[2] = {0.0, 0.0};  // plane passes, ranking
+    uint32_t num_meshes = 0, num_materials = 0;  // the scene's: the id counts of the two matte kinds
     // denoiser (denoise_device): work buffers over the cropped image, the four device images of
     // nart_hip_denoise / nart_hip_render_denoised (five with the moment image), events between its
     // kernels, the last run's times
@@ -1191,6 +1197,15 @@ struct CascadeLevels {
     float base = 0.f;
     float b[CASCADE_MAX_LAYERS] = {};
 };
+// matte: the ID mattes' coverage planes (include/nart_hip.h, "First-hit ID mattes"): planes[q] receives
+// the indicator records of ids 4q .. 4q+3 (k_matte_ids into ctx->d_L over the camera-ray hits, as
+// k_aov; then the plain splat), matte_ms their device time.  Like the first-hit AOVs they need no
+// path kernel.
+struct MatteRequest {
+    bool on = false;
+    uint32_t kind = 0, n_ids = 0;
+    uint32_t planes() const { return on ? (n_ids + 3) / 4 : 0; }
+};
 struct AovRequest {
     float* tiles[2] = {nullptr, nullptr};
     float* moment = nullptr;
@@ -1199,6 +1214,9 @@ struct AovRequest {
     const CascadeLevels* cascade = nullptr;
     float* layers[CASCADE_MAX_LAYERS] = {};
     double cascade_ms = 0.0;
+    MatteRequest matte;
+    float* planes[MATTE_MAX_PLANES] = {};
+    double matte_ms = 0.0;
 
     bool first_hit() const { return tiles[0] || tiles[1]; }
 };
@@ -1446,7 +1464,8 @@ int launch_splat(nart_ctx* ctx, const SplatPlan& plan, const SplatArgs& sa, uint
 // into the request's tiles; with aov->moment, between the two, the second-moment image (k_moment
 // squares the Li_alpha records in place, one more splat pass with MOM).  With aov->cascade, right
 // after the beauty's splat and before anything overwrites d_L, one k_cascade_split + plain splat per
-// layer; the second record buffer they go through is a temporary of this call.
+// layer; the second record buffer they go through is a temporary of this call.  With aov->matte,
+// after the AOVs and over the same camera-ray hits, one k_matte_ids + plain splat per coverage plane.
 int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n, float* d_tiles,
                    hipStream_t st, nart_render_stats* stats, AovRequest* aov = nullptr) {
     int rc = NART_OK;
@@ -1476,6 +1495,10 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
     if (cascade)
         for (int k = 0; k < 2; ++k)
             if (!ctx->ev_cas[k]) HIPCHK(hipEventCreate(&ctx->ev_cas[k]));
+    const uint32_t matte_planes = aov ? aov->matte.planes() : 0;
+    if (matte_planes)
+        for (int k = 0; k < 2; ++k)
+            if (!ctx->ev_mat[k]) HIPCHK(hipEventCreate(&ctx->ev_mat[k]));
     const size_t limit = batch_slot_limit(ctx, p->spp, cascade ? sizeof(float4) : 0);
     ScopedDeviceBufs layer_records;  // cascade: the second per-sample record buffer, 16 B per sample
     size_t layer_records_cap = 0;
@@ -1592,6 +1615,30 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             HIPCHK(hipEventRecord(ctx->ev_aov[1], st));
             HIPCHK(hipEventSynchronize(ctx->ev_aov[1]));
         }
+        if (matte_planes) {
+            // the same camera-ray hits as the AOVs'; one indicator record pass and plain splat per plane
+            if (!ctx->prim_valid && (rc = launch_aov_primary(ctx, ra, st))) return rc;
+            HIPCHK(hipEventRecord(ctx->ev_mat[0], st));
+            MatteIdArgs ma;
+            ma.hit = ctx->d_prim;
+            ma.tri_mesh = ctx->scene.tri_mesh;
+            ma.meshes = ctx->scene.meshes;
+            ma.out = ctx->d_L;
+            ma.n = (uint64_t)nslots * p->spp;
+            ma.num_tris = ctx->scene.num_tris;
+            ma.num_meshes = ctx->num_meshes;
+            ma.kind = aov->matte.kind;
+            ma.n_ids = aov->matte.n_ids;
+            for (uint32_t q = 0; q < matte_planes; ++q) {
+                ma.q = q;
+                hipLaunchKernelGGL(k_matte_ids, dim3((uint32_t)((ma.n + 255) / 256)), dim3(256), 0, st, ma);
+                HIPCHK(hipGetLastError());
+                sa.tiles = aov->planes[q] + (size_t)b0 * tpx * 5;
+                if ((rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
+            }
+            HIPCHK(hipEventRecord(ctx->ev_mat[1], st));
+            HIPCHK(hipEventSynchronize(ctx->ev_mat[1]));
+        }
         if (moment) HIPCHK(hipEventSynchronize(ctx->ev_aov[3]));
         if (cascade) HIPCHK(hipEventSynchronize(ctx->ev_cas[1]));
         HIPCHK(hipEventSynchronize(ctx->ev[2]));
@@ -1603,6 +1650,10 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         if (first_hit) {
             HIPCHK(hipEventElapsedTime(&ms, ctx->ev_aov[0], ctx->ev_aov[1]));
             aov->ms += ms;
+        }
+        if (matte_planes) {
+            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_mat[0], ctx->ev_mat[1]));
+            aov->matte_ms += ms;
         }
         if (moment) {
             HIPCHK(hipEventElapsedTime(&ms, ctx->ev_aov[2], ctx->ev_aov[3]));
@@ -1754,7 +1805,8 @@ int build_bvh_device(nart_ctx* ctx, const nart_scene_blob& blob, const std::vect
 // ---------------------------------------------------------------- whole frames
 // What a whole-frame render produces, where it goes and whose buffers it uses (render_frame).
 // Buffer k: 0 the beauty, 1 + a first-hit AOV a (AOV_ALBEDO, AOV_NORMAL), 3 the second-moment image.
-// With the firefly cascade (FrameRequest::cascade) buffer FRAME_BUFS + j is layer j's image.
+// With the firefly cascade (FrameRequest::cascade) buffer FRAME_BUFS + j is layer j's image; with the
+// ID mattes (FrameRequest::matte) it is coverage plane j's.
 constexpr int FRAME_BUFS = 4;
 constexpr int FRAME_BUFS_ALL = FRAME_BUFS + (int)CASCADE_MAX_LAYERS;
 
@@ -1795,8 +1847,14 @@ struct FrameRequest {
     // *cascade_ms receives the device time of the split and layer splats (the slowest device's).
     const CascadeLevels* cascade = nullptr;
     double* cascade_ms = nullptr;
+    // First-hit ID mattes: coverage plane q is buffer FRAME_BUFS + q (the buffers the cascade's layers
+    // use: not with the cascade, not with adaptive; no surfaces, no mattes: not the volume integrator);
+    // the beauty is optional.  *matte_ms receives the plane passes' device time (the slowest device's).
+    MatteRequest matte;
+    double* matte_ms = nullptr;
 
     bool wants(int k) const {
+        if (k >= FRAME_BUFS && matte.on) return (uint32_t)(k - FRAME_BUFS) < matte.planes();
         if (k >= FRAME_BUFS) return cascade && (uint32_t)(k - FRAME_BUFS) < cascade->K;
         return k == 0 ? beauty : (k == 3 ? moment : aov[k - 1]);
     }
@@ -1975,10 +2033,13 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
         return fail(ctx, NART_E_INVALID, "the moment image needs the path kernel: it cannot be rendered without the beauty");
     if (rq.cascade && (!rq.beauty || rq.adaptive))
         return fail(ctx, NART_E_UNSUPPORTED, "the cascade layers need the beauty and a uniform render");
+    if (rq.matte.on && (rq.cascade || rq.adaptive))
+        return fail(ctx, NART_E_UNSUPPORTED, "the matte planes need a uniform render without the cascade");
     if (rq.cascade_ms) *rq.cascade_ms = 0.0;
+    if (rq.matte_ms) *rq.matte_ms = 0.0;
     nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // device 0: combines, holds the images
     int rc = NART_OK;
-    if (rq.wants_aovs() && (rc = check_first_hit(ctx, p))) return rc;
+    if ((rq.wants_aovs() || rq.matte.on) && (rc = check_first_hit(ctx, p))) return rc;
     if (ctx->rccl_broken)
         return fail(ctx, NART_E_RCCL, "an earlier RCCL gather of this context failed; destroy it and create a new one");
     if ((rc = check_params(c0, p))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
@@ -2016,18 +2077,21 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     areq.tiles[1] = tiles[2];
     areq.moment = tiles[3];
     areq.cascade = rq.cascade;
-    for (uint32_t j = 0; j < CASCADE_MAX_LAYERS; ++j) areq.layers[j] = tiles[FRAME_BUFS + j];
+    for (uint32_t j = 0; j < CASCADE_MAX_LAYERS; ++j) areq.layers[j] = rq.cascade ? tiles[FRAME_BUFS + j] : nullptr;
+    areq.matte = rq.matte;
+    for (uint32_t q = 0; q < MATTE_MAX_PLANES; ++q) areq.planes[q] = rq.matte.on ? tiles[FRAME_BUFS + q] : nullptr;
     if (rq.adaptive) {
         rc = render_buckets_adaptive(ctx, p, ids.data(), nb, tiles, 0, stats, *rq.adaptive);
         areq.ms = rq.adaptive->aov_ms;
         areq.moment_ms = rq.adaptive->moment_ms;
     } else {
         rc = render_buckets(ctx, p, ids.data(), nb, tiles[0], 0, stats,
-                            rq.wants_aovs() || rq.moment || rq.cascade ? &areq : nullptr);
+                            rq.wants_aovs() || rq.moment || rq.cascade || rq.matte.on ? &areq : nullptr);
     }
     if (aov_ms) *aov_ms = areq.ms;
     if (moment_ms) *moment_ms = areq.moment_ms;
     if (rq.cascade_ms) *rq.cascade_ms = areq.cascade_ms;
+    if (rq.matte_ms) *rq.matte_ms = areq.matte_ms;
     for (int k = 0, i = 0; k < FRAME_BUFS_ALL && !rc; ++k) {
         if (!rq.wants(k) || (!rq.on_device && !rq.dst[k])) continue;
         float* img = static_cast<float*>(d_img) + (rq.on_device ? (size_t)(i++) * img_floats : 0);
@@ -2425,6 +2489,170 @@ int cascade_host(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_
     return NART_OK;
 }
 
+// ---------------------------------------------------------------- first-hit ID mattes (device/matte.h)
+void matte_defaults(nart_matte_params* mp) {
+    mp->kind = NART_MATTE_MESH;
+    mp->ranks = 6;
+}
+
+// mp (null: the defaults) into out; the message of what is wrong, or null.
+const char* matte_params_error(const nart_matte_params* mp, nart_matte_params& out) {
+    if (mp) out = *mp;
+    else matte_defaults(&out);
+    if (out.kind != NART_MATTE_MESH && out.kind != NART_MATTE_MATERIAL) return "unknown matte id kind";
+    if (out.ranks < 2 || out.ranks > MATTE_MAX_RANKS || (out.ranks & 1u)) return "matte ranks must be even and in 2..8";
+    return nullptr;
+}
+
+int check_matte_frame(nart_ctx* ctx, const nart_render_params* p) {
+    if (!p->image_width || !p->image_height || !(p->filter_width > 0.f))
+        return fail(ctx, NART_E_INVALID, "imageWidth, imageHeight and filterWidth must be > 0");
+    return NART_OK;
+}
+
+// The ranking over device images on a single-device context: the P plane images back to back (null
+// with no ids), the R / 2 rank images out; synchronous.  The time goes to ctx->mat_ms[1].
+int matte_rank_device(nart_ctx* ctx, const nart_render_params* p, uint32_t n_ids, uint32_t R, const float* d_planes,
+                      float* d_ranks, hipStream_t st) {
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    for (int k = 2; k < 4; ++k)
+        if (!ctx->ev_mat[k]) HIPCHK(hipEventCreate(&ctx->ev_mat[k]));
+    MatteRankArgs a;
+    a.planes = d_planes;
+    a.out = d_ranks;
+    a.W = p->image_width;
+    a.H = p->image_height;
+    a.totalW = g.total_width;
+    a.totalH = g.total_height;
+    a.fb = g.filter_bounds;
+    a.n_ids = n_ids;
+    a.R = R;
+    HIPCHK(hipEventRecord(ctx->ev_mat[2], st));
+    // the border stays zero: the kernel writes the cropped pixels only
+    HIPCHK(hipMemsetAsync(d_ranks, 0, (size_t)(R / 2) * g.total_width * g.total_height * sizeof(nart_pixel), st));
+    const dim3 grid((a.W + MT_TW - 1) / MT_TW, (a.H + MT_TH - 1) / MT_TH), block(MT_LANES);
+    const size_t lds = (size_t)((n_ids + 3) / 4) * 4 * MT_LANES * sizeof(float);
+    hipLaunchKernelGGL(k_matte_rank, grid, block, lds, st, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev_mat[3], st));
+    HIPCHK(hipEventSynchronize(ctx->ev_mat[3]));
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, ctx->ev_mat[2], ctx->ev_mat[3]));
+    ctx->mat_ms[1] = t;
+    return NART_OK;
+}
+
+// nart_hip_render_mattes: the planes (and the beauty, if asked for) through render_frame into device
+// images of the call, the ranking on device 0 after them, then what the caller asked for to the host.
+// A scene without ids renders no plane: its ranks are empty.
+int render_mattes(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params& mp, nart_pixel* ranks,
+                  nart_pixel* image, nart_pixel* planes, nart_render_stats* stats) {
+    nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];
+    ctx->mat_ms[0] = ctx->mat_ms[1] = 0.0;
+    if (int rc = check_first_hit(ctx, p)) return rc;
+    const uint32_t n_ids = mp.kind == NART_MATTE_MATERIAL ? c0->num_materials : c0->num_meshes;
+    if (n_ids > MATTE_MAX_IDS)
+        return fail(ctx, NART_E_UNSUPPORTED, "the scene has " + std::to_string(n_ids) + " matte ids; at most 32 are supported");
+    CascadeTileGuard guard(ctx);  // up to nine tile buffers: what they grow by is given back
+    ScopedDeviceBufs imgs;        // the device images of the call, on device 0
+    size_t imgs_cap = 0;
+    const uint32_t P = (n_ids + 3) / 4, R = mp.ranks, B = image ? 1 : 0;
+    FrameRequest rq;
+    rq.beauty = image != nullptr;
+    rq.matte.on = true;
+    rq.matte.kind = mp.kind;
+    rq.matte.n_ids = n_ids;
+    rq.matte_ms = &ctx->mat_ms[0];
+    rq.on_device = true;
+    rq.image = &imgs.p[0];
+    rq.image_cap = &imgs_cap;
+    rq.images = B + P + R / 2;  // the beauty, the planes, the rank images
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
+    int rc = NART_OK;
+    if (B + P) {
+        if ((rc = render_frame(ctx, p, rq, stats, nullptr))) return rc;
+    } else {
+        if ((rc = check_params(c0, p))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
+        if ((rc = ensure_dev(ctx, c0->device, imgs.p[0], imgs_cap, (size_t)(R / 2) * img_bytes, "image"))) return rc;
+    }
+    RenderTimer timer(stats);  // render_ms covers the whole call
+    float* d = static_cast<float*>(imgs.p[0]);
+    float* d_planes = d + (size_t)B * img_floats;
+    float* d_ranks = d_planes + (size_t)P * img_floats;
+    if ((rc = matte_rank_device(c0, p, n_ids, R, P ? d_planes : nullptr, d_ranks, 0)))
+        return c0 == ctx ? rc : fail(ctx, rc, c0->err);
+    ctx->mat_ms[1] = c0->mat_ms[1];
+    HIPCHK(hipSetDevice(c0->device));
+    HIPCHK(hipMemcpy(ranks, d_ranks, (size_t)(R / 2) * img_bytes, hipMemcpyDeviceToHost));
+    if (image) HIPCHK(hipMemcpy(image, d, img_bytes, hipMemcpyDeviceToHost));
+    if (planes && P) HIPCHK(hipMemcpy(planes, d_planes, (size_t)P * img_bytes, hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+// nart_hip_matte_rank: host planes through the (first) device.
+int matte_rank_host(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params& mp, uint32_t n_ids,
+                    const nart_pixel* planes, nart_pixel* ranks) {
+    if (!ctx->subs.empty()) {
+        const int rc = matte_rank_host(ctx->subs[0], p, mp, n_ids, planes, ranks);
+        ctx->mat_ms[0] = 0.0;
+        ctx->mat_ms[1] = ctx->subs[0]->mat_ms[1];
+        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
+    }
+    ctx->mat_ms[0] = ctx->mat_ms[1] = 0.0;
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const uint32_t P = (n_ids + 3) / 4, R = mp.ranks;
+    const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
+    ScopedDeviceBufs imgs;  // the planes, the rank images
+    if (int rc = dmalloc(ctx, &imgs.p[0], (size_t)(P + R / 2) * img_bytes, "matte images")) return rc;
+    float* d = static_cast<float*>(imgs.p[0]);
+    float* d_ranks = d + (size_t)P * img_floats;
+    if (P) HIPCHK(hipMemcpy(d, planes, (size_t)P * img_bytes, hipMemcpyHostToDevice));
+    if (int rc = matte_rank_device(ctx, p, n_ids, R, P ? d : nullptr, d_ranks, 0)) return rc;
+    HIPCHK(hipMemcpy(ranks, d_ranks, (size_t)(R / 2) * img_bytes, hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+// nart_hip_matte_extract: host rank images through the (first) device.
+int matte_extract_host(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params& mp, const nart_pixel* ranks,
+                       uint64_t id_mask, nart_pixel* out) {
+    if (!ctx->subs.empty()) {
+        const int rc = matte_extract_host(ctx->subs[0], p, mp, ranks, id_mask, out);
+        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    const uint32_t R = mp.ranks;
+    const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
+    ScopedDeviceBufs imgs;  // the rank images, the matte
+    if (int rc = dmalloc(ctx, &imgs.p[0], (size_t)(R / 2 + 1) * img_bytes, "matte images")) return rc;
+    float* d = static_cast<float*>(imgs.p[0]);
+    float* d_out = d + (size_t)(R / 2) * img_floats;
+    HIPCHK(hipMemcpy(d, ranks, (size_t)(R / 2) * img_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(d_out, 0, img_bytes, 0));  // the border stays zero
+    MatteExtractArgs a;
+    a.ranks = d;
+    a.out = d_out;
+    a.W = p->image_width;
+    a.H = p->image_height;
+    a.totalW = g.total_width;
+    a.totalH = g.total_height;
+    a.fb = g.filter_bounds;
+    a.R = R;
+    a.mask = id_mask;
+    const uint64_t n = (uint64_t)a.W * a.H;
+    hipLaunchKernelGGL(k_matte_extract, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, 0, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, d_out, img_bytes, hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
 // Largest coordinate magnitude of the scene (triangles and camera position; at least 1): the scale
 // of the BVH box padding and of the octree margins (nart_hip_create, nart_hip_bvh_dump).
 float scene_maxabs(const nart_scene_blob& blob) {
@@ -2565,6 +2793,8 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
     if (blob->num_meshes >= (1u << 24)) return bail(NART_E_UNSUPPORTED);
     if ((rc = upload(ctx, ctx->d_tri_mesh, tri_mesh.data(), tri_mesh.size()))) return bail(rc);
     if ((rc = upload(ctx, ctx->d_meshes, meshes.data(), meshes.size()))) return bail(rc);
+    ctx->num_meshes = blob->num_meshes;
+    ctx->num_materials = blob->num_materials;
     std::vector<DMaterial> mats(blob->num_materials);
     for (uint32_t i = 0; i < blob->num_materials; ++i) {
         const nart_material& m = blob->materials[i];
@@ -2706,6 +2936,8 @@ void nart_hip_destroy(nart_ctx* ctx) {
     for (auto& e : ctx->ev_ad)
         if (e) hipEventDestroy(e);
     for (auto& e : ctx->ev_cas)
+        if (e) hipEventDestroy(e);
+    for (auto& e : ctx->ev_mat)
         if (e) hipEventDestroy(e);
     delete ctx;
 }
@@ -2912,6 +3144,51 @@ int nart_hip_cascade_timings(const nart_ctx* ctx, double* cascade_ms, double* re
     if (!ctx) return NART_E_INVALID;
     if (cascade_ms) *cascade_ms = ctx->cas_ms[0];
     if (reweight_ms) *reweight_ms = ctx->cas_ms[1];
+    return NART_OK;
+}
+
+void nart_hip_matte_defaults(nart_matte_params* mp) {
+    if (mp) matte_defaults(mp);
+}
+
+int nart_hip_matte_ids(const nart_scene_blob* scene, uint32_t kind, uint32_t* n_ids) {
+    if (!scene || !n_ids || (kind != NART_MATTE_MESH && kind != NART_MATTE_MATERIAL)) return NART_E_INVALID;
+    *n_ids = kind == NART_MATTE_MATERIAL ? scene->num_materials : scene->num_meshes;
+    return *n_ids > MATTE_MAX_IDS ? NART_E_UNSUPPORTED : NART_OK;
+}
+
+int nart_hip_render_mattes(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params* mp, nart_pixel* ranks,
+                           nart_pixel* image, nart_pixel* planes, nart_render_stats* stats) {
+    nart_matte_params m;
+    if (const char* why = matte_params_error(mp, m)) return fail(ctx, NART_E_INVALID, why);
+    if (!ctx || !p || !ranks) return NART_E_INVALID;
+    if (int rc = check_matte_frame(ctx, p)) return rc;
+    return render_mattes(ctx, p, m, ranks, image, planes, stats);
+}
+
+int nart_hip_matte_rank(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params* mp, uint32_t n_ids,
+                        const nart_pixel* planes, nart_pixel* ranks) {
+    nart_matte_params m;
+    if (const char* why = matte_params_error(mp, m)) return fail(ctx, NART_E_INVALID, why);
+    if (n_ids > MATTE_MAX_IDS) return fail(ctx, NART_E_INVALID, "n_ids must be <= 32");
+    if (!ctx || !p || !ranks || (n_ids && !planes)) return NART_E_INVALID;
+    if (int rc = check_matte_frame(ctx, p)) return rc;
+    return matte_rank_host(ctx, p, m, n_ids, planes, ranks);
+}
+
+int nart_hip_matte_extract(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params* mp, const nart_pixel* ranks,
+                           uint64_t id_mask, nart_pixel* out) {
+    nart_matte_params m;
+    if (const char* why = matte_params_error(mp, m)) return fail(ctx, NART_E_INVALID, why);
+    if (!ctx || !p || !ranks || !out) return NART_E_INVALID;
+    if (int rc = check_matte_frame(ctx, p)) return rc;
+    return matte_extract_host(ctx, p, m, ranks, id_mask, out);
+}
+
+int nart_hip_matte_timings(const nart_ctx* ctx, double* matte_ms, double* rank_ms) {
+    if (!ctx) return NART_E_INVALID;
+    if (matte_ms) *matte_ms = ctx->mat_ms[0];
+    if (rank_ms) *rank_ms = ctx->mat_ms[1];
     return NART_OK;
 }
 
