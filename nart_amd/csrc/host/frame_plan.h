@@ -1,0 +1,134 @@
+// What one render produces, decided once from plain values (no HIP, no context): the entry points of
+// render.hip state a FrameAsk, plan_frame turns it into an error or a FramePlan, and render_frame,
+// render_multi, render_buckets_adaptive and render_buckets execute the plan.  tests/test_frame_plan.py
+// compares plan_frame with a restatement of the rules over every combination that can be asked for.
+#pragma once
+#include <cstdint>
+#include <string>
+
+#include "../../../include/nart_hip.h"
+
+namespace nd {
+
+// device/cascade.h CASCADE_MAX_LAYERS; device/matte.h MATTE_MAX_PLANES (four ids a plane), MATTE_MAX_IDS
+constexpr uint32_t FRAME_MAX_LAYERS = 8, FRAME_MAX_PLANES = 8, FRAME_MAX_MATTE_IDS = 4 * FRAME_MAX_PLANES;
+// beauty, two first-hit AOVs, moment, layers, planes (a frame has layers or planes: at most twelve)
+constexpr uint32_t FRAME_MAX_OUTPUTS = 4 + FRAME_MAX_LAYERS + FRAME_MAX_PLANES;
+
+// The firefly cascade's levels (include/nart_hip.h, "Firefly cascade"): layer j takes the share of
+// every Li_alpha record around brightness b[j] = start * base^j.  K = 0: no cascade.
+struct CascadeLevels {
+    uint32_t K = 0;
+    float base = 0.f;
+    float b[FRAME_MAX_LAYERS] = {};
+};
+// The ID mattes' coverage planes (include/nart_hip.h, "First-hit ID mattes"): plane q holds the
+// indicator records of ids 4q .. 4q+3 of `kind` (NART_MATTE_MESH, NART_MATTE_MATERIAL).
+struct MatteRequest {
+    bool on = false;
+    uint32_t kind = 0, n_ids = 0;
+    uint32_t planes() const { return on ? (n_ids + 3) / 4 : 0; }
+};
+
+struct FrameAsk {  // what the caller asks for
+    uint32_t integrator;           // nart_render_params::integrator: first-hit outputs need surfaces
+    bool beauty = true;            // false: no path kernel runs
+    bool aov[2] = {false, false};  // first-hit AOVs: AOV_ALBEDO, AOV_NORMAL (kernels.h)
+    bool moment = false;           // the second-moment image of the beauty's samples
+    bool adaptive = false;         // buckets refined level by level, not rendered once at p->spp
+    CascadeLevels cascade;
+    MatteRequest matte;
+    explicit FrameAsk(uint32_t integrator_) : integrator(integrator_) {}
+};
+
+// One tile buffer (and image) of a render; index: j of cascade layer j, q of matte plane q, else 0.
+enum class OutputKind : uint32_t { Beauty, Albedo, Normal, Moment, Layer, Plane };
+struct FrameOutput { OutputKind kind = OutputKind::Beauty; uint32_t index = 0; };
+
+// The passes of a batch after the path kernel and the beauty's splat, in the order they must run.
+// Each fills a record buffer once per output it feeds and splats it into that output's tiles:
+//   PASS_CASCADE    reads the Li_alpha records in d_L before anything else touches them
+//                   (k_cascade_split into a second record buffer, one layer at a time);
+//   PASS_MOMENT     k_moment squares d_L in place: after the cascade, the last reader of Li_alpha;
+//   PASS_FIRST_HIT  k_aov overwrites d_L from the camera-ray hits (d_prim), one AOV at a time;
+//   PASS_MATTE      k_matte_ids overwrites d_L from the same hits, one plane at a time.
+enum PassKind : uint32_t { PASS_CASCADE, PASS_MOMENT, PASS_FIRST_HIT, PASS_MATTE, N_PASSES };
+// The pass that fills an output's records, by OutputKind; N_PASSES: the beauty, the path kernel's own.
+constexpr PassKind PASS_OF[6] = {N_PASSES, PASS_FIRST_HIT, PASS_FIRST_HIT, PASS_MOMENT, PASS_CASCADE, PASS_MATTE};
+inline PassKind pass_of(OutputKind k) { return PASS_OF[(uint32_t)k]; }
+
+struct FramePlan {
+    int code = NART_OK;  // not NART_OK: the first broken rule and its message; nothing else is set
+    std::string message;
+    FrameAsk ask{NART_INTEGRATOR_PATH};
+    // Tile buffers and images in delivery order: beauty, albedo, normal, moment, then the layers or
+    // the planes ascending.  On-device delivery lays the images out back to back in this order.
+    FrameOutput outputs[FRAME_MAX_OUTPUTS];
+    uint32_t n_outputs = 0;
+    PassKind passes[N_PASSES] = {};  // the passes that run, ascending
+    uint32_t n_passes = 0;
+    bool path_kernel = false;   // false: camera rays only (first-hit outputs without the beauty)
+    uint32_t record_bytes = 0;  // per-sample record memory beyond d_L (batch_slot_limit): the cascade's buffer
+
+    int find(OutputKind kind, uint32_t index = 0) const {  // position in the list, or -1
+        for (uint32_t i = 0; i < n_outputs; ++i)
+            if (outputs[i].kind == kind && outputs[i].index == index) return (int)i;
+        return -1;
+    }
+};
+
+// Whose rules apply: a whole frame's (render_frame), or those of a bare bucket-list render (a level
+// of an adaptive render, nart_hip_render_buckets_async), which is not told how its tiles are used.
+enum class PlanRules { Frame, Buckets };
+
+inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
+    FramePlan plan;
+    const bool frame = rules == PlanRules::Frame, first_hit = a.aov[0] || a.aov[1] || a.matte.on;
+    int code = NART_E_UNSUPPORTED;
+    std::string why;
+    if (a.moment && !a.beauty) {
+        code = NART_E_INVALID;
+        why = frame ? "the moment image needs the path kernel: it cannot be rendered without the beauty"
+                    : "the moment image needs the path kernel (the beauty)";
+    } else if (frame && a.cascade.K && (!a.beauty || a.adaptive)) {
+        why = "the cascade layers need the beauty and a uniform render";
+    } else if (frame && a.matte.on && (a.cascade.K || a.adaptive)) {
+        why = "the matte planes need a uniform render without the cascade";
+    } else if (frame && first_hit && a.integrator == NART_INTEGRATOR_VOLUME) {
+        why = "first-hit AOVs need surfaces: the volume integrator has none";
+    } else if (!frame && a.cascade.K && !a.beauty) {
+        code = NART_E_INVALID;
+        why = "the cascade layers need the path kernel (the beauty)";
+    } else if (a.matte.on && a.matte.n_ids > FRAME_MAX_MATTE_IDS) {  // (what the list of outputs holds)
+        why = "the scene has " + std::to_string(a.matte.n_ids) + " matte ids; at most 32 are supported";
+    }
+    if (!why.empty()) {
+        plan.code = code;
+        plan.message = why;
+        return plan;
+    }
+    plan.ask = a;
+    auto add = [&plan](OutputKind kind, uint32_t index) { plan.outputs[plan.n_outputs++] = {kind, index}; };
+    if (a.beauty) add(OutputKind::Beauty, 0);
+    if (a.aov[0]) add(OutputKind::Albedo, 0);
+    if (a.aov[1]) add(OutputKind::Normal, 0);
+    if (a.moment) add(OutputKind::Moment, 0);
+    for (uint32_t j = 0; j < a.cascade.K; ++j) add(OutputKind::Layer, j);
+    for (uint32_t q = 0; q < a.matte.planes(); ++q) add(OutputKind::Plane, q);
+    // An adaptive render estimates a bucket's error from its moment tiles: every level runs the moment
+    // pass, wanted or not (adaptive_level_ask).
+    bool runs[N_PASSES + 1] = {};
+    runs[PASS_MOMENT] = a.adaptive;
+    for (uint32_t i = 0; i < plan.n_outputs; ++i) runs[pass_of(plan.outputs[i].kind)] = true;
+    for (uint32_t k = 0; k < N_PASSES; ++k)
+        if (runs[k]) plan.passes[plan.n_passes++] = (PassKind)k;
+    plan.path_kernel = a.beauty;
+    plan.record_bytes = a.cascade.K ? 16 : 0;  // one float4 per sample
+    return plan;
+}
+
+// What one level of an adaptive render asks of render_buckets: a uniform render of the beauty, the
+// wanted AOVs and, always, the moment tiles.
+inline FrameAsk adaptive_level_ask(FrameAsk a) { a.moment = true; a.adaptive = false; return a; }
+
+}  // namespace nd

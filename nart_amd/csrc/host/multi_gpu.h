@@ -110,36 +110,16 @@ __global__ void k_unshard(const float* slabs, float* by_id, const uint32_t* map,
     for (uint32_t k = threadIdx.x; k < tile_floats; k += blockDim.x) dst[k] = src[k];
 }
 
-int ensure_dev(nart_ctx* ctx, int dev, void*& buf, size_t& cap, size_t bytes, const char* what) {
-    if (bytes <= cap) return NART_OK;
-    HIPCHK(hipSetDevice(dev));
-    if (buf) hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-    if (int rc = dmalloc(ctx, &buf, bytes, what)) return rc;
-    cap = bytes;
-    return NART_OK;
-}
-
 // The multi-device half of render_frame (which has validated p and sized a borrowed image buffer):
 // shard, render concurrently, gather to device 0, combine, deliver.
-// The gather runs over the request's list of tile buffers: the beauty (unless an AOV-only frame)
-// and each first-hit AOV requested, the second-moment image and the cascade's layers or the ID
-// mattes' coverage planes.  Every device keeps its buffers' slabs back to back in
-// sub_tiles[d], all are gathered in the one RCCL group (or by device copies), and each buffer is
-// then permuted and combined into ctx->d_image on device 0 in turn, and copied from there to its
-// destination (none where the request borrows ctx->d_image itself: nart_hip_render_device).
-// aov_ms, moment_ms: the slowest device's AOV and moment-pass times.
-int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest& rq, nart_render_stats* stats,
-                 double* aov_ms, double* moment_ms) {
+// The gather runs over the plan's outputs.  Every device keeps their slabs back to back in
+// sub_tiles[d] (slab i: output i), all are gathered in the one RCCL group (or by device copies), and
+// each output is then permuted and combined into ctx->d_image on device 0 in turn, and copied to its
+// destination (none where the request borrows ctx->d_image itself).  times: the slowest device's.
+int render_multi(nart_ctx* ctx, const nart_render_params* p, const FramePlan& plan, const FrameRequest& rq,
+                 nart_render_stats* stats, PassTimes& times) {
     const uint32_t n = (uint32_t)ctx->subs.size();
-    // the tile buffers of this render: -1 the beauty, 0 and 1 AOV k, 2 the moment image, 3 + j
-    // cascade layer j or matte plane j
-    std::vector<int> kinds;
-    for (int k = 0; k < FRAME_BUFS_ALL; ++k)
-        if (rq.wants(k)) kinds.push_back(k - 1);
-    const size_t K = kinds.size();
-    const bool want_aov = rq.wants_aovs() || rq.moment || rq.cascade || rq.matte.on;
+    const size_t K = plan.n_outputs;
     int rc = NART_OK;
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
@@ -162,7 +142,7 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     // 1. every device renders its buckets (one host thread each, like the TBB task group)
     std::vector<int> rcs(n, NART_OK);
     std::vector<nart_render_stats> st(n);
-    std::vector<AovRequest> areq(n);
+    std::vector<PassTimes> pass(n);
     std::vector<AdaptiveRun> runs;  // adaptive: one per device, parameters and levels copied in
     if (rq.adaptive) {
         runs.resize(n);
@@ -178,28 +158,15 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
             rcs[d] = NART_E_HIP;
             return;
         }
-        // buffer i of the list: slab i of sub_tiles[d]
-        const size_t slab = ids[d].size() * tile_floats;
-        areq[d].beauty = rq.beauty;
-        areq[d].cascade = rq.cascade;
-        areq[d].matte = rq.matte;
-        for (size_t i = 0; i < K; ++i) {
-            float* buf = static_cast<float*>(ctx->sub_tiles[d]) + i * slab;
-            if (kinds[i] >= 3) (rq.matte.on ? areq[d].planes : areq[d].layers)[kinds[i] - 3] = buf;
-            else if (kinds[i] >= 0) (kinds[i] == 2 ? areq[d].moment : areq[d].tiles[kinds[i]]) = buf;
-        }
+        const FrameTiles out(plan, static_cast<float*>(ctx->sub_tiles[d]), ids[d].size() * tile_floats);
         if (rq.adaptive) {
             // the device refines its own shard: a bucket's error needs its own tiles only
-            float* frame[FRAME_BUFS] = {nullptr, nullptr, nullptr, nullptr};
-            for (size_t i = 0; i < K; ++i) frame[kinds[i] + 1] = static_cast<float*>(ctx->sub_tiles[d]) + i * slab;
-            rcs[d] = render_buckets_adaptive(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(), frame,
+            rcs[d] = render_buckets_adaptive(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(), out,
                                              ctx->streams[d], &st[d], runs[d]);
-            areq[d].ms = runs[d].aov_ms;
-            areq[d].moment_ms = runs[d].moment_ms;
+            pass[d] = runs[d].passes;
         } else {
-            rcs[d] = render_buckets(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(),
-                                    static_cast<float*>(ctx->sub_tiles[d]), ctx->streams[d], &st[d],
-                                    want_aov ? &areq[d] : nullptr);
+            rcs[d] = render_buckets(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(), out, ctx->streams[d],
+                                    &st[d], &pass[d]);
         }
         if (rcs[d] == NART_OK && hipStreamSynchronize(ctx->streams[d]) != hipSuccess) rcs[d] = NART_E_HIP;
     };
@@ -305,7 +272,7 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     HIPCHK(hipMemcpyAsync(ctx->d_slab_map, map.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s0));
     // (stream order lets the buffers share d_byid and d_image)
     for (size_t i = 0; i < K; ++i) {
-        if (!rq.on_device && !rq.dst[kinds[i] + 1]) continue;  // rendered for another buffer's sake, not delivered
+        if (!rq.on_device && !rq.dst[i]) continue;  // rendered for another output's sake, not delivered
         hipLaunchKernelGGL(k_unshard, dim3(nb), dim3(256), 0, s0, slabs + i * nb * tile_floats,
                            static_cast<float*>(ctx->d_byid), static_cast<const uint32_t*>(ctx->d_slab_map), nb,
                            (uint32_t)tile_floats);
@@ -313,22 +280,16 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
         if ((rc = nart_hip_combine_async(ctx->subs[0], p, static_cast<const nart_pixel*>(ctx->d_byid),
                                          static_cast<nart_pixel*>(ctx->d_image), s0)))
             return fail(ctx, rc, ctx->subs[0]->err);
-        // the request's i-th buffer: to its host image, or to image i of the borrowed device buffer
+        // output i: to its host image, or to image i of the borrowed device buffer
         void* dst = rq.on_device ? static_cast<char*>(*rq.image) + i * img_bytes
-                                 : static_cast<void*>(rq.dst[kinds[i] + 1]);
+                                 : static_cast<void*>(rq.dst[i]);
         if (dst != ctx->d_image)
             HIPCHK(hipMemcpyAsync(dst, ctx->d_image, img_bytes,
                                   rq.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s0));
     }
     HIPCHK(hipStreamSynchronize(s0));
-    if (aov_ms)
-        for (uint32_t d = 0; d < n; ++d) *aov_ms = std::max(*aov_ms, areq[d].ms);
-    if (moment_ms)
-        for (uint32_t d = 0; d < n; ++d) *moment_ms = std::max(*moment_ms, areq[d].moment_ms);
-    if (rq.cascade_ms)
-        for (uint32_t d = 0; d < n; ++d) *rq.cascade_ms = std::max(*rq.cascade_ms, areq[d].cascade_ms);
-    if (rq.matte_ms)
-        for (uint32_t d = 0; d < n; ++d) *rq.matte_ms = std::max(*rq.matte_ms, areq[d].matte_ms);
+    for (uint32_t d = 0; d < n; ++d)
+        for (uint32_t k = 0; k < N_PASSES; ++k) times.ms[k] = std::max(times.ms[k], pass[d].ms[k]);
     if (stats) {
         // one render: device times of the slowest device (they run concurrently), work counts
         // summed; added to the caller's stats as the single-device path adds a render's

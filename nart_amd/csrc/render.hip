@@ -23,6 +23,7 @@
 #include "device/matte.h"
 #include "device/volume.h"
 #include "host/bvh_build.h"
+#include "host/frame_plan.h"
 #include "host/path_schedule.h"
 
 using namespace nd;
@@ -80,18 +81,14 @@ struct nart_ctx {
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ev[4]: after k_primary
     bool primary_ran = false;  // the last dispatch launched k_primary (ev[4] recorded)
     bool prim_valid = false;   // d_prim holds the current batch's camera-ray hits (first-hit AOVs)
-    // around the AOV passes ([0], [1]) and the moment pass ([2], [3]) of a batch (render_buckets)
-    hipEvent_t ev_aov[4] = {nullptr, nullptr, nullptr, nullptr};
+    // around each pass of a batch after the beauty's splat (render_buckets; host/frame_plan.h PassKind)
+    hipEvent_t ev_pass[N_PASSES][2] = {};
     // around the error and scatter kernels of an adaptive level (render_buckets_adaptive)
     hipEvent_t ev_ad[2] = {nullptr, nullptr};
-    // firefly cascade: around the split + layer splats of a batch ([0], [1]: render_buckets) and
-    // around the reweighting ([2], [3]: cascade_device); the last cascade call's times
-    hipEvent_t ev_cas[4] = {nullptr, nullptr, nullptr, nullptr};
-    double cas_ms[2] = {0.0, 0.0};  // split + layer splats, reweighting
-    // first-hit ID mattes: around the plane passes of a batch ([0], [1]: render_buckets) and around
-    // the ranking ([2], [3]: matte_rank_device); the last matte call's times
-    hipEvent_t ev_mat[4] = {nullptr, nullptr, nullptr, nullptr};
-    double mat_ms[2] = {0.0, 0.0};  // plane passes, ranking
+    // around the cascade's reweighting (cascade_device) and the mattes' ranking (matte_rank_device)
+    hipEvent_t ev_cas[2] = {nullptr, nullptr}, ev_mat[2] = {nullptr, nullptr};
+    double cas_ms[2] = {0.0, 0.0};  // the last cascade call's times: split + layer splats, reweighting
+    double mat_ms[2] = {0.0, 0.0};  // the last matte call's times: plane passes, ranking
     uint32_t num_meshes = 0, num_materials = 0;  // the scene's: the id counts of the two matte kinds
     // denoiser (denoise_device): work buffers over the cropped image, the four device images of
     // nart_hip_denoise / nart_hip_render_denoised (five with the moment image), events between its
@@ -463,6 +460,18 @@ int dmalloc(nart_ctx* ctx, void** p, size_t bytes, const char* what) {
     (void)hipGetLastError();
     return fail(ctx, e == hipErrorOutOfMemory ? NART_E_OOM : NART_E_HIP,
                 std::string("hipMalloc ") + what + " (" + std::to_string(bytes) + " B): " + hipGetErrorString(e));
+}
+
+// A buffer on device `dev` that only grows: at least `bytes`, its capacity reset before it is freed.
+int ensure_dev(nart_ctx* ctx, int dev, void*& buf, size_t& cap, size_t bytes, const char* what) {
+    if (bytes <= cap) return NART_OK;
+    HIPCHK(hipSetDevice(dev));
+    if (buf) hipFree(buf);
+    buf = nullptr;
+    cap = 0;
+    if (int rc = dmalloc(ctx, &buf, bytes, what)) return rc;
+    cap = bytes;
+    return NART_OK;
 }
 
 // Work buffers for a batch.  Each group's capacity is reset before its buffers are freed, so a
@@ -1184,41 +1193,27 @@ int launch_latin(nart_ctx* ctx, const RenderArgs& ra, hipStream_t st) {
 
 
 // ---------------------------------------------------------------- first-hit AOVs
-// A render's AOV request (nart_hip_render_aovs): tiles[k] receives the splatted records of AOV k
-// (AOV_ALBEDO, AOV_NORMAL; null: not requested), laid out like the beauty tiles.  beauty false: an
-// AOV-only render, which launches no path kernel.  ms: device time of the k_aov + AOV splat launches.
-// moment: tiles of the second-moment image (k_moment + the MOM splat over the batch's Li_alpha, so it
-// needs the beauty's path kernel), moment_ms their device time.
-// cascade: the firefly cascade's layer tiles (include/nart_hip.h, "Firefly cascade"): layers[j]
-// receives layer j's share of every Li_alpha record (k_cascade_split into a second record buffer of
-// the call, then the plain splat), cascade_ms their device time.  Needs the beauty as well.
-struct CascadeLevels {
-    uint32_t K = 0;
-    float base = 0.f;
-    float b[CASCADE_MAX_LAYERS] = {};
-};
-// matte: the ID mattes' coverage planes (include/nart_hip.h, "First-hit ID mattes"): planes[q] receives
-// the indicator records of ids 4q .. 4q+3 (k_matte_ids into ctx->d_L over the camera-ray hits, as
-// k_aov; then the plain splat), matte_ms their device time.  Like the first-hit AOVs they need no
-// path kernel.
-struct MatteRequest {
-    bool on = false;
-    uint32_t kind = 0, n_ids = 0;
-    uint32_t planes() const { return on ? (n_ids + 3) / 4 : 0; }
-};
-struct AovRequest {
-    float* tiles[2] = {nullptr, nullptr};
-    float* moment = nullptr;
-    bool beauty = true;
-    double ms = 0.0, moment_ms = 0.0;
-    const CascadeLevels* cascade = nullptr;
-    float* layers[CASCADE_MAX_LAYERS] = {};
-    double cascade_ms = 0.0;
-    MatteRequest matte;
-    float* planes[MATTE_MAX_PLANES] = {};
-    double matte_ms = 0.0;
+// A plan (host/frame_plan.h) with its outputs' tile buffers: tiles[i] receives the splatted records of
+// plan.outputs[i], laid out like the beauty tiles, in the order of the bucket list rendered.
+static_assert(FRAME_MAX_LAYERS == CASCADE_MAX_LAYERS && FRAME_MAX_PLANES == MATTE_MAX_PLANES &&
+                  FRAME_MAX_MATTE_IDS == MATTE_MAX_IDS,
+              "frame_plan.h restates the device headers' limits");
+struct FrameTiles {
+    FramePlan plan;
+    float* tiles[FRAME_MAX_OUTPUTS] = {};
 
-    bool first_hit() const { return tiles[0] || tiles[1]; }
+    // the outputs' buffers back to back from `base`, `slab` floats each
+    FrameTiles(const FramePlan& pl, float* base, size_t slab) : plan(pl) {
+        for (uint32_t i = 0; i < plan.n_outputs; ++i) tiles[i] = base + i * slab;
+    }
+    float* of(OutputKind kind) const {
+        const int i = plan.find(kind);
+        return i < 0 ? nullptr : tiles[i];
+    }
+};
+// Device time of each pass of a render (frame_plan.h PassKind), added up over its batches.
+struct PassTimes {
+    double ms[N_PASSES] = {};
 };
 
 // Camera-ray hits of the batch in `a` into ctx->d_prim, for AOVs of a dispatch that did not run
@@ -1244,12 +1239,6 @@ int launch_aov(nart_ctx* ctx, const RenderArgs& a, int rec, float4* out, hipStre
     if (rec == AOV_ALBEDO) hipLaunchKernelGGL((k_aov<AOV_ALBEDO>), grid, block, 0, st, ctx->scene, a, ctx->d_prim, out);
     else hipLaunchKernelGGL((k_aov<AOV_NORMAL>), grid, block, 0, st, ctx->scene, a, ctx->d_prim, out);
     HIPCHK(hipGetLastError());
-    return NART_OK;
-}
-
-int check_first_hit(nart_ctx* ctx, const nart_render_params* p) {
-    if (p->integrator == NART_INTEGRATOR_VOLUME)
-        return fail(ctx, NART_E_UNSUPPORTED, "first-hit AOVs need surfaces: the volume integrator has none");
     return NART_OK;
 }
 
@@ -1459,21 +1448,16 @@ int launch_splat(nart_ctx* ctx, const SplatPlan& plan, const SplatArgs& sa, uint
 }
 
 // Render a bucket list into device tiles (list order); p is validated by the caller (check_params).
-// Shared by all entry points.  With `aov` each batch also splats the requested first-hit AOV records
-// (k_aov into ctx->d_L, which the beauty splat has consumed by then: no extra per-sample memory)
-// into the request's tiles; with aov->moment, between the two, the second-moment image (k_moment
-// squares the Li_alpha records in place, one more splat pass with MOM).  With aov->cascade, right
-// after the beauty's splat and before anything overwrites d_L, one k_cascade_split + plain splat per
-// layer; the second record buffer they go through is a temporary of this call.  With aov->matte,
-// after the AOVs and over the same camera-ray hits, one k_matte_ids + plain splat per coverage plane.
-int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n, float* d_tiles,
-                   hipStream_t st, nart_render_stats* stats, AovRequest* aov = nullptr) {
+// Shared by all entry points.  After the path kernel and the beauty's splat each batch runs the
+// frame plan's passes (frame_plan.h PassKind, which gives their order and why): per output of the pass, one
+// small kernel fills a record buffer -- ctx->d_L, which the beauty splat has consumed by then, so no
+// extra per-sample memory; for the cascade a second record buffer, a temporary of this call -- and the
+// same splat kernel takes it into that output's tiles.  times: the passes' device times are added.
+int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n, const FrameTiles& out,
+                   hipStream_t st, nart_render_stats* stats, PassTimes* times = nullptr) {
     int rc = NART_OK;
-    const bool beauty = !aov || aov->beauty;
-    const bool first_hit = aov && aov->first_hit(), moment = aov && aov->moment;
-    if (moment && !beauty) return fail(ctx, NART_E_INVALID, "the moment image needs the path kernel (the beauty)");
-    const CascadeLevels* cascade = aov ? aov->cascade : nullptr;
-    if (cascade && !beauty) return fail(ctx, NART_E_INVALID, "the cascade layers need the path kernel (the beauty)");
+    const FramePlan& frame = out.plan;
+    const bool beauty = frame.path_kernel;
     HIPCHK(hipSetDevice(ctx->device));
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
@@ -1489,19 +1473,12 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         for (auto& e : ctx->ev) HIPCHK(hipEventCreate(&e));
         ctx->events = true;
     }
-    if (aov)
-        for (auto& e : ctx->ev_aov)
+    for (uint32_t i = 0; i < frame.n_passes; ++i)
+        for (auto& e : ctx->ev_pass[frame.passes[i]])
             if (!e) HIPCHK(hipEventCreate(&e));
-    if (cascade)
-        for (int k = 0; k < 2; ++k)
-            if (!ctx->ev_cas[k]) HIPCHK(hipEventCreate(&ctx->ev_cas[k]));
-    const uint32_t matte_planes = aov ? aov->matte.planes() : 0;
-    if (matte_planes)
-        for (int k = 0; k < 2; ++k)
-            if (!ctx->ev_mat[k]) HIPCHK(hipEventCreate(&ctx->ev_mat[k]));
-    const size_t limit = batch_slot_limit(ctx, p->spp, cascade ? sizeof(float4) : 0);
+    const size_t limit = batch_slot_limit(ctx, p->spp, frame.record_bytes);
     ScopedDeviceBufs layer_records;  // cascade: the second per-sample record buffer, 16 B per sample
-    size_t layer_records_cap = 0;
+    size_t layer_records_cap = 0;    // bytes
     const uint32_t tpx = g.tile_size * g.tile_size;
     nart_render_stats acc;  // this call's share, added to *stats at the end
     std::memset(&acc, 0, sizeof(acc));
@@ -1556,108 +1533,84 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         sa.bucket_base = ctx->d_bucket_base;
         sa.samples = ctx->d_samples;
         sa.Lout = ctx->d_L;
-        sa.tiles = beauty ? d_tiles + (size_t)b0 * tpx * 5 : nullptr;
+        sa.tiles = beauty ? out.of(OutputKind::Beauty) + (size_t)b0 * tpx * 5 : nullptr;
         sa.n_buckets = nbk;
         if (beauty && (rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
         HIPCHK(hipEventRecord(ctx->ev[2], st));
-        if (cascade) {
-            const uint64_t ns = (uint64_t)nslots * p->spp;
-            if (ns > layer_records_cap) {
-                void* smaller = layer_records.p[0];
-                layer_records.p[0] = nullptr;
-                layer_records_cap = 0;
-                if (smaller) HIPCHK(hipFree(smaller));
-                if ((rc = dmalloc(ctx, &layer_records.p[0], ns * sizeof(float4), "cascade layer records"))) return rc;
-                layer_records_cap = ns;
-            }
-            HIPCHK(hipEventRecord(ctx->ev_cas[0], st));
-            CascadeSplitArgs ca;
-            ca.L = ctx->d_L;
-            ca.out = static_cast<float4*>(layer_records.p[0]);
-            ca.n = ns;
-            ca.K = cascade->K;
-            ca.b_first = cascade->b[0];
-            ca.b_top = cascade->b[cascade->K - 1];
-            ca.base_m1 = cascade->base - 1.f;
-            sa.Lout = ca.out;
-            for (uint32_t j = 0; j < cascade->K; ++j) {
-                ca.j = j;
-                ca.b_prev = j > 0 ? cascade->b[j - 1] : 0.f;
-                ca.b_cur = cascade->b[j];
-                ca.b_next = j + 1 < cascade->K ? cascade->b[j + 1] : 0.f;
-                hipLaunchKernelGGL(k_cascade_split, dim3((uint32_t)((ns + 255) / 256)), dim3(256), 0, st, ca);
-                HIPCHK(hipGetLastError());
-                sa.tiles = aov->layers[j] + (size_t)b0 * tpx * 5;
-                if ((rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
-            }
-            sa.Lout = ctx->d_L;
-            HIPCHK(hipEventRecord(ctx->ev_cas[1], st));
-        }
-        if (moment) {
-            HIPCHK(hipEventRecord(ctx->ev_aov[2], st));
-            const uint64_t ns = (uint64_t)nslots * p->spp;
-            hipLaunchKernelGGL(k_moment, dim3((uint32_t)((ns + 255) / 256)), dim3(256), 0, st, ctx->d_L, ns);
-            HIPCHK(hipGetLastError());
-            sa.tiles = aov->moment + (size_t)b0 * tpx * 5;
-            if ((rc = launch_splat(ctx, plan, sa, nbk, st, true))) return rc;
-            HIPCHK(hipEventRecord(ctx->ev_aov[3], st));
-        }
-        if (first_hit) {
+        const uint64_t ns = (uint64_t)nslots * p->spp;
+        const dim3 rec_grid((uint32_t)((ns + 255) / 256)), rec_block(256);
+        hipEvent_t last = ctx->ev[2];
+        for (uint32_t i = 0; i < frame.n_passes; ++i) {
+            const PassKind pass = frame.passes[i];
+            if (pass == PASS_CASCADE && (rc = ensure_dev(ctx, ctx->device, layer_records.p[0], layer_records_cap,
+                                                         ns * sizeof(float4), "cascade layer records")))
+                return rc;
             // the dispatch's own camera-ray hits where it traced them first, else k_primary now
-            if (!ctx->prim_valid && (rc = launch_aov_primary(ctx, ra, st))) return rc;
-            HIPCHK(hipEventRecord(ctx->ev_aov[0], st));
-            for (int k = 0; k < 2; ++k) {
-                if (!aov->tiles[k]) continue;
-                if ((rc = launch_aov(ctx, ra, k, ctx->d_L, st))) return rc;
-                sa.tiles = aov->tiles[k] + (size_t)b0 * tpx * 5;
-                if ((rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
-            }
-            HIPCHK(hipEventRecord(ctx->ev_aov[1], st));
-            HIPCHK(hipEventSynchronize(ctx->ev_aov[1]));
-        }
-        if (matte_planes) {
-            // the same camera-ray hits as the AOVs'; one indicator record pass and plain splat per plane
-            if (!ctx->prim_valid && (rc = launch_aov_primary(ctx, ra, st))) return rc;
-            HIPCHK(hipEventRecord(ctx->ev_mat[0], st));
-            MatteIdArgs ma;
-            ma.hit = ctx->d_prim;
-            ma.tri_mesh = ctx->scene.tri_mesh;
-            ma.meshes = ctx->scene.meshes;
-            ma.out = ctx->d_L;
-            ma.n = (uint64_t)nslots * p->spp;
-            ma.num_tris = ctx->scene.num_tris;
-            ma.num_meshes = ctx->num_meshes;
-            ma.kind = aov->matte.kind;
-            ma.n_ids = aov->matte.n_ids;
-            for (uint32_t q = 0; q < matte_planes; ++q) {
-                ma.q = q;
-                hipLaunchKernelGGL(k_matte_ids, dim3((uint32_t)((ma.n + 255) / 256)), dim3(256), 0, st, ma);
+            if ((pass == PASS_FIRST_HIT || pass == PASS_MATTE) && !ctx->prim_valid && (rc = launch_aov_primary(ctx, ra, st)))
+                return rc;
+            HIPCHK(hipEventRecord(ctx->ev_pass[pass][0], st));
+            float4* const records = pass == PASS_CASCADE ? static_cast<float4*>(layer_records.p[0]) : ctx->d_L;
+            sa.Lout = records;
+            for (uint32_t o = 0; o < frame.n_outputs; ++o) {
+                const FrameOutput& w = frame.outputs[o];
+                if (pass_of(w.kind) != pass) continue;
+                switch (w.kind) {
+                case OutputKind::Layer: {
+                    const CascadeLevels& lv = frame.ask.cascade;
+                    CascadeSplitArgs ca;
+                    ca.L = ctx->d_L;
+                    ca.out = records;
+                    ca.n = ns;
+                    ca.K = lv.K;
+                    ca.b_first = lv.b[0];
+                    ca.b_top = lv.b[lv.K - 1];
+                    ca.base_m1 = lv.base - 1.f;
+                    ca.j = w.index;
+                    ca.b_prev = ca.j > 0 ? lv.b[ca.j - 1] : 0.f;
+                    ca.b_cur = lv.b[ca.j];
+                    ca.b_next = ca.j + 1 < lv.K ? lv.b[ca.j + 1] : 0.f;
+                    hipLaunchKernelGGL(k_cascade_split, rec_grid, rec_block, 0, st, ca);
+                    break;
+                }
+                case OutputKind::Moment:
+                    hipLaunchKernelGGL(k_moment, rec_grid, rec_block, 0, st, ctx->d_L, ns);
+                    break;
+                case OutputKind::Albedo:
+                case OutputKind::Normal:
+                    if ((rc = launch_aov(ctx, ra, w.kind == OutputKind::Albedo ? AOV_ALBEDO : AOV_NORMAL, ctx->d_L, st)))
+                        return rc;
+                    break;
+                case OutputKind::Plane: {
+                    MatteIdArgs ma;
+                    ma.hit = ctx->d_prim;
+                    ma.tri_mesh = ctx->scene.tri_mesh;
+                    ma.meshes = ctx->scene.meshes;
+                    ma.out = ctx->d_L;
+                    ma.n = ns;
+                    ma.num_tris = ctx->scene.num_tris;
+                    ma.num_meshes = ctx->num_meshes;
+                    ma.kind = frame.ask.matte.kind;
+                    ma.n_ids = frame.ask.matte.n_ids;
+                    ma.q = w.index;
+                    hipLaunchKernelGGL(k_matte_ids, rec_grid, rec_block, 0, st, ma);
+                    break;
+                }
+                case OutputKind::Beauty: break;  // (no pass: pass_of)
+                }
                 HIPCHK(hipGetLastError());
-                sa.tiles = aov->planes[q] + (size_t)b0 * tpx * 5;
-                if ((rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
+                sa.tiles = out.tiles[o] + (size_t)b0 * tpx * 5;
+                if ((rc = launch_splat(ctx, plan, sa, nbk, st, pass == PASS_MOMENT))) return rc;
             }
-            HIPCHK(hipEventRecord(ctx->ev_mat[1], st));
-            HIPCHK(hipEventSynchronize(ctx->ev_mat[1]));
+            HIPCHK(hipEventRecord(ctx->ev_pass[pass][1], st));
+            last = ctx->ev_pass[pass][1];
         }
-        if (moment) HIPCHK(hipEventSynchronize(ctx->ev_aov[3]));
-        if (cascade) HIPCHK(hipEventSynchronize(ctx->ev_cas[1]));
-        HIPCHK(hipEventSynchronize(ctx->ev[2]));
+        // one stream: waiting for the last event recorded is waiting for all of them
+        HIPCHK(hipEventSynchronize(last));
         float ms = 0.f;
-        if (cascade) {
-            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_cas[0], ctx->ev_cas[1]));
-            aov->cascade_ms += ms;
-        }
-        if (first_hit) {
-            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_aov[0], ctx->ev_aov[1]));
-            aov->ms += ms;
-        }
-        if (matte_planes) {
-            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_mat[0], ctx->ev_mat[1]));
-            aov->matte_ms += ms;
-        }
-        if (moment) {
-            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_aov[2], ctx->ev_aov[3]));
-            aov->moment_ms += ms;
+        for (uint32_t i = 0; i < frame.n_passes && times; ++i) {
+            const PassKind pass = frame.passes[i];
+            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_pass[pass][0], ctx->ev_pass[pass][1]));
+            times->ms[pass] += ms;
         }
         HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
         acc.kernel_ms += ms;
@@ -1803,62 +1756,46 @@ int build_bvh_device(nart_ctx* ctx, const nart_scene_blob& blob, const std::vect
 }
 
 // ---------------------------------------------------------------- whole frames
-// What a whole-frame render produces, where it goes and whose buffers it uses (render_frame).
-// Buffer k: 0 the beauty, 1 + a first-hit AOV a (AOV_ALBEDO, AOV_NORMAL), 3 the second-moment image.
-// With the firefly cascade (FrameRequest::cascade) buffer FRAME_BUFS + j is layer j's image; with the
-// ID mattes (FrameRequest::matte) it is coverage plane j's.
-constexpr int FRAME_BUFS = 4;
-constexpr int FRAME_BUFS_ALL = FRAME_BUFS + (int)CASCADE_MAX_LAYERS;
-
 // One adaptive render (include/nart_hip.h, "Adaptive sampling"): the validated parameters and the
 // level list going in; coming out, per bucket (in the order of the list rendered: bucket-id order for
 // a whole frame) the sample count it ended on and the error of that level, the buckets rendered per
-// level, and the device times of the error and scatter kernels, the AOV passes and the moment passes.
+// level, and the device times of the error and scatter kernels and of the levels' passes.
 struct AdaptiveRun {
     nart_adaptive_params ap;
     std::vector<uint32_t> levels;
     std::vector<uint32_t> spp;
     std::vector<float> err;
     std::vector<uint32_t> rendered;
-    double ms = 0.0, aov_ms = 0.0, moment_ms = 0.0;
+    double ms = 0.0;
+    PassTimes passes;
 };
 
+// Where the images of a whole frame go and whose buffers it uses (render_frame); what the frame
+// produces is its FramePlan, and everything here that counts outputs follows the plan's list.
 struct FrameRequest {
-    bool beauty = true;            // false: an AOV-only frame, which launches no path kernel
-    bool aov[2] = {false, false};
-    bool moment = false;           // needs the path kernel: NART_E_INVALID without the beauty
-    // Delivery: the image of buffer k to the host at dst[k] (null: rendered, not delivered); or
-    // on_device, the images of the requested buffers back to back, in buffer order, from the start of
+    // Delivery: the image of output i to the host at dst[i] (null: rendered, not delivered); or
+    // on_device, the images of the plan's outputs back to back, in list order, from the start of
     // *image on device 0 (ordered on its null stream: single-device frames do not wait for them).
-    nart_pixel* dst[FRAME_BUFS_ALL] = {};
+    nart_pixel* dst[FRAME_MAX_OUTPUTS] = {};
     bool on_device = false;
     // The call's tile and image buffers.  image null: temporaries, allocated by the call and freed on
     // every return path.  Else borrowed from a context, which keeps them for its next call (the
     // memory a context holds between calls sets batch_slot_limit): the image buffer *image of
-    // capacity *image_cap on device 0, grown to max(images, buffers requested) images; tiles in
-    // d_gather.  A multi-device context always gathers and combines in its own cached buffers.
+    // capacity *image_cap on device 0, grown to max(images, outputs) images; tiles in d_gather.  A
+    // multi-device context always gathers and combines in its own cached buffers.
     void** image = nullptr;
     size_t* image_cap = nullptr;
     uint32_t images = 0;
-    // Adaptive sampling: every device refines its own buckets (render_buckets_adaptive) instead of
-    // rendering them once at p->spp; needs the beauty.  Null: the uniform render.
+    // With plan.ask.adaptive (every device refines its own buckets): the run's parameters and results.
     AdaptiveRun* adaptive = nullptr;
-    // Firefly cascade: the K layer images next to the beauty (needs it; not with adaptive);
-    // *cascade_ms receives the device time of the split and layer splats (the slowest device's).
-    const CascadeLevels* cascade = nullptr;
-    double* cascade_ms = nullptr;
-    // First-hit ID mattes: coverage plane q is buffer FRAME_BUFS + q (the buffers the cascade's layers
-    // use: not with the cascade, not with adaptive; no surfaces, no mattes: not the volume integrator);
-    // the beauty is optional.  *matte_ms receives the plane passes' device time (the slowest device's).
-    MatteRequest matte;
-    double* matte_ms = nullptr;
 
-    bool wants(int k) const {
-        if (k >= FRAME_BUFS && matte.on) return (uint32_t)(k - FRAME_BUFS) < matte.planes();
-        if (k >= FRAME_BUFS) return cascade && (uint32_t)(k - FRAME_BUFS) < cascade->K;
-        return k == 0 ? beauty : (k == 3 ? moment : aov[k - 1]);
+    FrameRequest() = default;
+    FrameRequest(void** image_, size_t* cap, uint32_t n) : on_device(true), image(image_), image_cap(cap), images(n) {}
+    // `img` is where the plan's output of `kind` goes on the host (a failed plan has no outputs).
+    void to_host(const FramePlan& plan, OutputKind kind, nart_pixel* img) {
+        const int i = plan.find(kind);
+        if (i >= 0) dst[i] = img;
     }
-    bool wants_aovs() const { return aov[0] || aov[1]; }
 };
 
 // The buffers a context keeps for whole frames (render_frame, render_multi) and the denoiser.
@@ -1899,18 +1836,20 @@ std::vector<uint32_t> adaptive_levels(const nart_adaptive_params& ap, uint32_t s
 }
 
 // The adaptive counterpart of render_buckets: the listed buckets, refined level by level, into the
-// frame's tile buffers frame[k] (FrameRequest's buffer k, list order: slot i is ids[i]; null: not
-// wanted).  Every level renders its list at that level's sample count into list-ordered scratch
-// tiles -- the beauty and the second-moment tiles always, an AOV where frame[] asks for it --
-// k_bucket_error reduces each bucket's two tiles to its error, k_scatter_tiles moves the wanted
-// buffers' tiles to their slots (replacing the earlier level's: a pixel's RNG stream is seeded by
-// its coordinates, so a second pass would replay the first one's numbers and must not be
-// accumulated), and the buckets whose error is not <= threshold form the next list.  A bucket's tiles
-// are therefore those of a uniform render at the sample count it ended on.  The scratch is a
-// temporary of the call.  p and run.ap are validated by the caller; run.levels is set.
+// frame's tile buffers (list order: slot i is ids[i]).  Every level renders its list at that level's
+// sample count into list-ordered scratch tiles -- the outputs of adaptive_level_ask: what the frame
+// asks for and, wanted or not, the second-moment tiles -- k_bucket_error reduces each bucket's beauty
+// and moment tiles to its error, k_scatter_tiles moves the frame's outputs' tiles to their slots
+// (replacing the earlier level's: a pixel's RNG stream is seeded by its coordinates, so a second pass
+// would replay the first one's numbers and must not be accumulated), and the buckets whose error is
+// not <= threshold form the next list.  A bucket's tiles are therefore those of a uniform render at
+// the sample count it ended on.  The scratch is a temporary of the call.  p and run.ap are validated
+// by the caller; run.levels is set.
 int render_buckets_adaptive(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n,
-                            float* const frame[FRAME_BUFS], hipStream_t st, nart_render_stats* stats, AdaptiveRun& run) {
+                            const FrameTiles& frame, hipStream_t st, nart_render_stats* stats, AdaptiveRun& run) {
     HIPCHK(hipSetDevice(ctx->device));
+    const FramePlan level = plan_frame(adaptive_level_ask(frame.plan.ask), PlanRules::Buckets);
+    if (level.code) return fail(ctx, level.code, level.message);
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
     const size_t tile_floats = (size_t)g.tile_size * g.tile_size * 5;
@@ -1920,18 +1859,12 @@ int render_buckets_adaptive(nart_ctx* ctx, const nart_render_params* p, const ui
     if (!n) return NART_OK;
     for (auto& e : ctx->ev_ad)
         if (!e) HIPCHK(hipEventCreate(&e));
-    // scratch buffer k: FrameRequest's numbering (0 the beauty, 1 + AOV, 3 the moment tiles)
-    bool use[FRAME_BUFS] = {true, frame[1] != nullptr, frame[2] != nullptr, true};
     ScopedDeviceBufs own;
-    size_t nS = 0;
-    for (bool u : use) nS += u;
     const size_t slab = (size_t)n * tile_floats;
-    int rc = dmalloc(ctx, &own.p[0], nS * slab * sizeof(float), "adaptive scratch tiles");
+    int rc = dmalloc(ctx, &own.p[0], level.n_outputs * slab * sizeof(float), "adaptive scratch tiles");
     if (!rc) rc = dmalloc(ctx, &own.p[1], (size_t)n * 12, "adaptive bucket lists");
     if (rc) return rc;
-    float* scratch[FRAME_BUFS] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0, i = 0; k < FRAME_BUFS; ++k)
-        if (use[k]) scratch[k] = static_cast<float*>(own.p[0]) + (size_t)(i++) * slab;
+    const FrameTiles scratch(level, static_cast<float*>(own.p[0]), slab);
     uint32_t* d_ids = static_cast<uint32_t*>(own.p[1]);
     uint32_t* d_slot = d_ids + n;
     float* d_err = reinterpret_cast<float*>(d_slot + n);
@@ -1950,20 +1883,14 @@ int render_buckets_adaptive(nart_ctx* ctx, const nart_render_params* p, const ui
         pl.spp = run.levels[li];
         cur_ids.resize(m);
         for (uint32_t i = 0; i < m; ++i) cur_ids[i] = ids[cur[i]];
-        AovRequest areq;
-        areq.tiles[0] = scratch[1];
-        areq.tiles[1] = scratch[2];
-        areq.moment = scratch[3];
-        rc = render_buckets(ctx, &pl, cur_ids.data(), m, scratch[0], st, stats, &areq);
-        run.aov_ms += areq.ms;
-        run.moment_ms += areq.moment_ms;
+        rc = render_buckets(ctx, &pl, cur_ids.data(), m, scratch, st, stats, &run.passes);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(d_ids, cur_ids.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_slot, cur.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipEventRecord(ctx->ev_ad[0], st));
         BucketErrorArgs ea;
-        ea.beauty = scratch[0];
-        ea.moment = scratch[3];
+        ea.beauty = scratch.of(OutputKind::Beauty);
+        ea.moment = scratch.of(OutputKind::Moment);
         ea.ids = d_ids;
         ea.err = d_err;
         ea.n = m;
@@ -1977,16 +1904,11 @@ int render_buckets_adaptive(nart_ctx* ctx, const nart_render_params* p, const ui
         if (stage) hipLaunchKernelGGL((k_bucket_error<true>), dim3(m), dim3(64), stage_lds, st, ea);
         else hipLaunchKernelGGL((k_bucket_error<false>), dim3(m), dim3(64), 2 * (size_t)p->bucket_size * sizeof(float), st, ea);
         HIPCHK(hipGetLastError());
-        ScatterArgs sc;
+        ScatterArgs sc = {};  // (unused buffers null)
         uint32_t nsc = 0;
-        for (int k = 0; k < FRAME_BUFS; ++k)
-            if (frame[k] && scratch[k]) {
-                sc.src[nsc] = scratch[k];
-                sc.dst[nsc++] = frame[k];
-            }
-        for (uint32_t k = nsc; k < (uint32_t)SCATTER_BUFS; ++k) {
-            sc.src[k] = nullptr;
-            sc.dst[k] = nullptr;
+        for (uint32_t o = 0; o < frame.plan.n_outputs && nsc < (uint32_t)SCATTER_BUFS; ++o) {
+            sc.src[nsc] = scratch.of(frame.plan.outputs[o].kind);
+            sc.dst[nsc++] = frame.tiles[o];
         }
         sc.slot = d_slot;
         sc.n = m;
@@ -2022,24 +1944,18 @@ namespace {
 
 // Render(): every bucket of the session, combined in bucket raster order, delivered as the request
 // says.  The one whole-frame path behind nart_hip_render, _render_aovs, _render_moment,
-// _render_device, _render_denoised and _render_denoised_moment.  Errors of a multi-device context's
-// sub-contexts are re-raised on ctx.
-int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest& rq, nart_render_stats* stats,
-                 double* aov_ms, double* moment_ms = nullptr) {
+// _render_adaptive, _render_device, _render_denoised, _render_cascade and _render_mattes: `plan` is
+// plan_frame(ask, PlanRules::Frame) of the entry point's ask, its error raised here.  times: the passes'
+// device times.  Errors of a multi-device context's sub-contexts are re-raised on ctx.
+int render_frame(nart_ctx* ctx, const nart_render_params* p, const FramePlan& plan, const FrameRequest& rq,
+                 nart_render_stats* stats, PassTimes* times = nullptr) {
     RenderTimer timer(stats);
-    if (aov_ms) *aov_ms = 0.0;
-    if (moment_ms) *moment_ms = 0.0;
-    if (rq.moment && !rq.beauty)
-        return fail(ctx, NART_E_INVALID, "the moment image needs the path kernel: it cannot be rendered without the beauty");
-    if (rq.cascade && (!rq.beauty || rq.adaptive))
-        return fail(ctx, NART_E_UNSUPPORTED, "the cascade layers need the beauty and a uniform render");
-    if (rq.matte.on && (rq.cascade || rq.adaptive))
-        return fail(ctx, NART_E_UNSUPPORTED, "the matte planes need a uniform render without the cascade");
-    if (rq.cascade_ms) *rq.cascade_ms = 0.0;
-    if (rq.matte_ms) *rq.matte_ms = 0.0;
+    PassTimes unused;
+    if (!times) times = &unused;
+    *times = PassTimes();
+    if (plan.code) return fail(ctx, plan.code, plan.message);
     nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // device 0: combines, holds the images
     int rc = NART_OK;
-    if ((rq.wants_aovs() || rq.matte.on) && (rc = check_first_hit(ctx, p))) return rc;
     if (ctx->rccl_broken)
         return fail(ctx, NART_E_RCCL, "an earlier RCCL gather of this context failed; destroy it and create a new one");
     if ((rc = check_params(c0, p))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
@@ -2048,16 +1964,15 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     const uint32_t nb = g.n_buckets_x * g.n_buckets_y;
     const size_t tile_floats = (size_t)nb * g.tile_size * g.tile_size * 5;
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5;
-    size_t K = 0;  // buffers requested
-    for (int k = 0; k < FRAME_BUFS_ALL; ++k) K += rq.wants(k);
+    const size_t K = plan.n_outputs;
     if (rq.image && (rc = ensure_dev(ctx, c0->device, *rq.image, *rq.image_cap,
                                      std::max<size_t>(K, rq.images) * img_floats * sizeof(float), "image")))
         return rc;
-    if (c0 != ctx) return render_multi(ctx, p, rq, stats, aov_ms, moment_ms);
+    if (c0 != ctx) return render_multi(ctx, p, plan, rq, stats, *times);
 
     HIPCHK(hipSetDevice(ctx->device));
-    // tile buffers back to back: the beauty (if any), then the requested AOVs and the moment image;
-    // one image to combine into on the way to the host, or the borrowed images
+    // the outputs' tile buffers back to back; one image to combine into on the way to the host, or
+    // the borrowed images
     ScopedDeviceBufs own;
     void*& d_tiles = rq.image ? ctx->d_gather : own.p[0];
     void*& d_img = rq.image ? *rq.image : own.p[1];
@@ -2066,39 +1981,22 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FrameRequest&
     else if (!(rc = dmalloc(ctx, &d_tiles, tile_bytes, "tiles")))
         rc = dmalloc(ctx, &d_img, img_floats * sizeof(float), "image");
     if (rc) return rc;
-    float* tiles[FRAME_BUFS_ALL] = {};
-    for (int k = 0, i = 0; k < FRAME_BUFS_ALL; ++k)
-        if (rq.wants(k)) tiles[k] = static_cast<float*>(d_tiles) + (size_t)(i++) * tile_floats;
+    const FrameTiles out(plan, static_cast<float*>(d_tiles), tile_floats);
     std::vector<uint32_t> ids(nb);
     for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
-    AovRequest areq;
-    areq.beauty = rq.beauty;
-    areq.tiles[0] = tiles[1];
-    areq.tiles[1] = tiles[2];
-    areq.moment = tiles[3];
-    areq.cascade = rq.cascade;
-    for (uint32_t j = 0; j < CASCADE_MAX_LAYERS; ++j) areq.layers[j] = rq.cascade ? tiles[FRAME_BUFS + j] : nullptr;
-    areq.matte = rq.matte;
-    for (uint32_t q = 0; q < MATTE_MAX_PLANES; ++q) areq.planes[q] = rq.matte.on ? tiles[FRAME_BUFS + q] : nullptr;
     if (rq.adaptive) {
-        rc = render_buckets_adaptive(ctx, p, ids.data(), nb, tiles, 0, stats, *rq.adaptive);
-        areq.ms = rq.adaptive->aov_ms;
-        areq.moment_ms = rq.adaptive->moment_ms;
+        rc = render_buckets_adaptive(ctx, p, ids.data(), nb, out, 0, stats, *rq.adaptive);
+        *times = rq.adaptive->passes;
     } else {
-        rc = render_buckets(ctx, p, ids.data(), nb, tiles[0], 0, stats,
-                            rq.wants_aovs() || rq.moment || rq.cascade || rq.matte.on ? &areq : nullptr);
+        rc = render_buckets(ctx, p, ids.data(), nb, out, 0, stats, times);
     }
-    if (aov_ms) *aov_ms = areq.ms;
-    if (moment_ms) *moment_ms = areq.moment_ms;
-    if (rq.cascade_ms) *rq.cascade_ms = areq.cascade_ms;
-    if (rq.matte_ms) *rq.matte_ms = areq.matte_ms;
-    for (int k = 0, i = 0; k < FRAME_BUFS_ALL && !rc; ++k) {
-        if (!rq.wants(k) || (!rq.on_device && !rq.dst[k])) continue;
-        float* img = static_cast<float*>(d_img) + (rq.on_device ? (size_t)(i++) * img_floats : 0);
-        rc = nart_hip_combine_async(ctx, p, reinterpret_cast<const nart_pixel*>(tiles[k]),
+    for (size_t i = 0; i < K && !rc; ++i) {
+        if (!rq.on_device && !rq.dst[i]) continue;
+        float* img = static_cast<float*>(d_img) + (rq.on_device ? i * img_floats : 0);
+        rc = nart_hip_combine_async(ctx, p, reinterpret_cast<const nart_pixel*>(out.tiles[i]),
                                     reinterpret_cast<nart_pixel*>(img), 0);
         if (rc || rq.on_device) continue;
-        if (hipMemcpy(rq.dst[k], img, img_floats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipMemcpy(rq.dst[i], img, img_floats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(ctx, NART_E_HIP, "copy image");
     }
     return rc;
@@ -2248,6 +2146,13 @@ int denoise_device(nart_ctx* ctx, const nart_render_params* p, const nart_denois
     return NART_OK;
 }
 
+// What the stages over whole images (denoiser, reweighting, ranking) need of p without check_params.
+int check_image_size(nart_ctx* ctx, const nart_render_params* p) {
+    if (!p->image_width || !p->image_height || !(p->filter_width > 0.f))
+        return fail(ctx, NART_E_INVALID, "imageWidth, imageHeight and filterWidth must be > 0");
+    return NART_OK;
+}
+
 int check_sample_variance(nart_ctx* ctx, const nart_render_params* p) {
     if (p->spp < 2) return fail(ctx, NART_E_INVALID, "sample variance needs spp >= 2");
     return NART_OK;
@@ -2264,8 +2169,7 @@ int denoise_host(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_
         rc = denoise_host(ctx->subs[0], p, &d, beauty, albedo, normal, moment, out, denoise_ms);
         return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
     }
-    if (!p->image_width || !p->image_height || !(p->filter_width > 0.f))
-        return fail(ctx, NART_E_INVALID, "imageWidth, imageHeight and filterWidth must be > 0");
+    if ((rc = check_image_size(ctx, p))) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
@@ -2290,26 +2194,25 @@ int render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoi
     nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // the context that denoises
     // beauty, both AOVs (and the moment image) into the first of its device images, the denoised image
     // after them: nothing passes the host
+    FrameAsk ask(p->integrator);
+    ask.aov[AOV_ALBEDO] = ask.aov[AOV_NORMAL] = true;
+    ask.moment = sample_variance;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
     const int n = sample_variance ? 5 : 4;
-    FrameRequest rq;
-    rq.aov[AOV_ALBEDO] = rq.aov[AOV_NORMAL] = true;
-    rq.moment = sample_variance;
-    rq.on_device = true;
-    rq.image = &c0->d_dn_img;
-    rq.image_cap = &c0->cap_dn_img;
-    rq.images = (uint32_t)n;
-    if ((rc = render_frame(ctx, p, rq, stats, nullptr))) return rc;
+    const FrameRequest rq(&c0->d_dn_img, &c0->cap_dn_img, (uint32_t)n);
+    if ((rc = render_frame(ctx, p, plan, rq, stats))) return rc;
     RenderTimer timer(stats);  // render_ms covers the whole call
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
     const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
     float* img[5];
     if ((rc = denoise_images(c0, g, img, n)) ||  // (sized by the frame: this lays them out)
-        (rc = denoise_device(c0, p, d, img[0], img[1], img[2], sample_variance ? img[3] : nullptr, img[n - 1], 0,
-                             denoise_ms)))
+        (rc = denoise_device(c0, p, d, img[plan.find(OutputKind::Beauty)], img[plan.find(OutputKind::Albedo)],
+                             img[plan.find(OutputKind::Normal)],
+                             sample_variance ? img[plan.find(OutputKind::Moment)] : nullptr, img[n - 1], 0, denoise_ms)))
         return c0 == ctx ? rc : fail(ctx, rc, c0->err);
     HIPCHK(hipSetDevice(c0->device));
-    if (image) HIPCHK(hipMemcpy(image, img[0], img_bytes, hipMemcpyDeviceToHost));
+    if (image) HIPCHK(hipMemcpy(image, img[plan.find(OutputKind::Beauty)], img_bytes, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out, img[n - 1], img_bytes, hipMemcpyDeviceToHost));
     return NART_OK;
 }
@@ -2320,17 +2223,23 @@ int render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_
     if (aovs & ~(NART_AOV_ALBEDO | NART_AOV_NORMAL)) return fail(ctx, NART_E_INVALID, "unknown AOV bit");
     if (((aovs & NART_AOV_ALBEDO) && !albedo) || ((aovs & NART_AOV_NORMAL) && !normal))
         return fail(ctx, NART_E_INVALID, "an AOV is requested without its image buffer");
-    FrameRequest rq;
+    FrameAsk ask(p->integrator);
     // the moment image needs the path kernel: with it the beauty is rendered even where it is not asked for
-    rq.beauty = image != nullptr || moment != nullptr;
-    rq.moment = moment != nullptr;
-    rq.aov[AOV_ALBEDO] = (aovs & NART_AOV_ALBEDO) != 0;
-    rq.aov[AOV_NORMAL] = (aovs & NART_AOV_NORMAL) != 0;
-    rq.dst[0] = image;
-    rq.dst[1 + AOV_ALBEDO] = albedo;
-    rq.dst[1 + AOV_NORMAL] = normal;
-    rq.dst[3] = moment;
-    return render_frame(ctx, p, rq, stats, aov_ms, moment_ms);
+    ask.beauty = image != nullptr || moment != nullptr;
+    ask.moment = moment != nullptr;
+    ask.aov[AOV_ALBEDO] = (aovs & NART_AOV_ALBEDO) != 0;
+    ask.aov[AOV_NORMAL] = (aovs & NART_AOV_NORMAL) != 0;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    FrameRequest rq;
+    rq.to_host(plan, OutputKind::Beauty, image);
+    rq.to_host(plan, OutputKind::Albedo, albedo);
+    rq.to_host(plan, OutputKind::Normal, normal);
+    rq.to_host(plan, OutputKind::Moment, moment);
+    PassTimes times;
+    const int rc = render_frame(ctx, p, plan, rq, stats, &times);
+    if (aov_ms) *aov_ms = times.ms[PASS_FIRST_HIT];
+    if (moment_ms) *moment_ms = times.ms[PASS_MOMENT];
+    return rc;
 }
 
 // ---------------------------------------------------------------- firefly cascade (device/cascade.h)
@@ -2368,8 +2277,8 @@ int cascade_device(nart_ctx* ctx, const nart_render_params* p, const nart_cascad
     HIPCHK(hipSetDevice(ctx->device));
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
-    for (int k = 2; k < 4; ++k)
-        if (!ctx->ev_cas[k]) HIPCHK(hipEventCreate(&ctx->ev_cas[k]));
+    for (auto& e : ctx->ev_cas)
+        if (!e) HIPCHK(hipEventCreate(&e));
     CascadeReweightArgs a;
     a.beauty = d_beauty;
     a.layers = d_layers;
@@ -2383,30 +2292,30 @@ int cascade_device(nart_ctx* ctx, const nart_render_params* p, const nart_cascad
     a.N = (float)p->spp;
     a.kappa = cp.kappa;
     for (uint32_t j = 0; j < CASCADE_MAX_LAYERS; ++j) a.b[j] = j < lv.K ? lv.b[j] : 0.f;
-    HIPCHK(hipEventRecord(ctx->ev_cas[2], st));
+    HIPCHK(hipEventRecord(ctx->ev_cas[0], st));
     // the border stays zero: the kernel writes the cropped pixels only
     HIPCHK(hipMemsetAsync(d_out, 0, (size_t)g.total_width * g.total_height * sizeof(nart_pixel), st));
     const dim3 grid((a.W + CS_TW - 1) / CS_TW, (a.H + CS_TH - 1) / CS_TH), block(CS_TW * CS_TH);
     hipLaunchKernelGGL(k_cascade_reweight, grid, block, (size_t)lv.K * CS_PLANE * sizeof(float), st, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev_cas[3], st));
-    HIPCHK(hipEventSynchronize(ctx->ev_cas[3]));
+    HIPCHK(hipEventRecord(ctx->ev_cas[1], st));
+    HIPCHK(hipEventSynchronize(ctx->ev_cas[1]));
     float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, ctx->ev_cas[2], ctx->ev_cas[3]));
+    HIPCHK(hipEventElapsedTime(&t, ctx->ev_cas[0], ctx->ev_cas[1]));
     ctx->cas_ms[1] = t;
     return NART_OK;
 }
 
-// The tile buffers a context keeps between whole frames grow with the number of buffers a frame
-// asks for.  A cascade frame asks for up to nine: what it made them grow by is given back when the
+// The tile buffers a context keeps between whole frames grow with the number of outputs a frame
+// has.  A cascade or matte frame has up to twelve: what it made them grow by is given back when the
 // call returns, so that a later render finds the free memory (batch_slot_limit) it found before.
-struct CascadeTileGuard {
+struct TileGrowthGuard {
     nart_ctx* ctx;
     size_t gather_cap;
     std::vector<size_t> sub_cap;
-    explicit CascadeTileGuard(nart_ctx* c) : ctx(c), gather_cap(c->cap_gather), sub_cap(c->sub_cap) {}
-    CascadeTileGuard(const CascadeTileGuard&) = delete;
-    ~CascadeTileGuard() {
+    explicit TileGrowthGuard(nart_ctx* c) : ctx(c), gather_cap(c->cap_gather), sub_cap(c->sub_cap) {}
+    TileGrowthGuard(const TileGrowthGuard&) = delete;
+    ~TileGrowthGuard() {
         const int dev0 = ctx->subs.empty() ? ctx->device : ctx->devs[0];
         if (ctx->cap_gather > gather_cap && hipSetDevice(dev0) == hipSuccess) {
             hipFree(ctx->d_gather);
@@ -2423,8 +2332,7 @@ struct CascadeTileGuard {
 };
 
 int check_cascade_frame(nart_ctx* ctx, const nart_render_params* p) {
-    if (!p->image_width || !p->image_height || !(p->filter_width > 0.f))
-        return fail(ctx, NART_E_INVALID, "imageWidth, imageHeight and filterWidth must be > 0");
+    if (int rc = check_image_size(ctx, p)) return rc;
     if (p->spp < 1) return fail(ctx, NART_E_INVALID, "the cascade needs spp >= 1");
     return NART_OK;
 }
@@ -2435,31 +2343,32 @@ int render_cascade(nart_ctx* ctx, const nart_render_params* p, const nart_cascad
                    nart_pixel* image, nart_pixel* beauty, nart_pixel* layers, nart_render_stats* stats) {
     nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];
     ctx->cas_ms[0] = ctx->cas_ms[1] = 0.0;
-    CascadeTileGuard guard(ctx);
+    TileGrowthGuard guard(ctx);
     ScopedDeviceBufs imgs;  // the device images of the call, on device 0
     size_t imgs_cap = 0;
     const uint32_t K = lv.K;
-    FrameRequest rq;
-    rq.cascade = &lv;
-    rq.cascade_ms = &ctx->cas_ms[0];
-    rq.on_device = true;
-    rq.image = &imgs.p[0];
-    rq.image_cap = &imgs_cap;
-    rq.images = K + 2;  // the beauty, the layers, the robust image
-    int rc = render_frame(ctx, p, rq, stats, nullptr);
+    FrameAsk ask(p->integrator);
+    ask.cascade = lv;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    const FrameRequest rq(&imgs.p[0], &imgs_cap, K + 2);  // the beauty, the layers, the robust image
+    PassTimes times;
+    int rc = render_frame(ctx, p, plan, rq, stats, &times);
+    ctx->cas_ms[0] = times.ms[PASS_CASCADE];
     if (rc) return rc;
     RenderTimer timer(stats);  // render_ms covers the whole call
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
-    float* d = static_cast<float*>(imgs.p[0]);
-    float* d_out = d + (size_t)(K + 1) * img_floats;
-    if ((rc = cascade_device(c0, p, cp, lv, d, d + img_floats, d_out, 0))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
+    // the plan's images back to back (the layers follow one another), the robust image after them
+    float* d_beauty = static_cast<float*>(imgs.p[0]) + (size_t)plan.find(OutputKind::Beauty) * img_floats;
+    float* d_layers = static_cast<float*>(imgs.p[0]) + (size_t)plan.find(OutputKind::Layer, 0) * img_floats;
+    float* d_out = static_cast<float*>(imgs.p[0]) + (size_t)plan.n_outputs * img_floats;
+    if ((rc = cascade_device(c0, p, cp, lv, d_beauty, d_layers, d_out, 0))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
     ctx->cas_ms[1] = c0->cas_ms[1];
     HIPCHK(hipSetDevice(c0->device));
     HIPCHK(hipMemcpy(image, d_out, img_bytes, hipMemcpyDeviceToHost));
-    if (beauty) HIPCHK(hipMemcpy(beauty, d, img_bytes, hipMemcpyDeviceToHost));
-    if (layers) HIPCHK(hipMemcpy(layers, d + img_floats, (size_t)K * img_bytes, hipMemcpyDeviceToHost));
+    if (beauty) HIPCHK(hipMemcpy(beauty, d_beauty, img_bytes, hipMemcpyDeviceToHost));
+    if (layers) HIPCHK(hipMemcpy(layers, d_layers, (size_t)K * img_bytes, hipMemcpyDeviceToHost));
     return NART_OK;
 }
 
@@ -2504,12 +2413,6 @@ const char* matte_params_error(const nart_matte_params* mp, nart_matte_params& o
     return nullptr;
 }
 
-int check_matte_frame(nart_ctx* ctx, const nart_render_params* p) {
-    if (!p->image_width || !p->image_height || !(p->filter_width > 0.f))
-        return fail(ctx, NART_E_INVALID, "imageWidth, imageHeight and filterWidth must be > 0");
-    return NART_OK;
-}
-
 // The ranking over device images on a single-device context: the P plane images back to back (null
 // with no ids), the R / 2 rank images out; synchronous.  The time goes to ctx->mat_ms[1].
 int matte_rank_device(nart_ctx* ctx, const nart_render_params* p, uint32_t n_ids, uint32_t R, const float* d_planes,
@@ -2517,8 +2420,8 @@ int matte_rank_device(nart_ctx* ctx, const nart_render_params* p, uint32_t n_ids
     HIPCHK(hipSetDevice(ctx->device));
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
-    for (int k = 2; k < 4; ++k)
-        if (!ctx->ev_mat[k]) HIPCHK(hipEventCreate(&ctx->ev_mat[k]));
+    for (auto& e : ctx->ev_mat)
+        if (!e) HIPCHK(hipEventCreate(&e));
     MatteRankArgs a;
     a.planes = d_planes;
     a.out = d_ranks;
@@ -2529,17 +2432,17 @@ int matte_rank_device(nart_ctx* ctx, const nart_render_params* p, uint32_t n_ids
     a.fb = g.filter_bounds;
     a.n_ids = n_ids;
     a.R = R;
-    HIPCHK(hipEventRecord(ctx->ev_mat[2], st));
+    HIPCHK(hipEventRecord(ctx->ev_mat[0], st));
     // the border stays zero: the kernel writes the cropped pixels only
     HIPCHK(hipMemsetAsync(d_ranks, 0, (size_t)(R / 2) * g.total_width * g.total_height * sizeof(nart_pixel), st));
     const dim3 grid((a.W + MT_TW - 1) / MT_TW, (a.H + MT_TH - 1) / MT_TH), block(MT_LANES);
     const size_t lds = (size_t)((n_ids + 3) / 4) * 4 * MT_LANES * sizeof(float);
     hipLaunchKernelGGL(k_matte_rank, grid, block, lds, st, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev_mat[3], st));
-    HIPCHK(hipEventSynchronize(ctx->ev_mat[3]));
+    HIPCHK(hipEventRecord(ctx->ev_mat[1], st));
+    HIPCHK(hipEventSynchronize(ctx->ev_mat[1]));
     float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, ctx->ev_mat[2], ctx->ev_mat[3]));
+    HIPCHK(hipEventElapsedTime(&t, ctx->ev_mat[0], ctx->ev_mat[1]));
     ctx->mat_ms[1] = t;
     return NART_OK;
 }
@@ -2551,44 +2454,42 @@ int render_mattes(nart_ctx* ctx, const nart_render_params* p, const nart_matte_p
                   nart_pixel* image, nart_pixel* planes, nart_render_stats* stats) {
     nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];
     ctx->mat_ms[0] = ctx->mat_ms[1] = 0.0;
-    if (int rc = check_first_hit(ctx, p)) return rc;
-    const uint32_t n_ids = mp.kind == NART_MATTE_MATERIAL ? c0->num_materials : c0->num_meshes;
-    if (n_ids > MATTE_MAX_IDS)
-        return fail(ctx, NART_E_UNSUPPORTED, "the scene has " + std::to_string(n_ids) + " matte ids; at most 32 are supported");
-    CascadeTileGuard guard(ctx);  // up to nine tile buffers: what they grow by is given back
-    ScopedDeviceBufs imgs;        // the device images of the call, on device 0
+    FrameAsk ask(p->integrator);
+    ask.beauty = image != nullptr;
+    ask.matte.on = true;
+    ask.matte.kind = mp.kind;
+    ask.matte.n_ids = mp.kind == NART_MATTE_MATERIAL ? c0->num_materials : c0->num_meshes;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    if (plan.code) return fail(ctx, plan.code, plan.message);  // (before anything is allocated)
+    TileGrowthGuard guard(ctx);
+    ScopedDeviceBufs imgs;  // the device images of the call, on device 0
     size_t imgs_cap = 0;
-    const uint32_t P = (n_ids + 3) / 4, R = mp.ranks, B = image ? 1 : 0;
-    FrameRequest rq;
-    rq.beauty = image != nullptr;
-    rq.matte.on = true;
-    rq.matte.kind = mp.kind;
-    rq.matte.n_ids = n_ids;
-    rq.matte_ms = &ctx->mat_ms[0];
-    rq.on_device = true;
-    rq.image = &imgs.p[0];
-    rq.image_cap = &imgs_cap;
-    rq.images = B + P + R / 2;  // the beauty, the planes, the rank images
+    const uint32_t n_ids = ask.matte.n_ids, P = ask.matte.planes(), R = mp.ranks;
+    const FrameRequest rq(&imgs.p[0], &imgs_cap, plan.n_outputs + R / 2);  // the beauty, the planes, the rank images
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
     int rc = NART_OK;
-    if (B + P) {
-        if ((rc = render_frame(ctx, p, rq, stats, nullptr))) return rc;
+    if (plan.n_outputs) {
+        PassTimes times;
+        rc = render_frame(ctx, p, plan, rq, stats, &times);
+        ctx->mat_ms[0] = times.ms[PASS_MATTE];
+        if (rc) return rc;
     } else {
         if ((rc = check_params(c0, p))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
         if ((rc = ensure_dev(ctx, c0->device, imgs.p[0], imgs_cap, (size_t)(R / 2) * img_bytes, "image"))) return rc;
     }
     RenderTimer timer(stats);  // render_ms covers the whole call
+    // the plan's images back to back (the planes follow one another), the rank images after them
     float* d = static_cast<float*>(imgs.p[0]);
-    float* d_planes = d + (size_t)B * img_floats;
-    float* d_ranks = d_planes + (size_t)P * img_floats;
-    if ((rc = matte_rank_device(c0, p, n_ids, R, P ? d_planes : nullptr, d_ranks, 0)))
+    float* d_planes = P ? d + (size_t)plan.find(OutputKind::Plane, 0) * img_floats : nullptr;
+    float* d_ranks = d + (size_t)plan.n_outputs * img_floats;
+    if ((rc = matte_rank_device(c0, p, n_ids, R, d_planes, d_ranks, 0)))
         return c0 == ctx ? rc : fail(ctx, rc, c0->err);
     ctx->mat_ms[1] = c0->mat_ms[1];
     HIPCHK(hipSetDevice(c0->device));
     HIPCHK(hipMemcpy(ranks, d_ranks, (size_t)(R / 2) * img_bytes, hipMemcpyDeviceToHost));
-    if (image) HIPCHK(hipMemcpy(image, d, img_bytes, hipMemcpyDeviceToHost));
+    if (image) HIPCHK(hipMemcpy(image, d + (size_t)plan.find(OutputKind::Beauty) * img_floats, img_bytes, hipMemcpyDeviceToHost));
     if (planes && P) HIPCHK(hipMemcpy(planes, d_planes, (size_t)P * img_bytes, hipMemcpyDeviceToHost));
     return NART_OK;
 }
@@ -2931,8 +2832,9 @@ void nart_hip_destroy(nart_ctx* ctx) {
     for (void* b : ctx->env_bufs) hipFree(b);
     if (ctx->events)
         for (auto& e : ctx->ev) hipEventDestroy(e);
-    for (auto& e : ctx->ev_aov)
-        if (e) hipEventDestroy(e);
+    for (auto& pair : ctx->ev_pass)
+        for (auto& e : pair)
+            if (e) hipEventDestroy(e);
     for (auto& e : ctx->ev_ad)
         if (e) hipEventDestroy(e);
     for (auto& e : ctx->ev_cas)
@@ -3007,7 +2909,8 @@ int nart_hip_render_buckets_async(nart_ctx* ctx, const nart_render_params* p, co
         return fail(ctx, NART_E_UNSUPPORTED, "render_buckets_async takes a single-device context (one per rank)");
     RenderTimer timer(stats);
     if (int rc = check_params(ctx, p)) return rc;
-    return render_buckets(ctx, p, bucket_ids, n_buckets, reinterpret_cast<float*>(d_tiles), (hipStream_t)stream, stats);
+    const FrameTiles out(plan_frame(FrameAsk(p->integrator), PlanRules::Buckets), reinterpret_cast<float*>(d_tiles), 0);
+    return render_buckets(ctx, p, bucket_ids, n_buckets, out, (hipStream_t)stream, stats);
 }
 
 int nart_hip_combine_async(nart_ctx* ctx, const nart_render_params* p, const nart_pixel* d_tiles, nart_pixel* d_image,
@@ -3037,17 +2940,15 @@ int nart_hip_combine_async(nart_ctx* ctx, const nart_render_params* p, const nar
 
 int nart_hip_render(nart_ctx* ctx, const nart_render_params* p, nart_pixel* image, nart_render_stats* stats) {
     if (!ctx || !p || !image) return NART_E_INVALID;
+    const FramePlan plan = plan_frame(FrameAsk(p->integrator), PlanRules::Frame);
     FrameRequest rq;
-    rq.dst[0] = image;
-    return render_frame(ctx, p, rq, stats, nullptr);
+    rq.to_host(plan, OutputKind::Beauty, image);
+    return render_frame(ctx, p, plan, rq, stats);
 }
 
 int nart_hip_render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_pixel* image,
                          nart_pixel* albedo, nart_pixel* normal, nart_render_stats* stats, double* aov_ms) {
     if (!ctx || !p) return NART_E_INVALID;
-    if (aovs & ~(NART_AOV_ALBEDO | NART_AOV_NORMAL)) return fail(ctx, NART_E_INVALID, "unknown AOV bit");
-    if (((aovs & NART_AOV_ALBEDO) && !albedo) || ((aovs & NART_AOV_NORMAL) && !normal))
-        return fail(ctx, NART_E_INVALID, "an AOV is requested without its image buffer");
     if (!aovs && !image) return fail(ctx, NART_E_INVALID, "neither the beauty nor an AOV is requested");
     if (!aovs) return nart_hip_render(ctx, p, image, stats);
     return render_aovs(ctx, p, aovs, image, albedo, normal, nullptr, stats, aov_ms, nullptr);
@@ -3090,16 +2991,19 @@ int nart_hip_render_adaptive(nart_ctx* ctx, const nart_render_params* p, const n
     else adaptive_defaults(&run.ap);
     if (const char* why = adaptive_params_error(run.ap, p->spp)) return fail(ctx, NART_E_INVALID, why);
     run.levels = adaptive_levels(run.ap, p->spp);
+    FrameAsk ask(p->integrator);
+    ask.adaptive = true;
+    ask.moment = moment != nullptr;
+    ask.aov[AOV_ALBEDO] = (aovs & NART_AOV_ALBEDO) != 0;
+    ask.aov[AOV_NORMAL] = (aovs & NART_AOV_NORMAL) != 0;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
     FrameRequest rq;
     rq.adaptive = &run;
-    rq.moment = moment != nullptr;
-    rq.aov[AOV_ALBEDO] = (aovs & NART_AOV_ALBEDO) != 0;
-    rq.aov[AOV_NORMAL] = (aovs & NART_AOV_NORMAL) != 0;
-    rq.dst[0] = image;
-    rq.dst[1 + AOV_ALBEDO] = albedo;
-    rq.dst[1 + AOV_NORMAL] = normal;
-    rq.dst[3] = moment;
-    if (int rc = render_frame(ctx, p, rq, stats, nullptr, nullptr)) return rc;
+    rq.to_host(plan, OutputKind::Beauty, image);
+    rq.to_host(plan, OutputKind::Albedo, albedo);
+    rq.to_host(plan, OutputKind::Normal, normal);
+    rq.to_host(plan, OutputKind::Moment, moment);
+    if (int rc = render_frame(ctx, p, plan, rq, stats)) return rc;
     if (bucket_spp) std::copy(run.spp.begin(), run.spp.end(), bucket_spp);
     if (bucket_error) std::copy(run.err.begin(), run.err.end(), bucket_error);
     if (adaptive_ms) *adaptive_ms = run.ms;
@@ -3162,7 +3066,7 @@ int nart_hip_render_mattes(nart_ctx* ctx, const nart_render_params* p, const nar
     nart_matte_params m;
     if (const char* why = matte_params_error(mp, m)) return fail(ctx, NART_E_INVALID, why);
     if (!ctx || !p || !ranks) return NART_E_INVALID;
-    if (int rc = check_matte_frame(ctx, p)) return rc;
+    if (int rc = check_image_size(ctx, p)) return rc;
     return render_mattes(ctx, p, m, ranks, image, planes, stats);
 }
 
@@ -3172,7 +3076,7 @@ int nart_hip_matte_rank(nart_ctx* ctx, const nart_render_params* p, const nart_m
     if (const char* why = matte_params_error(mp, m)) return fail(ctx, NART_E_INVALID, why);
     if (n_ids > MATTE_MAX_IDS) return fail(ctx, NART_E_INVALID, "n_ids must be <= 32");
     if (!ctx || !p || !ranks || (n_ids && !planes)) return NART_E_INVALID;
-    if (int rc = check_matte_frame(ctx, p)) return rc;
+    if (int rc = check_image_size(ctx, p)) return rc;
     return matte_rank_host(ctx, p, m, n_ids, planes, ranks);
 }
 
@@ -3181,7 +3085,7 @@ int nart_hip_matte_extract(nart_ctx* ctx, const nart_render_params* p, const nar
     nart_matte_params m;
     if (const char* why = matte_params_error(mp, m)) return fail(ctx, NART_E_INVALID, why);
     if (!ctx || !p || !ranks || !out) return NART_E_INVALID;
-    if (int rc = check_matte_frame(ctx, p)) return rc;
+    if (int rc = check_image_size(ctx, p)) return rc;
     return matte_extract_host(ctx, p, m, ranks, id_mask, out);
 }
 
@@ -3200,7 +3104,9 @@ int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint
         return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
     }
     int rc = check_params(ctx, p);
-    if (rc || (rc = check_first_hit(ctx, p))) return rc;
+    if (rc) return rc;
+    if (p->integrator == NART_INTEGRATOR_VOLUME)  // (frames: plan_frame's rule)
+        return fail(ctx, NART_E_UNSUPPORTED, "first-hit AOVs need surfaces: the volume integrator has none");
     if (!w || !h) return fail(ctx, NART_E_INVALID, "empty rect");  // (nart_hip_render_samples launches over it)
     RenderArgs ra;
     // k_primary<false, ...> and k_aov count nothing
@@ -3262,11 +3168,8 @@ int nart_hip_render_device(nart_ctx* ctx, const nart_render_params* p, const nar
                            nart_render_stats* stats) {
     if (!ctx || !p || !d_image) return NART_E_INVALID;
     // tiles gathered to device 0 and combined there (a multi-device context), into the context's image
-    FrameRequest rq;
-    rq.on_device = true;
-    rq.image = &ctx->d_image;
-    rq.image_cap = &ctx->cap_image;
-    if (int rc = render_frame(ctx, p, rq, stats, nullptr)) return rc;
+    const FrameRequest rq(&ctx->d_image, &ctx->cap_image, 0);
+    if (int rc = render_frame(ctx, p, plan_frame(FrameAsk(p->integrator), PlanRules::Frame), rq, stats)) return rc;
     if (ctx->subs.empty()) {  // (a multi-device frame has waited for its gather stream)
         RenderTimer timer(stats);
         if (hipStreamSynchronize(0) != hipSuccess) return fail(ctx, NART_E_HIP, "render");

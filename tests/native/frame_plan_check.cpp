@@ -1,0 +1,46 @@
+// Prints the decisions of host/frame_plan.h for tests/test_frame_plan.py.  One request per line of
+// standard input:
+//   rules beauty aov_bits moment adaptive K matte n_ids integrator
+//        (rules: "frame" or "buckets"; aov_bits: 1 albedo, 2 normal; K: cascade layers, 0 none;
+//         matte: 0 / 1; integrator: NART_INTEGRATOR_*)
+// One answer per line:
+//   code|message|kind:index,...|pass,...|path_kernel|record_bytes
+#include <cstdio>
+#include <iostream>
+#include <sstream>
+#include <string>
+
+#include "../../nart_amd/csrc/host/frame_plan.h"
+
+using namespace nd;
+
+int main() {
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        std::istringstream is(line);
+        std::string rules;
+        unsigned beauty = 0, bits = 0, moment = 0, adaptive = 0, K = 0, matte = 0, n_ids = 0, integrator = 0;
+        is >> rules >> beauty >> bits >> moment >> adaptive >> K >> matte >> n_ids >> integrator;
+        if (!is || (rules != "frame" && rules != "buckets")) {
+            std::fprintf(stderr, "bad request: %s\n", line.c_str());
+            return 1;
+        }
+        FrameAsk a(integrator);
+        a.beauty = beauty != 0;
+        a.aov[0] = (bits & 1u) != 0;
+        a.aov[1] = (bits & 2u) != 0;
+        a.moment = moment != 0;
+        a.adaptive = adaptive != 0;
+        a.cascade.K = K;
+        a.matte.on = matte != 0;
+        a.matte.n_ids = n_ids;
+        const FramePlan plan = plan_frame(a, rules == "frame" ? PlanRules::Frame : PlanRules::Buckets);
+        std::printf("%d|%s|", plan.code, plan.message.c_str());
+        for (uint32_t i = 0; i < plan.n_outputs; ++i)
+            std::printf("%s%u:%u", i ? "," : "", (unsigned)plan.outputs[i].kind, plan.outputs[i].index);
+        std::printf("|");
+        for (uint32_t i = 0; i < plan.n_passes; ++i) std::printf("%s%u", i ? "," : "", (unsigned)plan.passes[i]);
+        std::printf("|%d|%u\n", plan.path_kernel ? 1 : 0, plan.record_bytes);
+    }
+    return 0;
+}

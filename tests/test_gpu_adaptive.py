@@ -267,6 +267,30 @@ def test_two_rank_rehearsal(gpu, glass_scene, glass_renderer):
     m.close()
 
 
+def test_widest_frame_two_ranks_in_batches(gpu, glass_scene, monkeypatch):
+    """The widest request one frame carries -- adaptive, both first-hit AOVs and the moment image --
+    on two ranks whose every level goes in several batches (NART_BATCH_BYTES=1 leaves 256 slots),
+    against the same call on one device in one batch: test_moment_batches' frame (28 x 24 total, four
+    buckets), threshold 0, so every bucket refines once and both levels run."""
+    p = _params(glass_scene, 24, 20, 4, **CONFIGS["b16_fw2"])
+    g = nart_amd.session_geometry(p)
+    assert (g.total_width, g.total_height, g.n_buckets_x * g.n_buckets_y) == (28, 24, 4)
+    ap = _ap(min_spp=2, growth=2, threshold=0.0)
+    one = nart_amd.HipRenderer(glass_scene)
+    st1 = nart_amd.RenderStats()
+    ref = one.render_adaptive(p, ap, albedo=True, normal=True, moment=True, stats=st1)
+    one.close()
+    assert (ref["bucket_spp"] == 4).all()
+    monkeypatch.setenv("NART_BATCH_BYTES", "1")
+    m = nart_amd.HipRenderer(glass_scene, devices=[0, 0])
+    st = nart_amd.RenderStats()
+    got = m.render_adaptive(p, ap, albedo=True, normal=True, moment=True, stats=st)
+    m.close()
+    for name in IMAGES + ("bucket_spp",):
+        assert _bits_equal(got[name], ref[name]), (name, _report(got[name], ref[name]))
+    assert (st.samples, st.traced_samples) == (st1.samples, st1.traced_samples)
+
+
 # ---------------------------------------------------------------- 6. volume integrator
 def test_adaptive_volume_session(gpu, volume_scenes):
     vol = volume_scenes["c5"]
