@@ -179,7 +179,8 @@ struct RenderArgs {
     uint32_t ilist_stride = 0;
     // k_render_rq lean build (WV = 3): traversal-stack entries per lane kept in LDS (the LDS layout
     // uses stack_lds, not stack_depth); entries beyond them in gstack, (stack_depth - stack_lds)
-    // 8-B entries per launched thread, lane-major
+    // 8-B entries per launched thread, thread-major: thread gid's levels are contiguous, level l at
+    // gstack[gid * (stack_depth - stack_lds) + l - stack_lds]
     uint32_t stack_lds = 0;
     int2* gstack = nullptr;
 };
@@ -965,6 +966,56 @@ __global__ __launch_bounds__(256, NART_PRIMARY_WAVES) void k_primary(DScene S, R
     }
     if (COUNT) {
         atomicAdd(&A.counters[0], (unsigned long long)A.spp);
+        atomicAdd(&A.counters[2], (unsigned long long)cnt.nodes);
+        atomicAdd(&A.counters[3], (unsigned long long)cnt.tris);
+        atomicAdd(&A.counters[5], (unsigned long long)cnt.oc_checks);
+        atomicAdd(&A.counters[6], (unsigned long long)cnt.oc_replays);
+    }
+}
+
+// k_primary with one pixel per wave: a packet is 64 consecutive samples of one slot (lane = sample
+// index within the chunk), and a wave walks all spp / 64 chunks of its slot.  The rays of a packet
+// differ only by their sub-pixel jitter, so the packet walks about what one ray walks (one or two
+// leaves, not every leaf under a 16x4-pixel footprint), nearly always on one major axis (the
+// triangle records come through scalar loads), and with pixel-major rows (stride 1) a chunk is one
+// coalesced 512-B read and one 256-B write; the slot lookup is wave-uniform and paid once per
+// slot.  hit[] is word for word k_primary's: the closest hit does not depend on which rays share a
+// packet (path.h traverse_packet).  Launched with spp % 64 == 0 only, so a live wave never has
+// a masked lane; any stride indexes correctly, stride 1 is what makes it fast.  Block: 4 waves =
+// 4 slots; LDS: one stack_depth x 16 B wave stack per wave.  With COUNT the extend-ray total is
+// k_primary's; node and triangle counts are per participating lane and so depend on the packets.
+#ifndef NART_PRIMARY_PX_WAVES
+#define NART_PRIMARY_PX_WAVES 4
+#endif
+template <bool COUNT, bool ENV, uint32_t FM = FT_ALL>
+__global__ __launch_bounds__(256, NART_PRIMARY_PX_WAVES) void k_primary_px(DScene S, RenderArgs A, uint32_t* hit) {
+    extern __shared__ __attribute__((aligned(16))) int s_dyn[];
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t slot = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (slot >= A.n_slots) return;  // wave-uniform
+    uint4* wstk = reinterpret_cast<uint4*>(s_dyn) + wave * A.stack_depth;
+    const uint32_t xy = A.slot_xy[slot];
+    const uint32_t px = xy & 0xFFFFu, py = xy >> 16;
+    const SlotSO so = A.slot_so[slot];
+    TraceCounters cnt = {0u, 0u, 0u, 0u};
+#pragma unroll 1
+    for (uint32_t c = 0; c < (A.spp >> 6); ++c) {  // wave-uniform trip count
+        const uint64_t idx = so.first + (uint64_t)(64u * c + (threadIdx.x & 63u)) * so.stride;
+        const float2 sm = A.samples[idx];
+        const Ray ray = cast_ray(S, F2(sm.x, sm.y), A.W, A.H, px, py);
+        float lightTMax = __builtin_inff();
+        for (uint32_t j = 0; j < S.num_lights; ++j) {
+            float lt = __builtin_inff();
+            light_bound<ENV, FM>(uniform_light(S, j), ray.o, ray.d, lt);  // only the bound: no radiance
+            if (lt < lightTMax) lightTMax = lt;
+        }
+        float bt;
+        uint32_t bg;
+        traverse_packet<COUNT>(S, ray, lightTMax, bt, bg, wstk, cnt);
+        hit[idx] = bg;
+    }
+    if (COUNT) {
+        atomicAdd(&A.counters[0], (unsigned long long)(A.spp >> 6));
         atomicAdd(&A.counters[2], (unsigned long long)cnt.nodes);
         atomicAdd(&A.counters[3], (unsigned long long)cnt.tris);
         atomicAdd(&A.counters[5], (unsigned long long)cnt.oc_checks);

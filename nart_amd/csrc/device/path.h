@@ -380,8 +380,9 @@ ND bool traverse(const DScene& S, const Ray& r, float tmax, bool ANY, float& bes
     return bestG != NO_HIT;
 }
 
-// Packet traversal of a wave's coherent closest-hit queries (k_primary: the camera rays of a 16x4
-// pixel block at one sample index).  The wave walks one node at a time (node index, lane mask and
+// Packet traversal of a wave's coherent closest-hit queries (the camera rays of 64 consecutive
+// samples of one pixel in k_primary_px, of a 16x4 pixel block at one sample index in k_primary).
+// The wave walks one node at a time (node index, lane mask and
 // stack wave-uniform: the node and triangle records are read once per wave, not once per lane);
 // each lane in the node's mask tests the node's child boxes against its own ray and cull
 // distance, and a child is entered with the mask of the lanes that hit it, nearer child first by

@@ -81,6 +81,7 @@ struct nart_ctx {
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ev[4]: after k_primary
     bool primary_ran = false;  // the last dispatch launched k_primary (ev[4] recorded)
     bool prim_valid = false;   // d_prim holds the current batch's camera-ray hits (first-hit AOVs)
+    bool rows_pixel_major = false;  // d_slot_so as last written: every slot's samples a contiguous row (stride 1)
     // around each pass of a batch after the beauty's splat (render_buckets; host/frame_plan.h PassKind)
     hipEvent_t ev_pass[N_PASSES][2] = {};
     // around the error and scatter kernels of an adaptive level (render_buckets_adaptive)
@@ -811,6 +812,21 @@ int schedule_pixel_queue(const PathLaunch& L, RenderArgs& b) {
 
 uint32_t lean_stack(const nart_ctx* ctx);
 
+// The camera rays of the batch in `pa` (pa.packet set) into ctx->d_prim.  Packets of one pixel's
+// samples (k_primary_px: 4 slots per block, one wave stack each) where the rows are pixel-major, spp
+// is a multiple of 64 and packet traversal is on; NART_PRIMARY_PIXEL=0 (a test hook: same hits) and
+// every other case: k_primary, a 16x4-pixel block per wave, the per-lane stacks' LDS.
+template <bool COUNT, bool ENV, uint32_t FM>
+void launch_primary(nart_ctx* ctx, const RenderArgs& pa, hipStream_t st) {
+    const bool pixel = pa.packet && ctx->rows_pixel_major && pa.spp % 64u == 0u && env_num("NART_PRIMARY_PIXEL", 1.0) != 0.0;
+    if (pixel)
+        hipLaunchKernelGGL((k_primary_px<COUNT, ENV, FM>), dim3((pa.n_slots + 3) / 4), dim3(256),
+                           (size_t)ctx->stack_depth * 4 * sizeof(uint4), st, ctx->scene, pa, ctx->d_prim);
+    else
+        hipLaunchKernelGGL((k_primary<COUNT, ENV, FM>), dim3((pa.n_slots + 255) / 256), dim3(256),
+                           (size_t)ctx->stack_depth * 256 * 8, st, ctx->scene, pa, ctx->d_prim);
+}
+
 // One batch of the path integrator: k_primary, what the plan's shape prepares, the path kernel.
 // The template parameters select kernel builds; host/path_schedule.h plan_path decides the rest.
 // resident_k: resident blocks of k_render (dispatch_megakernel's occupancy query).
@@ -860,8 +876,7 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, uint32_t resident_k, hi
     if (plan.primary) {
         RenderArgs pa = a;
         pa.packet = plan.packet;
-        hipLaunchKernelGGL((k_primary<COUNT, ENV, FM>), dim3((a.n_slots + 255) / 256), dim3(256),
-                           (size_t)ctx->stack_depth * 256 * 8, st, ctx->scene, pa, ctx->d_prim);
+        launch_primary<COUNT, ENV, FM>(ctx, pa, st);
         HIPCHK(hipGetLastError());
         if (ctx->events) {
             HIPCHK(hipEventRecord(ctx->ev[4], st));
@@ -1222,12 +1237,10 @@ struct PassTimes {
 int launch_aov_primary(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
     RenderArgs pa = a;
     pa.packet = env_num("NART_PRIMARY_PACKET", 1.0) != 0.0 ? 1u : 0u;
-    const size_t lds = (size_t)ctx->stack_depth * 256 * 8;
     const void* f = ctx->has_env ? (const void*)k_primary<false, true, FT_ALL> : (const void*)k_primary<false, false, FT_ALL>;
     HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    const dim3 grid((a.n_slots + 255) / 256), block(256);
-    if (ctx->has_env) hipLaunchKernelGGL((k_primary<false, true, FT_ALL>), grid, block, lds, st, ctx->scene, pa, ctx->d_prim);
-    else hipLaunchKernelGGL((k_primary<false, false, FT_ALL>), grid, block, lds, st, ctx->scene, pa, ctx->d_prim);
+    if (ctx->has_env) launch_primary<false, true, FT_ALL>(ctx, pa, st);
+    else launch_primary<false, false, FT_ALL>(ctx, pa, st);
     HIPCHK(hipGetLastError());
     ctx->prim_valid = true;
     return NART_OK;
@@ -1516,6 +1529,7 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         HIPCHK(hipMemcpyAsync(ctx->d_bucket_base, base.data(), (size_t)nbk * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_slot_table, dim3(nbk), dim3(256), 0, st, ctx->d_bucket_base, nbk, nslots, p->spp,
                            ctx->d_slot_so, plan.skew);
+        ctx->rows_pixel_major = plan.skew;
         const RenderArgs ra = make_render_args(ctx, p, g, nslots, ctx->d_counters);
         HIPCHK(hipEventRecord(ctx->ev[3], st));
         rc = launch_latin(ctx, ra, st);
@@ -2020,6 +2034,7 @@ int rect_slots(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t
     if (int rc = ensure(ctx, n, p->spp, 1)) return rc;
     HIPCHK(hipMemcpy(ctx->d_slot_xy, xy.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_slot_rows, dim3((n + 255) / 256), dim3(256), 0, 0, n, p->spp, ctx->d_slot_so);
+    ctx->rows_pixel_major = true;
     ra = make_render_args(ctx, p, g, n, counters);
     return NART_OK;
 }

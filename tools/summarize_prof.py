@@ -112,7 +112,8 @@ def main(src, tag, config="1920x1080x256"):
     dur = lambda k: out["kernels"][k].get("duration_ms_fetch_pass", 0.0)  # noqa: E731
     rq = sorted([k for k in out["kernels"] if timed(k, "k_render_rq")], key=dur, reverse=True)
     rq = rq or sorted([k for k in out["kernels"] if timed(k, "k_render_volume_sm")], key=dur, reverse=True)
-    pr = sorted([k for k in out["kernels"] if timed(k, "k_primary")], key=dur, reverse=True)
+    # (k_primary_px: the one-pixel-per-wave form of k_primary, the one whole frames run)
+    pr = sorted([k for k in out["kernels"] if timed(k, "k_primary") or timed(k, "k_primary_px")], key=dur, reverse=True)
     if rq and "hbm_bytes" in out["kernels"][rq[0]]:
         r = out["kernels"][rq[0]]
         out["render_kernel"] = rq[0]
