@@ -129,15 +129,16 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
     for (uint32_t d = 0; d < n; ++d) {
         ids[d] = shard_ids(g.n_buckets_x, nb, n, d);
         const size_t bytes = std::max<size_t>(1, ids[d].size()) * tile_floats * 4 * K;
-        if ((rc = ensure_dev(ctx, ctx->devs[d], ctx->sub_tiles[d], ctx->sub_cap[d], bytes, "device tiles"))) return rc;
+        if ((rc = reserve(ctx, ctx->sub_tiles[d], ctx->devs[d], bytes, "device tiles"))) return rc;
     }
     const int dev0 = ctx->devs[0];
     const size_t all_bytes = (size_t)nb * tile_floats * 4;
     const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
-    if ((rc = ensure_dev(ctx, dev0, ctx->d_gather, ctx->cap_gather, all_bytes * K, "gathered tiles")) ||
-        (rc = ensure_dev(ctx, dev0, ctx->d_byid, ctx->cap_byid, all_bytes, "tiles by bucket id")) ||
-        (rc = ensure_dev(ctx, dev0, ctx->d_image, ctx->cap_image, img_bytes, "image")))
+    if ((rc = reserve(ctx, ctx->d_gather, dev0, all_bytes * K, "gathered tiles")) ||
+        (rc = reserve(ctx, ctx->d_byid, dev0, all_bytes, "tiles by bucket id")) ||
+        (rc = reserve(ctx, ctx->d_image, dev0, img_bytes, "image")))
         return rc;
+    HIPCHK(hipSetDevice(dev0));
 
     // 1. every device renders its buckets (one host thread each, like the TBB task group)
     std::vector<int> rcs(n, NART_OK);
@@ -158,17 +159,17 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
             rcs[d] = NART_E_HIP;
             return;
         }
-        const FrameTiles out(plan, static_cast<float*>(ctx->sub_tiles[d]), ids[d].size() * tile_floats);
+        const FrameTiles out(plan, ctx->sub_tiles[d].as<float>(), ids[d].size() * tile_floats);
         if (rq.adaptive) {
             // the device refines its own shard: a bucket's error needs its own tiles only
             rcs[d] = render_buckets_adaptive(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(), out,
-                                             ctx->streams[d], &st[d], runs[d]);
+                                             ctx->streams[d].s, &st[d], runs[d]);
             pass[d] = runs[d].passes;
         } else {
-            rcs[d] = render_buckets(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(), out, ctx->streams[d],
+            rcs[d] = render_buckets(ctx->subs[d], p, ids[d].data(), (uint32_t)ids[d].size(), out, ctx->streams[d].s,
                                     &st[d], &pass[d]);
         }
-        if (rcs[d] == NART_OK && hipStreamSynchronize(ctx->streams[d]) != hipSuccess) rcs[d] = NART_E_HIP;
+        if (rcs[d] == NART_OK && hipStreamSynchronize(ctx->streams[d].s) != hipSuccess) rcs[d] = NART_E_HIP;
     };
     for (uint32_t d = 0; d < n; ++d) std::memset(&st[d], 0, sizeof(st[d]));
     try {
@@ -203,8 +204,8 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
     // 2. gather the slabs to device 0 (rank order), RCCL over xGMI or device copies
     std::vector<size_t> first_b(n, 0);
     for (uint32_t d = 1; d < n; ++d) first_b[d] = first_b[d - 1] + ids[d - 1].size();
-    float* slabs = static_cast<float*>(ctx->d_gather);
-    hipStream_t s0 = ctx->streams[0];
+    float* slabs = ctx->d_gather.as<float>();
+    hipStream_t s0 = ctx->streams[0].s;
     if (ctx->gather_rccl) {
         // every error inside the group is recorded and the group is always closed (an open group
         // would capture the next render's calls); a failed gather leaves the communicator in an
@@ -230,8 +231,8 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
                 for (uint32_t d = 0; d < n; ++d) {
                     if (ids[d].empty()) continue;
                     const size_t cnt = ids[d].size() * tile_floats;
-                    note(R.Send(static_cast<const float*>(ctx->sub_tiles[d]) + i * cnt, cnt, ncclFloat32,
-                                d == last ? bad_peer : 0, ctx->comms[d], ctx->streams[d]),
+                    note(R.Send(ctx->sub_tiles[d].as<const float>() + i * cnt, cnt, ncclFloat32,
+                                d == last ? bad_peer : 0, ctx->comms[d], ctx->streams[d].s),
                          "ncclSend");
                     note(R.Recv(slabs + (i * nb + first_b[d]) * tile_floats, cnt, ncclFloat32, (int)d, ctx->comms[0], s0),
                          "ncclRecv");
@@ -243,7 +244,7 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
             ctx->rccl_broken = true;
             for (uint32_t d = 0; d < n; ++d) {
                 hipSetDevice(ctx->devs[d]);
-                hipStreamSynchronize(ctx->streams[d]);
+                hipStreamSynchronize(ctx->streams[d].s);
             }
             (void)hipGetLastError();
             return fail(ctx, NART_E_RCCL, where + ": " + R.ErrStr(first) +
@@ -251,7 +252,7 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
         }
         for (uint32_t d = 1; d < n; ++d) {
             HIPCHK(hipSetDevice(ctx->devs[d]));
-            HIPCHK(hipStreamSynchronize(ctx->streams[d]));
+            HIPCHK(hipStreamSynchronize(ctx->streams[d].s));
         }
         HIPCHK(hipSetDevice(dev0));
     } else {
@@ -260,7 +261,7 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
             for (uint32_t d = 0; d < n; ++d)
                 if (!ids[d].empty())
                     HIPCHK(hipMemcpyPeerAsync(slabs + (i * nb + first_b[d]) * tile_floats, dev0,
-                                              static_cast<const float*>(ctx->sub_tiles[d]) + i * ids[d].size() * tile_floats,
+                                              ctx->sub_tiles[d].as<const float>() + i * ids[d].size() * tile_floats,
                                               ctx->devs[d], ids[d].size() * tile_floats * 4, s0));
     }
 
@@ -268,23 +269,22 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
     std::vector<uint32_t> map;
     map.reserve(nb);
     for (uint32_t d = 0; d < n; ++d) map.insert(map.end(), ids[d].begin(), ids[d].end());
-    if ((rc = ensure_dev(ctx, dev0, ctx->d_slab_map, ctx->cap_slab_map, (size_t)nb * 4, "slab map"))) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_slab_map, map.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s0));
+    if ((rc = reserve(ctx, ctx->d_slab_map, dev0, (size_t)nb * 4, "slab map"))) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_slab_map.as<uint32_t>(), map.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s0));
     // (stream order lets the buffers share d_byid and d_image)
     for (size_t i = 0; i < K; ++i) {
         if (!rq.on_device && !rq.dst[i]) continue;  // rendered for another output's sake, not delivered
         hipLaunchKernelGGL(k_unshard, dim3(nb), dim3(256), 0, s0, slabs + i * nb * tile_floats,
-                           static_cast<float*>(ctx->d_byid), static_cast<const uint32_t*>(ctx->d_slab_map), nb,
+                           ctx->d_byid.as<float>(), ctx->d_slab_map.as<const uint32_t>(), nb,
                            (uint32_t)tile_floats);
         HIPCHK(hipGetLastError());
-        if ((rc = nart_hip_combine_async(ctx->subs[0], p, static_cast<const nart_pixel*>(ctx->d_byid),
-                                         static_cast<nart_pixel*>(ctx->d_image), s0)))
+        if ((rc = nart_hip_combine_async(ctx->subs[0], p, ctx->d_byid.as<const nart_pixel>(),
+                                         ctx->d_image.as<nart_pixel>(), s0)))
             return fail(ctx, rc, ctx->subs[0]->err);
         // output i: to its host image, or to image i of the borrowed device buffer
-        void* dst = rq.on_device ? static_cast<char*>(*rq.image) + i * img_bytes
-                                 : static_cast<void*>(rq.dst[i]);
-        if (dst != ctx->d_image)
-            HIPCHK(hipMemcpyAsync(dst, ctx->d_image, img_bytes,
+        void* dst = rq.on_device ? rq.image->as<char>() + i * img_bytes : static_cast<void*>(rq.dst[i]);
+        if (dst != ctx->d_image.as<void>())
+            HIPCHK(hipMemcpyAsync(dst, ctx->d_image.as<void>(), img_bytes,
                                   rq.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s0));
     }
     HIPCHK(hipStreamSynchronize(s0));

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/nart_hip.h"
@@ -23,10 +24,37 @@
 #include "device/matte.h"
 #include "device/volume.h"
 #include "host/bvh_build.h"
+#include "host/device_buf.h"
 #include "host/frame_plan.h"
 #include "host/path_schedule.h"
 
 using namespace nd;
+
+// The HIP backend of host/device_buf.h: the only calls that allocate or free device memory and events.
+struct HipBackend {
+    using event_t = hipEvent_t;
+    static int malloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static int free(void* p) { return hipFree(p); }
+    static int get_device(int* d) { return hipGetDevice(d); }
+    static int set_device(int d) { return hipSetDevice(d); }
+    static int event_create(event_t* e) { return hipEventCreate(e); }
+    static int event_destroy(event_t e) { return hipEventDestroy(e); }
+};
+using Buf = DevBuf<HipBackend>;
+using Event = DevEvent<HipBackend>;
+
+// A stream of a multi-device context, destroyed with its device current.
+struct Stream {
+    hipStream_t s = nullptr;
+    int device = 0;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s(std::exchange(o.s, nullptr)), device(o.device) {}
+    ~Stream() {
+        if (!s) return;
+        OnDevice<HipBackend> on(device);
+        hipStreamDestroy(s);
+    }
+};
 
 struct nart_ctx {
     int device = 0;
@@ -44,82 +72,59 @@ struct nart_ctx {
     uint32_t fm_used = FT_ALL;   // the feature mask of the last path-kernel build launched
     bool lean = true;            // the three-waves-per-SIMD build where it fits (lean_fits)
     // scene buffers
-    void* d_nodes = nullptr;
-    void* d_tri_isect = nullptr;
-    void* d_tri_perm = nullptr;
-    void* d_tris = nullptr;
-    void* d_tri_mesh = nullptr;
-    void* d_meshes = nullptr;
-    void* d_mesh_eta = nullptr;  // DScene::mesh_eta
-    void* d_mats = nullptr;
-    void* d_lights = nullptr;
-    void* d_texs = nullptr;
-    void* d_tex_pool = nullptr;
-    void* d_envs = nullptr;
-    void* d_density = nullptr;
-    void* d_oc_nodes = nullptr;   // reference octree (octree.h)
-    void* d_oc_chunks = nullptr;
-    void* d_oc_tris = nullptr;
-    void* d_tri_leaf = nullptr;
-    void* d_oc_lock = nullptr;    // replay heap pool
-    void* d_oc_heap = nullptr;
-    std::vector<void*> env_bufs;  // Piecewise2DDistribution tables
-    // work buffers
-    size_t cap_slot_bytes = 0, cap_misc = 0;
-    uint32_t* d_slot_xy = nullptr;
-    SlotSO* d_slot_so = nullptr;  // [slot] {first sample index, sample stride} (RenderArgs::slot_so)
-    uint32_t* d_rng = nullptr;
-    float2* d_samples = nullptr;
-    float4* d_L = nullptr;
-    uint32_t* d_prim = nullptr;  // camera-ray hits per sample (k_primary), same indexing as d_samples
-    uint32_t* d_bucket_ids = nullptr;
-    uint32_t* d_bucket_base = nullptr;
-    float* d_table = nullptr;
-    void* d_lut = nullptr;       // splat filter-weight cells (splat_lut)
-    unsigned long long* d_counters = nullptr;
+    Buf d_nodes, d_tri_isect, d_tri_perm, d_tris, d_tri_mesh, d_meshes;
+    Buf d_mesh_eta;  // DScene::mesh_eta
+    Buf d_mats, d_lights, d_texs, d_tex_pool, d_envs, d_density;
+    Buf d_oc_nodes, d_oc_chunks, d_oc_tris, d_tri_leaf;  // reference octree (octree.h)
+    Buf d_oc_lock, d_oc_heap;                            // replay heap pool
+    std::vector<Buf> env_bufs;                           // Piecewise2DDistribution tables
+    // work buffers of a batch, in three groups that each share a capacity counted in slots, samples
+    // and buckets (ensure)
+    Buf d_slot_xy;  // uint32_t
+    Buf d_slot_so;  // SlotSO [slot] {first sample index, sample stride} (RenderArgs::slot_so)
+    Buf d_rng;      // uint32_t
+    Buf d_samples;  // float2
+    Buf d_L;        // float4
+    Buf d_prim;     // uint32_t camera-ray hits per sample (k_primary), same indexing as d_samples
+    Buf d_bucket_ids, d_bucket_base;  // uint32_t
     size_t cap_slots = 0, cap_samples = 0, cap_buckets = 0;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ev[4]: after k_primary
-    bool primary_ran = false;  // the last dispatch launched k_primary (ev[4] recorded)
+    Buf d_table;     // float filter table and thresholds (plan_splat)
+    Buf d_lut;       // splat filter-weight cells (splat_lut)
+    Buf d_counters;  // unsigned long long (counter_buffer)
+    // around a batch's kernels (render_buckets); ev_primary is recorded by launch_render
+    Event ev_latin0, ev_path0, ev_primary, ev_path1, ev_splat1;
+    bool primary_ran = false;  // the last dispatch launched k_primary (ev_primary recorded)
     bool prim_valid = false;   // d_prim holds the current batch's camera-ray hits (first-hit AOVs)
     bool rows_pixel_major = false;  // d_slot_so as last written: every slot's samples a contiguous row (stride 1)
     // around each pass of a batch after the beauty's splat (render_buckets; host/frame_plan.h PassKind)
-    hipEvent_t ev_pass[N_PASSES][2] = {};
+    Event ev_pass[N_PASSES][2];
     // around the error and scatter kernels of an adaptive level (render_buckets_adaptive)
-    hipEvent_t ev_ad[2] = {nullptr, nullptr};
+    Event ev_ad[2];
     // around the cascade's reweighting (cascade_device) and the mattes' ranking (matte_rank_device)
-    hipEvent_t ev_cas[2] = {nullptr, nullptr}, ev_mat[2] = {nullptr, nullptr};
+    Event ev_cas[2], ev_mat[2];
     double cas_ms[2] = {0.0, 0.0};  // the last cascade call's times: split + layer splats, reweighting
     double mat_ms[2] = {0.0, 0.0};  // the last matte call's times: plane passes, ranking
     uint32_t num_meshes = 0, num_materials = 0;  // the scene's: the id counts of the two matte kinds
     // denoiser (denoise_device): work buffers over the cropped image, the four device images of
     // nart_hip_denoise / nart_hip_render_denoised (five with the moment image), events between its
     // kernels, the last run's times
-    void *d_dn = nullptr, *d_dn_img = nullptr;
-    size_t cap_dn = 0, cap_dn_img = 0;
-    hipEvent_t ev_dn[12] = {};
+    Buf d_dn, d_dn_img;
+    Event ev_dn[12];
     double dn_ms[11] = {};  // prepare, variance, passes 0..7, finalise
     uint32_t sched = 0;        // NART_SCHED_* bits of the current render (nart_render_stats::schedule)
-    bool events = false;
-    // path-kernel scheduling buffers (ensure_queue, ensure_ilist, ensure_gstack; launch_render, dispatch_volume)
-    uint32_t* d_queue = nullptr;
-    uint32_t* d_cost = nullptr;
-    void* d_ilist = nullptr;   // dielectric-list columns beyond ILIST_REG (bounces > ILIST_REG)
-    size_t cap_ilist = 0;
-    void* d_gstack = nullptr;  // lean build: traversal-stack levels beyond the LDS (RenderArgs::gstack)
-    size_t cap_gstack = 0;
-    uint32_t* d_keys[2] = {nullptr, nullptr};
-    uint32_t* d_vals[2] = {nullptr, nullptr};
-    uint32_t* d_qhead = nullptr;
-    void* d_sort_tmp = nullptr;
-    size_t cap_sort_tmp = 0;
-    uint32_t cap_queue = 0;
+    // path-kernel scheduling buffers (ensure_queue, ensure_ilist, ensure_gstack; launch_render,
+    // dispatch_volume): the queue group shares a capacity counted in queue entries
+    Buf d_queue, d_cost, d_keys[2], d_vals[2], d_qhead;  // uint32_t
+    Buf d_sort_tmp;
+    size_t cap_queue = 0;
+    Buf d_ilist;   // dielectric-list columns beyond ILIST_REG (bounces > ILIST_REG)
+    Buf d_gstack;  // lean build: traversal-stack levels beyond the LDS (RenderArgs::gstack)
     // multi-device context (nart_hip_create_multi, host/multi_gpu.h): one single-device
     // sub-context per listed device; device 0 gathers and combines
     std::vector<nart_ctx*> subs;
     std::vector<int> devs;
-    std::vector<hipStream_t> streams;
-    std::vector<void*> sub_tiles;
-    std::vector<size_t> sub_cap;
+    std::vector<Stream> streams;
+    std::vector<Buf> sub_tiles;
     std::vector<ncclComm_t> comms;
     bool gather_rccl = false;
     // RCCL requested implicitly (distinct devices) but unavailable: device-copy gather instead
@@ -135,8 +140,8 @@ struct nart_ctx {
     uint32_t num_leaf_tris = 0;
     int32_t root_code = -1;  // the traversal's root (DScene::root), kept for nart_hip_context_bvh_dump
     float bvh_pad = 0.f;     // what the child boxes were grown by
-    void *d_gather = nullptr, *d_byid = nullptr, *d_image = nullptr, *d_slab_map = nullptr;
-    size_t cap_gather = 0, cap_byid = 0, cap_image = 0, cap_slab_map = 0;
+    // whole frames (render_frame, render_multi): gathered tiles, tiles by bucket id, image, slab map
+    Buf d_gather, d_byid, d_image, d_slab_map;
 };
 
 namespace {
@@ -167,11 +172,35 @@ double env_num(const char* name, double def) {
     return e && *e ? std::atof(e) : def;
 }
 
+// The one way a device buffer of a context or a call grows: `buf` holds at least `bytes` on `device`
+// afterwards (DevBuf::reserve: only grows, frees before it allocates, empty after a failure).  A
+// failed allocation leaves no sticky error behind, so that the next render's hipGetLastError() does
+// not report it and the context renders normally afterwards.
+int reserve(nart_ctx* ctx, Buf& buf, int device, size_t bytes, const char* what) {
+    const hipError_t e = (hipError_t)buf.reserve(device, bytes);
+    if (e == hipSuccess) return NART_OK;
+    (void)hipGetLastError();
+    return fail(ctx, e == hipErrorOutOfMemory ? NART_E_OOM : NART_E_HIP,
+                std::string("hipMalloc ") + what + " (" + std::to_string(bytes) + " B): " + hipGetErrorString(e));
+}
+// The same for a group of the context's buffers that shares the capacity `cap` (reserve_group).
+int reserve(nart_ctx* ctx, size_t& cap, size_t count, std::initializer_list<GroupItem<HipBackend>> items) {
+    return reserve_group(cap, count, items, [ctx](Buf& buf, size_t bytes, const char* what) {
+        return reserve(ctx, buf, ctx->device, bytes, what);
+    });
+}
+
+// `e` recorded on `st`, created on its first use.
+hipError_t record(Event& e, hipStream_t st) {
+    hipEvent_t h = nullptr;
+    const int err = e.get(&h);
+    return err ? (hipError_t)err : hipEventRecord(h, st);
+}
+
 template <typename T>
-int upload(nart_ctx* ctx, void*& dst, const T* src, size_t count) {
-    size_t bytes = sizeof(T) * (count ? count : 1);
-    HIPCHK(hipMalloc(&dst, bytes));
-    if (count) HIPCHK(hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
+int upload(nart_ctx* ctx, Buf& dst, const T* src, size_t count, const char* what) {
+    if (int rc = reserve(ctx, dst, ctx->device, sizeof(T) * (count ? count : 1), what)) return rc;
+    if (count) HIPCHK(hipMemcpy(dst.as<T>(), src, sizeof(T) * count, hipMemcpyHostToDevice));
     return NART_OK;
 }
 
@@ -325,32 +354,24 @@ int build_env(nart_ctx* ctx, const nart_texture& t, DEnvDist& d) {
     std::vector<uint32_t> mguide(K), cguide((size_t)K * H);
     bool guided = W <= 65535 && H <= 65535 && guide(mcdf.data(), H, mguide.data());
     for (uint32_t j = 0; guided && j < H; ++j) guided = guide(ccdf.data() + (size_t)j * (W + 1), W, cguide.data() + (size_t)j * K);
-    void* bufs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const std::vector<float>* src[4] = {&mpdf, &cpdf, &mcdf, &ccdf};
-    for (int k = 0; k < 4; ++k) {
-        int rc = upload(ctx, bufs[k], src[k]->data(), src[k]->size());
-        if (bufs[k]) ctx->env_bufs.push_back(bufs[k]);
-        if (rc) return rc;
-    }
-    if (guided) {
-        for (int k = 4; k < 6; ++k) {
-            const std::vector<uint32_t>& g = k == 4 ? mguide : cguide;
-            int rc = upload(ctx, bufs[k], g.data(), g.size());
-            if (bufs[k]) ctx->env_bufs.push_back(bufs[k]);
-            if (rc) return rc;
-        }
-    }
-    d.mguide = (const uint32_t*)bufs[4];
-    d.cguide = (const uint32_t*)bufs[5];
+    // each table into a buffer of its own, kept by the context
+    int rc = NART_OK;
+    auto table = [&](const auto& v, const char* what) {
+        ctx->env_bufs.emplace_back();
+        if (!rc) rc = upload(ctx, ctx->env_bufs.back(), v.data(), v.size(), what);
+        return ctx->env_bufs.back().as<std::remove_reference_t<decltype(v[0])>>();  // const float / uint32_t
+    };
+    d.mpdf = table(mpdf, "environment row pdf");
+    d.cpdf = table(cpdf, "environment column pdfs");
+    d.mcdf = table(mcdf, "environment row cdf");
+    d.ccdf = table(ccdf, "environment column cdfs");
+    d.mguide = guided ? table(mguide, "environment row guide") : nullptr;
+    d.cguide = guided ? table(cguide, "environment column guides") : nullptr;
     d.w = W;
     d.h = H;
     d.invW = invW;
     d.invH = invH;
-    d.mpdf = (const float*)bufs[0];
-    d.cpdf = (const float*)bufs[1];
-    d.mcdf = (const float*)bufs[2];
-    d.ccdf = (const float*)bufs[3];
-    return NART_OK;
+    return rc;
 }
 
 // Camera medium: density grid upload + the width-1 MajorantGrid (media.cpp:47-130) on the host.
@@ -405,8 +426,8 @@ int build_medium(nart_ctx* ctx, const nart_medium& bm, DMedium& m) {
         m.grid2 = 1;
         for (int i = 0; i < 8; ++i) m.dens8[i] = bm.density[i];
     }
-    int rc = upload(ctx, ctx->d_density, bm.density, npts);
-    m.density = (const float*)ctx->d_density;
+    int rc = upload(ctx, ctx->d_density, bm.density, npts, "density grid");
+    m.density = ctx->d_density.as<const float>();
     return rc;
 }
 
@@ -452,108 +473,61 @@ size_t batch_slot_limit(const nart_ctx* ctx, uint32_t spp, size_t extra_per_samp
     return n < 256 ? 256 : n;
 }
 
-// hipMalloc that leaves no sticky error behind: a failed allocation must not make the next
-// render's hipGetLastError() report it.
-int dmalloc(nart_ctx* ctx, void** p, size_t bytes, const char* what) {
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) return NART_OK;
-    *p = nullptr;
-    (void)hipGetLastError();
-    return fail(ctx, e == hipErrorOutOfMemory ? NART_E_OOM : NART_E_HIP,
-                std::string("hipMalloc ") + what + " (" + std::to_string(bytes) + " B): " + hipGetErrorString(e));
-}
-
-// A buffer on device `dev` that only grows: at least `bytes`, its capacity reset before it is freed.
-int ensure_dev(nart_ctx* ctx, int dev, void*& buf, size_t& cap, size_t bytes, const char* what) {
-    if (bytes <= cap) return NART_OK;
-    HIPCHK(hipSetDevice(dev));
-    if (buf) hipFree(buf);
-    buf = nullptr;
-    cap = 0;
-    if (int rc = dmalloc(ctx, &buf, bytes, what)) return rc;
-    cap = bytes;
-    return NART_OK;
-}
-
-// Work buffers for a batch.  Each group's capacity is reset before its buffers are freed, so a
-// failed allocation leaves a state in which the next call allocates again (never a stale
-// capacity over null buffers).
+// Work buffers for a batch: three groups, each sharing a capacity counted in slots, samples and
+// buckets (batch_slot_limit reads cap_samples).
 int ensure(nart_ctx* ctx, size_t slots, uint32_t spp, size_t buckets) {
     const size_t samples = slots * spp;
-    int rc = NART_OK;
-    if (slots > ctx->cap_slots) {
-        ctx->cap_slots = 0;
-        for (void** b : {(void**)&ctx->d_slot_xy, (void**)&ctx->d_rng, (void**)&ctx->d_slot_so}) {
-            if (*b) hipFree(*b);
-            *b = nullptr;
-        }
-        if ((rc = dmalloc(ctx, (void**)&ctx->d_slot_xy, slots * 4, "slot pixels")) ||
-            (rc = dmalloc(ctx, (void**)&ctx->d_slot_so, slots * sizeof(SlotSO), "slot sample table")) ||
-            (rc = dmalloc(ctx, (void**)&ctx->d_rng, slots * 4, "slot RNG states")))
-            return rc;
-        ctx->cap_slots = slots;
-    }
-    if (samples > ctx->cap_samples) {
-        ctx->cap_samples = 0;
-        for (void** b : {(void**)&ctx->d_samples, (void**)&ctx->d_L, (void**)&ctx->d_prim}) {
-            if (*b) hipFree(*b);
-            *b = nullptr;
-        }
-        if ((rc = dmalloc(ctx, (void**)&ctx->d_samples, samples * sizeof(float2), "LatinSquare samples")) ||
-            (rc = dmalloc(ctx, (void**)&ctx->d_L, samples * sizeof(float4), "per-sample radiance")) ||
-            (rc = dmalloc(ctx, (void**)&ctx->d_prim, samples * sizeof(uint32_t), "camera-ray hits")))
-            return rc;
-        ctx->cap_samples = samples;
-    }
-    if (buckets > ctx->cap_buckets) {
-        ctx->cap_buckets = 0;
-        for (void** b : {(void**)&ctx->d_bucket_ids, (void**)&ctx->d_bucket_base}) {
-            if (*b) hipFree(*b);
-            *b = nullptr;
-        }
-        if ((rc = dmalloc(ctx, (void**)&ctx->d_bucket_ids, buckets * 4, "bucket ids")) ||
-            (rc = dmalloc(ctx, (void**)&ctx->d_bucket_base, buckets * 4, "bucket bases")))
-            return rc;
-        ctx->cap_buckets = buckets;
-    }
-    return NART_OK;
+    int rc = reserve(ctx, ctx->cap_slots, slots, {{&ctx->d_slot_xy, slots * 4, "slot pixels"},
+                                                  {&ctx->d_slot_so, slots * sizeof(SlotSO), "slot sample table"},
+                                                  {&ctx->d_rng, slots * 4, "slot RNG states"}});
+    if (!rc)
+        rc = reserve(ctx, ctx->cap_samples, samples, {{&ctx->d_samples, samples * sizeof(float2), "LatinSquare samples"},
+                                                      {&ctx->d_L, samples * sizeof(float4), "per-sample radiance"},
+                                                      {&ctx->d_prim, samples * sizeof(uint32_t), "camera-ray hits"}});
+    if (!rc)
+        rc = reserve(ctx, ctx->cap_buckets, buckets, {{&ctx->d_bucket_ids, buckets * 4, "bucket ids"},
+                                                      {&ctx->d_bucket_base, buckets * 4, "bucket bases"}});
+    return rc;
 }
 
-// Work-queue buffers of the megakernel scheduler (queue, cost probe, radix-sort scratch).
+// The queue group as the scheduling steps and their kernels take it.
+struct QueueBufs {
+    uint32_t *queue, *cost, *keys[2], *vals[2], *qhead;
+    void* sort_tmp;
+    size_t sort_bytes;
+    explicit QueueBufs(const nart_ctx* c)
+        : queue(c->d_queue.as<uint32_t>()), cost(c->d_cost.as<uint32_t>()),
+          keys{c->d_keys[0].as<uint32_t>(), c->d_keys[1].as<uint32_t>()},
+          vals{c->d_vals[0].as<uint32_t>(), c->d_vals[1].as<uint32_t>()}, qhead(c->d_qhead.as<uint32_t>()),
+          sort_tmp(c->d_sort_tmp.as<void>()), sort_bytes(c->d_sort_tmp.bytes()) {}
+};
+
+// Work-queue buffers of the megakernel scheduler (queue, cost probe, radix-sort scratch): one group
+// of capacity n queue entries, complete once the sort scratch (sized from the others) is allocated.
 int ensure_queue(nart_ctx* ctx, uint32_t n) {
     if (n <= ctx->cap_queue) return NART_OK;
-    void** bufs[7] = {(void**)&ctx->d_queue, (void**)&ctx->d_cost, (void**)&ctx->d_keys[0], (void**)&ctx->d_keys[1],
-                      (void**)&ctx->d_vals[0], (void**)&ctx->d_vals[1], (void**)&ctx->d_qhead};
-    for (void** b : bufs) {
-        if (*b) hipFree(*b);
-        *b = nullptr;
-    }
-    if (ctx->d_sort_tmp) hipFree(ctx->d_sort_tmp);
-    ctx->d_sort_tmp = nullptr;
     ctx->cap_queue = 0;
-    for (int i = 0; i < 6; ++i) HIPCHK(hipMalloc(bufs[i], (size_t)n * 4));
-    HIPCHK(hipMalloc(bufs[6], 256));
-    size_t tmp = 0, t1 = 0, t2 = 0;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, ctx->d_keys[0], ctx->d_keys[1], ctx->d_vals[0],
-                                              ctx->d_vals[1], (int)n, 0, 1));
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, t2, ctx->d_keys[0], ctx->d_keys[1], ctx->d_vals[0],
-                                              ctx->d_vals[1], (int)((n + 63) / 64), 0, 32));
-    tmp = std::max(t1, t2);
-    HIPCHK(hipMalloc(&ctx->d_sort_tmp, tmp + 256));
-    ctx->cap_sort_tmp = tmp + 256;
+    ctx->d_sort_tmp.release();
+    const size_t words = (size_t)n * 4;
+    size_t cap = 0;
+    if (int rc = reserve(ctx, cap, n, {{&ctx->d_queue, words, "work queue"}, {&ctx->d_cost, words, "probe costs"},
+                                       {&ctx->d_keys[0], words, "sort keys"}, {&ctx->d_keys[1], words, "sort keys"},
+                                       {&ctx->d_vals[0], words, "sort values"}, {&ctx->d_vals[1], words, "sort values"},
+                                       {&ctx->d_qhead, 256, "queue head"}}))
+        return rc;
+    const QueueBufs q(ctx);
+    size_t t1 = 0, t2 = 0;
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, q.keys[0], q.keys[1], q.vals[0], q.vals[1], (int)n, 0, 1));
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, t2, q.keys[0], q.keys[1], q.vals[0], q.vals[1],
+                                              (int)((n + 63) / 64), 0, 32));
+    if (int rc = reserve(ctx, ctx->d_sort_tmp, ctx->device, std::max(t1, t2) + 256, "sort scratch")) return rc;
     ctx->cap_queue = n;
     return NART_OK;
 }
 
-// Grow-only per-thread columns of the path kernels (capacity reset before the free, as in ensure).
-int grow(nart_ctx* ctx, void*& p, size_t& cap, size_t bytes, const char* what) {
-    if (bytes <= cap) return NART_OK;
-    cap = 0;
-    if (p) HIPCHK(hipFree(p));
-    p = nullptr;
-    const int rc = dmalloc(ctx, &p, bytes, what);
-    if (!rc) cap = bytes;
-    return rc;
+// The work counters of the path kernels (nart_hip_set_counters), allocated by a context's first render.
+int counter_buffer(nart_ctx* ctx) {
+    return reserve(ctx, ctx->d_counters, ctx->device, 24 * sizeof(unsigned long long), "work counters");
 }
 
 // The dielectric list's entries beyond ILIST_REG (bounces > ILIST_REG): one column per thread of
@@ -561,15 +535,16 @@ int grow(nart_ctx* ctx, void*& p, size_t& cap, size_t bytes, const char* what) {
 int ensure_ilist(nart_ctx* ctx, RenderArgs& a) {
     const size_t lanes = ((size_t)a.n_slots + 511) / 512 * 512;
     a.ilist_stride = (uint32_t)lanes;
-    const int rc = grow(ctx, ctx->d_ilist, ctx->cap_ilist, lanes * (ILIST_MAX - ILIST_REG) * sizeof(uint2), "dielectric lists");
-    a.ilist_ext = static_cast<uint2*>(ctx->d_ilist);
+    const size_t bytes = lanes * (ILIST_MAX - ILIST_REG) * sizeof(uint2);
+    const int rc = reserve(ctx, ctx->d_ilist, ctx->device, bytes, "dielectric lists");
+    a.ilist_ext = ctx->d_ilist.as<uint2>();
     return rc;
 }
 
 // The lean build's traversal-stack levels beyond the LDS: `levels` entries per launched thread.
 int ensure_gstack(nart_ctx* ctx, size_t threads, uint32_t levels, RenderArgs& a) {
-    const int rc = grow(ctx, ctx->d_gstack, ctx->cap_gstack, threads * levels * sizeof(int2), "traversal stack columns");
-    a.gstack = static_cast<int2*>(ctx->d_gstack);
+    const int rc = reserve(ctx, ctx->d_gstack, ctx->device, threads * levels * sizeof(int2), "traversal stack columns");
+    a.gstack = ctx->d_gstack.as<int2>();
     return rc;
 }
 
@@ -692,13 +667,14 @@ __global__ void k_iota(uint32_t* v, uint32_t n) {
 // costliest group first (ties keep slot order): group ids into ctx->d_vals[1], keys into d_keys[1];
 // with `out`, their pixel list too.
 int sort_groups_by_cost(nart_ctx* ctx, uint32_t n, uint32_t per, uint32_t* out, hipStream_t st) {
+    const QueueBufs q(ctx);
     const uint32_t ng = (n + 63) / 64;
-    hipLaunchKernelGGL(k_group_keys, dim3((ng + 255) / 256), dim3(256), 0, st, ctx->d_cost, n, ctx->d_keys[0],
-                       ctx->d_vals[0], per);
-    size_t tmp = ctx->cap_sort_tmp;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->d_sort_tmp, tmp, ctx->d_keys[0], ctx->d_keys[1], ctx->d_vals[0],
-                                              ctx->d_vals[1], (int)ng, 0, 32, st));
-    if (out) hipLaunchKernelGGL(k_expand_groups, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_vals[1], n, out);
+    hipLaunchKernelGGL(k_group_keys, dim3((ng + 255) / 256), dim3(256), 0, st, q.cost, n, q.keys[0],
+                       q.vals[0], per);
+    size_t tmp = q.sort_bytes;
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(q.sort_tmp, tmp, q.keys[0], q.keys[1], q.vals[0],
+                                              q.vals[1], (int)ng, 0, 32, st));
+    if (out) hipLaunchKernelGGL(k_expand_groups, dim3((n + 255) / 256), dim3(256), 0, st, q.vals[1], n, out);
     HIPCHK(hipGetLastError());
     return NART_OK;
 }
@@ -749,7 +725,7 @@ int run_probe(const PathLaunch& L) {
     nart_ctx* ctx = L.ctx;
     RenderArgs pb = L.args;
     pb.spp = 1;
-    pb.cost = ctx->d_cost;
+    pb.cost = ctx->d_cost.as<uint32_t>();
     pb.probe_sub = L.plan.probe == PathProbe::Sampled ? L.plan.probe_sub : 0u;
     hipLaunchKernelGGL(L.probe, dim3(L.plan.probe_blocks), dim3(256), L.lds, L.st, ctx->scene, pb);
     HIPCHK(hipGetLastError());
@@ -759,22 +735,23 @@ int run_probe(const PathLaunch& L) {
 // Groups: the persistent grid's waves take 64-slot groups from b.ghead, in slot order or in b.gorder.
 int schedule_groups(const PathLaunch& L, RenderArgs& b) {
     nart_ctx* ctx = L.ctx;
+    const QueueBufs q(ctx);
     const PathSchedule& plan = L.plan;
-    HIPCHK(hipMemsetAsync(ctx->d_qhead, 0, sizeof(uint32_t), L.st));
-    b.ghead = ctx->d_qhead;
+    HIPCHK(hipMemsetAsync(q.qhead, 0, sizeof(uint32_t), L.st));
+    b.ghead = q.qhead;
     if (plan.probe == PathProbe::None) return NART_OK;
     const uint32_t ng = (b.n_slots + 63) / 64;
     int rc = run_probe(L);
     if (!rc) rc = sort_groups_by_cost(ctx, b.n_slots, plan.probe_sub, nullptr, L.st);
     if (rc) return rc;
-    b.gorder = ctx->d_vals[1];
+    b.gorder = q.vals[1];
     if (plan.order == 2) {  // the E costliest groups first, each class in slot order
-        hipLaunchKernelGGL(k_group_class, dim3((ng + 255) / 256), dim3(256), 0, L.st, ctx->d_vals[1], ng, plan.E,
-                           ctx->d_keys[0], ctx->d_vals[0]);
-        size_t tmp = ctx->cap_sort_tmp;
-        HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->d_sort_tmp, tmp, ctx->d_keys[0], ctx->d_keys[1], ctx->d_vals[0],
-                                                  ctx->d_queue, (int)ng, 0, 1, L.st));
-        b.gorder = ctx->d_queue;
+        hipLaunchKernelGGL(k_group_class, dim3((ng + 255) / 256), dim3(256), 0, L.st, q.vals[1], ng, plan.E,
+                           q.keys[0], q.vals[0]);
+        size_t tmp = q.sort_bytes;
+        HIPCHK(hipcub::DeviceRadixSort::SortPairs(q.sort_tmp, tmp, q.keys[0], q.keys[1], q.vals[0],
+                                                  q.queue, (int)ng, 0, 1, L.st));
+        b.gorder = q.queue;
     }
     return NART_OK;
 }
@@ -783,29 +760,30 @@ int schedule_groups(const PathLaunch& L, RenderArgs& b) {
 // WholeGroupsByCost: one lane per pixel, the groups launched costliest first.
 int schedule_pixel_queue(const PathLaunch& L, RenderArgs& b) {
     nart_ctx* ctx = L.ctx;
+    const QueueBufs q(ctx);
     const PathSchedule& plan = L.plan;
     const uint32_t n = b.n_slots;
     const bool whole = plan.shape == PathShape::WholeGroupsByCost;
     const dim3 eg((n + 255) / 256), block(256);
     int rc = run_probe(L);
-    if (!rc) rc = sort_groups_by_cost(ctx, n, 64, whole ? ctx->d_queue : ctx->d_cost, L.st);
-    b.queue = ctx->d_queue;
+    if (!rc) rc = sort_groups_by_cost(ctx, n, 64, whole ? q.queue : q.cost, L.st);
+    b.queue = q.queue;
     if (rc || whole) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_vals[1], ctx->d_cost, (size_t)n * 4, hipMemcpyDeviceToDevice, L.st));
+    HIPCHK(hipMemcpyAsync(q.vals[1], q.cost, (size_t)n * 4, hipMemcpyDeviceToDevice, L.st));
     // d_vals[1] = pixels by cost class; partition the rest (slot order) from the top k*W
-    hipLaunchKernelGGL(k_flag_top, eg, block, 0, L.st, ctx->d_vals[1], n, plan.k * plan.W, ctx->d_keys[0]);
-    hipLaunchKernelGGL(k_iota, eg, block, 0, L.st, ctx->d_cost, n);
-    size_t tmp = ctx->cap_sort_tmp;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->d_sort_tmp, tmp, ctx->d_keys[0], ctx->d_keys[1], ctx->d_cost,
-                                              ctx->d_vals[0], (int)n, 0, 1, L.st));
-    hipLaunchKernelGGL(k_build_queue, dim3((plan.qlen + 255) / 256), block, 0, L.st, ctx->d_vals[1], ctx->d_vals[0], n,
-                       plan.W, plan.k, plan.rq_prio ? RQ_PRIO_BIT : 0u, plan.pairs, plan.half, plan.quad, ctx->d_queue);
+    hipLaunchKernelGGL(k_flag_top, eg, block, 0, L.st, q.vals[1], n, plan.k * plan.W, q.keys[0]);
+    hipLaunchKernelGGL(k_iota, eg, block, 0, L.st, q.cost, n);
+    size_t tmp = q.sort_bytes;
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(q.sort_tmp, tmp, q.keys[0], q.keys[1], q.cost,
+                                              q.vals[0], (int)n, 0, 1, L.st));
+    hipLaunchKernelGGL(k_build_queue, dim3((plan.qlen + 255) / 256), block, 0, L.st, q.vals[1], q.vals[0], n,
+                       plan.W, plan.k, plan.rq_prio ? RQ_PRIO_BIT : 0u, plan.pairs, plan.half, plan.quad, q.queue);
     b.rq_setprio = plan.rq_setprio;
     b.rq_prio = plan.rq_prio;
     b.rq_pairs = plan.pairs;
     b.qlen = plan.qlen;
-    HIPCHK(hipMemsetAsync(ctx->d_qhead, 0, sizeof(uint32_t), L.st));
-    b.qhead = ctx->d_qhead;
+    HIPCHK(hipMemsetAsync(q.qhead, 0, sizeof(uint32_t), L.st));
+    b.qhead = q.qhead;
     b.qbase = plan.qbase;
     return NART_OK;
 }
@@ -821,10 +799,10 @@ void launch_primary(nart_ctx* ctx, const RenderArgs& pa, hipStream_t st) {
     const bool pixel = pa.packet && ctx->rows_pixel_major && pa.spp % 64u == 0u && env_num("NART_PRIMARY_PIXEL", 1.0) != 0.0;
     if (pixel)
         hipLaunchKernelGGL((k_primary_px<COUNT, ENV, FM>), dim3((pa.n_slots + 3) / 4), dim3(256),
-                           (size_t)ctx->stack_depth * 4 * sizeof(uint4), st, ctx->scene, pa, ctx->d_prim);
+                           (size_t)ctx->stack_depth * 4 * sizeof(uint4), st, ctx->scene, pa, ctx->d_prim.as<uint32_t>());
     else
         hipLaunchKernelGGL((k_primary<COUNT, ENV, FM>), dim3((pa.n_slots + 255) / 256), dim3(256),
-                           (size_t)ctx->stack_depth * 256 * 8, st, ctx->scene, pa, ctx->d_prim);
+                           (size_t)ctx->stack_depth * 256 * 8, st, ctx->scene, pa, ctx->d_prim.as<uint32_t>());
 }
 
 // One batch of the path integrator: k_primary, what the plan's shape prepares, the path kernel.
@@ -867,7 +845,7 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, uint32_t resident_k, hi
     if (rq && (rc = resident_blocks(ctx, (const void*)kern_rq, RQB, lds_rq, &resident_rq))) return rc;
 
     const PathLaunchIn in{a.n_slots, resident_k, resident_rq * (RQB / 256), RQB, WV, PR, ENV, rq, FM != FT_ALL,
-                          ctx->d_prim && a.cost == nullptr};
+                          (bool)ctx->d_prim && a.cost == nullptr};
     const PathSchedule plan = plan_path(in, read_sched_knobs());
     if (plan.error) return fail(ctx, NART_E_INVALID, plan.error);
     ctx->sched |= plan.sched;
@@ -878,12 +856,10 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, uint32_t resident_k, hi
         pa.packet = plan.packet;
         launch_primary<COUNT, ENV, FM>(ctx, pa, st);
         HIPCHK(hipGetLastError());
-        if (ctx->events) {
-            HIPCHK(hipEventRecord(ctx->ev[4], st));
-            ctx->primary_ran = true;
-        }
+        HIPCHK(record(ctx->ev_primary, st));
+        ctx->primary_ran = true;
         ctx->prim_valid = true;
-        prim = ctx->d_prim;
+        prim = ctx->d_prim.as<uint32_t>();
     }
     if (plan.queue_room && (rc = ensure_queue(ctx, plan.queue_room))) return rc;
     const PathLaunch L{ctx, st, plan, k_render<EXT, true, ENV>, lds, b};
@@ -1024,13 +1000,14 @@ int dispatch_volume(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
     if (blocks > resident && rounds_of(n, resident) < 12.0 && a.spp > 4) {
         const uint32_t W = resident * 4;  // resident waves
         if ((rc = ensure_queue(ctx, n + 63u * W))) return rc;
+        const QueueBufs q(ctx);
         RenderArgs pb = b;
         pb.spp = 4;
-        pb.cost = ctx->d_cost;
+        pb.cost = q.cost;
         hipLaunchKernelGGL((k_render_volume_sm<false, 1>), dim3(blocks), block, dl, st, ctx->scene, pb);
-        rc = sort_groups_by_cost(ctx, n, 64, ctx->d_queue, st);
+        rc = sort_groups_by_cost(ctx, n, 64, q.queue, st);
         if (rc) return rc;
-        b.queue = ctx->d_queue;
+        b.queue = q.queue;
         ctx->sched |= NART_SCHED_VOL_QUEUE;
         // Sparse waves on shards of < NART_VOL_SPARSE_ROUNDS (default 2) rounds of resident
         // waves: the costliest groups (probe cost >= NART_VOL_SPARSE_F (4) x the median group's)
@@ -1045,7 +1022,7 @@ int dispatch_volume(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
         if (S < 64u && (64u % S) == 0u && (double)blocks / (double)resident < max_rounds) {
             const uint32_t ng = (n + 63) / 64;
             std::vector<uint32_t> keys(ng);
-            HIPCHK(hipMemcpyAsync(keys.data(), ctx->d_keys[1], (size_t)ng * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(keys.data(), q.keys[1], (size_t)ng * 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             std::vector<uint32_t> costs;  // sorted descending (partial last group excluded)
             for (uint32_t g = 0; g < ng; ++g)
@@ -1058,8 +1035,8 @@ int dispatch_volume(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
             H = std::min<uint32_t>(H, 63u * W / (64u / S * 64u));  // queue room (ensure_queue)
             if (H) {
                 const uint32_t qlen = H * (64u / S) * 64u + (n - 64u * H);
-                hipLaunchKernelGGL(k_sparse_groups, dim3((qlen + 255) / 256), block, 0, st, ctx->d_vals[1], n, H, S,
-                                   qlen, ctx->d_queue);
+                hipLaunchKernelGGL(k_sparse_groups, dim3((qlen + 255) / 256), block, 0, st, q.vals[1], n, H, S,
+                                   qlen, q.queue);
                 b.qlen = qlen;
                 grid = (qlen + 255) / 256;
                 ctx->sched |= NART_SCHED_VOL_SPARSE;
@@ -1249,8 +1226,9 @@ int launch_aov_primary(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
 // Per-sample records of AOV `rec` of the batch in `a` (ctx->d_prim valid) into `out`.
 int launch_aov(nart_ctx* ctx, const RenderArgs& a, int rec, float4* out, hipStream_t st) {
     const dim3 grid((a.n_slots + 255) / 256), block(256);
-    if (rec == AOV_ALBEDO) hipLaunchKernelGGL((k_aov<AOV_ALBEDO>), grid, block, 0, st, ctx->scene, a, ctx->d_prim, out);
-    else hipLaunchKernelGGL((k_aov<AOV_NORMAL>), grid, block, 0, st, ctx->scene, a, ctx->d_prim, out);
+    const uint32_t* hits = ctx->d_prim.as<uint32_t>();
+    if (rec == AOV_ALBEDO) hipLaunchKernelGGL((k_aov<AOV_ALBEDO>), grid, block, 0, st, ctx->scene, a, hits, out);
+    else hipLaunchKernelGGL((k_aov<AOV_NORMAL>), grid, block, 0, st, ctx->scene, a, hits, out);
     HIPCHK(hipGetLastError());
     return NART_OK;
 }
@@ -1290,26 +1268,15 @@ struct RenderTimer {
     }
 };
 
-// Temporaries of one call, freed when it returns.
-struct ScopedDeviceBufs {
-    void* p[2] = {nullptr, nullptr};
-    ScopedDeviceBufs() = default;
-    ScopedDeviceBufs(const ScopedDeviceBufs&) = delete;
-    ~ScopedDeviceBufs() {
-        for (void* b : p)
-            if (b) hipFree(b);
-    }
-};
-
 // Kernel arguments of n_slots slots laid out in the context's work buffers (ensure).
 RenderArgs make_render_args(const nart_ctx* ctx, const nart_render_params* p, const nart_session_geometry& g,
                             uint32_t n_slots, unsigned long long* counters) {
     RenderArgs ra;
-    ra.slot_xy = ctx->d_slot_xy;
-    ra.slot_so = ctx->d_slot_so;
-    ra.samples = ctx->d_samples;
-    ra.rng0 = ctx->d_rng;
-    ra.Lout = ctx->d_L;
+    ra.slot_xy = ctx->d_slot_xy.as<uint32_t>();
+    ra.slot_so = ctx->d_slot_so.as<SlotSO>();
+    ra.samples = ctx->d_samples.as<float2>();
+    ra.rng0 = ctx->d_rng.as<uint32_t>();
+    ra.Lout = ctx->d_L.as<float4>();
     ra.n_slots = n_slots;
     ra.spp = p->spp;
     ra.bounces = p->bounces;
@@ -1341,8 +1308,9 @@ int plan_splat(nart_ctx* ctx, const nart_render_params* p, const nart_session_ge
     float table[64 + 65];
     nart_filter_table(table);
     const bool thr_ok = splat_thresholds(p->filter_width, table + 64);
-    if (!ctx->d_table) HIPCHK(hipMalloc(&ctx->d_table, sizeof(table)));
-    HIPCHK(hipMemcpy(ctx->d_table, table, sizeof(table), hipMemcpyHostToDevice));
+    if (int rc = reserve(ctx, ctx->d_table, ctx->device, sizeof(table), "filter table")) return rc;
+    float* const d_table = ctx->d_table.as<float>();
+    HIPCHK(hipMemcpy(d_table, table, sizeof(table), hipMemcpyHostToDevice));
     std::vector<float4> lut;
     uint32_t lut_b0 = 0;
     const bool lut_ok = thr_ok && splat_lut(table + 64, table, lut, lut_b0);
@@ -1380,8 +1348,8 @@ int plan_splat(nart_ctx* ctx, const nart_render_params* p, const nart_session_ge
                       g.filter_bounds >= 1 && g.filter_bounds <= 3;
     const bool rows = skew && splat_mode == 5;
     if (lut_ok) {
-        if (!ctx->d_lut) HIPCHK(hipMalloc(&ctx->d_lut, SPLAT_LUT_MAX * sizeof(float4)));
-        HIPCHK(hipMemcpy(ctx->d_lut, lut.data(), lut.size() * sizeof(float4), hipMemcpyHostToDevice));
+        if (int rc = reserve(ctx, ctx->d_lut, ctx->device, SPLAT_LUT_MAX * sizeof(float4), "splat filter cells")) return rc;
+        HIPCHK(hipMemcpy(ctx->d_lut.as<float4>(), lut.data(), lut.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
     plan.mode = splat_mode;
     plan.skew = skew;
@@ -1389,8 +1357,8 @@ int plan_splat(nart_ctx* ctx, const nart_render_params* p, const nart_session_ge
     plan.bands = skew_bands;
     plan.lut_bytes = lut.size() * sizeof(float4);
     SplatArgs& sa = plan.sa;
-    sa.table = ctx->d_table;
-    sa.thr = thr_ok ? ctx->d_table + 64 : nullptr;
+    sa.table = d_table;
+    sa.thr = thr_ok ? d_table + 64 : nullptr;
     sa.idx_scale = 64.f / p->filter_width;
     sa.spp = p->spp;
     sa.B = p->bucket_size;
@@ -1401,7 +1369,7 @@ int plan_splat(nart_ctx* ctx, const nart_render_params* p, const nart_session_ge
     sa.totalH = g.total_height;
     sa.fw = p->filter_width;
     sa.invB = (B & (B - 1)) == 0 ? 1.f / (float)B : 0.f;
-    sa.lut = lut_ok ? static_cast<const float4*>(ctx->d_lut) : nullptr;
+    sa.lut = lut_ok ? ctx->d_lut.as<const float4>() : nullptr;
     sa.lut_b0 = lut_b0;
     sa.lut_n = (uint32_t)lut.size();
     int ex = 0;
@@ -1479,19 +1447,11 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         if (ids[i] >= nb_total) return fail(ctx, NART_E_INVALID, "bucket id out of range");
     SplatPlan plan;
     if ((rc = plan_splat(ctx, p, g, n, plan))) return rc;
-    const size_t n_cnt = 24;
-    if (!ctx->d_counters) HIPCHK(hipMalloc(&ctx->d_counters, n_cnt * sizeof(unsigned long long)));
-    if (ctx->counters) HIPCHK(hipMemsetAsync(ctx->d_counters, 0, n_cnt * sizeof(unsigned long long), st));
-    if (!ctx->events) {
-        for (auto& e : ctx->ev) HIPCHK(hipEventCreate(&e));
-        ctx->events = true;
-    }
-    for (uint32_t i = 0; i < frame.n_passes; ++i)
-        for (auto& e : ctx->ev_pass[frame.passes[i]])
-            if (!e) HIPCHK(hipEventCreate(&e));
+    if ((rc = counter_buffer(ctx))) return rc;
+    unsigned long long* const d_counters = ctx->d_counters.as<unsigned long long>();
+    if (ctx->counters) HIPCHK(hipMemsetAsync(d_counters, 0, ctx->d_counters.bytes(), st));
     const size_t limit = batch_slot_limit(ctx, p->spp, frame.record_bytes);
-    ScopedDeviceBufs layer_records;  // cascade: the second per-sample record buffer, 16 B per sample
-    size_t layer_records_cap = 0;    // bytes
+    Buf layer_records;  // cascade: the second per-sample record buffer, 16 B per sample; freed on return
     const uint32_t tpx = g.tile_size * g.tile_size;
     nart_render_stats acc;  // this call's share, added to *stats at the end
     std::memset(&acc, 0, sizeof(acc));
@@ -1524,46 +1484,46 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         acc.traced_samples += (uint64_t)nslots * p->spp;
         rc = ensure(ctx, nslots, p->spp, nbk);
         if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(ctx->d_slot_xy, xy.data(), (size_t)nslots * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->d_bucket_ids, ids + b0, (size_t)nbk * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->d_bucket_base, base.data(), (size_t)nbk * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_slot_table, dim3(nbk), dim3(256), 0, st, ctx->d_bucket_base, nbk, nslots, p->spp,
-                           ctx->d_slot_so, plan.skew);
+        HIPCHK(hipMemcpyAsync(ctx->d_slot_xy.as<uint32_t>(), xy.data(), (size_t)nslots * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->d_bucket_ids.as<uint32_t>(), ids + b0, (size_t)nbk * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->d_bucket_base.as<uint32_t>(), base.data(), (size_t)nbk * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_slot_table, dim3(nbk), dim3(256), 0, st, ctx->d_bucket_base.as<uint32_t>(), nbk, nslots, p->spp,
+                           ctx->d_slot_so.as<SlotSO>(), plan.skew);
         ctx->rows_pixel_major = plan.skew;
-        const RenderArgs ra = make_render_args(ctx, p, g, nslots, ctx->d_counters);
-        HIPCHK(hipEventRecord(ctx->ev[3], st));
+        const RenderArgs ra = make_render_args(ctx, p, g, nslots, d_counters);
+        HIPCHK(record(ctx->ev_latin0, st));
         rc = launch_latin(ctx, ra, st);
         if (rc) return rc;
-        HIPCHK(hipEventRecord(ctx->ev[0], st));
+        HIPCHK(record(ctx->ev_path0, st));
         ctx->primary_ran = false;
         ctx->prim_valid = false;
         if (beauty) {
             rc = dispatch_render(ctx, ra, p->integrator, st);
             if (rc) return rc;
         }
-        HIPCHK(hipEventRecord(ctx->ev[1], st));
+        HIPCHK(record(ctx->ev_path1, st));
         SplatArgs sa = plan.sa;
-        sa.bucket_ids = ctx->d_bucket_ids;
-        sa.bucket_base = ctx->d_bucket_base;
-        sa.samples = ctx->d_samples;
-        sa.Lout = ctx->d_L;
+        sa.bucket_ids = ctx->d_bucket_ids.as<uint32_t>();
+        sa.bucket_base = ctx->d_bucket_base.as<uint32_t>();
+        sa.samples = ctx->d_samples.as<float2>();
+        sa.Lout = ctx->d_L.as<float4>();
         sa.tiles = beauty ? out.of(OutputKind::Beauty) + (size_t)b0 * tpx * 5 : nullptr;
         sa.n_buckets = nbk;
         if (beauty && (rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
-        HIPCHK(hipEventRecord(ctx->ev[2], st));
+        HIPCHK(record(ctx->ev_splat1, st));
         const uint64_t ns = (uint64_t)nslots * p->spp;
         const dim3 rec_grid((uint32_t)((ns + 255) / 256)), rec_block(256);
-        hipEvent_t last = ctx->ev[2];
+        hipEvent_t last = ctx->ev_splat1.handle();
         for (uint32_t i = 0; i < frame.n_passes; ++i) {
             const PassKind pass = frame.passes[i];
-            if (pass == PASS_CASCADE && (rc = ensure_dev(ctx, ctx->device, layer_records.p[0], layer_records_cap,
-                                                         ns * sizeof(float4), "cascade layer records")))
+            if (pass == PASS_CASCADE &&
+                (rc = reserve(ctx, layer_records, ctx->device, ns * sizeof(float4), "cascade layer records")))
                 return rc;
             // the dispatch's own camera-ray hits where it traced them first, else k_primary now
             if ((pass == PASS_FIRST_HIT || pass == PASS_MATTE) && !ctx->prim_valid && (rc = launch_aov_primary(ctx, ra, st)))
                 return rc;
-            HIPCHK(hipEventRecord(ctx->ev_pass[pass][0], st));
-            float4* const records = pass == PASS_CASCADE ? static_cast<float4*>(layer_records.p[0]) : ctx->d_L;
+            HIPCHK(record(ctx->ev_pass[pass][0], st));
+            float4* const records = (pass == PASS_CASCADE ? layer_records : ctx->d_L).as<float4>();
             sa.Lout = records;
             for (uint32_t o = 0; o < frame.n_outputs; ++o) {
                 const FrameOutput& w = frame.outputs[o];
@@ -1572,7 +1532,7 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
                 case OutputKind::Layer: {
                     const CascadeLevels& lv = frame.ask.cascade;
                     CascadeSplitArgs ca;
-                    ca.L = ctx->d_L;
+                    ca.L = ctx->d_L.as<float4>();
                     ca.out = records;
                     ca.n = ns;
                     ca.K = lv.K;
@@ -1587,19 +1547,19 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
                     break;
                 }
                 case OutputKind::Moment:
-                    hipLaunchKernelGGL(k_moment, rec_grid, rec_block, 0, st, ctx->d_L, ns);
+                    hipLaunchKernelGGL(k_moment, rec_grid, rec_block, 0, st, ctx->d_L.as<float4>(), ns);
                     break;
                 case OutputKind::Albedo:
                 case OutputKind::Normal:
-                    if ((rc = launch_aov(ctx, ra, w.kind == OutputKind::Albedo ? AOV_ALBEDO : AOV_NORMAL, ctx->d_L, st)))
+                    if ((rc = launch_aov(ctx, ra, w.kind == OutputKind::Albedo ? AOV_ALBEDO : AOV_NORMAL, records, st)))
                         return rc;
                     break;
                 case OutputKind::Plane: {
                     MatteIdArgs ma;
-                    ma.hit = ctx->d_prim;
+                    ma.hit = ctx->d_prim.as<uint32_t>();
                     ma.tri_mesh = ctx->scene.tri_mesh;
                     ma.meshes = ctx->scene.meshes;
-                    ma.out = ctx->d_L;
+                    ma.out = ctx->d_L.as<float4>();
                     ma.n = ns;
                     ma.num_tris = ctx->scene.num_tris;
                     ma.num_meshes = ctx->num_meshes;
@@ -1615,26 +1575,26 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
                 sa.tiles = out.tiles[o] + (size_t)b0 * tpx * 5;
                 if ((rc = launch_splat(ctx, plan, sa, nbk, st, pass == PASS_MOMENT))) return rc;
             }
-            HIPCHK(hipEventRecord(ctx->ev_pass[pass][1], st));
-            last = ctx->ev_pass[pass][1];
+            HIPCHK(record(ctx->ev_pass[pass][1], st));
+            last = ctx->ev_pass[pass][1].handle();
         }
         // one stream: waiting for the last event recorded is waiting for all of them
         HIPCHK(hipEventSynchronize(last));
         float ms = 0.f;
         for (uint32_t i = 0; i < frame.n_passes && times; ++i) {
             const PassKind pass = frame.passes[i];
-            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_pass[pass][0], ctx->ev_pass[pass][1]));
+            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_pass[pass][0].handle(), ctx->ev_pass[pass][1].handle()));
             times->ms[pass] += ms;
         }
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_path0.handle(), ctx->ev_path1.handle()));
         acc.kernel_ms += ms;
         if (ctx->primary_ran) {
-            HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
+            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_path0.handle(), ctx->ev_primary.handle()));
             acc.primary_ms += ms;
         }
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
+        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_path1.handle(), ctx->ev_splat1.handle()));
         acc.splat_ms += ms;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[0]));
+        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_latin0.handle(), ctx->ev_path0.handle()));
         acc.latin_ms += ms;
         if (beauty) ++acc.kernel_launches;
         b0 = b1;
@@ -1644,7 +1604,7 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         acc.samples = counted * p->spp;
         if (ctx->counters) {
             unsigned long long c[8];
-            HIPCHK(hipMemcpy(c, ctx->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(c, d_counters, sizeof(c), hipMemcpyDeviceToHost));
             acc.rays_extend = c[0];
             acc.rays_shadow = c[1];
             acc.node_visits = c[2];
@@ -1676,21 +1636,18 @@ int build_bvh_device(nart_ctx* ctx, const nart_scene_blob& blob, const std::vect
     out.num_leaf_tris = m;
     if (m == 0) {  // nothing the octree can return: never traversed (geometry_visible = 0)
         BVHNode dummy{};
-        int rc = upload(ctx, ctx->d_nodes, &dummy, 0);
-        if (!rc) rc = upload(ctx, ctx->d_tri_isect, (const float*)nullptr, 0);
-        if (!rc) rc = upload(ctx, ctx->d_tri_perm, (const float*)nullptr, 0);
+        int rc = upload(ctx, ctx->d_nodes, &dummy, 0, "BVH nodes");
+        if (!rc) rc = upload(ctx, ctx->d_tri_isect, (const float*)nullptr, 0, "triangle records");
+        if (!rc) rc = upload(ctx, ctx->d_tri_perm, (const float*)nullptr, 0, "permuted triangle records");
         return rc;
     }
     const int n = (int)((m + LBVH_LEAF - 1) / LBVH_LEAF);  // leaves
     const int ninner = n - 1;
-    std::vector<void*> tmp;
-    auto alloc = [&](void** p, size_t bytes) {
-        const int rc = dmalloc(ctx, p, bytes ? bytes : 4, "BVH build scratch");
-        if (!rc) tmp.push_back(*p);
-        return rc;
-    };
-    auto cleanup = [&](int rc) {
-        for (void* p : tmp) hipFree(p);
+    std::vector<Buf> tmp;  // the build's scratch, freed on every return path
+    auto alloc = [&](auto*& p, size_t bytes) {
+        tmp.emplace_back();
+        const int rc = reserve(ctx, tmp.back(), ctx->device, bytes ? bytes : 4, "BVH build scratch");
+        p = tmp.back().as<std::remove_reference_t<decltype(*p)>>();
         return rc;
     };
     uint32_t *d_vis, *d_info, *d_keys[2], *d_vals[2], *d_lkey, *d_flag, *d_maxd, *d_ord[2];
@@ -1702,37 +1659,37 @@ int build_bvh_device(nart_ctx* ctx, const nart_scene_blob& blob, const std::vect
     const uint32_t nb = std::min<uint32_t>(1024, (m + 255) / 256);
     const size_t ni = (size_t)std::max(ninner, 1);
     int rc = NART_OK;
-    if ((rc = alloc((void**)&d_vis, m * 4)) || (rc = alloc((void**)&d_info, blob.num_triangles * 4)) ||
-        (rc = alloc((void**)&d_prims, m * sizeof(LbvhPrim))) || (rc = alloc((void**)&d_sorted, m * sizeof(LbvhPrim))) ||
-        (rc = alloc((void**)&d_part, nb * 6 * 4)) || (rc = alloc((void**)&d_keys[0], m * 4)) ||
-        (rc = alloc((void**)&d_keys[1], m * 4)) || (rc = alloc((void**)&d_vals[0], m * 4)) ||
-        (rc = alloc((void**)&d_vals[1], m * 4)) || (rc = alloc((void**)&d_lkey, n * 4)) ||
-        (rc = alloc((void**)&d_child, ni * sizeof(int2))) || (rc = alloc((void**)&d_pin, ni * 4)) ||
-        (rc = alloc((void**)&d_pleaf, (size_t)n * 4)) || (rc = alloc((void**)&d_box, ni * sizeof(LbvhBox))) ||
-        (rc = alloc((void**)&d_flag, ni * 4)) || (rc = alloc((void**)&d_maxd, 4)) ||
-        (rc = alloc((void**)&d_ord[0], ni * 4)) || (rc = alloc((void**)&d_ord[1], ni * 4)) ||
-        (rc = alloc((void**)&d_remap, ni * 4)))
-        return cleanup(rc);
+    if ((rc = alloc(d_vis, m * 4)) || (rc = alloc(d_info, blob.num_triangles * 4)) ||
+        (rc = alloc(d_prims, m * sizeof(LbvhPrim))) || (rc = alloc(d_sorted, m * sizeof(LbvhPrim))) ||
+        (rc = alloc(d_part, nb * 6 * 4)) || (rc = alloc(d_keys[0], m * 4)) ||
+        (rc = alloc(d_keys[1], m * 4)) || (rc = alloc(d_vals[0], m * 4)) ||
+        (rc = alloc(d_vals[1], m * 4)) || (rc = alloc(d_lkey, n * 4)) ||
+        (rc = alloc(d_child, ni * sizeof(int2))) || (rc = alloc(d_pin, ni * 4)) ||
+        (rc = alloc(d_pleaf, (size_t)n * 4)) || (rc = alloc(d_box, ni * sizeof(LbvhBox))) ||
+        (rc = alloc(d_flag, ni * 4)) || (rc = alloc(d_maxd, 4)) ||
+        (rc = alloc(d_ord[0], ni * 4)) || (rc = alloc(d_ord[1], ni * 4)) ||
+        (rc = alloc(d_remap, ni * 4)))
+        return rc;
     if (hipMemcpy(d_vis, vis.data(), m * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_info, info.data(), blob.num_triangles * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(d_pin, 0xFF, ni * 4) != hipSuccess || hipMemset(d_pleaf, 0xFF, (size_t)n * 4) != hipSuccess ||
         hipMemset(d_flag, 0, ni * 4) != hipSuccess || hipMemset(d_maxd, 0, 4) != hipSuccess)
-        return cleanup(fail(ctx, NART_E_HIP, "BVH build: upload"));
+        return fail(ctx, NART_E_HIP, "BVH build: upload");
     const dim3 blk(256);
     const uint32_t gm = (m + 255) / 256, gn = ((uint32_t)n + 255) / 256, gi = ((uint32_t)ni + 255) / 256;
-    hipLaunchKernelGGL(k_lbvh_prims, dim3(gm), blk, 0, 0, (const nart_triangle*)ctx->d_tris, d_vis, m, d_prims);
+    hipLaunchKernelGGL(k_lbvh_prims, dim3(gm), blk, 0, 0, ctx->d_tris.as<const nart_triangle>(), d_vis, m, d_prims);
     hipLaunchKernelGGL(k_lbvh_bounds, dim3(nb), blk, 0, 0, d_prims, m, d_part);
     hipLaunchKernelGGL(k_lbvh_bounds_final, dim3(1), dim3(64), 0, 0, d_part, nb);
     hipLaunchKernelGGL(k_lbvh_morton, dim3(gm), blk, 0, 0, d_prims, m, d_part, d_keys[0], d_vals[0]);
     size_t ts = 0;
     if (hipcub::DeviceRadixSort::SortPairs(nullptr, ts, d_keys[0], d_keys[1], d_vals[0], d_vals[1], (int)m, 0, 30) !=
         hipSuccess)
-        return cleanup(fail(ctx, NART_E_HIP, "BVH build: sort size"));
-    void* d_ts = nullptr;
-    if ((rc = alloc(&d_ts, ts))) return cleanup(rc);
+        return fail(ctx, NART_E_HIP, "BVH build: sort size");
+    char* d_ts = nullptr;
+    if ((rc = alloc(d_ts, ts))) return rc;
     if (hipcub::DeviceRadixSort::SortPairs(d_ts, ts, d_keys[0], d_keys[1], d_vals[0], d_vals[1], (int)m, 0, 30) !=
         hipSuccess)
-        return cleanup(fail(ctx, NART_E_HIP, "BVH build: sort"));
+        return fail(ctx, NART_E_HIP, "BVH build: sort");
     hipLaunchKernelGGL(k_lbvh_gather, dim3(gm), blk, 0, 0, d_prims, d_vals[1], m, d_sorted);
     hipLaunchKernelGGL(k_lbvh_leaf_keys, dim3(gn), blk, 0, 0, d_keys[1], m, n, d_lkey);
     if (ninner > 0) {
@@ -1742,31 +1699,31 @@ int build_bvh_device(nart_ctx* ctx, const nart_scene_blob& blob, const std::vect
         size_t ts2 = 0;
         if (hipcub::DeviceRadixSort::SortPairs(nullptr, ts2, d_keys[0], d_keys[1], d_vals[0], d_ord[0], ninner, 0, 8) !=
             hipSuccess)
-            return cleanup(fail(ctx, NART_E_HIP, "BVH build: sort size"));
-        void* d_ts2 = nullptr;
-        if ((rc = alloc(&d_ts2, ts2))) return cleanup(rc);
+            return fail(ctx, NART_E_HIP, "BVH build: sort size");
+        char* d_ts2 = nullptr;
+        if ((rc = alloc(d_ts2, ts2))) return rc;
         if (hipcub::DeviceRadixSort::SortPairs(d_ts2, ts2, d_keys[0], d_keys[1], d_vals[0], d_ord[0], ninner, 0, 8) !=
             hipSuccess)
-            return cleanup(fail(ctx, NART_E_HIP, "BVH build: sort"));
+            return fail(ctx, NART_E_HIP, "BVH build: sort");
         hipLaunchKernelGGL(k_lbvh_remap, dim3(gi), blk, 0, 0, d_ord[0], ninner, d_remap);
     }
-    if ((rc = dmalloc(ctx, &ctx->d_nodes, ni * sizeof(BVHNode), "BVH nodes")) ||
-        (rc = dmalloc(ctx, &ctx->d_tri_isect, (size_t)m * 64, "triangle records")) ||
-        (rc = dmalloc(ctx, &ctx->d_tri_perm, ((size_t)m * 3 + NART_TRI_PAD) * 64, "permuted triangle records")))
-        return cleanup(rc);
+    if ((rc = reserve(ctx, ctx->d_nodes, ctx->device, ni * sizeof(BVHNode), "BVH nodes")) ||
+        (rc = reserve(ctx, ctx->d_tri_isect, ctx->device, (size_t)m * 64, "triangle records")) ||
+        (rc = reserve(ctx, ctx->d_tri_perm, ctx->device, ((size_t)m * 3 + NART_TRI_PAD) * 64, "permuted triangle records")))
+        return rc;
     if (ninner > 0)
         hipLaunchKernelGGL(k_lbvh_emit, dim3(gi), blk, 0, 0, d_ord[0], ninner, d_child, d_remap, d_box, d_sorted, m, pad,
-                           (BVHNode*)ctx->d_nodes);
-    hipLaunchKernelGGL(k_lbvh_tris, dim3(gm), blk, 0, 0, (const nart_triangle*)ctx->d_tris, d_sorted, m, d_info,
-                       (float*)ctx->d_tri_isect);
-    hipLaunchKernelGGL(k_lbvh_perm, dim3(gm), blk, 0, 0, (const float*)ctx->d_tri_isect, m, (float*)ctx->d_tri_perm);
+                           ctx->d_nodes.as<BVHNode>());
+    hipLaunchKernelGGL(k_lbvh_tris, dim3(gm), blk, 0, 0, ctx->d_tris.as<const nart_triangle>(), d_sorted, m, d_info,
+                       ctx->d_tri_isect.as<float>());
+    hipLaunchKernelGGL(k_lbvh_perm, dim3(gm), blk, 0, 0, ctx->d_tri_isect.as<const float>(), m, ctx->d_tri_perm.as<float>());
     uint32_t maxd = 0;
     if (hipGetLastError() != hipSuccess || hipMemcpy(&maxd, d_maxd, 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return cleanup(fail(ctx, NART_E_HIP, "BVH build: kernels"));
+        return fail(ctx, NART_E_HIP, "BVH build: kernels");
     out.num_nodes = (uint32_t)std::max(ninner, 0);
     out.max_stack = ninner > 0 ? maxd + 1 : 1;
     out.root_code = ninner > 0 ? 0 : ~(int32_t)(m - 1);  // one leaf of m <= LBVH_LEAF triangles
-    return cleanup(NART_OK);
+    return NART_OK;
 }
 
 // ---------------------------------------------------------------- whole frames
@@ -1794,29 +1751,22 @@ struct FrameRequest {
     bool on_device = false;
     // The call's tile and image buffers.  image null: temporaries, allocated by the call and freed on
     // every return path.  Else borrowed from a context, which keeps them for its next call (the
-    // memory a context holds between calls sets batch_slot_limit): the image buffer *image of
-    // capacity *image_cap on device 0, grown to max(images, outputs) images; tiles in d_gather.  A
+    // memory a context holds between calls sets batch_slot_limit): the image buffer *image on
+    // device 0, grown to max(images, outputs) images; tiles in d_gather.  A
     // multi-device context always gathers and combines in its own cached buffers.
-    void** image = nullptr;
-    size_t* image_cap = nullptr;
+    Buf* image = nullptr;
     uint32_t images = 0;
     // With plan.ask.adaptive (every device refines its own buckets): the run's parameters and results.
     AdaptiveRun* adaptive = nullptr;
 
     FrameRequest() = default;
-    FrameRequest(void** image_, size_t* cap, uint32_t n) : on_device(true), image(image_), image_cap(cap), images(n) {}
+    FrameRequest(Buf* image_, uint32_t n) : on_device(true), image(image_), images(n) {}
     // `img` is where the plan's output of `kind` goes on the host (a failed plan has no outputs).
     void to_host(const FramePlan& plan, OutputKind kind, nart_pixel* img) {
         const int i = plan.find(kind);
         if (i >= 0) dst[i] = img;
     }
 };
-
-// The buffers a context keeps for whole frames (render_frame, render_multi) and the denoiser.
-void free_frame_buffers(nart_ctx* ctx) {
-    for (void* b : {ctx->d_gather, ctx->d_byid, ctx->d_image, ctx->d_slab_map, ctx->d_dn, ctx->d_dn_img})
-        if (b) hipFree(b);
-}
 
 // ---------------------------------------------------------------- adaptive sampling (device/adaptive.h)
 void adaptive_defaults(nart_adaptive_params* ap) {
@@ -1871,15 +1821,13 @@ int render_buckets_adaptive(nart_ctx* ctx, const nart_render_params* p, const ui
     run.err.assign(n, 0.f);
     run.rendered.assign(run.levels.size(), 0);
     if (!n) return NART_OK;
-    for (auto& e : ctx->ev_ad)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    ScopedDeviceBufs own;
+    Buf own_tiles, own_lists;  // freed on return
     const size_t slab = (size_t)n * tile_floats;
-    int rc = dmalloc(ctx, &own.p[0], level.n_outputs * slab * sizeof(float), "adaptive scratch tiles");
-    if (!rc) rc = dmalloc(ctx, &own.p[1], (size_t)n * 12, "adaptive bucket lists");
+    int rc = reserve(ctx, own_tiles, ctx->device, level.n_outputs * slab * sizeof(float), "adaptive scratch tiles");
+    if (!rc) rc = reserve(ctx, own_lists, ctx->device, (size_t)n * 12, "adaptive bucket lists");
     if (rc) return rc;
-    const FrameTiles scratch(level, static_cast<float*>(own.p[0]), slab);
-    uint32_t* d_ids = static_cast<uint32_t*>(own.p[1]);
+    const FrameTiles scratch(level, own_tiles.as<float>(), slab);
+    uint32_t* d_ids = own_lists.as<uint32_t>();
     uint32_t* d_slot = d_ids + n;
     float* d_err = reinterpret_cast<float*>(d_slot + n);
 
@@ -1901,7 +1849,7 @@ int render_buckets_adaptive(nart_ctx* ctx, const nart_render_params* p, const ui
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(d_ids, cur_ids.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_slot, cur.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(ctx->ev_ad[0], st));
+        HIPCHK(record(ctx->ev_ad[0], st));
         BucketErrorArgs ea;
         ea.beauty = scratch.of(OutputKind::Beauty);
         ea.moment = scratch.of(OutputKind::Moment);
@@ -1931,12 +1879,12 @@ int render_buckets_adaptive(nart_ctx* ctx, const nart_render_params* p, const ui
             hipLaunchKernelGGL(k_scatter_tiles, dim3(m, nsc), dim3(256), 0, st, sc);
             HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipEventRecord(ctx->ev_ad[1], st));
+        HIPCHK(record(ctx->ev_ad[1], st));
         E.resize(m);
         HIPCHK(hipMemcpyAsync(E.data(), d_err, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_ad[0], ctx->ev_ad[1]));
+        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_ad[0].handle(), ctx->ev_ad[1].handle()));
         run.ms += ms;
         run.rendered[li] = m;
         next.clear();
@@ -1979,23 +1927,21 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
     const size_t tile_floats = (size_t)nb * g.tile_size * g.tile_size * 5;
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5;
     const size_t K = plan.n_outputs;
-    if (rq.image && (rc = ensure_dev(ctx, c0->device, *rq.image, *rq.image_cap,
-                                     std::max<size_t>(K, rq.images) * img_floats * sizeof(float), "image")))
+    if (rq.image &&
+        (rc = reserve(ctx, *rq.image, c0->device, std::max<size_t>(K, rq.images) * img_floats * sizeof(float), "image")))
         return rc;
     if (c0 != ctx) return render_multi(ctx, p, plan, rq, stats, *times);
 
     HIPCHK(hipSetDevice(ctx->device));
     // the outputs' tile buffers back to back; one image to combine into on the way to the host, or
     // the borrowed images
-    ScopedDeviceBufs own;
-    void*& d_tiles = rq.image ? ctx->d_gather : own.p[0];
-    void*& d_img = rq.image ? *rq.image : own.p[1];
-    const size_t tile_bytes = K * tile_floats * sizeof(float);
-    if (rq.image) rc = ensure_dev(ctx, ctx->device, ctx->d_gather, ctx->cap_gather, tile_bytes, "tiles");
-    else if (!(rc = dmalloc(ctx, &d_tiles, tile_bytes, "tiles")))
-        rc = dmalloc(ctx, &d_img, img_floats * sizeof(float), "image");
+    Buf own_tiles, own_img;  // freed on return
+    Buf& tiles = rq.image ? ctx->d_gather : own_tiles;
+    Buf& image = rq.image ? *rq.image : own_img;
+    rc = reserve(ctx, tiles, ctx->device, K * tile_floats * sizeof(float), "tiles");
+    if (!rc && !rq.image) rc = reserve(ctx, image, ctx->device, img_floats * sizeof(float), "image");
     if (rc) return rc;
-    const FrameTiles out(plan, static_cast<float*>(d_tiles), tile_floats);
+    const FrameTiles out(plan, tiles.as<float>(), tile_floats);
     std::vector<uint32_t> ids(nb);
     for (uint32_t i = 0; i < nb; ++i) ids[i] = i;
     if (rq.adaptive) {
@@ -2006,7 +1952,7 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
     }
     for (size_t i = 0; i < K && !rc; ++i) {
         if (!rq.on_device && !rq.dst[i]) continue;
-        float* img = static_cast<float*>(d_img) + (rq.on_device ? i * img_floats : 0);
+        float* img = image.as<float>() + (rq.on_device ? i * img_floats : 0);
         rc = nart_hip_combine_async(ctx, p, reinterpret_cast<const nart_pixel*>(out.tiles[i]),
                                     reinterpret_cast<nart_pixel*>(img), 0);
         if (rc || rq.on_device) continue;
@@ -2032,8 +1978,8 @@ int rect_slots(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t
         for (uint32_t x = x0; x < x0 + w; ++x) xy.push_back(x | (y << 16));
     const uint32_t n = (uint32_t)xy.size();
     if (int rc = ensure(ctx, n, p->spp, 1)) return rc;
-    HIPCHK(hipMemcpy(ctx->d_slot_xy, xy.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_slot_rows, dim3((n + 255) / 256), dim3(256), 0, 0, n, p->spp, ctx->d_slot_so);
+    HIPCHK(hipMemcpy(ctx->d_slot_xy.as<uint32_t>(), xy.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_slot_rows, dim3((n + 255) / 256), dim3(256), 0, 0, n, p->spp, ctx->d_slot_so.as<SlotSO>());
     ctx->rows_pixel_major = true;
     ra = make_render_args(ctx, p, g, n, counters);
     return NART_OK;
@@ -2067,8 +2013,8 @@ int check_denoise(nart_ctx* ctx, const nart_denoise_params* dp, nart_denoise_par
 int denoise_images(nart_ctx* ctx, const nart_session_geometry& g, float* img[5], int n = 4) {
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5;
     const size_t bytes = (size_t)n * img_floats * sizeof(float);
-    if (int rc = ensure_dev(ctx, ctx->device, ctx->d_dn_img, ctx->cap_dn_img, bytes, "denoiser images")) return rc;
-    for (int k = 0; k < n; ++k) img[k] = static_cast<float*>(ctx->d_dn_img) + (size_t)k * img_floats;
+    if (int rc = reserve(ctx, ctx->d_dn_img, ctx->device, bytes, "denoiser images")) return rc;
+    for (int k = 0; k < n; ++k) img[k] = ctx->d_dn_img.as<float>() + (size_t)k * img_floats;
     return NART_OK;
 }
 
@@ -2085,11 +2031,8 @@ int denoise_device(nart_ctx* ctx, const nart_render_params* p, const nart_denois
     const size_t npx = (size_t)p->image_width * p->image_height;
     // guide, signal x 2, centre (float4 each), then cov and slope
     const size_t work_bytes = npx * (4 * sizeof(float4) + 2 * sizeof(float));
-    if (int rc = ensure_dev(ctx, ctx->device, ctx->d_dn, ctx->cap_dn, work_bytes, "denoiser work buffers")) return rc;
-    const uint32_t n_ev = dp.iterations + 4;
-    for (uint32_t k = 0; k < n_ev; ++k)
-        if (!ctx->ev_dn[k]) HIPCHK(hipEventCreate(&ctx->ev_dn[k]));
-    float4* f4 = static_cast<float4*>(ctx->d_dn);
+    if (int rc = reserve(ctx, ctx->d_dn, ctx->device, work_bytes, "denoiser work buffers")) return rc;
+    float4* f4 = ctx->d_dn.as<float4>();
     float4* sig[2] = {f4 + npx, f4 + 2 * npx};
     DnArgs a;
     a.beauty = d_beauty;
@@ -2115,21 +2058,21 @@ int denoise_device(nart_ctx* ctx, const nart_render_params* p, const nart_denois
     a.albedo_floor = dp.albedo_floor;
     const dim3 grid((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH), block(256);
     uint32_t e = 0;
-    HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+    HIPCHK(record(ctx->ev_dn[e++], st));
     a.sig_in = nullptr;
     if (d_moment) {  // signal and variance at once, where the variance pass would have left them
         a.sig_out = sig[1];
         hipLaunchKernelGGL(k_dn_prepare<true>, grid, block, 0, st, a);
-        HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+        HIPCHK(record(ctx->ev_dn[e++], st));
     } else {
         a.sig_out = sig[0];
         hipLaunchKernelGGL(k_dn_prepare<false>, grid, block, 0, st, a);
-        HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+        HIPCHK(record(ctx->ev_dn[e++], st));
         a.sig_in = sig[0];
         a.sig_out = sig[1];
         hipLaunchKernelGGL(k_dn_variance, grid, block, 0, st, a);
     }
-    HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+    HIPCHK(record(ctx->ev_dn[e++], st));
     int cur = 1;
     for (uint32_t i = 0; i < dp.iterations; ++i) {
         a.sig_in = sig[cur];
@@ -2138,21 +2081,21 @@ int denoise_device(nart_ctx* ctx, const nart_render_params* p, const nart_denois
         if (i == 0) hipLaunchKernelGGL(k_dn_atrous<2>, grid, block, 0, st, a);
         else if (i == 1) hipLaunchKernelGGL(k_dn_atrous<4>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(k_dn_atrous<0>, grid, block, 0, st, a);
-        HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
+        HIPCHK(record(ctx->ev_dn[e++], st));
         cur ^= 1;
     }
     a.sig_in = sig[cur];
     const size_t n_total = (size_t)g.total_width * g.total_height;
     hipLaunchKernelGGL(k_dn_finalize, dim3((uint32_t)((n_total + 255) / 256)), block, 0, st, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev_dn[e++], st));
-    HIPCHK(hipEventSynchronize(ctx->ev_dn[e - 1]));
+    HIPCHK(record(ctx->ev_dn[e++], st));
+    HIPCHK(hipEventSynchronize(ctx->ev_dn[e - 1].handle()));
     for (double& t : ctx->dn_ms) t = 0.0;
     double total = 0.0;
     for (uint32_t k = 0; k + 1 < e; ++k) {
         if (d_moment && k == 1) continue;  // no variance kernel ran between these two events
         float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, ctx->ev_dn[k], ctx->ev_dn[k + 1]));
+        HIPCHK(hipEventElapsedTime(&t, ctx->ev_dn[k].handle(), ctx->ev_dn[k + 1].handle()));
         // events 0..2 bracket prepare and variance, the last pair the finalise kernel
         ctx->dn_ms[k + 2 == e ? 10 : k] = t;
         total += t;
@@ -2214,7 +2157,7 @@ int render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoi
     ask.moment = sample_variance;
     const FramePlan plan = plan_frame(ask, PlanRules::Frame);
     const int n = sample_variance ? 5 : 4;
-    const FrameRequest rq(&c0->d_dn_img, &c0->cap_dn_img, (uint32_t)n);
+    const FrameRequest rq(&c0->d_dn_img, (uint32_t)n);
     if ((rc = render_frame(ctx, p, plan, rq, stats))) return rc;
     RenderTimer timer(stats);  // render_ms covers the whole call
     nart_session_geometry g;
@@ -2292,8 +2235,6 @@ int cascade_device(nart_ctx* ctx, const nart_render_params* p, const nart_cascad
     HIPCHK(hipSetDevice(ctx->device));
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
-    for (auto& e : ctx->ev_cas)
-        if (!e) HIPCHK(hipEventCreate(&e));
     CascadeReweightArgs a;
     a.beauty = d_beauty;
     a.layers = d_layers;
@@ -2307,16 +2248,16 @@ int cascade_device(nart_ctx* ctx, const nart_render_params* p, const nart_cascad
     a.N = (float)p->spp;
     a.kappa = cp.kappa;
     for (uint32_t j = 0; j < CASCADE_MAX_LAYERS; ++j) a.b[j] = j < lv.K ? lv.b[j] : 0.f;
-    HIPCHK(hipEventRecord(ctx->ev_cas[0], st));
+    HIPCHK(record(ctx->ev_cas[0], st));
     // the border stays zero: the kernel writes the cropped pixels only
     HIPCHK(hipMemsetAsync(d_out, 0, (size_t)g.total_width * g.total_height * sizeof(nart_pixel), st));
     const dim3 grid((a.W + CS_TW - 1) / CS_TW, (a.H + CS_TH - 1) / CS_TH), block(CS_TW * CS_TH);
     hipLaunchKernelGGL(k_cascade_reweight, grid, block, (size_t)lv.K * CS_PLANE * sizeof(float), st, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev_cas[1], st));
-    HIPCHK(hipEventSynchronize(ctx->ev_cas[1]));
+    HIPCHK(record(ctx->ev_cas[1], st));
+    HIPCHK(hipEventSynchronize(ctx->ev_cas[1].handle()));
     float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, ctx->ev_cas[0], ctx->ev_cas[1]));
+    HIPCHK(hipEventElapsedTime(&t, ctx->ev_cas[0].handle(), ctx->ev_cas[1].handle()));
     ctx->cas_ms[1] = t;
     return NART_OK;
 }
@@ -2326,23 +2267,16 @@ int cascade_device(nart_ctx* ctx, const nart_render_params* p, const nart_cascad
 // call returns, so that a later render finds the free memory (batch_slot_limit) it found before.
 struct TileGrowthGuard {
     nart_ctx* ctx;
-    size_t gather_cap;
-    std::vector<size_t> sub_cap;
-    explicit TileGrowthGuard(nart_ctx* c) : ctx(c), gather_cap(c->cap_gather), sub_cap(c->sub_cap) {}
+    size_t gather_bytes;
+    std::vector<size_t> sub_bytes;
+    explicit TileGrowthGuard(nart_ctx* c) : ctx(c), gather_bytes(c->d_gather.bytes()) {
+        for (const Buf& b : c->sub_tiles) sub_bytes.push_back(b.bytes());
+    }
     TileGrowthGuard(const TileGrowthGuard&) = delete;
     ~TileGrowthGuard() {
-        const int dev0 = ctx->subs.empty() ? ctx->device : ctx->devs[0];
-        if (ctx->cap_gather > gather_cap && hipSetDevice(dev0) == hipSuccess) {
-            hipFree(ctx->d_gather);
-            ctx->d_gather = nullptr;
-            ctx->cap_gather = 0;
-        }
-        for (size_t d = 0; d < sub_cap.size(); ++d)
-            if (ctx->sub_cap[d] > sub_cap[d] && hipSetDevice(ctx->devs[d]) == hipSuccess) {
-                hipFree(ctx->sub_tiles[d]);
-                ctx->sub_tiles[d] = nullptr;
-                ctx->sub_cap[d] = 0;
-            }
+        if (ctx->d_gather.bytes() > gather_bytes) ctx->d_gather.release();
+        for (size_t d = 0; d < sub_bytes.size(); ++d)
+            if (ctx->sub_tiles[d].bytes() > sub_bytes[d]) ctx->sub_tiles[d].release();
     }
 };
 
@@ -2359,13 +2293,12 @@ int render_cascade(nart_ctx* ctx, const nart_render_params* p, const nart_cascad
     nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];
     ctx->cas_ms[0] = ctx->cas_ms[1] = 0.0;
     TileGrowthGuard guard(ctx);
-    ScopedDeviceBufs imgs;  // the device images of the call, on device 0
-    size_t imgs_cap = 0;
+    Buf imgs;  // the device images of the call, on device 0; freed on return
     const uint32_t K = lv.K;
     FrameAsk ask(p->integrator);
     ask.cascade = lv;
     const FramePlan plan = plan_frame(ask, PlanRules::Frame);
-    const FrameRequest rq(&imgs.p[0], &imgs_cap, K + 2);  // the beauty, the layers, the robust image
+    const FrameRequest rq(&imgs, K + 2);  // the beauty, the layers, the robust image
     PassTimes times;
     int rc = render_frame(ctx, p, plan, rq, stats, &times);
     ctx->cas_ms[0] = times.ms[PASS_CASCADE];
@@ -2375,9 +2308,9 @@ int render_cascade(nart_ctx* ctx, const nart_render_params* p, const nart_cascad
     nart_session_geometry_of(p, &g);
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
     // the plan's images back to back (the layers follow one another), the robust image after them
-    float* d_beauty = static_cast<float*>(imgs.p[0]) + (size_t)plan.find(OutputKind::Beauty) * img_floats;
-    float* d_layers = static_cast<float*>(imgs.p[0]) + (size_t)plan.find(OutputKind::Layer, 0) * img_floats;
-    float* d_out = static_cast<float*>(imgs.p[0]) + (size_t)plan.n_outputs * img_floats;
+    float* d_beauty = imgs.as<float>() + (size_t)plan.find(OutputKind::Beauty) * img_floats;
+    float* d_layers = imgs.as<float>() + (size_t)plan.find(OutputKind::Layer, 0) * img_floats;
+    float* d_out = imgs.as<float>() + (size_t)plan.n_outputs * img_floats;
     if ((rc = cascade_device(c0, p, cp, lv, d_beauty, d_layers, d_out, 0))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
     ctx->cas_ms[1] = c0->cas_ms[1];
     HIPCHK(hipSetDevice(c0->device));
@@ -2402,9 +2335,9 @@ int cascade_host(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_
     nart_session_geometry_of(p, &g);
     const uint32_t K = lv.K;
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
-    ScopedDeviceBufs imgs;  // the beauty, the layers, the robust image
-    if (int rc = dmalloc(ctx, &imgs.p[0], (size_t)(K + 2) * img_bytes, "cascade images")) return rc;
-    float* d = static_cast<float*>(imgs.p[0]);
+    Buf imgs;  // the beauty, the layers, the robust image; freed on return
+    if (int rc = reserve(ctx, imgs, ctx->device, (size_t)(K + 2) * img_bytes, "cascade images")) return rc;
+    float* d = imgs.as<float>();
     float* d_out = d + (size_t)(K + 1) * img_floats;
     HIPCHK(hipMemcpy(d, beauty, img_bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d + img_floats, layers, (size_t)K * img_bytes, hipMemcpyHostToDevice));
@@ -2435,8 +2368,6 @@ int matte_rank_device(nart_ctx* ctx, const nart_render_params* p, uint32_t n_ids
     HIPCHK(hipSetDevice(ctx->device));
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
-    for (auto& e : ctx->ev_mat)
-        if (!e) HIPCHK(hipEventCreate(&e));
     MatteRankArgs a;
     a.planes = d_planes;
     a.out = d_ranks;
@@ -2447,17 +2378,17 @@ int matte_rank_device(nart_ctx* ctx, const nart_render_params* p, uint32_t n_ids
     a.fb = g.filter_bounds;
     a.n_ids = n_ids;
     a.R = R;
-    HIPCHK(hipEventRecord(ctx->ev_mat[0], st));
+    HIPCHK(record(ctx->ev_mat[0], st));
     // the border stays zero: the kernel writes the cropped pixels only
     HIPCHK(hipMemsetAsync(d_ranks, 0, (size_t)(R / 2) * g.total_width * g.total_height * sizeof(nart_pixel), st));
     const dim3 grid((a.W + MT_TW - 1) / MT_TW, (a.H + MT_TH - 1) / MT_TH), block(MT_LANES);
     const size_t lds = (size_t)((n_ids + 3) / 4) * 4 * MT_LANES * sizeof(float);
     hipLaunchKernelGGL(k_matte_rank, grid, block, lds, st, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev_mat[1], st));
-    HIPCHK(hipEventSynchronize(ctx->ev_mat[1]));
+    HIPCHK(record(ctx->ev_mat[1], st));
+    HIPCHK(hipEventSynchronize(ctx->ev_mat[1].handle()));
     float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, ctx->ev_mat[0], ctx->ev_mat[1]));
+    HIPCHK(hipEventElapsedTime(&t, ctx->ev_mat[0].handle(), ctx->ev_mat[1].handle()));
     ctx->mat_ms[1] = t;
     return NART_OK;
 }
@@ -2477,10 +2408,9 @@ int render_mattes(nart_ctx* ctx, const nart_render_params* p, const nart_matte_p
     const FramePlan plan = plan_frame(ask, PlanRules::Frame);
     if (plan.code) return fail(ctx, plan.code, plan.message);  // (before anything is allocated)
     TileGrowthGuard guard(ctx);
-    ScopedDeviceBufs imgs;  // the device images of the call, on device 0
-    size_t imgs_cap = 0;
+    Buf imgs;  // the device images of the call, on device 0; freed on return
     const uint32_t n_ids = ask.matte.n_ids, P = ask.matte.planes(), R = mp.ranks;
-    const FrameRequest rq(&imgs.p[0], &imgs_cap, plan.n_outputs + R / 2);  // the beauty, the planes, the rank images
+    const FrameRequest rq(&imgs, plan.n_outputs + R / 2);  // the beauty, the planes, the rank images
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
@@ -2492,11 +2422,11 @@ int render_mattes(nart_ctx* ctx, const nart_render_params* p, const nart_matte_p
         if (rc) return rc;
     } else {
         if ((rc = check_params(c0, p))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
-        if ((rc = ensure_dev(ctx, c0->device, imgs.p[0], imgs_cap, (size_t)(R / 2) * img_bytes, "image"))) return rc;
+        if ((rc = reserve(ctx, imgs, c0->device, (size_t)(R / 2) * img_bytes, "image"))) return rc;
     }
     RenderTimer timer(stats);  // render_ms covers the whole call
     // the plan's images back to back (the planes follow one another), the rank images after them
-    float* d = static_cast<float*>(imgs.p[0]);
+    float* d = imgs.as<float>();
     float* d_planes = P ? d + (size_t)plan.find(OutputKind::Plane, 0) * img_floats : nullptr;
     float* d_ranks = d + (size_t)plan.n_outputs * img_floats;
     if ((rc = matte_rank_device(c0, p, n_ids, R, d_planes, d_ranks, 0)))
@@ -2524,9 +2454,9 @@ int matte_rank_host(nart_ctx* ctx, const nart_render_params* p, const nart_matte
     nart_session_geometry_of(p, &g);
     const uint32_t P = (n_ids + 3) / 4, R = mp.ranks;
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
-    ScopedDeviceBufs imgs;  // the planes, the rank images
-    if (int rc = dmalloc(ctx, &imgs.p[0], (size_t)(P + R / 2) * img_bytes, "matte images")) return rc;
-    float* d = static_cast<float*>(imgs.p[0]);
+    Buf imgs;  // the planes, the rank images; freed on return
+    if (int rc = reserve(ctx, imgs, ctx->device, (size_t)(P + R / 2) * img_bytes, "matte images")) return rc;
+    float* d = imgs.as<float>();
     float* d_ranks = d + (size_t)P * img_floats;
     if (P) HIPCHK(hipMemcpy(d, planes, (size_t)P * img_bytes, hipMemcpyHostToDevice));
     if (int rc = matte_rank_device(ctx, p, n_ids, R, P ? d : nullptr, d_ranks, 0)) return rc;
@@ -2546,9 +2476,9 @@ int matte_extract_host(nart_ctx* ctx, const nart_render_params* p, const nart_ma
     nart_session_geometry_of(p, &g);
     const uint32_t R = mp.ranks;
     const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
-    ScopedDeviceBufs imgs;  // the rank images, the matte
-    if (int rc = dmalloc(ctx, &imgs.p[0], (size_t)(R / 2 + 1) * img_bytes, "matte images")) return rc;
-    float* d = static_cast<float*>(imgs.p[0]);
+    Buf imgs;  // the rank images, the matte; freed on return
+    if (int rc = reserve(ctx, imgs, ctx->device, (size_t)(R / 2 + 1) * img_bytes, "matte images")) return rc;
+    float* d = imgs.as<float>();
     float* d_out = d + (size_t)(R / 2) * img_floats;
     HIPCHK(hipMemcpy(d, ranks, (size_t)(R / 2) * img_bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemsetAsync(d_out, 0, img_bytes, 0));  // the border stays zero
@@ -2641,7 +2571,7 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
     }
     int rc = NART_OK;
     auto bail = [&](int code) {
-        nart_hip_destroy(ctx);
+        delete ctx;
         return code;
     };
     if (hipSetDevice(device_id) != hipSuccess) return bail(NART_E_HIP);
@@ -2669,7 +2599,7 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
     // hit points deviate from the reference's slab arithmetic by far less than 2^-14 * scene
     // scale (|o| + |t d| <= 3 * maxabs, errors of a few ulps): octree.h oc_clear
     const float pad = maxabs * 6.103515625e-05f + 1e-6f, margin = maxabs * 6.103515625e-05f;
-    if ((rc = upload(ctx, ctx->d_tris, blob->triangles, blob->num_triangles))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_tris, blob->triangles, blob->num_triangles, "triangles"))) return bail(rc);
     // NART_BVH_BUILD=device: linear BVH built on the GPU (device/lbvh.h); default: binned SAH on
     // the host (host/bvh_build.cpp) -- same node / record format, same images
     const char* bb = env_opt("NART_BVH_BUILD");
@@ -2686,11 +2616,12 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
         lb.num_nodes = (uint32_t)bvh.nodes.size();
         lb.root_code = bvh.root_code;
         lb.num_leaf_tris = (uint32_t)(bvh.tri_isect.size() / 16);
-        if ((rc = upload(ctx, ctx->d_nodes, bvh.nodes.data(), bvh.nodes.size()))) return bail(rc);
-        if ((rc = upload(ctx, ctx->d_tri_isect, bvh.tri_isect.data(), bvh.tri_isect.size()))) return bail(rc);
+        if ((rc = upload(ctx, ctx->d_nodes, bvh.nodes.data(), bvh.nodes.size(), "BVH nodes"))) return bail(rc);
+        if ((rc = upload(ctx, ctx->d_tri_isect, bvh.tri_isect.data(), bvh.tri_isect.size(), "triangle records")))
+            return bail(rc);
         std::vector<float> perm;
         permute_tri_records(bvh.tri_isect, perm);
-        if ((rc = upload(ctx, ctx->d_tri_perm, perm.data(), perm.size()))) return bail(rc);
+        if ((rc = upload(ctx, ctx->d_tri_perm, perm.data(), perm.size(), "permuted triangle records"))) return bail(rc);
     }
     ctx->bvh_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
     ctx->stack_depth = std::max<uint32_t>(lb.max_stack + 1, 2);
@@ -2707,8 +2638,8 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
         for (uint32_t i = 0; i < blob->meshes[m].num_tris; ++i) tri_mesh[blob->meshes[m].first_tri + i] = m;
     }
     if (blob->num_meshes >= (1u << 24)) return bail(NART_E_UNSUPPORTED);
-    if ((rc = upload(ctx, ctx->d_tri_mesh, tri_mesh.data(), tri_mesh.size()))) return bail(rc);
-    if ((rc = upload(ctx, ctx->d_meshes, meshes.data(), meshes.size()))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_tri_mesh, tri_mesh.data(), tri_mesh.size(), "triangle meshes"))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_meshes, meshes.data(), meshes.size(), "meshes"))) return bail(rc);
     ctx->num_meshes = blob->num_meshes;
     ctx->num_materials = blob->num_materials;
     std::vector<DMaterial> mats(blob->num_materials);
@@ -2724,7 +2655,7 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
         d.alpha = dpat(m.alpha);
         d.normal = dpat(m.normal);
     }
-    if ((rc = upload(ctx, ctx->d_mats, mats.data(), mats.size()))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_mats, mats.data(), mats.size(), "materials"))) return bail(rc);
     // per mesh: bxdf_eta of its one-lobe constant-pattern BSDF (the compact dielectric list,
     // kernels.h IList): B_LAMBERT -> 0, every other one-lobe kind -> the material's eta value
     std::vector<float> mesh_eta(blob->num_meshes);
@@ -2732,7 +2663,7 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
         const uint32_t mi = blob->meshes[m].material;
         mesh_eta[m] = (mi >= mats.size() || mats[mi].type == NART_MAT_LAMBERT) ? 0.f : mats[mi].eta.v[0];
     }
-    if ((rc = upload(ctx, ctx->d_mesh_eta, mesh_eta.data(), mesh_eta.size()))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_mesh_eta, mesh_eta.data(), mesh_eta.size(), "mesh etas"))) return bail(rc);
     std::vector<DLight> lights;
     std::vector<DEnvDist> envs;
     for (uint32_t l = 0; l < blob->num_lights; ++l) {
@@ -2746,8 +2677,8 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
             envs.push_back(d);
         }
     }
-    if ((rc = upload(ctx, ctx->d_envs, envs.data(), envs.size()))) return bail(rc);
-    if ((rc = upload(ctx, ctx->d_lights, lights.data(), lights.size()))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_envs, envs.data(), envs.size(), "environment distributions"))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_lights, lights.data(), lights.size(), "lights"))) return bail(rc);
     ctx->features = scene_features(blob);
     std::vector<DTexture> texs(blob->num_textures);
     size_t pool = 0;
@@ -2760,23 +2691,23 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
     std::vector<uint16_t> tex_pool(pool ? pool : 1);
     for (uint32_t t = 0; t < blob->num_textures; ++t)
         std::memcpy(&tex_pool[texs[t].offset], blob->textures[t].rgba, (size_t)texs[t].w * texs[t].h * 8);
-    if ((rc = upload(ctx, ctx->d_texs, texs.data(), texs.size()))) return bail(rc);
-    if ((rc = upload(ctx, ctx->d_tex_pool, tex_pool.data(), tex_pool.size()))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_texs, texs.data(), texs.size(), "textures"))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_tex_pool, tex_pool.data(), tex_pool.size(), "texels"))) return bail(rc);
 
     DScene& S = ctx->scene;
     std::memset(&S, 0, sizeof(S));
-    S.nodes = (const BVHNode*)ctx->d_nodes;
-    S.tri_isect = (const float4*)ctx->d_tri_isect;
-    S.tri_perm = (const float4*)ctx->d_tri_perm;
-    S.tris = (const nart_triangle*)ctx->d_tris;
-    S.tri_mesh = (const uint32_t*)ctx->d_tri_mesh;
-    S.meshes = (const DMesh*)ctx->d_meshes;
-    S.mats = (const DMaterial*)ctx->d_mats;
-    S.mesh_eta = (const float*)ctx->d_mesh_eta;
-    S.lights = (const DLight*)ctx->d_lights;
-    S.texs = (const DTexture*)ctx->d_texs;
-    S.tex_pool = (const uint16_t*)ctx->d_tex_pool;
-    S.envs = (const DEnvDist*)ctx->d_envs;
+    S.nodes = ctx->d_nodes.as<const BVHNode>();
+    S.tri_isect = ctx->d_tri_isect.as<const float4>();
+    S.tri_perm = ctx->d_tri_perm.as<const float4>();
+    S.tris = ctx->d_tris.as<const nart_triangle>();
+    S.tri_mesh = ctx->d_tri_mesh.as<const uint32_t>();
+    S.meshes = ctx->d_meshes.as<const DMesh>();
+    S.mats = ctx->d_mats.as<const DMaterial>();
+    S.mesh_eta = ctx->d_mesh_eta.as<const float>();
+    S.lights = ctx->d_lights.as<const DLight>();
+    S.texs = ctx->d_texs.as<const DTexture>();
+    S.tex_pool = ctx->d_tex_pool.as<const uint16_t>();
+    S.envs = ctx->d_envs.as<const DEnvDist>();
     if ((rc = build_medium(ctx, blob->medium, S.medium))) return bail(rc);
     S.num_lights = blob->num_lights;
     S.num_tris = blob->num_triangles;
@@ -2789,14 +2720,14 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
     // reference octree + replay heap pool: entries of 64 heaps (one per lane of a replaying
     // wave, octree.h oc_replay), held only while a wave replays; up to 512 entries within 256 MiB
     // (NART_OC_POOL overrides the count: tests force a single entry)
-    if ((rc = upload(ctx, ctx->d_oc_nodes, oct.nodes.data(), oct.nodes.size()))) return bail(rc);
-    if ((rc = upload(ctx, ctx->d_oc_chunks, oct.chunks.data(), oct.chunks.size()))) return bail(rc);
-    if ((rc = upload(ctx, ctx->d_oc_tris, oct.tris.data(), oct.tris.size()))) return bail(rc);
-    if ((rc = upload(ctx, ctx->d_tri_leaf, oct.tri_leaf.data(), oct.tri_leaf.size()))) return bail(rc);
-    S.oc_nodes = (const OcNode*)ctx->d_oc_nodes;
-    S.oc_chunks = (const uint32_t*)ctx->d_oc_chunks;
-    S.oc_tris = (const uint32_t*)ctx->d_oc_tris;
-    S.tri_leaf = (const int32_t*)ctx->d_tri_leaf;
+    if ((rc = upload(ctx, ctx->d_oc_nodes, oct.nodes.data(), oct.nodes.size(), "octree nodes"))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_oc_chunks, oct.chunks.data(), oct.chunks.size(), "octree chunks"))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_oc_tris, oct.tris.data(), oct.tris.size(), "octree triangles"))) return bail(rc);
+    if ((rc = upload(ctx, ctx->d_tri_leaf, oct.tri_leaf.data(), oct.tri_leaf.size(), "triangle leaves"))) return bail(rc);
+    S.oc_nodes = ctx->d_oc_nodes.as<const OcNode>();
+    S.oc_chunks = ctx->d_oc_chunks.as<const uint32_t>();
+    S.oc_tris = ctx->d_oc_tris.as<const uint32_t>();
+    S.tri_leaf = ctx->d_tri_leaf.as<const int32_t>();
     S.oc_root = oct.root;
     S.oc_cap = (uint32_t)std::max<size_t>(oct.nodes.size(), 1);
     S.oc_pool = (uint32_t)std::max<size_t>(1, std::min<size_t>(512, (256ull << 20) / (64ull * 8ull * S.oc_cap)));
@@ -2805,57 +2736,23 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
     S.oc_exact = 1;
     // NART_OCTREE_EXACT: 0 off (A/B timing only), 2 every query replays the octree search (tests)
     if (const char* v = env_opt("NART_OCTREE_EXACT")) S.oc_exact = std::max(0, std::min(2, std::atoi(v)));
-    if (hipMalloc(&ctx->d_oc_lock, sizeof(uint32_t) * S.oc_pool) != hipSuccess ||
-        hipMemset(ctx->d_oc_lock, 0, sizeof(uint32_t) * S.oc_pool) != hipSuccess ||
-        hipMalloc(&ctx->d_oc_heap, sizeof(unsigned long long) * 64 * S.oc_pool * S.oc_cap) != hipSuccess)
+    if (reserve(ctx, ctx->d_oc_lock, ctx->device, sizeof(uint32_t) * S.oc_pool, "octree replay locks") ||
+        hipMemset(ctx->d_oc_lock.as<void>(), 0, sizeof(uint32_t) * S.oc_pool) != hipSuccess ||
+        reserve(ctx, ctx->d_oc_heap, ctx->device, sizeof(unsigned long long) * 64 * S.oc_pool * S.oc_cap,
+                "octree replay heaps"))
         return bail(NART_E_OOM);
-    S.oc_lock = (uint32_t*)ctx->d_oc_lock;
-    S.oc_heap = (unsigned long long*)ctx->d_oc_heap;
+    S.oc_lock = ctx->d_oc_lock.as<uint32_t>();
+    S.oc_heap = ctx->d_oc_heap.as<unsigned long long>();
     *out = ctx;
     return NART_OK;
 }
 
+// The context's buffers, events and streams free themselves (host/device_buf.h).
 void nart_hip_destroy(nart_ctx* ctx) {
     if (!ctx) return;
-    if (!ctx->subs.empty()) {  // multi-device context
-        const RcclApi& R = rccl_api();
-        for (ncclComm_t c : ctx->comms)
-            if (c && R.ok) R.CommDestroy(c);
-        for (size_t d = 0; d < ctx->subs.size(); ++d) {
-            hipSetDevice(ctx->devs[d]);
-            if (d < ctx->sub_tiles.size() && ctx->sub_tiles[d]) hipFree(ctx->sub_tiles[d]);
-            if (d < ctx->streams.size() && ctx->streams[d]) hipStreamDestroy(ctx->streams[d]);
-        }
-        hipSetDevice(ctx->devs[0]);
-        free_frame_buffers(ctx);
-        for (nart_ctx* c : ctx->subs) nart_hip_destroy(c);
-        delete ctx;
-        return;
-    }
-    hipSetDevice(ctx->device);
-    void* bufs[] = {ctx->d_nodes, ctx->d_tri_isect, ctx->d_tri_perm, ctx->d_tris, ctx->d_tri_mesh, ctx->d_meshes, ctx->d_mesh_eta, ctx->d_mats,
-                    ctx->d_lights, ctx->d_texs, ctx->d_tex_pool, ctx->d_slot_xy, ctx->d_slot_so, ctx->d_rng, ctx->d_samples, ctx->d_prim,
-                    ctx->d_L, ctx->d_bucket_ids, ctx->d_bucket_base, ctx->d_table, ctx->d_lut, ctx->d_counters, ctx->d_envs, ctx->d_density,
-                    ctx->d_oc_nodes, ctx->d_oc_chunks, ctx->d_oc_tris, ctx->d_tri_leaf, ctx->d_oc_lock, ctx->d_oc_heap,
-                    ctx->d_queue, ctx->d_cost, ctx->d_keys[0], ctx->d_keys[1], ctx->d_vals[0], ctx->d_vals[1],
-                    ctx->d_qhead, ctx->d_sort_tmp, ctx->d_ilist, ctx->d_gstack};
-    for (void* b : bufs)
-        if (b) hipFree(b);
-    free_frame_buffers(ctx);
-    for (auto& e : ctx->ev_dn)
-        if (e) hipEventDestroy(e);
-    for (void* b : ctx->env_bufs) hipFree(b);
-    if (ctx->events)
-        for (auto& e : ctx->ev) hipEventDestroy(e);
-    for (auto& pair : ctx->ev_pass)
-        for (auto& e : pair)
-            if (e) hipEventDestroy(e);
-    for (auto& e : ctx->ev_ad)
-        if (e) hipEventDestroy(e);
-    for (auto& e : ctx->ev_cas)
-        if (e) hipEventDestroy(e);
-    for (auto& e : ctx->ev_mat)
-        if (e) hipEventDestroy(e);
+    for (ncclComm_t c : ctx->comms)
+        if (c && rccl_api().ok) rccl_api().CommDestroy(c);
+    for (nart_ctx* c : ctx->subs) nart_hip_destroy(c);
     delete ctx;
 }
 
@@ -3130,11 +3027,11 @@ int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint
     const size_t ns = (size_t)ra.n_slots * p->spp;
     std::vector<float> rec(ns * 4);
     for (int k = 0; k < 2; ++k) {
-        if ((rc = launch_aov(ctx, ra, k, ctx->d_L, 0))) return rc;
-        HIPCHK(hipMemcpy(rec.data(), ctx->d_L, ns * sizeof(float4), hipMemcpyDeviceToHost));
+        if ((rc = launch_aov(ctx, ra, k, ctx->d_L.as<float4>(), 0))) return rc;
+        HIPCHK(hipMemcpy(rec.data(), ctx->d_L.as<float4>(), ns * sizeof(float4), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < ns; ++i) std::memcpy(out8 + i * 8 + 4 * k, rec.data() + i * 4, 4 * sizeof(float));
     }
-    if (tri) HIPCHK(hipMemcpy(tri, ctx->d_prim, ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (tri) HIPCHK(hipMemcpy(tri, ctx->d_prim.as<uint32_t>(), ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return NART_OK;
 }
 
@@ -3183,13 +3080,13 @@ int nart_hip_render_device(nart_ctx* ctx, const nart_render_params* p, const nar
                            nart_render_stats* stats) {
     if (!ctx || !p || !d_image) return NART_E_INVALID;
     // tiles gathered to device 0 and combined there (a multi-device context), into the context's image
-    const FrameRequest rq(&ctx->d_image, &ctx->cap_image, 0);
+    const FrameRequest rq(&ctx->d_image, 0);
     if (int rc = render_frame(ctx, p, plan_frame(FrameAsk(p->integrator), PlanRules::Frame), rq, stats)) return rc;
     if (ctx->subs.empty()) {  // (a multi-device frame has waited for its gather stream)
         RenderTimer timer(stats);
         if (hipStreamSynchronize(0) != hipSuccess) return fail(ctx, NART_E_HIP, "render");
     }
-    *d_image = static_cast<const nart_pixel*>(ctx->d_image);
+    *d_image = ctx->d_image.as<const nart_pixel>();
     return NART_OK;
 }
 
@@ -3203,13 +3100,13 @@ int nart_hip_render_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t
     int rc = check_params(ctx, p);
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t n_cnt = 24;
-    if (!ctx->d_counters) HIPCHK(hipMalloc(&ctx->d_counters, n_cnt * sizeof(unsigned long long)));
-    if (ctx->counters) HIPCHK(hipMemset(ctx->d_counters, 0, n_cnt * sizeof(unsigned long long)));
+    if ((rc = counter_buffer(ctx))) return rc;
+    unsigned long long* const d_counters = ctx->d_counters.as<unsigned long long>();
+    if (ctx->counters) HIPCHK(hipMemset(d_counters, 0, ctx->d_counters.bytes()));
     RenderArgs ra;
-    if ((rc = rect_slots(ctx, p, x0, y0, w, h, ctx->d_counters, ra))) return rc;
+    if ((rc = rect_slots(ctx, p, x0, y0, w, h, d_counters, ra))) return rc;
     if ((rc = launch_latin(ctx, ra, 0)) || (rc = dispatch_render(ctx, ra, p->integrator, 0))) return rc;
-    HIPCHK(hipMemcpy(out, ctx->d_L, (size_t)ra.n_slots * p->spp * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, ctx->d_L.as<float4>(), (size_t)ra.n_slots * p->spp * sizeof(float4), hipMemcpyDeviceToHost));
     return NART_OK;
 }
 
@@ -3275,9 +3172,10 @@ int nart_hip_context_bvh_dump(const nart_ctx* ctx, nart_bvh_dump_info* info, voi
     if (hipSetDevice(c->device) != hipSuccess) return NART_E_HIP;
     const size_t nt = info->num_leaf_tris;
     if ((info->num_nodes &&
-         hipMemcpy(nodes, c->d_nodes, (size_t)info->num_nodes * sizeof(BVHNode), hipMemcpyDeviceToHost) != hipSuccess) ||
-        (nt && (hipMemcpy(tri_isect, c->d_tri_isect, nt * 64, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(tri_perm, c->d_tri_perm, nt * 3 * 64, hipMemcpyDeviceToHost) != hipSuccess))) {
+         hipMemcpy(nodes, c->d_nodes.as<void>(), (size_t)info->num_nodes * sizeof(BVHNode), hipMemcpyDeviceToHost) !=
+             hipSuccess) ||
+        (nt && (hipMemcpy(tri_isect, c->d_tri_isect.as<void>(), nt * 64, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(tri_perm, c->d_tri_perm.as<void>(), nt * 3 * 64, hipMemcpyDeviceToHost) != hipSuccess))) {
         (void)hipGetLastError();
         return NART_E_HIP;
     }
@@ -3316,18 +3214,16 @@ int nart_hip_eval_sincos(nart_ctx* ctx, const float* x, uint32_t n, float* s, fl
     if (!ctx || !x || !s || !c) return NART_E_INVALID;
     if (!ctx->subs.empty()) return nart_hip_eval_sincos(ctx->subs[0], x, n, s, c);
     HIPCHK(hipSetDevice(ctx->device));
-    float *dx = nullptr, *ds = nullptr, *dc = nullptr;
-    HIPCHK(hipMalloc(&dx, (size_t)n * 4 + 4));
-    HIPCHK(hipMalloc(&ds, (size_t)n * 4 + 4));
-    HIPCHK(hipMalloc(&dc, (size_t)n * 4 + 4));
+    Buf bx, bs, bc;  // freed on return
+    int rc = NART_OK;
+    for (Buf* b : {&bx, &bs, &bc})
+        if ((rc = reserve(ctx, *b, ctx->device, (size_t)n * 4 + 4, "sincos values"))) return rc;
+    float *const dx = bx.as<float>(), *const ds = bs.as<float>(), *const dc = bc.as<float>();
     HIPCHK(hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_sincos, dim3((n + 255) / 256), dim3(256), 0, 0, dx, n, ds, dc);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(s, ds, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(c, dc, (size_t)n * 4, hipMemcpyDeviceToHost));
-    hipFree(dx);
-    hipFree(ds);
-    hipFree(dc);
     return NART_OK;
 }
 
@@ -3385,12 +3281,12 @@ int nart_hip_create_multi(const nart_scene_blob* blob, const int* device_ids, in
         if (int rc = nart_hip_create(blob, device_ids[d], &sub)) return bail(rc);
         ctx->subs.push_back(sub);
         ctx->devs.push_back(device_ids[d]);
-        ctx->sub_tiles.push_back(nullptr);
-        ctx->sub_cap.push_back(0);
-        hipStream_t st = nullptr;
-        if (hipSetDevice(device_ids[d]) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess)
+        ctx->sub_tiles.emplace_back();
+        ctx->streams.emplace_back();
+        ctx->streams.back().device = device_ids[d];
+        if (hipSetDevice(device_ids[d]) != hipSuccess ||
+            hipStreamCreateWithFlags(&ctx->streams.back().s, hipStreamNonBlocking) != hipSuccess)
             return bail(NART_E_HIP);
-        ctx->streams.push_back(st);
     }
     for (int d = 0; d < n_devices; ++d)
         for (int j = 0; j < n_devices; ++j) ctx->subs[d]->mem_share += (j != d && device_ids[j] == device_ids[d]) ? 1u : 0u;
