@@ -12,15 +12,7 @@
 namespace nd {
 
 // ---------------------------------------------------------------- nested-dielectric list
-// IntersectionInfo list (pathintegrator.h:9-19, pathintegrator.cpp:7-36, 123-142).  The first
-// ILIST_REG entries live in registers (every access an unrolled compare/select, no dynamic
-// indexing); a path can only grow the list by one entry per bounce, so renders with bounces <=
-// ILIST_REG never need more.  With EXT (bounces up to 32) entries ILIST_REG.. live in a per-lane
-// column of global memory, entry k at x[(k - ILIST_REG) * xs] as {id, eta bits}: deep nesting is
-// rare, so the kernels keep the register footprint of the short list and spill nothing (the
-// former 16- and 32-entry register lists spilled 50-97 VGPRs to scratch on every access).
-#define ILIST_REG 10
-#define ILIST_MAX 32
+// The list of path_layout.h (ILIST_REG entries in registers, the rest in a per-lane global column).
 // this lane's overflow column (formed at each use: no registers held across the kernel)
 #define ILIST_X(A) (EXT ? (A).ilist_ext + (blockIdx.x * blockDim.x + threadIdx.x) : nullptr)
 // COMPACT (scenes without textures or plastic: kernels built for such a feature mask): an entry's
@@ -583,12 +575,7 @@ enum { ST_EXT = 0, ST_SH1 = 1, ST_SH2 = 2 };
 // stream.  Each loop iteration traces exactly one ray (extension or shadow) through the
 // shared traversal loop, then advances the lane's path state machine; a lane whose path
 // ends starts its next sample immediately (path regeneration), so lanes of a wave stay busy.
-// Min waves per SIMD requested from the register allocator.  Without it the allocator takes
-// >256 registers (VGPR + AGPR) once the environment-light code is inlined and the kernel drops
-// to 1 wave/SIMD (C3 at 64 spp: 260 ms vs 151 ms at 2 waves; 3 waves spills: 178 ms).
-#ifndef NART_RENDER_WAVES
-#define NART_RENDER_WAVES 2
-#endif
+// NART_RENDER_WAVES (path_layout.h): the min waves per SIMD requested from the register allocator.
 #define NART_RENDER_LB __launch_bounds__(256, NART_RENDER_WAVES)
 // (Round 5: the traversal-quorum form of this kernel -- variant 2/3, C3 whole frame 517 vs 569 ms
 // before the ray-queue kernel replaced it -- was retired; k_render is the cost probe and the
@@ -1132,30 +1119,9 @@ __global__ __launch_bounds__(256) void k_aov(DScene S, RenderArgs A, const uint3
 // samples per chain step instead of one for the costliest pixels, whose chains bound a small
 // shard; the frame is unchanged (bit-identical).
 #define RQ_PENDING 0xFFFFFFFEu
-#define RQ_RING 256u
-NHD size_t rq_lds_bytes(uint32_t stack_depth, uint32_t block) {
-    const uint32_t waves = block / 64;
-    return (size_t)stack_depth * block * 8 + (size_t)waves * 3 * 64 * 32 + (size_t)block * 16 +
-           (size_t)waves * 2 * RQ_RING;
-}
 
-// 512-thread blocks: one block of 8 waves per CU shares one copy of the staged BVH nodes (twice
-// as many nodes in LDS).  With the wave-group refill (no wave waits for its block) C3 392 vs
-// 407 ms per frame (profiles/r02m_rq_block_ab.log); before it, blocks retiring as a whole made
-// 256 faster (132.6 vs 121.5 ms at 64 spp)
-#ifndef NART_RQ_BLOCK
-#define NART_RQ_BLOCK 512
-#endif
-// The counter pass (COUNT: untimed; its path counts are per accepted sample and do not depend on the
-// schedule, its traversal counts include the speculative lanes' dropped work) runs
-// 256-lane blocks at one wave per SIMD, so its counters do not push the kernel past 256 VGPRs.
-//
-// WV = 3: the lean throughput build for launches of >= 3 rounds of resident waves (whole frames),
-// which never use priority lanes or speculative pairs: that code and its state compiled out, 768-lane
-// blocks (12 waves per CU) at three waves per SIMD; only for scenes whose specialised build fits
-// 168 VGPRs and whose traversal stack fits the block's LDS (render.hip lean_fits).
-#define RQ_BLOCK_OF(COUNT, WV) ((COUNT) ? 256 : ((WV) == 3 ? 768 : NART_RQ_BLOCK))
-//
+// Block sizes (RQ_BLOCK_OF: 512 lanes, 256 for the counter pass, 768 for the lean build WV = 3) and
+// the bytes of this layout (rq_lds_bytes): path_layout.h.
 // PR = false (with WV = 3): the lean build proper.  PR = true keeps the small-shard schedule's code
 // (priority lanes, speculative pairs, raised issue priority) at three waves per SIMD.
 template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true>

@@ -8,31 +8,14 @@
 
 #include "dmath.h"
 #include "dscene.h"
+#include "path_layout.h"
 
 namespace nd {
 
 enum { F_SPECULAR = 1, F_GLOSSY = 2, F_DIFFUSE = 4, F_TRANSMISSIVE = 8 };
 #define SHADOW_BIAS 0.001f
 
-// Scene feature mask (template parameter FM of the shading functions and k_render_rq): the
-// material, light and pattern kinds a scene holds (scene_features, render.hip).  A kernel built
-// for a mask compiles only those kinds' code -- no plastic lobes, ring lights, texture fetches or
-// normal-map frames in glassSphere's build -- and serves every scene whose mask it covers; FT_ALL
-// is the generic build.  Each kind's operations are unchanged, so every build renders the same bits.
-enum : uint32_t {
-    FT_LAMBERT = 1u << 0,   // diffusematerial.cpp
-    FT_SPECMAT = 1u << 1,   // specularmaterial.cpp
-    FT_GLASS = 1u << 2,     // glassmaterial.cpp
-    FT_GLOSSY = 1u << 3,    // glossydielectricmaterial.cpp
-    FT_PLASTIC = 1u << 4,   // plasticmaterial.cpp (the only two-lobe BSDF)
-    FT_DISK = 1u << 5,      // disklight.cpp
-    FT_RING = 1u << 6,      // ringlight.cpp
-    FT_ENV = 1u << 7,       // environmentlight.cpp
-    FT_TEX = 1u << 8,       // any TexturePattern (materials or light Le)
-    FT_NMAP = 1u << 9,      // any material with a normal map
-    FT_ALL = (1u << 10) - 1u
-};
-// BxDF kinds a mask can create (the roughening factor moves a material between its two kinds)
+// BxDF kinds a scene feature mask (FT_*, path_layout.h) can create (the roughening factor moves a material between its two kinds)
 NHD constexpr bool ft_lambert(uint32_t FM) { return (FM & (FT_LAMBERT | FT_PLASTIC)) != 0u; }
 NHD constexpr bool ft_ts(uint32_t FM) { return (FM & (FT_SPECMAT | FT_GLOSSY | FT_PLASTIC)) != 0u; }
 NHD constexpr bool ft_spec(uint32_t FM) { return ft_ts(FM); }
@@ -195,11 +178,7 @@ ND bool trav_pop1(Trav& t, const int* sc, const int2* gs, int stride, int sk = 0
 // One step: descend to the next leaf, test all its triangles, pop the next subtree.  Returns
 // true when the query is resolved (t.bestG = winner or NO_HIT).  (A one-node-or-one-triangle
 // "if-if" step measured slower on C3: 123 vs 95 ms per frame in the wavefront trace kernel.)
-// LDS-staged nodes, 64 B each (a 16-B pad after every 4 nodes measured C3 276.3 -> 282.5 ms,
-// C4 51.9 -> 51.6 ms and was retired, profiles/r05ae_node_pad_ab.txt).  node_slot: first float4 of
-// node i.
-NHD uint32_t node_slot(uint32_t i) { return 4u * i; }
-NHD size_t node_lds_bytes(uint32_t n) { return (size_t)16 * (n ? node_slot(n - 1u) + 4u : 0u); }
+// LDS-staged nodes: 64 B each, node i at float4 node_slot(i) (path_layout.h).
 // LDS quarter of 16-B part k of BVH node i (stage_nodes, kernels.h).  ROT: rotate by (i >> 2) & 3,
 // in the environment-light builds, whose larger BVHs gain from the bank spread (C4 path kernel
 // 52.1 -> 51.3 ms at 1080p/32; C3 276.2 -> 279.4 ms, so the other builds do not rotate:

@@ -176,10 +176,10 @@ ND bool maj_next(const DMedium& m, MajIter& it, float& sigma, float& t0, float& 
 // sample, a new ray segment, the next majorant segment), and a lane whose sample ends starts its
 // next sample at once, so the wave costs about max_lane sum_s(collisions).  Each lane performs
 // exactly the reference's RNG draws and float operations in its order: bit-identical.
-// WV: minimum waves per SIMD requested from the register allocator (dispatch_volume: 4 on
+// WV: minimum waves per SIMD requested from the register allocator (plan_volume: 4 on
 // throughput-bound launches, 1 on small shards)
 #ifndef NART_VOL_WV
-#define NART_VOL_WV 4  // waves per SIMD of the throughput-bound launches (dispatch_volume)
+#define NART_VOL_WV 4  // waves per SIMD of the throughput-bound launches (plan_volume)
 #endif
 template <bool COUNT, int WV>
 __global__ __launch_bounds__(256, WV) void k_render_volume_sm(DScene S, RenderArgs A) {

@@ -1,6 +1,9 @@
 // The schedule of one path-kernel launch, decided once from plain values (no HIP, no context, no
 // environment): render.hip launch_render reads the knobs and the occupancy, calls plan_path and executes
 // what it returns; tests/test_path_schedule.py compares plan_path with a restatement of the policy.
+// The volume integrator's launch is decided the same way at the end of this file (plan_volume and
+// sparse_hot_groups, executed by dispatch_volume, compared by tests/test_path_build.py); which build of
+// the path kernels runs, in host/path_build.h.
 //
 // A pixel's samples are one serial chain (its RNG stream), so a frame can finish no earlier than its
 // costliest pixels, and a wave of 64 costly pixels runs several times longer than one such pixel alone
@@ -207,6 +210,89 @@ inline PathSchedule plan_path(const PathLaunchIn& in, const SchedKnobs& kn) {
     // the size ensure_queue is called with must hold the queue
     if (s.qlen > s.queue_room) s.error = "pixel queue longer than its buffers (n + 63 W)";
     return s;
+}
+
+// ---------------------------------------------------------------- the volume integrator's launch
+// k_render_volume_sm: lanes advance one tentative collision per iteration and start their next sample
+// independently.  When the shard spans several rounds of resident waves, the costliest wave-sized pixel
+// groups (cost probe: tentative collisions of 4 samples per pixel) are launched first.
+struct VolumeIn {
+    uint32_t n_slots = 0, spp = 0;
+    uint32_t resident = 1;    // resident 256-lane blocks of the plain build, with the grid's LDS
+    uint32_t grid_cells = 0;  // cells of the medium's density grid (0: no medium)
+    bool counters = false;    // the counter pass
+    Knob sparse, sparse_f, sparse_rounds;  // test hooks: NART_VOL_SPARSE, _F, _ROUNDS
+};
+enum class VolumeBuild { Counter, FourWave, Plain };  // k_render_volume_sm<true, 1>, <false, NART_VOL_WV>, <false, 1>
+struct VolumePlan {
+    uint32_t lds_nodes = 0;  // density-grid cells read from LDS
+    VolumeBuild build = VolumeBuild::Plain;
+    uint32_t blocks = 0;      // a lane per slot, in blocks of 256
+    bool queue = false;       // cost probe, then the groups costliest first
+    uint32_t queue_room = 0;  // entries the queue buffers must hold
+    bool sparse = false;      // the sorted group keys are read back for sparse_hot_groups
+    uint32_t S = 0, W = 0;    // pixels per sparse wave; resident waves
+    double f = 0.0;           // a hot group costs >= f x the median group
+    uint32_t sched = 0;       // NART_SCHED_* bits known before the readback
+};
+
+// small density grids (C5: 2x2x2) are read from LDS (1 % faster than L1-hitting global loads); the
+// occupancy query behind VolumeIn::resident needs the figure first
+inline uint32_t volume_lds_cells(uint32_t grid_cells) { return grid_cells <= 4096u ? grid_cells : 0u; }
+
+inline VolumePlan plan_volume(const VolumeIn& in) {
+    VolumePlan v;
+    const uint32_t n = in.n_slots;
+    v.lds_nodes = volume_lds_cells(in.grid_cells);
+    v.blocks = (n + 255u) / 256u;
+    // occupancy: launches of >= 8 rounds of resident waves use the 4-waves-per-SIMD build (C5 frame,
+    // 10.5 rounds: 134 -> 122 ms); smaller ones keep the unconstrained build, whose lanes' serial
+    // chains are shorter (C5 1/2, 1/4, 1/8 shards: 79 / 74 / 71 ms vs 83 / 80 / 76 with 4 waves;
+    // profiles/r03h_vol_w4_ab.log).  (Whole blocks per resident block here and below for the sparse
+    // waves; the queue's 12 rounds count slots, rounds_of.)
+    const double block_rounds = (double)v.blocks / (double)in.resident;
+    v.build = in.counters ? VolumeBuild::Counter : (block_rounds >= 8.0 ? VolumeBuild::FourWave : VolumeBuild::Plain);
+    v.W = in.resident * 4u;  // resident waves
+    v.queue = v.blocks > in.resident && rounds_of(n, in.resident) < 12.0 && in.spp > 4u;
+    if (!v.queue) return v;
+    v.queue_room = n + 63u * v.W;
+    v.sched |= NART_SCHED_VOL_QUEUE;
+    // Sparse waves on shards of < NART_VOL_SPARSE_ROUNDS (default 2) rounds of resident
+    // waves: the costliest groups (probe cost >= NART_VOL_SPARSE_F (4) x the median group's)
+    // spread NART_VOL_SPARSE (16) pixels per wave, the other lanes idle.  A wave executes
+    // the union of its lanes' divergent chains, and a frame's costliest volume pixels
+    // cluster: C5's centre pixels take 30 ms alone at 1,024 spp, 69 ms as a wave of 64.
+    // C5 1/8 shard 73.7 -> 65.3 ms; on larger shards (2+ rounds) the mostly idle sparse
+    // waves hold slots the other groups need (1/2 shard 78 -> 127 ms), and 1-8 pixels per
+    // wave measured worse (profiles/r04h_c5_sparse.log).  Only the order of work changes.
+    v.S = (uint32_t)std::max(1.0, std::min(64.0, in.sparse.or_(16.0)));
+    v.f = in.sparse_f.or_(4.0);
+    v.sparse = v.S < 64u && (64u % v.S) == 0u && block_rounds < in.sparse_rounds.or_(2.0);
+    return v;
+}
+
+// The sparse part of the volume queue, from the cost-sorted group keys read back from the device
+// (k_group_keys: 0xFFFFFFFE - cost, ascending; 0xFFFFFFFF for a partial last group, which is no
+// candidate): the H costliest groups, those of at least f x the median group's cost, as many as the
+// queue's room beyond n (63 W entries, VolumePlan::queue_room) lets spread S pixels per wave.
+struct SparseGroups {
+    uint32_t H = 0;     // hot groups (0: the dense queue stays)
+    uint32_t qlen = 0;  // queue entries with them spread
+    uint32_t grid = 0;  // blocks of 256 lanes of the launch
+};
+inline SparseGroups sparse_hot_groups(const uint32_t* keys, uint32_t ng, double f, uint32_t S, uint32_t W, uint32_t n) {
+    SparseGroups g;
+    g.grid = (n + 255u) / 256u;
+    uint32_t full = 0;  // whole groups: their costs, 0xFFFFFFFE - key, descend
+    while (full < ng && keys[full] != 0xFFFFFFFFu) ++full;
+    if (!full) return g;
+    const double med = 0xFFFFFFFEu - keys[full / 2u];
+    while (g.H < full && (double)(0xFFFFFFFEu - keys[g.H]) >= f * med) ++g.H;
+    g.H = std::min<uint32_t>(g.H, 63u * W / (64u / S * 64u));
+    if (!g.H) return g;
+    g.qlen = g.H * (64u / S) * 64u + (n - 64u * g.H);
+    g.grid = (g.qlen + 255u) / 256u;
+    return g;
 }
 
 }  // namespace nd

@@ -26,6 +26,7 @@
 #include "host/bvh_build.h"
 #include "host/device_buf.h"
 #include "host/frame_plan.h"
+#include "host/path_build.h"
 #include "host/path_schedule.h"
 
 using namespace nd;
@@ -70,7 +71,7 @@ struct nart_ctx {
     uint32_t features = FT_ALL;  // scene feature mask (scene_features): selects the k_render_rq build
     bool specialize = true;      // nart_hip_set_specialize: scene-specialised path kernels
     uint32_t fm_used = FT_ALL;   // the feature mask of the last path-kernel build launched
-    bool lean = true;            // the three-waves-per-SIMD build where it fits (lean_fits)
+    bool lean = true;            // the three-waves-per-SIMD build where it fits (plan_build)
     // scene buffers
     Buf d_nodes, d_tri_isect, d_tri_perm, d_tris, d_tri_mesh, d_meshes;
     Buf d_mesh_eta;  // DScene::mesh_eta
@@ -548,23 +549,6 @@ int ensure_gstack(nart_ctx* ctx, size_t threads, uint32_t levels, RenderArgs& a)
     return rc;
 }
 
-// LDS of one k_render block: traversal stack + as many top BVH nodes as fit while
-// NART_RENDER_WAVES blocks share a CU's 160 KiB (NART_LDS_NODES overrides the node count).
-uint32_t render_lds_nodes(const nart_ctx* ctx, size_t fixed = 0, uint32_t blocks_of_256 = 1) {
-    const size_t stack = fixed ? fixed : (size_t)ctx->stack_depth * 256 * 8;
-    const size_t budget = (size_t)160 * 1024 * blocks_of_256 / NART_RENDER_WAVES;
-    size_t n = budget > stack ? (budget - stack) / sizeof(BVHNode) : 0;
-    while (n && node_lds_bytes((uint32_t)n) > budget - stack) --n;  // NART_NODE_PAD padding
-    return (uint32_t)std::min<size_t>(n, ctx->num_nodes);
-}
-
-// The ray-queue kernel's fixed LDS (stack + outboxes + results + id rings) fits one block per CU
-// (stack_depth <= 24 at 512 lanes).  NART_RQ_LDS_LIMIT lowers the budget (tests of the fallback).
-bool rq_fits(const nart_ctx* ctx) {
-    const size_t limit = (size_t)std::min(env_num("NART_RQ_LDS_LIMIT", 160.0 * 1024), 160.0 * 1024);
-    return rq_lds_bytes(ctx->stack_depth, NART_RQ_BLOCK) <= limit;
-}
-
 // ---------------------------------------------------------------- megakernel scheduling
 // host/path_schedule.h decides a launch's schedule (plan_path: the policy, its measurements and the
 // knobs); the kernels below prepare what it asks for and launch_render executes it.
@@ -689,24 +673,27 @@ int resident_blocks(nart_ctx* ctx, const void* kernel, int block, size_t lds, ui
     return NART_OK;
 }
 
-// LDS of a k_render block: the traversal stack and the staged BVH nodes.
-size_t k_render_lds(const nart_ctx* ctx) {
-    return (size_t)ctx->stack_depth * 256 * 8 + node_lds_bytes(render_lds_nodes(ctx));
-}
-
-// The path schedule's knobs, each read once per launch.
-SchedKnobs read_sched_knobs() {
-    SchedKnobs k;
-    const std::pair<const char*, Knob*> all[] = {
-        {"NART_PRIMARY_PACKET", &k.primary_packet}, {"NART_RQ_PRIO", &k.rq_prio}, {"NART_RQ_PAIRS", &k.rq_pairs},
-        {"NART_RQ_HALF", &k.rq_half}, {"NART_RQ_QUAD", &k.rq_quad}, {"NART_RQ_SETPRIO", &k.rq_setprio},
-        {"NART_RQ_ORDER", &k.rq_order}, {"NART_RQ_TOPF", &k.rq_topf}, {"NART_PROBE_SUB", &k.probe_sub},
-        {"NART_QUEUE_K", &k.queue_k}};
+// The knobs of the pure launch decisions (plan_path, plan_build, plan_volume), each read once per launch:
+// the GPU tests set them between renders of one context.
+void read_knobs(std::initializer_list<std::pair<const char*, Knob*>> all) {
     for (const auto& [name, knob] : all) {
         const char* e = env_opt(name);
         *knob = Knob{e != nullptr, e && *e, e && *e ? std::atof(e) : 0.0};
     }
+}
+SchedKnobs read_sched_knobs() {
+    SchedKnobs k;
+    read_knobs({{"NART_PRIMARY_PACKET", &k.primary_packet}, {"NART_RQ_PRIO", &k.rq_prio}, {"NART_RQ_PAIRS", &k.rq_pairs},
+                {"NART_RQ_HALF", &k.rq_half}, {"NART_RQ_QUAD", &k.rq_quad}, {"NART_RQ_SETPRIO", &k.rq_setprio},
+                {"NART_RQ_ORDER", &k.rq_order}, {"NART_RQ_TOPF", &k.rq_topf}, {"NART_PROBE_SUB", &k.probe_sub},
+                {"NART_QUEUE_K", &k.queue_k}});
     return k;
+}
+void read_build_knobs(PathBuildIn& in) {
+    read_knobs({{"NART_RQ_LDS_LIMIT", &in.rq_lds_limit}, {"NART_LEAN_STACK", &in.lean_stack}, {"NART_LEAN_ROUNDS", &in.lean_rounds}});
+}
+void read_volume_knobs(VolumeIn& in) {
+    read_knobs({{"NART_VOL_SPARSE", &in.sparse}, {"NART_VOL_SPARSE_F", &in.sparse_f}, {"NART_VOL_SPARSE_ROUNDS", &in.sparse_rounds}});
 }
 
 // What the scheduling steps of one launch_render share.
@@ -788,8 +775,6 @@ int schedule_pixel_queue(const PathLaunch& L, RenderArgs& b) {
     return NART_OK;
 }
 
-uint32_t lean_stack(const nart_ctx* ctx);
-
 // The camera rays of the batch in `pa` (pa.packet set) into ctx->d_prim.  Packets of one pixel's
 // samples (k_primary_px: 4 slots per block, one wave stack each) where the rows are pixel-major, spp
 // is a multiple of 64 and packet traversal is on; NART_PRIMARY_PIXEL=0 (a test hook: same hits) and
@@ -806,13 +791,14 @@ void launch_primary(nart_ctx* ctx, const RenderArgs& pa, hipStream_t st) {
 }
 
 // One batch of the path integrator: k_primary, what the plan's shape prepares, the path kernel.
-// The template parameters select kernel builds; host/path_schedule.h plan_path decides the rest.
+// The template parameters are the kernel builds of `B.id` (dispatch_megakernel's table), `B` their LDS
+// layout (host/path_build.h plan_build); host/path_schedule.h plan_path decides the rest.
 // resident_k: resident blocks of k_render (dispatch_megakernel's occupancy query).
 template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true>
-int launch_render(nart_ctx* ctx, const RenderArgs& a_in, uint32_t resident_k, hipStream_t st) {
+int launch_render(nart_ctx* ctx, const RenderArgs& a_in, const PathBuild& B, uint32_t resident_k, hipStream_t st) {
     auto kern = k_render<EXT, COUNT, ENV>;
     auto kern_rq = k_render_rq<EXT, COUNT, ENV, FM, WV, PR>;
-    constexpr uint32_t RQB = RQ_BLOCK_OF(COUNT, WV);  // ray-queue block (kernels.h)
+    const uint32_t RQB = B.rq_block;
     RenderArgs a = a_in;
     int rc = EXT ? ensure_ilist(ctx, a) : NART_OK;
     if (rc) return rc;
@@ -824,23 +810,11 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, uint32_t resident_k, hi
             hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr.fetch_or(dbit);
     }
-    // variant 0: ray-queue kernel; 3: k_render (one lane per pixel, the fallback below).
-    // The ray-queue kernel's 512-lane blocks keep a stack_depth * 4 KiB traversal stack plus
-    // 60 KiB of ray outboxes in LDS: a BVH deeper than 24 levels does not fit, and those scenes
-    // run k_render (256-lane blocks, stack_depth * 2 KiB) instead -- same image.
-    const bool rq = ctx->variant == 0 && rq_fits(ctx);
-    ctx->fm_used = rq ? FM : FT_ALL;
-    // k_render (the cost probe, the fallback): top BVH nodes staged in LDS.  The ray-queue kernel,
-    // one block per CU (2 or 3 waves per SIMD): outbox, results and id lists take part of the LDS;
-    // the lean build keeps lean_stack(ctx) stack levels there and the rest in a global column per
-    // thread.  (Staging the top BVH nodes in LDS for k_primary too measured slower: a wave's
-    // coherent rays read the same node, which the L1 broadcasts: 9.7 vs 8.2 ms at 64 spp)
-    RenderArgs b = a;
-    b.lds_nodes = render_lds_nodes(ctx);
-    const size_t lds = k_render_lds(ctx);
-    const uint32_t skd = WV == 3 ? lean_stack(ctx) : ctx->stack_depth;
-    const uint32_t rq_nodes = render_lds_nodes(ctx, rq_lds_bytes(skd, RQB), NART_RENDER_WAVES);
-    const size_t lds_rq = rq_lds_bytes(skd, RQB) + node_lds_bytes(rq_nodes);
+    const bool rq = B.rq;
+    ctx->fm_used = B.fm_used;
+    RenderArgs b = a;  // k_render's (the cost probe, the fallback), until the ray-queue kernel takes its place
+    b.lds_nodes = B.k_render.nodes;
+    const size_t lds = B.k_render.bytes, lds_rq = B.rq_lds.bytes;
     uint32_t resident_rq = 1;
     if (rq && (rc = resident_blocks(ctx, (const void*)kern_rq, RQB, lds_rq, &resident_rq))) return rc;
 
@@ -877,176 +851,125 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, uint32_t resident_k, hi
         return NART_OK;
     }
     // the ray-queue kernel takes k_render's place, with its own LDS layout
-    b.lds_nodes = rq_nodes;
+    b.lds_nodes = B.rq_lds.nodes;
     b.prim = prim;
-    b.stack_lds = skd;
+    b.stack_lds = B.stack_lds;
     b.rq_quorum = plan.rq_quorum;
     const uint32_t per = RQB / 256;  // the plan counts launches in blocks of 256
     const uint32_t grid = (plan.blocks + per - 1) / per;
     const size_t threads = (size_t)grid * RQB;
-    if (b.stack_lds < 1 || b.stack_lds > ctx->stack_depth || lds_rq > (size_t)160 * 1024)
-        return fail(ctx, NART_E_INVALID, "ray-queue LDS layout out of range");
     // per-thread global columns, indexed by the global thread id: sized from this grid
     if (EXT && threads > b.ilist_stride) return fail(ctx, NART_E_INVALID, "dielectric-list columns smaller than the launch");
-    if (skd < ctx->stack_depth && (rc = ensure_gstack(ctx, threads, ctx->stack_depth - skd, b))) return rc;
+    if (B.stack_lds < ctx->stack_depth && (rc = ensure_gstack(ctx, threads, ctx->stack_depth - B.stack_lds, b))) return rc;
     hipLaunchKernelGGL(kern_rq, dim3(grid), dim3(RQB), lds_rq, st, ctx->scene, b);
     HIPCHK(hipGetLastError());
     return NART_OK;
 }
 
-template <bool ENV>
-int launch_render_maxl(nart_ctx* ctx, const RenderArgs& a, uint32_t res, hipStream_t st) {
-    // a path grows the dielectric list by at most one entry per bounce: the register list alone
-    // serves bounces <= ILIST_REG; deeper ones (up to 32) spill it to the per-lane columns
-    const bool c = ctx->counters;
-    if (a.bounces <= ILIST_REG)
-        return c ? launch_render<false, true, ENV>(ctx, a, res, st) : launch_render<false, false, ENV>(ctx, a, res, st);
-    return c ? launch_render<true, true, ENV>(ctx, a, res, st) : launch_render<true, false, ENV>(ctx, a, res, st);
-}
-
-// Scene-specialised builds of the path kernels (k_render_rq, k_primary): glassSphere's (C3:
-// Lambert + glass, one kind of area light, constant patterns), the Cornell box's (C2: Lambert,
-// disk) and the textured environment-lit plastic of C4.  A render takes the first build whose mask
-// covers the scene's (ctx->features); others, the counter pass and renders with bounces > ILIST_REG
-// run the generic build.  Same operations per kind, so every build renders the same image
-// (tests/test_gpu_specialize.py compares them on every suite scene).
-constexpr uint32_t FM_DIFFUSE = FT_LAMBERT | FT_DISK;
-constexpr uint32_t FM_GLASS = FT_LAMBERT | FT_GLASS | FT_DISK;
-constexpr uint32_t FM_ENVTEX = FT_LAMBERT | FT_PLASTIC | FT_ENV | FT_TEX | FT_NMAP;
-
-// Traversal-stack levels the lean build keeps in LDS: all of them where the 768-lane block's LDS
-// then still stages 320 BVH nodes (or the whole BVH), else as many as leave room for them (>= 4;
-// deeper levels go to per-thread global columns).  C3 (14 levels, 759 nodes): 8 levels and 352
-// nodes; 7 / 8 / 10 levels measured 241 / 241 / 245 ms per frame, +-7 ms run to run
-// (profiles/r06e_lean_stack_ab.log).  NART_LEAN_STACK (tests) forces a depth.
-uint32_t lean_stack(const nart_ctx* ctx) {
-    if (env_opt("NART_LEAN_STACK"))
-        return std::max<uint32_t>(1u, std::min<uint32_t>(ctx->stack_depth, (uint32_t)env_num("NART_LEAN_STACK", 1.0)));
-    const size_t nodes = std::min<size_t>(ctx->num_nodes, 320) * sizeof(BVHNode);
-    uint32_t k = ctx->stack_depth;
-    while (k > 4 && rq_lds_bytes(k, 768) + nodes > (size_t)160 * 1024) --k;
-    return k;
-}
-
-// The lean three-waves-per-SIMD build (kernels.h WV = 3) for throughput-bound launches.  It raises
-// throughput (C3 whole frame, 16 rounds of resident waves: path kernels 276.6 -> ~241 ms; C4 4K
-// frame and its 1/8 shards, 8 rounds: 492 -> 456 ms) but each of its waves runs slower, which
-// lengthens the serial sample chains of a scene's costliest pixels.  Glass scenes' chains (caustic
-// paths behind the dielectric) set the time of their smaller launches, where the two-wave build
-// stays faster (C3 1/2 and 1/4 shards, 8 and 4 rounds: 172-185 / 114 ms vs 202-206 / 131 ms lean;
-// profiles/r06k_lean_rounds_ab.log), so they take it from 12 rounds on, other scenes from 3.
-bool lean_fits(const nart_ctx* ctx, const RenderArgs& a, uint32_t resident_k) {
-    if (ctx->variant != 0 || !ctx->lean || !rq_fits(ctx)) return false;
-    // glass scenes' small launches are bound by their costly pixels' chains, which the priority
-    // lanes of the two-wave build shorten (C3 1/2, 1/4 shards: 183 / 115 ms two-wave vs 194 / 130
-    // lean); scenes without glass or an environment light take the lean build from 1.5 rounds
-    // (C2 1/8 shards, 2 rounds: mean 22.1 vs 23.9 ms, profiles/r06zg_c2_shard8.log)
-    const double from = (ctx->features & FT_GLASS) ? 12.0 : (ctx->has_env ? 3.0 : 1.5);
-    return rounds_of(a.n_slots, resident_k) >= env_num("NART_LEAN_ROUNDS", from);
+// One instantiation of launch_render per build of the path kernels that plan_build can name.
+using RenderLauncher = int (*)(nart_ctx*, const RenderArgs&, const PathBuild&, uint32_t, hipStream_t);
+struct BuildRow {
+    BuildId id;
+    RenderLauncher launch;
+};
+template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true>
+BuildRow build_row() {
+    return {BuildId{EXT, COUNT, ENV, FM, WV, PR}, launch_render<EXT, COUNT, ENV, FM, WV, PR>};
 }
 
 int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
+    PathBuildIn in;
+    in.features = ctx->features;
+    in.has_env = ctx->has_env;
+    in.specialize = !ctx->specialize ? Specialize::Off : (ctx->lean ? Specialize::Lean : Specialize::On);
+    in.counters = ctx->counters;
+    in.bounces = a.bounces;
+    in.variant = ctx->variant;
+    in.stack_depth = ctx->stack_depth;
+    in.num_nodes = ctx->num_nodes;
+    in.n_slots = a.n_slots;
     // resident blocks of k_render, the figure every threshold in rounds of resident waves refers to
-    // (lean_fits, plan_path).  Every k_render build is compiled for two waves per SIMD and has the
+    // (plan_build, plan_path).  Every k_render build is compiled for two waves per SIMD and has the
     // same LDS, so one build's occupancy stands for all of them.
-    uint32_t res = 0;
-    int rc = resident_blocks(ctx, (const void*)k_render<false, false, false>, 256, k_render_lds(ctx), &res);
+    int rc = resident_blocks(ctx, (const void*)k_render<false, false, false>, 256,
+                             k_render_layout(ctx->stack_depth, ctx->num_nodes).bytes, &in.resident_k);
     if (rc) return rc;
-    const uint32_t f = ctx->features;
-    auto covers = [f](uint32_t m) { return (f & ~m) == 0u; };
-    if (ctx->specialize && !ctx->counters && a.bounces <= ILIST_REG) {
-        if (!ctx->has_env && covers(FM_DIFFUSE)) {
-            if (lean_fits(ctx, a, res)) return launch_render<false, false, false, FM_DIFFUSE, 3, false>(ctx, a, res, st);
-            return launch_render<false, false, false, FM_DIFFUSE>(ctx, a, res, st);
-        }
-        if (!ctx->has_env && covers(FM_GLASS)) {
-            if (lean_fits(ctx, a, res)) return launch_render<false, false, false, FM_GLASS, 3, false>(ctx, a, res, st);
-            // (small shards keep two waves per SIMD: the priority-lane build at three, 168 VGPRs with
-            // 14 spilled, measured C3 1/8 shards worst 83-85 vs 79-81 ms, mean 79.5-79.8 vs 75.9-76.0;
-            // profiles/r06l_three_wave_prio_ab.log)
-            return launch_render<false, false, false, FM_GLASS>(ctx, a, res, st);
-        }
-        if (ctx->has_env && covers(FM_ENVTEX)) {
-            if (lean_fits(ctx, a, res)) return launch_render<false, false, true, FM_ENVTEX, 3, false>(ctx, a, res, st);
-            return launch_render<false, false, true, FM_ENVTEX>(ctx, a, res, st);
-        }
-    }
-    return ctx->has_env ? launch_render_maxl<true>(ctx, a, res, st) : launch_render_maxl<false>(ctx, a, res, st);
+    read_build_knobs(in);
+    const PathBuild B = plan_build(in);
+    if (B.error) return fail(ctx, NART_E_INVALID, B.error);
+    // every build plan_build can name (tests/test_path_build.py holds the same list).  The compiler emits
+    // the kernels in the order of the rows: keep it, and the gfx950 code object stays byte for byte the same
+    static const BuildRow builds[] = {
+        build_row<false, false, false, FM_DIFFUSE, 3, false>(),  // scene-specialised: lean, two waves per SIMD
+        build_row<false, false, false, FM_DIFFUSE>(),
+        build_row<false, false, false, FM_GLASS, 3, false>(),
+        build_row<false, false, false, FM_GLASS>(),
+        build_row<false, false, true, FM_ENVTEX, 3, false>(),
+        build_row<false, false, true, FM_ENVTEX>(),
+        build_row<false, true, true>(),  // generic: EXT x COUNT x ENV
+        build_row<false, false, true>(),
+        build_row<true, true, true>(),
+        build_row<true, false, true>(),
+        build_row<false, true, false>(),
+        build_row<false, false, false>(),
+        build_row<true, true, false>(),
+        build_row<true, false, false>(),
+    };
+    for (const BuildRow& row : builds)
+        if (row.id == B.id) return row.launch(ctx, a, B, in.resident_k, st);
+    return fail(ctx, NART_E_INVALID, "no path-kernel build for the plan");
 }
 
-// Volume integrator: k_render_volume_sm (lanes advance one tentative collision per iteration and
-// start their next sample independently).  When the shard spans several rounds of resident
-// waves, the costliest wave-sized pixel groups (cost probe: tentative collisions of 4 samples per
-// pixel) are launched first.
+// Volume integrator (k_render_volume_sm): host/path_schedule.h plan_volume and sparse_hot_groups decide
+// the launch, this executes it.
 int dispatch_volume(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
     const dim3 block(256);
-    const uint32_t blocks = (a.n_slots + 255) / 256;
-    RenderArgs b = a;
-    // small density grids (C5: 2x2x2) are read from LDS (1 % faster than L1-hitting global loads)
-    const uint32_t nd = ctx->scene.medium.present ? ctx->scene.medium.rx * ctx->scene.medium.ry * ctx->scene.medium.rz : 0;
-    b.lds_nodes = nd <= 4096u ? nd : 0u;
-    const size_t dl = (size_t)b.lds_nodes * sizeof(float);
-    // occupancy: launches of >= 8 rounds of resident waves use the 4-waves-per-SIMD build (C5 frame,
-    // 10.5 rounds: 134 -> 122 ms); smaller ones keep the unconstrained build, whose lanes' serial
-    // chains are shorter (C5 1/2, 1/4, 1/8 shards: 79 / 74 / 71 ms vs 83 / 80 / 76 with 4 waves;
-    // profiles/r03h_vol_w4_ab.log)
-    uint32_t resident = 0;
-    int rc = resident_blocks(ctx, (const void*)k_render_volume_sm<false, 1>, 256, dl, &resident);
-    if (rc) return rc;
-    const double w4_rounds = 8.0;
-    const bool w4 = (double)blocks / (double)resident >= w4_rounds;
-    uint32_t grid = blocks;
     const uint32_t n = a.n_slots;
-    if (blocks > resident && rounds_of(n, resident) < 12.0 && a.spp > 4) {
-        const uint32_t W = resident * 4;  // resident waves
-        if ((rc = ensure_queue(ctx, n + 63u * W))) return rc;
+    VolumeIn in;
+    in.n_slots = n;
+    in.spp = a.spp;
+    in.grid_cells = ctx->scene.medium.present ? ctx->scene.medium.rx * ctx->scene.medium.ry * ctx->scene.medium.rz : 0;
+    in.counters = ctx->counters;
+    const size_t dl = (size_t)volume_lds_cells(in.grid_cells) * sizeof(float);
+    int rc = resident_blocks(ctx, (const void*)k_render_volume_sm<false, 1>, 256, dl, &in.resident);
+    if (rc) return rc;
+    read_volume_knobs(in);
+    const VolumePlan plan = plan_volume(in);
+    RenderArgs b = a;
+    b.lds_nodes = plan.lds_nodes;
+    uint32_t grid = plan.blocks;
+    ctx->sched |= plan.sched;
+    if (plan.queue) {
+        if ((rc = ensure_queue(ctx, plan.queue_room))) return rc;
         const QueueBufs q(ctx);
         RenderArgs pb = b;
         pb.spp = 4;
         pb.cost = q.cost;
-        hipLaunchKernelGGL((k_render_volume_sm<false, 1>), dim3(blocks), block, dl, st, ctx->scene, pb);
+        hipLaunchKernelGGL((k_render_volume_sm<false, 1>), dim3(plan.blocks), block, dl, st, ctx->scene, pb);
         rc = sort_groups_by_cost(ctx, n, 64, q.queue, st);
         if (rc) return rc;
         b.queue = q.queue;
-        ctx->sched |= NART_SCHED_VOL_QUEUE;
-        // Sparse waves on shards of < NART_VOL_SPARSE_ROUNDS (default 2) rounds of resident
-        // waves: the costliest groups (probe cost >= NART_VOL_SPARSE_F (4) x the median group's)
-        // spread NART_VOL_SPARSE (16) pixels per wave, the other lanes idle.  A wave executes
-        // the union of its lanes' divergent chains, and a frame's costliest volume pixels
-        // cluster: C5's centre pixels take 30 ms alone at 1,024 spp, 69 ms as a wave of 64.
-        // C5 1/8 shard 73.7 -> 65.3 ms; on larger shards (2+ rounds) the mostly idle sparse
-        // waves hold slots the other groups need (1/2 shard 78 -> 127 ms), and 1-8 pixels per
-        // wave measured worse (profiles/r04h_c5_sparse.log).  Only the order of work changes.
-        const uint32_t S = (uint32_t)std::max(1.0, std::min(64.0, env_num("NART_VOL_SPARSE", 16.0)));
-        const double f = env_num("NART_VOL_SPARSE_F", 4.0), max_rounds = env_num("NART_VOL_SPARSE_ROUNDS", 2.0);
-        if (S < 64u && (64u % S) == 0u && (double)blocks / (double)resident < max_rounds) {
+        if (plan.sparse) {
             const uint32_t ng = (n + 63) / 64;
             std::vector<uint32_t> keys(ng);
             HIPCHK(hipMemcpyAsync(keys.data(), q.keys[1], (size_t)ng * 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            std::vector<uint32_t> costs;  // sorted descending (partial last group excluded)
-            for (uint32_t g = 0; g < ng; ++g)
-                if (keys[g] != 0xFFFFFFFFu) costs.push_back(0xFFFFFFFEu - keys[g]);
-            uint32_t H = 0;
-            if (!costs.empty()) {
-                const double med = costs[costs.size() / 2];
-                while (H < costs.size() && (double)costs[H] >= f * med) ++H;
-            }
-            H = std::min<uint32_t>(H, 63u * W / (64u / S * 64u));  // queue room (ensure_queue)
-            if (H) {
-                const uint32_t qlen = H * (64u / S) * 64u + (n - 64u * H);
-                hipLaunchKernelGGL(k_sparse_groups, dim3((qlen + 255) / 256), block, 0, st, q.vals[1], n, H, S,
-                                   qlen, q.queue);
-                b.qlen = qlen;
-                grid = (qlen + 255) / 256;
+            const SparseGroups hot = sparse_hot_groups(keys.data(), ng, plan.f, plan.S, plan.W, n);
+            if (hot.H) {
+                hipLaunchKernelGGL(k_sparse_groups, dim3(hot.grid), block, 0, st, q.vals[1], n, hot.H, plan.S,
+                                   hot.qlen, q.queue);
+                b.qlen = hot.qlen;
+                grid = hot.grid;
                 ctx->sched |= NART_SCHED_VOL_SPARSE;
             }
         }
         HIPCHK(hipGetLastError());
     }
-    if (ctx->counters) hipLaunchKernelGGL((k_render_volume_sm<true, 1>), dim3(grid), block, dl, st, ctx->scene, b);
-    else if (w4) hipLaunchKernelGGL((k_render_volume_sm<false, NART_VOL_WV>), dim3(grid), block, dl, st, ctx->scene, b);
-    else hipLaunchKernelGGL((k_render_volume_sm<false, 1>), dim3(grid), block, dl, st, ctx->scene, b);
+    switch (plan.build) {
+        case VolumeBuild::Counter: hipLaunchKernelGGL((k_render_volume_sm<true, 1>), dim3(grid), block, dl, st, ctx->scene, b); break;
+        case VolumeBuild::FourWave: hipLaunchKernelGGL((k_render_volume_sm<false, NART_VOL_WV>), dim3(grid), block, dl, st, ctx->scene, b); break;
+        case VolumeBuild::Plain: hipLaunchKernelGGL((k_render_volume_sm<false, 1>), dim3(grid), block, dl, st, ctx->scene, b); break;
+    }
     HIPCHK(hipGetLastError());
     return NART_OK;
 }

@@ -1,5 +1,5 @@
 """Scene feature masks (host only, no GPU): nart_hip_scene_features_of -- the mask that selects the
-scene-specialised path-kernel build (render.hip scene_features / dispatch_megakernel) -- against an
+scene-specialised path-kernel build (render.hip scene_features, host/path_build.h plan_build) -- against an
 independent reading of each suite scene's JSON: material kinds, light kinds, textured patterns,
 normal maps (glass ignores its normal map, glassmaterial.cpp:3-9).  The GPU suite
 (tests/test_gpu_specialize.py) checks that every build renders the same bits; this checks which
@@ -48,7 +48,7 @@ def json_features(path):
 
 
 def expected_build(f):
-    """dispatch_megakernel's choice (bounces <= 10, not the counter pass)."""
+    """plan_build's choice (bounces <= 10, not the counter pass)."""
     if f & FT["environment"]:
         return FM_ENVTEX if (f & ~FM_ENVTEX) == 0 else FT_ALL
     for m in (FM_DIFFUSE, FM_GLASS):

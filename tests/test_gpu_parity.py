@@ -255,8 +255,8 @@ def test_volume_integrator(gpu, volume_scenes, kind):
 def test_volume_queue_scheduler(gpu, volume_scenes, monkeypatch, kind, sparse, rounds):
     """More pixels than resident lanes: the volume kernel runs its cost probe (4 samples per
     pixel) and launches the costliest pixel groups first; on small shards the costliest groups run
-    as sparse waves (NART_VOL_SPARSE pixels per wave, the other lanes idle; render.hip
-    dispatch_volume).  Only the order of work changes."""
+    as sparse waves (NART_VOL_SPARSE pixels per wave, the other lanes idle;
+    host/path_schedule.h plan_volume, sparse_hot_groups).  Only the order of work changes."""
     monkeypatch.setenv("NART_VOL_SPARSE", sparse)
     monkeypatch.setenv("NART_VOL_SPARSE_ROUNDS", rounds)
     monkeypatch.setenv("NART_VOL_SPARSE_F", "1.1")  # some groups of this small frame count as costly

@@ -81,7 +81,7 @@ def test_glass_sphere_lean_build(gpu, glass_scene, monkeypatch, lds_levels):
     levels most pushes of the 14-level BVH go to the columns.  Same bits as the generic build."""
     if lds_levels:
         monkeypatch.setenv("NART_LEAN_STACK", lds_levels)
-    # a whole 1080p frame: 16 rounds of resident waves (glass scenes go lean from 12, render.hip lean_fits)
+    # a whole 1080p frame: 16 rounds of resident waves (glass scenes go lean from 12, host/path_build.h plan_build)
     a, b, feats, build, sched = _both(glass_scene, _params(glass_scene, 1920, 1080, 1))
     assert build == FM_GLASS and "lean" in sched, (hex(build), sched)
     assert sched == ["lean", "primary", "specialized", "splat_skew", "wave_groups"]
@@ -99,7 +99,7 @@ def test_cornell_lean_build(gpu, cornell_scene):
 
 def test_cornell_lean_probe_queue(gpu, cornell_scene):
     """Scenes without glass or an environment light run the lean build from 1.5 rounds of resident
-    waves (render.hip lean_fits): a 2-round Cornell frame takes it through the probe-ordered pixel
+    waves (host/path_build.h plan_build): a 2-round Cornell frame takes it through the probe-ordered pixel
     queue (no wave groups below 3 rounds).  Same bits as the generic build."""
     a, b, feats, build, sched = _both(cornell_scene, _params(cornell_scene, 640, 480, 2))
     assert build == FM_DIFFUSE and "lean" in sched and "wave_groups" not in sched, (hex(build), sched)
