@@ -547,6 +547,103 @@ int nart_hip_render_denoised_moment(nart_ctx* ctx, const nart_render_params* p, 
 int nart_hip_denoise_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
                              double* finalize_ms);
 
+/* Followed guides (no reference counterpart): denoiser guides taken at the first non-delta surface.
+   The first-hit AOVs of a pane of glass or a mirror show the glass or the mirror; these follow
+   perfect mirrors and smooth dielectrics deterministically until something diffuse, glossy or rough
+   is met, and record that surface.  Opt-in: no other entry point changes its bits, its launches or
+   the memory it finds; the path kernels and the denoise kernels are not touched.
+
+   The chain, per camera sample, draws no random numbers.  It is the path integrator's loop
+   (pathintegrator.cpp:166-258) without EstimateDirect and Russian roulette, with the three
+   continuation random numbers replaced by constants so that Fresnel reflection is never chosen, and
+   with alphaTweak fixed at 1 (along a purely delta prefix the path's own alphaTweak is exactly 1,
+   since every followed lobe reports alpha_i = 0).  All arithmetic is the path kernel's own float32
+   arithmetic (path.h), operation by operation:
+     state: ray = the camera ray (pinholecamera.cpp:9-40), an empty nested-dielectric list, D = 0, k = 0
+     1. tmax = the nearest analytic light along ray (the light loop bound, pathintegrator.cpp:167-182);
+        +inf without one.
+     2. the closest hit within tmax: the reference octree's answer.  For the camera ray this is the
+        first-hit AOVs' hit.
+     3. no hit: the sample is a MISS, both records are all zero and the chain ends (a light met
+        first is a miss, as for the first-hit AOVs).
+     4. the hit's attributes (geometry.cpp:84-112) and its BSDF (Material::CreateBSDF with
+        alphaTweak = 1).  t = (dot(v0, n) - dot(ray.o, n)) / dot(ray.d, n), n = cross(v1 - v0,
+        v2 - v0): the plane distance exactly as the first-hit depth.  D = D + t, one float32 add, so
+        D = ((t0 + t1) + t2) + ...
+     5. valid = IsectIsValid(meshID, priority) of the list, which also yields eta_outer
+        (pathintegrator.cpp:7-36).
+     6. if valid, k < max_follow, and the BSDF has one lobe which is the perfect mirror or the
+        smooth dielectric (specularbrdf.cpp, speculardielectricbrdf.cpp): wo = ToLocal(-ray.d);
+        BSDF::Sample_f in its continuation form with s1 = 0 and sample = (1, 0).  sample.x = 1 is
+        never < Fr, so a dielectric refracts, or reflects on total internal reflection; a mirror
+        reflects.  At an index-matched interface (eta_outer == eta: Sample_f returns pdf = 0 without
+        the specular flag, and the path ends there too) this hit is the guide hit.  Otherwise --
+        also where total internal reflection leaves Sample_f's refraction branch with pdf = 1 - Fr
+        = 0: the path, whose sample.x < 1 = Fr, takes the reflection branch there, with the same wi
+        -- ray = (p + gn * 0.001 * flip, ToWorld(wi)), flip = wi.z > 0 ? 1 : -1
+        (pathintegrator.cpp:216-220); a transmissive lobe updates the list with the lobe's eta; ++k,
+        and go to 1.
+     7. if not valid and k < max_follow: step through (pathintegrator.cpp:223-229): ray = (p + ray.d *
+        0.001, ray.d), the list is updated with the eta of the lobe BSDF::Sample_f would select at
+        s1 = 0; ++k, and go to 1.
+     8. otherwise this hit is the GUIDE HIT:
+          albedo record  {albedo.rgb, 1}, the pattern chosen by material kind as the first-hit albedo
+          normal record  {normalize(n_shading).xyz, D}
+   max_follow is 0..10: a chain costs at most 11 traversals, is bounded by that count and nothing
+   else (a NaN direction ends it as a miss), and its list never outgrows 10 entries.  Consequences:
+     - max_follow = 0 gives the first-hit AOV records bit for bit (validity is not applied to the
+       hit the chain stops on);
+     - a scene without mirror or smooth-glass hits gives the first-hit records bit for bit at any
+       max_follow;
+     - rough glass (alpha > 1e-4), glossy and plastic stop the chain.
+   Both record streams go through the call's splat plan and the tile combine exactly as the first-hit
+   AOVs' do, so the images have the same layout and filter_weight_sum has the beauty's bits.
+
+   On the device k_guide (device/guide.h) traces every sample's chain once per batch after the
+   beauty's splat and every other pass have consumed the per-sample record buffer: the albedo record
+   goes there, the normal record into a second record buffer of 16 B per sample held for the call
+   only, and only where both images are asked for (batches are then sized for 44 instead of 28 B per
+   sample); then the plan's splat runs once per guide image.
+
+   nart_hip_guide_defaults: max_follow 8.
+   nart_hip_render_guides: as nart_hip_render_moment -- aovs selects the images (NART_AOV_ALBEDO,
+   NART_AOV_NORMAL), which hold the followed guides; image and moment are optional, and the beauty and
+   the moment image have the bits nart_hip_render / nart_hip_render_moment give.  gp null: the
+   defaults.  guide_ms, if non-null, receives the device time of k_guide and the guide splats.
+   Multi-device contexts gather the guide tiles with the beauty's gather.
+   nart_hip_render_denoised_guides: as nart_hip_render_denoised, or with sample_variance != 0 as
+   nart_hip_render_denoised_moment, the filter fed with the followed guides instead of the first-hit
+   AOVs.  nart_hip_denoise / nart_hip_denoise_moment take the images of nart_hip_render_guides as they
+   take any guide images, and give the same bits.
+   nart_hip_render_guide_samples: debug / parity, as nart_hip_render_aov_samples: per sample i =
+   ((y-y0)*w + (x-x0))*spp + s of a rect in total-image coordinates, with M = max_follow + 1,
+       out8[i][8]       albedo record then normal record
+       n_seg[i]         segments traced, 1..M; 0 for a camera-ray miss
+       seg8[i][j][8]    {o.xyz, tmax, d.xyz, t} of segment j < max(n_seg[i], 1) (the camera ray is
+                        always reported): its ray, its bound and the plane distance t of step 4
+                        (tmax where the segment missed); zeros beyond
+       tri[i][j]        the triangle, or 0xFFFFFFFF where that segment missed or was never traced
+   seg8, tri and n_seg are optional.
+   NART_E_INVALID: a null ctx, p or required image, an unknown AOV bit, a bit without its buffer,
+   nothing requested, max_follow > 10, an empty or out-of-range rect; the denoise entry point also
+   the errors of nart_hip_render_denoised(_moment).  NART_E_UNSUPPORTED: the volume integrator (no
+   surfaces).  An error leaves the context usable.  Not offered: followed guides together with
+   adaptive sampling, the cascade, the mattes, or the first-hit AOVs in one call. */
+#define NART_GUIDE_MAX_FOLLOW 10u
+typedef struct nart_guide_params {
+    uint32_t max_follow; /* delta interfaces a chain follows or steps through, 0..10   default 8 */
+} nart_guide_params;
+void nart_hip_guide_defaults(nart_guide_params* gp);
+int nart_hip_render_guides(nart_ctx* ctx, const nart_render_params* p, const nart_guide_params* gp, uint32_t aovs,
+                           nart_pixel* image, nart_pixel* albedo, nart_pixel* normal, nart_pixel* moment,
+                           nart_render_stats* stats, double* guide_ms);
+int nart_hip_render_denoised_guides(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                                    const nart_guide_params* gp, int sample_variance, nart_pixel* image,
+                                    nart_pixel* out, nart_render_stats* stats, double* denoise_ms);
+int nart_hip_render_guide_samples(nart_ctx* ctx, const nart_render_params* p, const nart_guide_params* gp, uint32_t x0,
+                                  uint32_t y0, uint32_t w, uint32_t h, float* out8, float* seg8, uint32_t* tri,
+                                  uint32_t* n_seg);
+
 /* Multi-GPU building block: render the listed buckets (bucket id = by*nBucketsX + bx) into
    device-resident tiles d_tiles[i] (tile_size^2 nart_pixel each, same order as the list) on
    `stream` (a hipStream_t, may be 0).  bucket_ids is a host array.  Asynchronous w.r.t. the

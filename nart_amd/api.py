@@ -176,6 +176,23 @@ class MatteParams(ctypes.Structure):
 MATTE_MESH, MATTE_MATERIAL = 0, 1  # NART_MATTE_* (include/nart_hip.h)
 
 
+class GuideParams(ctypes.Structure):
+    """nart_guide_params (include/nart_hip.h, "Followed guides"); GuideParams.defaults() is
+    nart_hip_guide_defaults, keyword arguments override single fields."""
+    _fields_ = [("max_follow", ctypes.c_uint32)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        gp = cls()
+        hip_lib().nart_hip_guide_defaults(ctypes.byref(gp))
+        for k, v in kw.items():
+            setattr(gp, k, v)
+        return gp
+
+    def __repr__(self):
+        return "GuideParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
 class _Texture(ctypes.Structure):
     """nart_texture (include/nart_scene.h)."""
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("rgba", _P)]
@@ -270,6 +287,15 @@ _HIP_SIGS = {
                                                        _P, ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_denoised": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams), _P, _P,
                                                 ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_guide_defaults": (None, [ctypes.POINTER(GuideParams)]),
+    "nart_hip_render_guides": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(GuideParams), ctypes.c_uint32,
+                                              _P, _P, _P, _P, ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_denoised_guides": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams),
+                                                       ctypes.POINTER(GuideParams), ctypes.c_int, _P, _P,
+                                                       ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_guide_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(GuideParams),
+                                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                     _P, _P, _P, _P]),
     "nart_hip_denoise_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_device": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(_P),
@@ -838,6 +864,43 @@ class HipRenderer:
                                                           tri.ctypes.data))
         return out, tri
 
+    def render_guides(self, p, params=None, albedo=True, normal=True, beauty=True, moment=False, stats=None):
+        """Followed guides (nart_hip_render_guides; include/nart_hip.h has the chain): as render_aovs(),
+        with "albedo" and "normal" taken at the first surface behind perfect mirrors and smooth
+        dielectrics.  params a GuideParams (None: the defaults).  "guide_ms" is the device time of the
+        guide kernel and the guide splats; "beauty" and "moment" have the bits render() and
+        render_aovs(moment=True) give."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        out = {}
+        for name, want in (("beauty", beauty), ("albedo", albedo), ("normal", normal), ("moment", moment)):
+            if want:
+                out[name] = np.empty(shape, np.float32)
+        ptr = lambda name: out[name].ctypes.data if name in out else None
+        st = stats if stats is not None else RenderStats()
+        ms = ctypes.c_double()
+        mask = (AOV_ALBEDO if albedo else 0) | (AOV_NORMAL if normal else 0)
+        self._check(self._lib.nart_hip_render_guides(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
+                                                     mask, ptr("beauty"), ptr("albedo"), ptr("normal"), ptr("moment"),
+                                                     ctypes.byref(st), ctypes.byref(ms)))
+        out["guide_ms"] = ms.value
+        return out
+
+    def render_guide_samples(self, p, x0, y0, w, h, params=None):
+        """Per-sample guide chains of a rect in total-image coordinates (nart_hip_render_guide_samples),
+        M = max_follow + 1: a dict with "rec" (h, w, spp, 8) float32 = {albedo record, normal record},
+        "n_seg" (h, w, spp) uint32 segments traced (0: a camera-ray miss), "seg" (h, w, spp, M, 8)
+        float32 = {o.xyz, tmax, d.xyz, t} and "tri" (h, w, spp, M) uint32 (0xFFFFFFFF: that segment
+        missed or was never traced)."""
+        gp = params if params is not None else GuideParams.defaults()
+        M = int(gp.max_follow) + 1 if gp.max_follow <= 10 else 1  # (a bad value is the entry point's to refuse)
+        out = {"rec": np.empty((h, w, p.spp, 8), np.float32), "n_seg": np.empty((h, w, p.spp), np.uint32),
+               "seg": np.empty((h, w, p.spp, M, 8), np.float32), "tri": np.empty((h, w, p.spp, M), np.uint32)}
+        self._check(self._lib.nart_hip_render_guide_samples(self._ctx, ctypes.byref(p), ctypes.byref(gp), x0, y0, w, h,
+                                                            out["rec"].ctypes.data, out["seg"].ctypes.data,
+                                                            out["tri"].ctypes.data, out["n_seg"].ctypes.data))
+        return out
+
     def denoise(self, p, beauty, albedo, normal, params=None, moment=None):
         """Denoise host images (nart_hip_denoise): beauty, albedo and normal are (totalH, totalW, 5)
         float32 images as render_aovs() returns them; params a DenoiseParams (None: the defaults).
@@ -863,12 +926,14 @@ class HipRenderer:
                                                           out.ctypes.data, None))
         return out
 
-    def render_denoised(self, p, params=None, beauty=True, stats=None, sample_variance=False):
+    def render_denoised(self, p, params=None, beauty=True, stats=None, sample_variance=False, guides=None):
         """Render the beauty and both first-hit AOVs and denoise them on the device
         (nart_hip_render_denoised): a dict with "denoised", "beauty" (the noisy image, bit-identical to
         render(); only if requested) and "denoise_ms", the device time of the denoise kernels.
         sample_variance=True also renders the second-moment image and denoises with the variance
-        taken from it (nart_hip_render_denoised_moment; p.spp >= 2)."""
+        taken from it (nart_hip_render_denoised_moment; p.spp >= 2).
+        guides: a GuideParams feeds the filter with the followed guides instead of the first-hit AOVs
+        (nart_hip_render_denoised_guides); None is the first-hit call."""
         g = session_geometry(p)
         shape = (g.total_height, g.total_width, PIXEL_FLOATS)
         out = {"denoised": np.empty(shape, np.float32)}
@@ -876,10 +941,17 @@ class HipRenderer:
             out["beauty"] = np.empty(shape, np.float32)
         st = stats if stats is not None else RenderStats()
         ms = ctypes.c_double()
-        entry = self._lib.nart_hip_render_denoised_moment if sample_variance else self._lib.nart_hip_render_denoised
-        self._check(entry(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
-                          out["beauty"].ctypes.data if beauty else None, out["denoised"].ctypes.data, ctypes.byref(st),
-                          ctypes.byref(ms)))
+        dp = ctypes.byref(params) if params else None
+        img = out["beauty"].ctypes.data if beauty else None
+        if guides is not None:
+            self._check(self._lib.nart_hip_render_denoised_guides(self._ctx, ctypes.byref(p), dp, ctypes.byref(guides),
+                                                                  1 if sample_variance else 0, img,
+                                                                  out["denoised"].ctypes.data, ctypes.byref(st),
+                                                                  ctypes.byref(ms)))
+        else:
+            entry = self._lib.nart_hip_render_denoised_moment if sample_variance else self._lib.nart_hip_render_denoised
+            self._check(entry(self._ctx, ctypes.byref(p), dp, img, out["denoised"].ctypes.data, ctypes.byref(st),
+                              ctypes.byref(ms)))
         out["denoise_ms"] = ms.value
         return out
 

@@ -12,8 +12,10 @@ namespace nd {
 
 // device/cascade.h CASCADE_MAX_LAYERS; device/matte.h MATTE_MAX_PLANES (four ids a plane), MATTE_MAX_IDS
 constexpr uint32_t FRAME_MAX_LAYERS = 8, FRAME_MAX_PLANES = 8, FRAME_MAX_MATTE_IDS = 4 * FRAME_MAX_PLANES;
-// beauty, two first-hit AOVs, moment, layers, planes (a frame has layers or planes: at most twelve)
-constexpr uint32_t FRAME_MAX_OUTPUTS = 4 + FRAME_MAX_LAYERS + FRAME_MAX_PLANES;
+// beauty, two first-hit AOVs, moment, layers, planes, two followed guides (a frame has layers or
+// planes, and first-hit AOVs or followed guides: at most twelve)
+constexpr uint32_t FRAME_MAX_OUTPUTS = 4 + FRAME_MAX_LAYERS + FRAME_MAX_PLANES + 2;
+constexpr uint32_t FRAME_MAX_FOLLOW = 10;  // include/nart_hip.h NART_GUIDE_MAX_FOLLOW
 
 // The firefly cascade's levels (include/nart_hip.h, "Firefly cascade"): layer j takes the share of
 // every Li_alpha record around brightness b[j] = start * base^j.  K = 0: no cascade.
@@ -38,11 +40,13 @@ struct FrameAsk {  // what the caller asks for
     bool adaptive = false;         // buckets refined level by level, not rendered once at p->spp
     CascadeLevels cascade;
     MatteRequest matte;
+    bool guide[2] = {false, false};  // followed guides (include/nart_hip.h, "Followed guides"): albedo, normal
+    uint32_t max_follow = 0;         // delta interfaces a guide chain follows, 0..FRAME_MAX_FOLLOW
     explicit FrameAsk(uint32_t integrator_) : integrator(integrator_) {}
 };
 
 // One tile buffer (and image) of a render; index: j of cascade layer j, q of matte plane q, else 0.
-enum class OutputKind : uint32_t { Beauty, Albedo, Normal, Moment, Layer, Plane };
+enum class OutputKind : uint32_t { Beauty, Albedo, Normal, Moment, Layer, Plane, GuideAlbedo, GuideNormal };
 struct FrameOutput { OutputKind kind = OutputKind::Beauty; uint32_t index = 0; };
 
 // The passes of a batch after the path kernel and the beauty's splat, in the order they must run.
@@ -51,10 +55,13 @@ struct FrameOutput { OutputKind kind = OutputKind::Beauty; uint32_t index = 0; }
 //                   (k_cascade_split into a second record buffer, one layer at a time);
 //   PASS_MOMENT     k_moment squares d_L in place: after the cascade, the last reader of Li_alpha;
 //   PASS_FIRST_HIT  k_aov overwrites d_L from the camera-ray hits (d_prim), one AOV at a time;
-//   PASS_MATTE      k_matte_ids overwrites d_L from the same hits, one plane at a time.
-enum PassKind : uint32_t { PASS_CASCADE, PASS_MOMENT, PASS_FIRST_HIT, PASS_MATTE, N_PASSES };
+//   PASS_MATTE      k_matte_ids overwrites d_L from the same hits, one plane at a time;
+//   PASS_GUIDE      k_guide traces every sample's chain once: the albedo record overwrites d_L, the
+//                   normal record goes to a second record buffer where both are asked for.
+enum PassKind : uint32_t { PASS_CASCADE, PASS_MOMENT, PASS_FIRST_HIT, PASS_MATTE, PASS_GUIDE, N_PASSES };
 // The pass that fills an output's records, by OutputKind; N_PASSES: the beauty, the path kernel's own.
-constexpr PassKind PASS_OF[6] = {N_PASSES, PASS_FIRST_HIT, PASS_FIRST_HIT, PASS_MOMENT, PASS_CASCADE, PASS_MATTE};
+constexpr PassKind PASS_OF[8] = {N_PASSES,     PASS_FIRST_HIT, PASS_FIRST_HIT, PASS_MOMENT,
+                                 PASS_CASCADE, PASS_MATTE,     PASS_GUIDE,     PASS_GUIDE};
 inline PassKind pass_of(OutputKind k) { return PASS_OF[(uint32_t)k]; }
 
 struct FramePlan {
@@ -62,13 +69,16 @@ struct FramePlan {
     std::string message;
     FrameAsk ask{NART_INTEGRATOR_PATH};
     // Tile buffers and images in delivery order: beauty, albedo, normal, moment, then the layers or
-    // the planes ascending.  On-device delivery lays the images out back to back in this order.
+    // the planes ascending, then the followed guides.  On-device delivery lays the images out back to
+    // back in this order.
     FrameOutput outputs[FRAME_MAX_OUTPUTS];
     uint32_t n_outputs = 0;
     PassKind passes[N_PASSES] = {};  // the passes that run, ascending
     uint32_t n_passes = 0;
     bool path_kernel = false;   // false: camera rays only (first-hit outputs without the beauty)
-    uint32_t record_bytes = 0;  // per-sample record memory beyond d_L (batch_slot_limit): the cascade's buffer
+    // per-sample record memory beyond d_L (batch_slot_limit): the cascade's buffer, or the second
+    // guide record's where both guides are asked for
+    uint32_t record_bytes = 0;
 
     int find(OutputKind kind, uint32_t index = 0) const {  // position in the list, or -1
         for (uint32_t i = 0; i < n_outputs; ++i)
@@ -84,6 +94,7 @@ enum class PlanRules { Frame, Buckets };
 inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
     FramePlan plan;
     const bool frame = rules == PlanRules::Frame, first_hit = a.aov[0] || a.aov[1] || a.matte.on;
+    const bool guides = a.guide[0] || a.guide[1];
     int code = NART_E_UNSUPPORTED;
     std::string why;
     if (a.moment && !a.beauty) {
@@ -101,6 +112,15 @@ inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
         why = "the cascade layers need the path kernel (the beauty)";
     } else if (a.matte.on && a.matte.n_ids > FRAME_MAX_MATTE_IDS) {  // (what the list of outputs holds)
         why = "the scene has " + std::to_string(a.matte.n_ids) + " matte ids; at most 32 are supported";
+    } else if (guides && a.integrator == NART_INTEGRATOR_VOLUME) {
+        why = "followed guides need surfaces: the volume integrator has none";
+    } else if (guides && (a.adaptive || a.cascade.K || a.matte.on)) {
+        why = "followed guides need a uniform render without the cascade and the mattes";
+    } else if (guides && (a.aov[0] || a.aov[1])) {
+        why = "followed guides and first-hit AOVs are not rendered in one call";
+    } else if (guides && a.max_follow > FRAME_MAX_FOLLOW) {
+        code = NART_E_INVALID;
+        why = "max_follow must be 0..10";
     }
     if (!why.empty()) {
         plan.code = code;
@@ -115,6 +135,8 @@ inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
     if (a.moment) add(OutputKind::Moment, 0);
     for (uint32_t j = 0; j < a.cascade.K; ++j) add(OutputKind::Layer, j);
     for (uint32_t q = 0; q < a.matte.planes(); ++q) add(OutputKind::Plane, q);
+    if (a.guide[0]) add(OutputKind::GuideAlbedo, 0);
+    if (a.guide[1]) add(OutputKind::GuideNormal, 0);
     // An adaptive render estimates a bucket's error from its moment tiles: every level runs the moment
     // pass, wanted or not (adaptive_level_ask).
     bool runs[N_PASSES + 1] = {};
@@ -123,7 +145,7 @@ inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
     for (uint32_t k = 0; k < N_PASSES; ++k)
         if (runs[k]) plan.passes[plan.n_passes++] = (PassKind)k;
     plan.path_kernel = a.beauty;
-    plan.record_bytes = a.cascade.K ? 16 : 0;  // one float4 per sample
+    plan.record_bytes = (a.cascade.K || (a.guide[0] && a.guide[1])) ? 16 : 0;  // one float4 per sample
     return plan;
 }
 

@@ -38,6 +38,11 @@
 //                   after the main one.  Not offered together with --adaptive or --robust: an error
 //   --matte-ranks N with --mattes: the ranks kept per pixel, even and in 2..8 (default 6)
 //   --matte-ids a,b,..  with --mattes: also write <out>.matte.exr, the summed coverage of that id set
+//   --follow-specular [N]  with --aovs and/or --denoise: <out>.albedo.exr, <out>.normal.exr and
+//                   <out>.denoised.exr come from the followed guides (nart_hip_render_guides,
+//                   nart_hip_render_denoised_guides): the first surface behind perfect mirrors and smooth
+//                   glass, at most N (0..10, default 8) interfaces deep.  Without --aovs or --denoise,
+//                   or together with --adaptive, --robust or --mattes: an error
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -269,6 +274,24 @@ int main(int argc, char* argv[]) {
             }
         }
     }
+    // --follow-specular [N]: the AOVs and the denoiser's guides follow mirrors and smooth glass
+    nart_guide_params gp;
+    nart_hip_guide_defaults(&gp);
+    float follow_arg = (float)gp.max_follow;
+    const bool follow = take_optional_value_flag(args, "--follow-specular", follow_arg);
+    if (follow && !aovs && !denoise) {
+        std::fprintf(stderr, "Error: --follow-specular selects the guides of --aovs and --denoise and needs one of them\n");
+        return EXIT_FAILURE;
+    }
+    if (follow && (adaptive || robust || mattes)) {
+        std::fprintf(stderr, "Error: --follow-specular is not offered together with --adaptive, --robust or --mattes\n");
+        return EXIT_FAILURE;
+    }
+    if (follow && !(follow_arg >= 0.f && follow_arg <= (float)NART_GUIDE_MAX_FOLLOW && follow_arg == (float)(int)follow_arg)) {
+        std::fprintf(stderr, "Error: --follow-specular %g: a whole number in 0..10\n", follow_arg);
+        return EXIT_FAILURE;
+    }
+    if (follow) gp.max_follow = (uint32_t)follow_arg;
     nart_adaptive_params ap;
     nart_hip_adaptive_params_init(&ap);
     if (adaptive) {
@@ -366,6 +389,21 @@ int main(int argc, char* argv[]) {
                 std::printf(" %llu of %llu samples\n", (unsigned long long)st.samples,
                             (unsigned long long)p.image_width * p.image_height * p.spp);
             }
+        } else if (follow && aovs) {
+            albedo.resize(image.size());
+            normal.resize(image.size());
+            if (sample_variance) moment.resize(image.size());
+            rc = nart_hip_render_guides(ctx, &p, &gp, NART_AOV_ALBEDO | NART_AOV_NORMAL, image.data(), albedo.data(),
+                                        normal.data(), sample_variance ? moment.data() : nullptr, nullptr, nullptr);
+            if (rc == NART_OK && sample_variance)
+                rc = nart_hip_denoise_moment(ctx, &p, nullptr, image.data(), albedo.data(), normal.data(), moment.data(),
+                                             denoised.data(), nullptr);
+            else if (rc == NART_OK && denoise)
+                rc = nart_hip_denoise(ctx, &p, nullptr, image.data(), albedo.data(), normal.data(), denoised.data(),
+                                      nullptr);
+        } else if (follow) {
+            rc = nart_hip_render_denoised_guides(ctx, &p, nullptr, &gp, sample_variance ? 1 : 0, image.data(),
+                                                 denoised.data(), nullptr, nullptr);
         } else if (aovs && sample_variance) {
             albedo.resize(image.size());
             normal.resize(image.size());

@@ -20,6 +20,7 @@
 #include "device/adaptive.h"
 #include "device/cascade.h"
 #include "device/denoise.h"
+#include "device/guide.h"
 #include "device/lbvh.h"
 #include "device/matte.h"
 #include "device/volume.h"
@@ -1156,6 +1157,21 @@ int launch_aov(nart_ctx* ctx, const RenderArgs& a, int rec, float4* out, hipStre
     return NART_OK;
 }
 
+// The followed-guide chains of the batch in `a` (device/guide.h k_guide): ga.albedo and ga.normal
+// receive the records, either may be null.  Launched as the per-lane k_primary: 256-lane blocks on
+// stack_depth * 256 * 8 bytes of LDS.
+template <bool DUMP>
+int launch_guide(nart_ctx* ctx, const RenderArgs& a, const GuideArgs& ga, hipStream_t st) {
+    const void* f = ctx->has_env ? (const void*)k_guide<true, DUMP> : (const void*)k_guide<false, DUMP>;
+    HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    const dim3 grid((a.n_slots + 255) / 256), block(256);
+    const size_t lds = (size_t)ctx->stack_depth * 256 * 8;
+    if (ctx->has_env) hipLaunchKernelGGL((k_guide<true, DUMP>), grid, block, lds, st, ctx->scene, a, ga);
+    else hipLaunchKernelGGL((k_guide<false, DUMP>), grid, block, lds, st, ctx->scene, a, ga);
+    HIPCHK(hipGetLastError());
+    return NART_OK;
+}
+
 // s into `into`, field by field (render_ms is the caller's wall clock: RenderTimer).  Device times
 // and the launch count add up over the batches and renders of one device (Sum) and take the slowest
 // of devices that run concurrently (Max); work counts always add up.
@@ -1356,7 +1372,9 @@ int launch_splat(nart_ctx* ctx, const SplatPlan& plan, const SplatArgs& sa, uint
 // frame plan's passes (frame_plan.h PassKind, which gives their order and why): per output of the pass, one
 // small kernel fills a record buffer -- ctx->d_L, which the beauty splat has consumed by then, so no
 // extra per-sample memory; for the cascade a second record buffer, a temporary of this call -- and the
-// same splat kernel takes it into that output's tiles.  times: the passes' device times are added.
+// same splat kernel takes it into that output's tiles.  The guide pass fills the records of both its
+// outputs by one k_guide launch at its start (the normal record in a temporary of this call where
+// both are asked for).  times: the passes' device times are added.
 int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n, const FrameTiles& out,
                    hipStream_t st, nart_render_stats* stats, PassTimes* times = nullptr) {
     int rc = NART_OK;
@@ -1375,6 +1393,7 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
     if (ctx->counters) HIPCHK(hipMemsetAsync(d_counters, 0, ctx->d_counters.bytes(), st));
     const size_t limit = batch_slot_limit(ctx, p->spp, frame.record_bytes);
     Buf layer_records;  // cascade: the second per-sample record buffer, 16 B per sample; freed on return
+    Buf guide_records;  // both followed guides: the normal records, likewise
     const uint32_t tpx = g.tile_size * g.tile_size;
     nart_render_stats acc;  // this call's share, added to *stats at the end
     std::memset(&acc, 0, sizeof(acc));
@@ -1445,9 +1464,19 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             // the dispatch's own camera-ray hits where it traced them first, else k_primary now
             if ((pass == PASS_FIRST_HIT || pass == PASS_MATTE) && !ctx->prim_valid && (rc = launch_aov_primary(ctx, ra, st)))
                 return rc;
+            const bool two_guides = pass == PASS_GUIDE && frame.ask.guide[0] && frame.ask.guide[1];
+            if (two_guides && (rc = reserve(ctx, guide_records, ctx->device, ns * sizeof(float4), "guide normal records")))
+                return rc;
             HIPCHK(record(ctx->ev_pass[pass][0], st));
             float4* const records = (pass == PASS_CASCADE ? layer_records : ctx->d_L).as<float4>();
             sa.Lout = records;
+            GuideArgs ga;
+            if (pass == PASS_GUIDE) {
+                ga.max_follow = frame.ask.max_follow;
+                if (frame.ask.guide[0]) ga.albedo = records;
+                if (frame.ask.guide[1]) ga.normal = two_guides ? guide_records.as<float4>() : records;
+                if ((rc = launch_guide<false>(ctx, ra, ga, st))) return rc;
+            }
             for (uint32_t o = 0; o < frame.n_outputs; ++o) {
                 const FrameOutput& w = frame.outputs[o];
                 if (pass_of(w.kind) != pass) continue;
@@ -1492,6 +1521,8 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
                     hipLaunchKernelGGL(k_matte_ids, rec_grid, rec_block, 0, st, ma);
                     break;
                 }
+                case OutputKind::GuideAlbedo: sa.Lout = ga.albedo; break;  // (filled at the start of the pass)
+                case OutputKind::GuideNormal: sa.Lout = ga.normal; break;
                 case OutputKind::Beauty: break;  // (no pass: pass_of)
                 }
                 HIPCHK(hipGetLastError());
@@ -2066,9 +2097,18 @@ int denoise_host(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_
     return NART_OK;
 }
 
-// nart_hip_render_denoised and, with sample_variance, nart_hip_render_denoised_moment.
+// gp (null: the defaults) into out, or NART_E_INVALID.
+int check_guide(nart_ctx* ctx, const nart_guide_params* gp, nart_guide_params& out) {
+    out.max_follow = gp ? gp->max_follow : 8u;
+    if (out.max_follow > NART_GUIDE_MAX_FOLLOW) return fail(ctx, NART_E_INVALID, "max_follow must be 0..10");
+    return NART_OK;
+}
+
+// nart_hip_render_denoised and, with sample_variance, nart_hip_render_denoised_moment; with follow,
+// nart_hip_render_denoised_guides: the followed guides in the first-hit AOVs' place.
 int render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, bool sample_variance,
-                    nart_pixel* image, nart_pixel* out, nart_render_stats* stats, double* denoise_ms) {
+                    nart_pixel* image, nart_pixel* out, nart_render_stats* stats, double* denoise_ms,
+                    const nart_guide_params* follow = nullptr) {
     nart_denoise_params d;
     int rc = check_denoise(ctx, dp, d);
     if (rc || (sample_variance && (rc = check_sample_variance(ctx, p)))) return rc;
@@ -2076,7 +2116,14 @@ int render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoi
     // beauty, both AOVs (and the moment image) into the first of its device images, the denoised image
     // after them: nothing passes the host
     FrameAsk ask(p->integrator);
-    ask.aov[AOV_ALBEDO] = ask.aov[AOV_NORMAL] = true;
+    if (follow) {
+        ask.guide[0] = ask.guide[1] = true;
+        ask.max_follow = follow->max_follow;
+    } else {
+        ask.aov[AOV_ALBEDO] = ask.aov[AOV_NORMAL] = true;
+    }
+    const OutputKind albedo = follow ? OutputKind::GuideAlbedo : OutputKind::Albedo;
+    const OutputKind normal = follow ? OutputKind::GuideNormal : OutputKind::Normal;
     ask.moment = sample_variance;
     const FramePlan plan = plan_frame(ask, PlanRules::Frame);
     const int n = sample_variance ? 5 : 4;
@@ -2088,8 +2135,7 @@ int render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoi
     const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
     float* img[5];
     if ((rc = denoise_images(c0, g, img, n)) ||  // (sized by the frame: this lays them out)
-        (rc = denoise_device(c0, p, d, img[plan.find(OutputKind::Beauty)], img[plan.find(OutputKind::Albedo)],
-                             img[plan.find(OutputKind::Normal)],
+        (rc = denoise_device(c0, p, d, img[plan.find(OutputKind::Beauty)], img[plan.find(albedo)], img[plan.find(normal)],
                              sample_variance ? img[plan.find(OutputKind::Moment)] : nullptr, img[n - 1], 0, denoise_ms)))
         return c0 == ctx ? rc : fail(ctx, rc, c0->err);
     HIPCHK(hipSetDevice(c0->device));
@@ -2120,6 +2166,30 @@ int render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_
     const int rc = render_frame(ctx, p, plan, rq, stats, &times);
     if (aov_ms) *aov_ms = times.ms[PASS_FIRST_HIT];
     if (moment_ms) *moment_ms = times.ms[PASS_MOMENT];
+    return rc;
+}
+
+// nart_hip_render_guides: render_aovs with the followed guides in the first-hit AOVs' place.
+int render_guides(nart_ctx* ctx, const nart_render_params* p, const nart_guide_params& gp, uint32_t aovs, nart_pixel* image,
+                  nart_pixel* albedo, nart_pixel* normal, nart_pixel* moment, nart_render_stats* stats, double* guide_ms) {
+    if (aovs & ~(NART_AOV_ALBEDO | NART_AOV_NORMAL)) return fail(ctx, NART_E_INVALID, "unknown AOV bit");
+    if (((aovs & NART_AOV_ALBEDO) && !albedo) || ((aovs & NART_AOV_NORMAL) && !normal))
+        return fail(ctx, NART_E_INVALID, "a guide is requested without its image buffer");
+    FrameAsk ask(p->integrator);
+    ask.beauty = image != nullptr || moment != nullptr;  // (the moment image needs the path kernel)
+    ask.moment = moment != nullptr;
+    ask.guide[0] = (aovs & NART_AOV_ALBEDO) != 0;
+    ask.guide[1] = (aovs & NART_AOV_NORMAL) != 0;
+    ask.max_follow = gp.max_follow;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    FrameRequest rq;
+    rq.to_host(plan, OutputKind::Beauty, image);
+    rq.to_host(plan, OutputKind::GuideAlbedo, albedo);
+    rq.to_host(plan, OutputKind::GuideNormal, normal);
+    rq.to_host(plan, OutputKind::Moment, moment);
+    PassTimes times;
+    const int rc = render_frame(ctx, p, plan, rq, stats, &times);
+    if (guide_ms) *guide_ms = times.ms[PASS_GUIDE];
     return rc;
 }
 
@@ -2955,6 +3025,72 @@ int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint
         for (size_t i = 0; i < ns; ++i) std::memcpy(out8 + i * 8 + 4 * k, rec.data() + i * 4, 4 * sizeof(float));
     }
     if (tri) HIPCHK(hipMemcpy(tri, ctx->d_prim.as<uint32_t>(), ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+void nart_hip_guide_defaults(nart_guide_params* gp) {
+    if (gp) gp->max_follow = 8;
+}
+
+int nart_hip_render_guides(nart_ctx* ctx, const nart_render_params* p, const nart_guide_params* gp, uint32_t aovs,
+                           nart_pixel* image, nart_pixel* albedo, nart_pixel* normal, nart_pixel* moment,
+                           nart_render_stats* stats, double* guide_ms) {
+    if (!ctx || !p) return NART_E_INVALID;
+    nart_guide_params g;
+    if (int rc = check_guide(ctx, gp, g)) return rc;
+    if (!aovs && !image && !moment) return fail(ctx, NART_E_INVALID, "neither the beauty, the moment image nor a guide is requested");
+    return render_guides(ctx, p, g, aovs, image, albedo, normal, moment, stats, guide_ms);
+}
+
+int nart_hip_render_denoised_guides(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                                    const nart_guide_params* gp, int sample_variance, nart_pixel* image,
+                                    nart_pixel* out, nart_render_stats* stats, double* denoise_ms) {
+    if (!ctx || !p || !out) return NART_E_INVALID;
+    nart_guide_params g;
+    if (int rc = check_guide(ctx, gp, g)) return rc;
+    return render_denoised(ctx, p, dp, sample_variance != 0, image, out, stats, denoise_ms, &g);
+}
+
+int nart_hip_render_guide_samples(nart_ctx* ctx, const nart_render_params* p, const nart_guide_params* gp, uint32_t x0,
+                                  uint32_t y0, uint32_t w, uint32_t h, float* out8, float* seg8, uint32_t* tri,
+                                  uint32_t* n_seg) {
+    if (!ctx || !p || !out8) return NART_E_INVALID;
+    if (!ctx->subs.empty()) {  // per-sample debugging runs on the first device
+        const int rc = nart_hip_render_guide_samples(ctx->subs[0], p, gp, x0, y0, w, h, out8, seg8, tri, n_seg);
+        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
+    }
+    nart_guide_params g;
+    int rc = check_guide(ctx, gp, g);
+    if (rc || (rc = check_params(ctx, p))) return rc;
+    if (p->integrator == NART_INTEGRATOR_VOLUME)  // (frames: plan_frame's rule)
+        return fail(ctx, NART_E_UNSUPPORTED, "followed guides need surfaces: the volume integrator has none");
+    if (!w || !h) return fail(ctx, NART_E_INVALID, "empty rect");
+    RenderArgs ra;
+    if ((rc = rect_slots(ctx, p, x0, y0, w, h, nullptr, ra)) || (rc = launch_latin(ctx, ra, 0))) return rc;
+    const size_t ns = (size_t)ra.n_slots * p->spp, M = g.max_follow + 1;
+    // the normal records, the segments, their triangles and the counts: temporaries, freed on return
+    Buf d_normal, d_seg, d_tri, d_n;
+    if ((rc = reserve(ctx, d_normal, ctx->device, ns * sizeof(float4), "guide normal records")) ||
+        (rc = reserve(ctx, d_seg, ctx->device, ns * M * 8 * sizeof(float), "guide segments")) ||
+        (rc = reserve(ctx, d_tri, ctx->device, ns * M * sizeof(uint32_t), "guide segment triangles")) ||
+        (rc = reserve(ctx, d_n, ctx->device, ns * sizeof(uint32_t), "guide segment counts")))
+        return rc;
+    GuideArgs ga;
+    ga.albedo = ctx->d_L.as<float4>();
+    ga.normal = d_normal.as<float4>();
+    ga.max_follow = g.max_follow;
+    ga.seg8 = d_seg.as<float>();
+    ga.tri = d_tri.as<uint32_t>();
+    ga.n_seg = d_n.as<uint32_t>();
+    if ((rc = launch_guide<true>(ctx, ra, ga, 0))) return rc;
+    std::vector<float> rec(ns * 4);
+    for (int k = 0; k < 2; ++k) {
+        HIPCHK(hipMemcpy(rec.data(), k ? ga.normal : ga.albedo, ns * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < ns; ++i) std::memcpy(out8 + i * 8 + 4 * k, rec.data() + i * 4, 4 * sizeof(float));
+    }
+    if (seg8) HIPCHK(hipMemcpy(seg8, ga.seg8, ns * M * 8 * sizeof(float), hipMemcpyDeviceToHost));
+    if (tri) HIPCHK(hipMemcpy(tri, ga.tri, ns * M * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_seg) HIPCHK(hipMemcpy(n_seg, ga.n_seg, ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return NART_OK;
 }
 
