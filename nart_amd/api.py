@@ -101,96 +101,63 @@ class RenderStats(ctypes.Structure):
 _P = ctypes.c_void_p
 
 
-class DenoiseParams(ctypes.Structure):
+class _StageParams(ctypes.Structure):
+    """What the five parameter structs of the whole-image stages share: Class.defaults() is the C ABI's
+    init function named by the subclass (_init), keyword arguments override single fields."""
+    _init = None
+
+    @classmethod
+    def defaults(cls, **kw):
+        sp = cls()
+        getattr(hip_lib(), cls._init)(ctypes.byref(sp))
+        for k, v in kw.items():
+            setattr(sp, k, v)
+        return sp
+
+    def __repr__(self):
+        return "%s(%s)" % (type(self).__name__, ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_))
+
+
+class DenoiseParams(_StageParams):
     """nart_denoise_params (include/nart_hip.h); DenoiseParams.defaults() is
     nart_hip_denoise_params_init, keyword arguments override single fields."""
     _fields_ = [("iterations", ctypes.c_uint32), ("normal_squarings", ctypes.c_uint32),
                 ("sigma_color", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("depth_eps", ctypes.c_float),
                 ("sigma_coverage", ctypes.c_float), ("albedo_floor", ctypes.c_float)]
-
-    @classmethod
-    def defaults(cls, **kw):
-        dp = cls()
-        hip_lib().nart_hip_denoise_params_init(ctypes.byref(dp))
-        for k, v in kw.items():
-            setattr(dp, k, v)
-        return dp
-
-    def __repr__(self):
-        return "DenoiseParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
+    _init = "nart_hip_denoise_params_init"
 
 
-class AdaptiveParams(ctypes.Structure):
+class AdaptiveParams(_StageParams):
     """nart_adaptive_params (include/nart_hip.h, "Adaptive sampling"); AdaptiveParams.defaults() is
     nart_hip_adaptive_params_init, keyword arguments override single fields."""
     _fields_ = [("min_spp", ctypes.c_uint32), ("growth", ctypes.c_uint32), ("threshold", ctypes.c_float),
                 ("floor", ctypes.c_float)]
-
-    @classmethod
-    def defaults(cls, **kw):
-        ap = cls()
-        hip_lib().nart_hip_adaptive_params_init(ctypes.byref(ap))
-        for k, v in kw.items():
-            setattr(ap, k, v)
-        return ap
-
-    def __repr__(self):
-        return "AdaptiveParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
+    _init = "nart_hip_adaptive_params_init"
 
 
-class CascadeParams(ctypes.Structure):
+class CascadeParams(_StageParams):
     """nart_cascade_params (include/nart_hip.h, "Firefly cascade"); CascadeParams.defaults() is
     nart_hip_cascade_defaults, keyword arguments override single fields."""
     _fields_ = [("layers", ctypes.c_uint32), ("start", ctypes.c_float), ("base", ctypes.c_float),
                 ("kappa", ctypes.c_float)]
-
-    @classmethod
-    def defaults(cls, **kw):
-        cp = cls()
-        hip_lib().nart_hip_cascade_defaults(ctypes.byref(cp))
-        for k, v in kw.items():
-            setattr(cp, k, v)
-        return cp
-
-    def __repr__(self):
-        return "CascadeParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
+    _init = "nart_hip_cascade_defaults"
 
 
-class MatteParams(ctypes.Structure):
+class MatteParams(_StageParams):
     """nart_matte_params (include/nart_hip.h, "First-hit ID mattes"); MatteParams.defaults() is
     nart_hip_matte_defaults, keyword arguments override single fields."""
     _fields_ = [("kind", ctypes.c_uint32), ("ranks", ctypes.c_uint32)]
-
-    @classmethod
-    def defaults(cls, **kw):
-        mp = cls()
-        hip_lib().nart_hip_matte_defaults(ctypes.byref(mp))
-        for k, v in kw.items():
-            setattr(mp, k, v)
-        return mp
-
-    def __repr__(self):
-        return "MatteParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
+    _init = "nart_hip_matte_defaults"
 
 
 MATTE_MESH, MATTE_MATERIAL = 0, 1  # NART_MATTE_* (include/nart_hip.h)
 
 
-class GuideParams(ctypes.Structure):
+class GuideParams(_StageParams):
     """nart_guide_params (include/nart_hip.h, "Followed guides"); GuideParams.defaults() is
     nart_hip_guide_defaults, keyword arguments override single fields."""
     _fields_ = [("max_follow", ctypes.c_uint32)]
-
-    @classmethod
-    def defaults(cls, **kw):
-        gp = cls()
-        hip_lib().nart_hip_guide_defaults(ctypes.byref(gp))
-        for k, v in kw.items():
-            setattr(gp, k, v)
-        return gp
-
-    def __repr__(self):
-        return "GuideParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_)
+    _init = "nart_hip_guide_defaults"
 
 
 class _Texture(ctypes.Structure):

@@ -52,7 +52,7 @@ def hip_source_sha():
     import hashlib
     h = hashlib.sha256()
     for f in _sources("render.hip", "device", "host/bvh_build.cpp", "host/bvh_build.h", "host/multi_gpu.h",
-                      "host/path_schedule.h", "host/path_build.h"):
+                      "host/path_schedule.h", "host/path_build.h", "host/image_stages.h"):
         h.update(os.path.relpath(f, CSRC).encode())
         with open(f, "rb") as fh:
             h.update(fh.read())

@@ -1,0 +1,402 @@
+// The stages over whole images that follow a frame -- the denoiser, the firefly cascade's reweighting,
+// the ID mattes' ranking and extraction -- and the frames of the first-hit AOVs and followed guides;
+// included by render.hip after render_frame.  Every stage has the same two layers:
+//   X_device   its kernels over images of a view (Images, render.hip), named by their positions in it;
+//   X_host     host images through the first device: upload, X_device, download (host_stage);
+//   render_X   a frame into device images of the first device, X_device over them there, and what the
+//              caller asked for to the host (frame_stage).
+// The denoiser's images and work buffers are the context's, kept between calls; the cascade's and the
+// mattes' images are temporaries of the call.  The parameters' rules are host/stage_params.h's.
+#pragma once
+
+namespace {
+
+// Host images through device images of a single-device context: the inputs (k images each, where
+// k may be 0) laid out back to back in `buf` from image 0, `stage` over the view, its n_out output
+// images, which follow the inputs, to `out`.
+struct HostImages {
+    const nart_pixel* src;
+    size_t k;
+};
+template <typename Stage>
+int host_stage(nart_ctx* ctx, const nart_render_params* p, Buf& buf, const char* what,
+               std::initializer_list<HostImages> in, nart_pixel* out, size_t n_out, Stage&& stage) {
+    size_t n_in = 0;
+    for (const HostImages& h : in) n_in += h.k;
+    Images v(ctx, p);
+    if (int rc = v.in(buf, n_in + n_out, what)) return rc;
+    size_t i = 0;
+    for (const HostImages& h : in) {
+        if (int rc = v.upload(i, h.src, h.k)) return rc;
+        i += h.k;
+    }
+    if (int rc = stage(v)) return rc;
+    return v.download(n_in, out, n_out);
+}
+
+// The frame of `plan` into n_images device images in `buf` on the first device (the plan's outputs
+// back to back in delivery order, room for the stage's after them), then `stage` over them on that
+// device; render_ms covers the whole call.  A plan without outputs (the mattes of a scene without
+// ids) renders nothing.  Errors of the first device are re-raised on ctx.
+template <typename Stage>
+int frame_stage(nart_ctx* ctx, const nart_render_params* p, const FramePlan& plan, Buf& buf, uint32_t n_images,
+                nart_render_stats* stats, PassTimes* times, Stage&& stage) {
+    nart_ctx* c0 = first_device(ctx);
+    if (plan.code || plan.n_outputs) {
+        if (int rc = render_frame(ctx, p, plan, FrameRequest(&buf, n_images), stats, times)) return rc;
+    } else if (int rc = forwarded(ctx, check_params(c0, p))) {
+        return rc;
+    }
+    RenderTimer timer(stats);
+    Images v(c0, p);
+    int rc = v.in(buf, n_images, "image");  // (sized by the frame: this lays them out)
+    if (!rc) rc = stage(v);
+    return forwarded(ctx, rc);
+}
+
+// ---------------------------------------------------------------- first-hit AOVs, followed guides
+// The message of what is wrong with the AOV bits of a call and their image buffers, or null.
+const char* aov_request_error(uint32_t aovs, const nart_pixel* albedo, const nart_pixel* normal, bool followed = false) {
+    if (aovs & ~(NART_AOV_ALBEDO | NART_AOV_NORMAL)) return "unknown AOV bit";
+    if (((aovs & NART_AOV_ALBEDO) && !albedo) || ((aovs & NART_AOV_NORMAL) && !normal))
+        return followed ? "a guide is requested without its image buffer" : "an AOV is requested without its image buffer";
+    return nullptr;
+}
+
+// The AOVs of `aovs` into the ask: first-hit, or with `follow` the followed guides in their place.
+void ask_aovs(FrameAsk& ask, uint32_t aovs, const nart_guide_params* follow = nullptr) {
+    bool* which = follow ? ask.guide : ask.aov;
+    which[AOV_ALBEDO] = (aovs & NART_AOV_ALBEDO) != 0;
+    which[AOV_NORMAL] = (aovs & NART_AOV_NORMAL) != 0;
+    if (follow) ask.max_follow = follow->max_follow;
+}
+
+// Where the beauty, the two AOVs (or guides) and the moment image of `plan` go on the host.
+void aovs_to_host(FrameRequest& rq, const FramePlan& plan, bool followed, nart_pixel* image, nart_pixel* albedo,
+                  nart_pixel* normal, nart_pixel* moment) {
+    rq.to_host(plan, OutputKind::Beauty, image);
+    rq.to_host(plan, followed ? OutputKind::GuideAlbedo : OutputKind::Albedo, albedo);
+    rq.to_host(plan, followed ? OutputKind::GuideNormal : OutputKind::Normal, normal);
+    rq.to_host(plan, OutputKind::Moment, moment);
+}
+
+// nart_hip_render_aovs (moment null), nart_hip_render_moment and, with follow, nart_hip_render_guides:
+// the followed guides in the first-hit AOVs' place.  aov_ms: the first-hit or the guide pass.
+int render_aovs(nart_ctx* ctx, const nart_render_params* p, const nart_guide_params* follow, uint32_t aovs, nart_pixel* image,
+                nart_pixel* albedo, nart_pixel* normal, nart_pixel* moment, nart_render_stats* stats, double* aov_ms,
+                double* moment_ms) {
+    if (const char* why = aov_request_error(aovs, albedo, normal, follow != nullptr)) return fail(ctx, NART_E_INVALID, why);
+    FrameAsk ask(p->integrator);
+    // the moment image needs the path kernel: with it the beauty is rendered even where it is not asked for
+    ask.beauty = image != nullptr || moment != nullptr;
+    ask.moment = moment != nullptr;
+    ask_aovs(ask, aovs, follow);
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    FrameRequest rq;
+    aovs_to_host(rq, plan, follow != nullptr, image, albedo, normal, moment);
+    PassTimes times;
+    const int rc = render_frame(ctx, p, plan, rq, stats, &times);
+    if (aov_ms) *aov_ms = times.ms[follow ? PASS_GUIDE : PASS_FIRST_HIT];
+    if (moment_ms) *moment_ms = times.ms[PASS_MOMENT];
+    return rc;
+}
+
+// ---------------------------------------------------------------- denoiser (device/denoise.h)
+// Denoise images of the view: prepare, variance, the a-trous passes (LDS tiles for steps 1 and 2,
+// global reads beyond), finalise; synchronous.  ms: device time.  moment >= 0: the sample-variance
+// mode -- k_dn_prepare<true> takes the variance from the second-moment image and k_dn_variance is not
+// launched (its time reads 0).
+int denoise_device(const Images& v, const nart_denoise_params& dp, int beauty, int albedo, int normal, int moment, int out,
+                   hipStream_t st, double* ms) {
+    nart_ctx* ctx = v.ctx;
+    const size_t npx = (size_t)v.layout.W * v.layout.H;
+    // guide, signal x 2, centre (float4 each), then cov and slope
+    const size_t work_bytes = npx * (4 * sizeof(float4) + 2 * sizeof(float));
+    if (int rc = reserve(ctx, ctx->d_dn, ctx->device, work_bytes, "denoiser work buffers")) return rc;
+    float4* f4 = ctx->d_dn.as<float4>();
+    float4* sig[2] = {f4 + npx, f4 + 2 * npx};
+    const bool sample_variance = moment >= 0;
+    DnArgs a;
+    a.beauty = v.at(beauty);
+    a.albedo = v.at(albedo);
+    a.normal = v.at(normal);
+    a.moment = sample_variance ? v.at(moment) : nullptr;
+    a.out = v.at(out);
+    a.guide = f4;
+    a.centre = f4 + 3 * npx;
+    a.cov = reinterpret_cast<float*>(f4 + 4 * npx);
+    a.slope = a.cov + npx;
+    v.layout.fill(a);
+    a.step = 1;
+    a.normal_squarings = dp.normal_squarings;
+    a.sigma_color = dp.sigma_color;
+    a.sigma_depth = dp.sigma_depth;
+    a.depth_eps = dp.depth_eps;
+    a.sigma_coverage = dp.sigma_coverage;
+    a.albedo_floor = dp.albedo_floor;
+    const dim3 grid((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH), block(256);
+    uint32_t e = 0;
+    HIPCHK(record(ctx->ev_dn[e++], st));
+    a.sig_in = nullptr;
+    if (sample_variance) {  // signal and variance at once, where the variance pass would have left them
+        a.sig_out = sig[1];
+        hipLaunchKernelGGL(k_dn_prepare<true>, grid, block, 0, st, a);
+        HIPCHK(record(ctx->ev_dn[e++], st));
+    } else {
+        a.sig_out = sig[0];
+        hipLaunchKernelGGL(k_dn_prepare<false>, grid, block, 0, st, a);
+        HIPCHK(record(ctx->ev_dn[e++], st));
+        a.sig_in = sig[0];
+        a.sig_out = sig[1];
+        hipLaunchKernelGGL(k_dn_variance, grid, block, 0, st, a);
+    }
+    HIPCHK(record(ctx->ev_dn[e++], st));
+    int cur = 1;
+    for (uint32_t i = 0; i < dp.iterations; ++i) {
+        a.sig_in = sig[cur];
+        a.sig_out = sig[cur ^ 1];
+        a.step = 1u << i;
+        if (i == 0) hipLaunchKernelGGL(k_dn_atrous<2>, grid, block, 0, st, a);
+        else if (i == 1) hipLaunchKernelGGL(k_dn_atrous<4>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_dn_atrous<0>, grid, block, 0, st, a);
+        HIPCHK(record(ctx->ev_dn[e++], st));
+        cur ^= 1;
+    }
+    a.sig_in = sig[cur];
+    const size_t n_total = (size_t)a.totalW * a.totalH;
+    hipLaunchKernelGGL(k_dn_finalize, dim3((uint32_t)((n_total + 255) / 256)), block, 0, st, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(record(ctx->ev_dn[e++], st));
+    HIPCHK(hipEventSynchronize(ctx->ev_dn[e - 1].handle()));
+    for (double& t : ctx->dn_ms) t = 0.0;
+    double total = 0.0;
+    for (uint32_t k = 0; k + 1 < e; ++k) {
+        if (sample_variance && k == 1) continue;  // no variance kernel ran between these two events
+        float t = 0.f;
+        HIPCHK(hipEventElapsedTime(&t, ctx->ev_dn[k].handle(), ctx->ev_dn[k + 1].handle()));
+        // events 0..2 bracket prepare and variance, the last pair the finalise kernel
+        ctx->dn_ms[k + 2 == e ? 10 : k] = t;
+        total += t;
+    }
+    if (ms) *ms = total;
+    return NART_OK;
+}
+
+// dp (null: the defaults) into d for a call that denoises, with the second-moment image or not.
+int check_denoise(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, bool sample_variance,
+                  nart_denoise_params& d) {
+    const char* why = denoise_params_error(dp, d);
+    if (!why && sample_variance) why = check_sample_variance(p);
+    return why ? fail(ctx, NART_E_INVALID, why) : NART_OK;
+}
+
+// nart_hip_denoise (moment null) and nart_hip_denoise_moment.  The images are the context's: 4 (beauty,
+// albedo, normal, denoised), or 5 in the sample-variance mode (beauty, albedo, normal, moment, denoised).
+int denoise_host(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, const nart_pixel* beauty,
+                 const nart_pixel* albedo, const nart_pixel* normal, const nart_pixel* moment, nart_pixel* out,
+                 double* denoise_ms) {
+    nart_denoise_params d;
+    if (int rc = check_denoise(ctx, p, dp, moment != nullptr, d)) return rc;
+    if (!ctx->subs.empty())
+        return forwarded(ctx, denoise_host(first_device(ctx), p, &d, beauty, albedo, normal, moment, out, denoise_ms));
+    if (const char* why = check_image_size(p)) return fail(ctx, NART_E_INVALID, why);
+    const int n_in = moment ? 4 : 3;
+    return host_stage(ctx, p, ctx->d_dn_img, "denoiser images",
+                      {{beauty, 1}, {albedo, 1}, {normal, 1}, {moment, moment ? 1u : 0u}}, out, 1, [&](const Images& v) {
+                          return denoise_device(v, d, 0, 1, 2, moment ? 3 : -1, n_in, 0, denoise_ms);
+                      });
+}
+
+// nart_hip_render_denoised and, with sample_variance, nart_hip_render_denoised_moment; with follow,
+// nart_hip_render_denoised_guides: the followed guides in the first-hit AOVs' place.
+int render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, bool sample_variance,
+                    nart_pixel* image, nart_pixel* out, nart_render_stats* stats, double* denoise_ms,
+                    const nart_guide_params* follow = nullptr) {
+    nart_denoise_params d;
+    if (int rc = check_denoise(ctx, p, dp, sample_variance, d)) return rc;
+    // beauty, both AOVs (and the moment image) into the first of the denoising context's device images,
+    // the denoised image after them: nothing passes the host
+    FrameAsk ask(p->integrator);
+    ask_aovs(ask, NART_AOV_ALBEDO | NART_AOV_NORMAL, follow);
+    ask.moment = sample_variance;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    const int n = sample_variance ? 5 : 4;
+    return frame_stage(ctx, p, plan, first_device(ctx)->d_dn_img, (uint32_t)n, stats, nullptr, [&](const Images& v) {
+        const int b = plan.find(OutputKind::Beauty);
+        int rc = denoise_device(v, d, b, plan.find(follow ? OutputKind::GuideAlbedo : OutputKind::Albedo),
+                                plan.find(follow ? OutputKind::GuideNormal : OutputKind::Normal),
+                                sample_variance ? plan.find(OutputKind::Moment) : -1, n - 1, 0, denoise_ms);
+        if (!rc && image) rc = v.download(b, image);
+        if (!rc) rc = v.download(n - 1, out);
+        return rc;
+    });
+}
+
+// ---------------------------------------------------------------- firefly cascade (device/cascade.h)
+// The reweighting over images of the view: the beauty, the K layer images back to back, the robust
+// image out; synchronous.  The time goes to the view's context (cas_ms[1]).
+int cascade_device(const Images& v, const nart_cascade_params& cp, const CascadeLevels& lv, uint32_t spp, int beauty,
+                   int layers, int out, hipStream_t st) {
+    nart_ctx* ctx = v.ctx;
+    CascadeReweightArgs a;
+    a.beauty = v.at(beauty);
+    a.layers = v.at(layers);
+    a.out = v.at(out);
+    v.layout.fill(a);
+    a.K = lv.K;
+    a.N = (float)spp;
+    a.kappa = cp.kappa;
+    for (uint32_t j = 0; j < CASCADE_MAX_LAYERS; ++j) a.b[j] = j < lv.K ? lv.b[j] : 0.f;
+    return timed(ctx, ctx->ev_cas, st, &ctx->cas_ms[1], [&]() -> int {
+        // the border stays zero: the kernel writes the cropped pixels only
+        if (int rc = v.zero_async(out, 1, st)) return rc;
+        const dim3 grid((a.W + CS_TW - 1) / CS_TW, (a.H + CS_TH - 1) / CS_TH), block(CS_TW * CS_TH);
+        hipLaunchKernelGGL(k_cascade_reweight, grid, block, (size_t)lv.K * CS_PLANE * sizeof(float), st, a);
+        HIPCHK(hipGetLastError());
+        return NART_OK;
+    });
+}
+
+// The tile buffers a context keeps between whole frames grow with the number of outputs a frame
+// has.  A cascade or matte frame has up to twelve: what it made them grow by is given back when the
+// call returns, so that a later render finds the free memory (batch_slot_limit) it found before.
+struct TileGrowthGuard {
+    nart_ctx* ctx;
+    size_t gather_bytes;
+    std::vector<size_t> sub_bytes;
+    explicit TileGrowthGuard(nart_ctx* c) : ctx(c), gather_bytes(c->d_gather.bytes()) {
+        for (const Buf& b : c->sub_tiles) sub_bytes.push_back(b.bytes());
+    }
+    TileGrowthGuard(const TileGrowthGuard&) = delete;
+    ~TileGrowthGuard() {
+        if (ctx->d_gather.bytes() > gather_bytes) ctx->d_gather.release();
+        for (size_t d = 0; d < sub_bytes.size(); ++d)
+            if (ctx->sub_tiles[d].bytes() > sub_bytes[d]) ctx->sub_tiles[d].release();
+    }
+};
+
+// nart_hip_render_cascade: the beauty and the K layers, the robust image after them.
+int render_cascade(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params& cp, const CascadeLevels& lv,
+                   nart_pixel* image, nart_pixel* beauty, nart_pixel* layers, nart_render_stats* stats) {
+    ctx->cas_ms[0] = first_device(ctx)->cas_ms[1] = 0.0;  // (the reweighting's time is kept where it runs)
+    TileGrowthGuard guard(ctx);
+    Buf imgs;  // the device images of the call, on device 0; freed on return
+    const uint32_t K = lv.K;
+    FrameAsk ask(p->integrator);
+    ask.cascade = lv;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    PassTimes times;
+    const int rc = frame_stage(ctx, p, plan, imgs, K + 2, stats, &times, [&](const Images& v) {
+        // the plan's images back to back (the layers follow one another), the robust image after them
+        const int b = plan.find(OutputKind::Beauty), l = plan.find(OutputKind::Layer, 0), o = (int)plan.n_outputs;
+        int rc = cascade_device(v, cp, lv, p->spp, b, l, o, 0);
+        if (!rc) rc = v.download(o, image);
+        if (!rc && beauty) rc = v.download(b, beauty);
+        if (!rc && layers) rc = v.download(l, layers, K);
+        return rc;
+    });
+    ctx->cas_ms[0] = times.ms[PASS_CASCADE];
+    return rc;
+}
+
+// nart_hip_cascade_reweight.
+int cascade_host(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params& cp, const CascadeLevels& lv,
+                 const nart_pixel* beauty, const nart_pixel* layers, nart_pixel* image) {
+    ctx->cas_ms[0] = first_device(ctx)->cas_ms[1] = 0.0;  // (the reweighting's time is kept where it runs)
+    if (!ctx->subs.empty()) return forwarded(ctx, cascade_host(first_device(ctx), p, cp, lv, beauty, layers, image));
+    const uint32_t K = lv.K;
+    Buf imgs;  // the beauty, the layers, the robust image; freed on return
+    return host_stage(ctx, p, imgs, "cascade images", {{beauty, 1}, {layers, K}}, image, 1,
+                      [&](const Images& v) { return cascade_device(v, cp, lv, p->spp, 0, 1, (int)K + 1, 0); });
+}
+
+// ---------------------------------------------------------------- first-hit ID mattes (device/matte.h)
+// The ranking over images of the view: the planes back to back (none with no ids), the R / 2 rank
+// images out; synchronous.  The time goes to the view's context (mat_ms[1]).
+int matte_rank_device(const Images& v, uint32_t n_ids, uint32_t R, int planes, int ranks, hipStream_t st) {
+    nart_ctx* ctx = v.ctx;
+    MatteRankArgs a;
+    a.planes = n_ids ? v.at(planes) : nullptr;
+    a.out = v.at(ranks);
+    v.layout.fill(a);
+    a.n_ids = n_ids;
+    a.R = R;
+    return timed(ctx, ctx->ev_mat, st, &ctx->mat_ms[1], [&]() -> int {
+        // the border stays zero: the kernel writes the cropped pixels only
+        if (int rc = v.zero_async(ranks, R / 2, st)) return rc;
+        const dim3 grid((a.W + MT_TW - 1) / MT_TW, (a.H + MT_TH - 1) / MT_TH), block(MT_LANES);
+        const size_t lds = (size_t)((n_ids + 3) / 4) * 4 * MT_LANES * sizeof(float);
+        hipLaunchKernelGGL(k_matte_rank, grid, block, lds, st, a);
+        HIPCHK(hipGetLastError());
+        return NART_OK;
+    });
+}
+
+// The matte of the ids in `mask` from the R / 2 rank images of the view.
+int matte_extract_device(const Images& v, uint32_t R, uint64_t mask, int ranks, int out, hipStream_t st) {
+    nart_ctx* ctx = v.ctx;
+    if (int rc = v.zero_async(out, 1, st)) return rc;  // the border stays zero
+    MatteExtractArgs a;
+    a.ranks = v.at(ranks);
+    a.out = v.at(out);
+    v.layout.fill(a);
+    a.R = R;
+    a.mask = mask;
+    const uint64_t n = (uint64_t)a.W * a.H;
+    hipLaunchKernelGGL(k_matte_extract, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
+    HIPCHK(hipGetLastError());
+    return NART_OK;
+}
+
+// nart_hip_render_mattes: the planes (and the beauty, if asked for), the rank images after them.  A
+// scene without ids renders no plane: its ranks are empty.
+int render_mattes(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params& mp, nart_pixel* ranks,
+                  nart_pixel* image, nart_pixel* planes, nart_render_stats* stats) {
+    nart_ctx* c0 = first_device(ctx);
+    ctx->mat_ms[0] = c0->mat_ms[1] = 0.0;  // (the ranking's time is kept where it runs)
+    FrameAsk ask(p->integrator);
+    ask.beauty = image != nullptr;
+    ask.matte.on = true;
+    ask.matte.kind = mp.kind;
+    ask.matte.n_ids = mp.kind == NART_MATTE_MATERIAL ? c0->num_materials : c0->num_meshes;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    if (plan.code) return fail(ctx, plan.code, plan.message);  // (before anything is allocated)
+    TileGrowthGuard guard(ctx);
+    Buf imgs;  // the device images of the call, on device 0; freed on return
+    const uint32_t n_ids = ask.matte.n_ids, P = ask.matte.planes(), R = mp.ranks;
+    PassTimes times;
+    const int rc = frame_stage(ctx, p, plan, imgs, plan.n_outputs + R / 2, stats, &times, [&](const Images& v) {
+        // the plan's images back to back (the planes follow one another), the rank images after them
+        const int pl = P ? plan.find(OutputKind::Plane, 0) : 0, rk = (int)plan.n_outputs;
+        int rc = matte_rank_device(v, n_ids, R, pl, rk, 0);
+        if (!rc) rc = v.download(rk, ranks, R / 2);
+        if (!rc && image) rc = v.download(plan.find(OutputKind::Beauty), image);
+        if (!rc && planes) rc = v.download(pl, planes, P);
+        return rc;
+    });
+    ctx->mat_ms[0] = times.ms[PASS_MATTE];
+    return rc;
+}
+
+// nart_hip_matte_rank.
+int matte_rank_host(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params& mp, uint32_t n_ids,
+                    const nart_pixel* planes, nart_pixel* ranks) {
+    ctx->mat_ms[0] = first_device(ctx)->mat_ms[1] = 0.0;
+    if (!ctx->subs.empty()) return forwarded(ctx, matte_rank_host(first_device(ctx), p, mp, n_ids, planes, ranks));
+    const uint32_t P = (n_ids + 3) / 4, R = mp.ranks;
+    Buf imgs;  // the planes, the rank images; freed on return
+    return host_stage(ctx, p, imgs, "matte images", {{planes, P}}, ranks, R / 2,
+                      [&](const Images& v) { return matte_rank_device(v, n_ids, R, 0, (int)P, 0); });
+}
+
+// nart_hip_matte_extract.
+int matte_extract_host(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params& mp, const nart_pixel* ranks,
+                       uint64_t id_mask, nart_pixel* out) {
+    if (!ctx->subs.empty()) return forwarded(ctx, matte_extract_host(first_device(ctx), p, mp, ranks, id_mask, out));
+    const uint32_t R = mp.ranks;
+    Buf imgs;  // the rank images, the matte; freed on return
+    return host_stage(ctx, p, imgs, "matte images", {{ranks, R / 2}}, out, 1,
+                      [&](const Images& v) { return matte_extract_device(v, R, id_mask, 0, (int)R / 2, 0); });
+}
+
+}  // namespace

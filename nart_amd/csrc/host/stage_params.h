@@ -1,0 +1,115 @@
+// The parameter structs of the stages that work on whole images (include/nart_hip.h: denoiser,
+// adaptive sampling, firefly cascade, ID mattes, followed guides), as far as they need no device: their
+// defaults, their rules and what is computed from them alone (no HIP, no context).  Every X_params_error
+// has one shape: `in` (null: the defaults) is copied into `out`, and the message of the first broken
+// rule is returned, or null.  The entry points of render.hip raise the message as NART_E_INVALID.
+// tests/test_stage_params.py compares all of this with a restatement of the rules.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "../../../include/nart_hip.h"
+#include "frame_plan.h"
+
+namespace nd {
+
+constexpr uint32_t STAGE_MAX_RANKS = 8;  // device/matte.h MATTE_MAX_RANKS
+
+// The defaults, field by field in the structs' order, as include/nart_hip.h documents them.
+constexpr nart_denoise_params DENOISE_DEFAULTS = {5, 5, 4.f, 1.f, 1e-3f, 0.05f, 0.01f};
+constexpr nart_guide_params GUIDE_DEFAULTS = {8};
+constexpr nart_adaptive_params ADAPTIVE_DEFAULTS = {16, 4, 0.1f, 0.01f};
+constexpr nart_cascade_params CASCADE_DEFAULTS = {6, 1.f, 8.f, 2.f};
+constexpr nart_matte_params MATTE_DEFAULTS = {NART_MATTE_MESH, 6};
+
+// ---------------------------------------------------------------- denoiser
+inline const char* denoise_params_error(const nart_denoise_params* in, nart_denoise_params& out) {
+    out = in ? *in : DENOISE_DEFAULTS;
+    if (out.iterations < 1 || out.iterations > 8) return "denoise iterations must be 1..8";
+    if (out.normal_squarings > 16) return "denoise normal_squarings must be <= 16";
+    if (!(out.sigma_color > 0.f) || !(out.sigma_depth > 0.f) || !(out.depth_eps > 0.f) || !(out.sigma_coverage > 0.f) ||
+        !(out.albedo_floor > 0.f))
+        return "denoise sigmas, depth_eps and albedo_floor must be > 0";
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- followed guides
+inline const char* guide_params_error(const nart_guide_params* in, nart_guide_params& out) {
+    out = in ? *in : GUIDE_DEFAULTS;
+    if (out.max_follow > NART_GUIDE_MAX_FOLLOW) return "max_follow must be 0..10";
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- adaptive sampling
+// spp: the render's sample count (nart_render_params::spp).
+inline const char* adaptive_params_error(const nart_adaptive_params* in, nart_adaptive_params& out, uint32_t spp) {
+    out = in ? *in : ADAPTIVE_DEFAULTS;
+    if (out.min_spp < 2) return "adaptive min_spp must be >= 2 (one sample has no variance)";
+    if (spp < 2) return "adaptive sampling needs spp >= 2 (one sample has no variance)";
+    if (out.growth < 2 || out.growth > 16) return "adaptive growth must be in 2..16";
+    if (!(out.threshold >= 0.f)) return "adaptive threshold must be >= 0 (+inf: nothing refines)";
+    if (!(out.floor > 0.f) || !std::isfinite(out.floor)) return "adaptive floor must be finite and > 0";
+    return nullptr;
+}
+
+// L_0 = min_spp, L_{i+1} = min(L_i * growth, spp), ending on spp; the one level spp if min_spp >= spp.
+constexpr uint32_t ADAPTIVE_MAX_LEVELS = 32;
+inline std::vector<uint32_t> adaptive_levels(const nart_adaptive_params& ap, uint32_t spp) {
+    std::vector<uint32_t> levels;
+    uint64_t L = ap.min_spp;
+    while (L < spp && levels.size() + 1 < ADAPTIVE_MAX_LEVELS) {
+        levels.push_back((uint32_t)L);
+        L = std::min<uint64_t>(L * ap.growth, spp);
+    }
+    levels.push_back(spp);
+    return levels;
+}
+
+// ---------------------------------------------------------------- firefly cascade
+// Also the levels b[j] = start * base^j into lv, by repeated float multiplication.
+inline const char* cascade_params_error(const nart_cascade_params* in, nart_cascade_params& out, CascadeLevels& lv) {
+    out = in ? *in : CASCADE_DEFAULTS;
+    if (out.layers < 2 || out.layers > FRAME_MAX_LAYERS) return "cascade layers must be in 2..8";
+    if (!std::isfinite(out.start) || !(out.start > 0.f)) return "cascade start must be finite and > 0";
+    if (!std::isfinite(out.base) || !(out.base > 1.f)) return "cascade base must be finite and > 1";
+    if (!std::isfinite(out.kappa) || !(out.kappa > 0.f)) return "cascade kappa must be finite and > 0";
+    lv.K = out.layers;
+    lv.base = out.base;
+    float b = out.start;
+    for (uint32_t j = 0; j < lv.K; ++j) {
+        if (!std::isfinite(b)) return "a cascade level is not finite";
+        if (j > 0 && !(b > lv.b[j - 1])) return "the cascade levels do not increase (start too small for base)";
+        lv.b[j] = b;
+        b = b * out.base;
+    }
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- first-hit ID mattes
+inline const char* matte_params_error(const nart_matte_params* in, nart_matte_params& out) {
+    out = in ? *in : MATTE_DEFAULTS;
+    if (out.kind != NART_MATTE_MESH && out.kind != NART_MATTE_MATERIAL) return "unknown matte id kind";
+    if (out.ranks < 2 || out.ranks > STAGE_MAX_RANKS || (out.ranks & 1u)) return "matte ranks must be even and in 2..8";
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- what the stages need of p
+// What the stages over whole images (denoiser, reweighting, ranking) need of p without check_params.
+inline const char* check_image_size(const nart_render_params* p) {
+    if (!p->image_width || !p->image_height || !(p->filter_width > 0.f))
+        return "imageWidth, imageHeight and filterWidth must be > 0";
+    return nullptr;
+}
+
+inline const char* check_sample_variance(const nart_render_params* p) {
+    return p->spp < 2 ? "sample variance needs spp >= 2" : nullptr;
+}
+
+inline const char* check_cascade_frame(const nart_render_params* p) {
+    if (const char* why = check_image_size(p)) return why;
+    return p->spp < 1 ? "the cascade needs spp >= 1" : nullptr;
+}
+
+}  // namespace nd

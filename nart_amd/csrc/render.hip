@@ -29,6 +29,7 @@
 #include "host/frame_plan.h"
 #include "host/path_build.h"
 #include "host/path_schedule.h"
+#include "host/stage_params.h"
 
 using namespace nd;
 
@@ -104,8 +105,10 @@ struct nart_ctx {
     Event ev_ad[2];
     // around the cascade's reweighting (cascade_device) and the mattes' ranking (matte_rank_device)
     Event ev_cas[2], ev_mat[2];
-    double cas_ms[2] = {0.0, 0.0};  // the last cascade call's times: split + layer splats, reweighting
-    double mat_ms[2] = {0.0, 0.0};  // the last matte call's times: plane passes, ranking
+    // the last cascade call's times: split + layer splats, reweighting; the last matte call's: plane
+    // passes, ranking.  [0] is kept on the caller's context, [1] on the first device's (first_device)
+    double cas_ms[2] = {0.0, 0.0};
+    double mat_ms[2] = {0.0, 0.0};
     uint32_t num_meshes = 0, num_materials = 0;  // the scene's: the id counts of the two matte kinds
     // denoiser (denoise_device): work buffers over the cropped image, the four device images of
     // nart_hip_denoise / nart_hip_render_denoised (five with the moment image), events between its
@@ -205,6 +208,77 @@ int upload(nart_ctx* ctx, Buf& dst, const T* src, size_t count, const char* what
     if (count) HIPCHK(hipMemcpy(dst.as<T>(), src, sizeof(T) * count, hipMemcpyHostToDevice));
     return NART_OK;
 }
+
+// The context that does the work of one device for ctx: device 0's sub-context of a multi-device
+// context (it combines, holds the images and runs the stages over them), else ctx itself.
+nart_ctx* first_device(nart_ctx* ctx) { return ctx->subs.empty() ? ctx : ctx->subs[0]; }
+const nart_ctx* first_device(const nart_ctx* ctx) { return ctx->subs.empty() ? ctx : ctx->subs[0]; }
+// rc of a call made on first_device(ctx): its error is re-raised on the caller's context.
+int forwarded(nart_ctx* ctx, int rc) { return rc && !ctx->subs.empty() ? fail(ctx, rc, ctx->subs[0]->err) : rc; }
+
+// The device time in ms of what `launch` (returning a code) puts on `st`, between the event pair
+// `ev`; waits for it.
+template <typename Launch>
+int timed(nart_ctx* ctx, Event (&ev)[2], hipStream_t st, double* ms, Launch&& launch) {
+    HIPCHK(record(ev[0], st));
+    if (int rc = launch()) return rc;
+    HIPCHK(record(ev[1], st));
+    HIPCHK(hipEventSynchronize(ev[1].handle()));
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, ev[0].handle(), ev[1].handle()));
+    *ms = t;
+    return NART_OK;
+}
+
+// How the images of p lie in memory: the cropped window W x H inside totalW x totalH pixels of five
+// floats (nart_pixel), the filter's border fb around it.
+struct ImageLayout {
+    nart_session_geometry g;
+    uint32_t W, H;
+    size_t img_floats, img_bytes;
+    explicit ImageLayout(const nart_render_params* p) : W(p->image_width), H(p->image_height) {
+        nart_session_geometry_of(p, &g);
+        img_floats = (size_t)g.total_width * g.total_height * 5;
+        img_bytes = img_floats * sizeof(float);
+    }
+    // into the kernel arguments of a stage over whole images (device/denoise.h, cascade.h, matte.h)
+    template <typename Args>
+    void fill(Args& a) const {
+        a.W = W;
+        a.H = H;
+        a.totalW = g.total_width;
+        a.totalH = g.total_height;
+        a.fb = g.filter_bounds;
+    }
+};
+
+// Images back to back in a buffer on ctx's device (a single-device context; errors go to it).
+struct Images {
+    nart_ctx* ctx;
+    ImageLayout layout;
+    float* base = nullptr;
+    Images(nart_ctx* c, const nart_render_params* p) : ctx(c), layout(p) {}
+    // over `buf`, grown to hold n images; makes the device current for what follows
+    int in(Buf& buf, size_t n, const char* what) {
+        HIPCHK(hipSetDevice(ctx->device));
+        if (int rc = reserve(ctx, buf, ctx->device, n * layout.img_bytes, what)) return rc;
+        base = buf.as<float>();
+        return NART_OK;
+    }
+    float* at(size_t i) const { return base + i * layout.img_floats; }
+    int upload(size_t i, const nart_pixel* src, size_t k = 1) const {  // k host images to image i onwards
+        if (k) HIPCHK(hipMemcpy(at(i), src, k * layout.img_bytes, hipMemcpyHostToDevice));
+        return NART_OK;
+    }
+    int download(size_t i, nart_pixel* dst, size_t k = 1) const {  // k images from image i to the host
+        if (k) HIPCHK(hipMemcpy(dst, at(i), k * layout.img_bytes, hipMemcpyDeviceToHost));
+        return NART_OK;
+    }
+    int zero_async(size_t i, size_t k, hipStream_t st) const {
+        HIPCHK(hipMemsetAsync(at(i), 0, k * layout.img_bytes, st));
+        return NART_OK;
+    }
+};
 
 // Feature mask of a scene (FT_*, path.h): every material kind, light kind, textured pattern and
 // normal map the scene's records hold (a glass material's normal map is ignored, as the device
@@ -1723,36 +1797,6 @@ struct FrameRequest {
 };
 
 // ---------------------------------------------------------------- adaptive sampling (device/adaptive.h)
-void adaptive_defaults(nart_adaptive_params* ap) {
-    ap->min_spp = 16;
-    ap->growth = 4;
-    ap->threshold = 0.1f;
-    ap->floor = 0.01f;
-}
-
-// The message of what is wrong with the parameters, or null.
-const char* adaptive_params_error(const nart_adaptive_params& ap, uint32_t spp) {
-    if (ap.min_spp < 2) return "adaptive min_spp must be >= 2 (one sample has no variance)";
-    if (spp < 2) return "adaptive sampling needs spp >= 2 (one sample has no variance)";
-    if (ap.growth < 2 || ap.growth > 16) return "adaptive growth must be in 2..16";
-    if (!(ap.threshold >= 0.f)) return "adaptive threshold must be >= 0 (+inf: nothing refines)";
-    if (!(ap.floor > 0.f) || !std::isfinite(ap.floor)) return "adaptive floor must be finite and > 0";
-    return nullptr;
-}
-
-// L_0 = min_spp, L_{i+1} = min(L_i * growth, spp), ending on spp; the one level spp if min_spp >= spp.
-constexpr uint32_t ADAPTIVE_MAX_LEVELS = 32;
-std::vector<uint32_t> adaptive_levels(const nart_adaptive_params& ap, uint32_t spp) {
-    std::vector<uint32_t> levels;
-    uint64_t L = ap.min_spp;
-    while (L < spp && levels.size() + 1 < ADAPTIVE_MAX_LEVELS) {
-        levels.push_back((uint32_t)L);
-        L = std::min<uint64_t>(L * ap.growth, spp);
-    }
-    levels.push_back(spp);
-    return levels;
-}
-
 // The adaptive counterpart of render_buckets: the listed buckets, refined level by level, into the
 // frame's tile buffers (list order: slot i is ids[i]).  Every level renders its list at that level's
 // sample count into list-ordered scratch tiles -- the outputs of adaptive_level_ask: what the frame
@@ -1803,7 +1847,6 @@ int render_buckets_adaptive(nart_ctx* ctx, const nart_render_params* p, const ui
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(d_ids, cur_ids.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_slot, cur.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(record(ctx->ev_ad[0], st));
         BucketErrorArgs ea;
         ea.beauty = scratch.of(OutputKind::Beauty);
         ea.moment = scratch.of(OutputKind::Moment);
@@ -1817,9 +1860,6 @@ int render_buckets_adaptive(nart_ctx* ctx, const nart_render_params* p, const ui
         ea.totalW = g.total_width;
         ea.totalH = g.total_height;
         ea.floor = run.ap.floor;
-        if (stage) hipLaunchKernelGGL((k_bucket_error<true>), dim3(m), dim3(64), stage_lds, st, ea);
-        else hipLaunchKernelGGL((k_bucket_error<false>), dim3(m), dim3(64), 2 * (size_t)p->bucket_size * sizeof(float), st, ea);
-        HIPCHK(hipGetLastError());
         ScatterArgs sc = {};  // (unused buffers null)
         uint32_t nsc = 0;
         for (uint32_t o = 0; o < frame.plan.n_outputs && nsc < (uint32_t)SCATTER_BUFS; ++o) {
@@ -1829,17 +1869,22 @@ int render_buckets_adaptive(nart_ctx* ctx, const nart_render_params* p, const ui
         sc.slot = d_slot;
         sc.n = m;
         sc.tile_floats = (uint32_t)tile_floats;
-        if (nsc) {
-            hipLaunchKernelGGL(k_scatter_tiles, dim3(m, nsc), dim3(256), 0, st, sc);
+        double ms = 0.0;
+        rc = timed(ctx, ctx->ev_ad, st, &ms, [&]() -> int {
+            if (stage) hipLaunchKernelGGL((k_bucket_error<true>), dim3(m), dim3(64), stage_lds, st, ea);
+            else hipLaunchKernelGGL((k_bucket_error<false>), dim3(m), dim3(64), 2 * (size_t)p->bucket_size * sizeof(float), st, ea);
             HIPCHK(hipGetLastError());
-        }
-        HIPCHK(record(ctx->ev_ad[1], st));
+            if (nsc) {
+                hipLaunchKernelGGL(k_scatter_tiles, dim3(m, nsc), dim3(256), 0, st, sc);
+                HIPCHK(hipGetLastError());
+            }
+            return NART_OK;
+        });
+        if (rc) return rc;
+        run.ms += ms;
         E.resize(m);
         HIPCHK(hipMemcpyAsync(E.data(), d_err, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_ad[0].handle(), ctx->ev_ad[1].handle()));
-        run.ms += ms;
         run.rendered[li] = m;
         next.clear();
         for (uint32_t i = 0; i < m; ++i) {
@@ -1870,11 +1915,11 @@ int render_frame(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
     if (!times) times = &unused;
     *times = PassTimes();
     if (plan.code) return fail(ctx, plan.code, plan.message);
-    nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // device 0: combines, holds the images
+    nart_ctx* c0 = first_device(ctx);  // device 0: combines, holds the images
     int rc = NART_OK;
     if (ctx->rccl_broken)
         return fail(ctx, NART_E_RCCL, "an earlier RCCL gather of this context failed; destroy it and create a new one");
-    if ((rc = check_params(c0, p))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
+    if ((rc = forwarded(ctx, check_params(c0, p)))) return rc;
     nart_session_geometry g;
     nart_session_geometry_of(p, &g);
     const uint32_t nb = g.n_buckets_x * g.n_buckets_y;
@@ -1939,558 +1984,11 @@ int rect_slots(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t
     return NART_OK;
 }
 
-// ---------------------------------------------------------------- denoiser (device/denoise.h)
-void denoise_defaults(nart_denoise_params* dp) {
-    dp->iterations = 5;
-    dp->normal_squarings = 5;
-    dp->sigma_color = 4.f;
-    dp->sigma_depth = 1.f;
-    dp->depth_eps = 1e-3f;
-    dp->sigma_coverage = 0.05f;
-    dp->albedo_floor = 0.01f;
-}
+}  // namespace
 
-// dp (null: the defaults) into out, or NART_E_INVALID.
-int check_denoise(nart_ctx* ctx, const nart_denoise_params* dp, nart_denoise_params& out) {
-    if (dp) out = *dp;
-    else denoise_defaults(&out);
-    if (out.iterations < 1 || out.iterations > 8) return fail(ctx, NART_E_INVALID, "denoise iterations must be 1..8");
-    if (out.normal_squarings > 16) return fail(ctx, NART_E_INVALID, "denoise normal_squarings must be <= 16");
-    if (!(out.sigma_color > 0.f) || !(out.sigma_depth > 0.f) || !(out.depth_eps > 0.f) || !(out.sigma_coverage > 0.f) ||
-        !(out.albedo_floor > 0.f))
-        return fail(ctx, NART_E_INVALID, "denoise sigmas, depth_eps and albedo_floor must be > 0");
-    return NART_OK;
-}
+#include "host/image_stages.h"
 
-// The n device images of a single-device context: 4 (beauty, albedo, normal, denoised), or 5 in the
-// sample-variance mode (beauty, albedo, normal, moment, denoised).
-int denoise_images(nart_ctx* ctx, const nart_session_geometry& g, float* img[5], int n = 4) {
-    const size_t img_floats = (size_t)g.total_width * g.total_height * 5;
-    const size_t bytes = (size_t)n * img_floats * sizeof(float);
-    if (int rc = reserve(ctx, ctx->d_dn_img, ctx->device, bytes, "denoiser images")) return rc;
-    for (int k = 0; k < n; ++k) img[k] = ctx->d_dn_img.as<float>() + (size_t)k * img_floats;
-    return NART_OK;
-}
-
-// Denoise device images on a single-device context: prepare, variance, the a-trous passes (LDS
-// tiles for steps 1 and 2, global reads beyond), finalise; synchronous.  ms: device time.
-// d_moment non-null: the sample-variance mode -- k_dn_prepare<true> takes the variance from the
-// second-moment image and k_dn_variance is not launched (its time reads 0).
-int denoise_device(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params& dp, const float* d_beauty,
-                   const float* d_albedo, const float* d_normal, const float* d_moment, float* d_out, hipStream_t st,
-                   double* ms) {
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const size_t npx = (size_t)p->image_width * p->image_height;
-    // guide, signal x 2, centre (float4 each), then cov and slope
-    const size_t work_bytes = npx * (4 * sizeof(float4) + 2 * sizeof(float));
-    if (int rc = reserve(ctx, ctx->d_dn, ctx->device, work_bytes, "denoiser work buffers")) return rc;
-    float4* f4 = ctx->d_dn.as<float4>();
-    float4* sig[2] = {f4 + npx, f4 + 2 * npx};
-    DnArgs a;
-    a.beauty = d_beauty;
-    a.albedo = d_albedo;
-    a.normal = d_normal;
-    a.moment = d_moment;
-    a.out = d_out;
-    a.guide = f4;
-    a.centre = f4 + 3 * npx;
-    a.cov = reinterpret_cast<float*>(f4 + 4 * npx);
-    a.slope = a.cov + npx;
-    a.W = p->image_width;
-    a.H = p->image_height;
-    a.totalW = g.total_width;
-    a.totalH = g.total_height;
-    a.fb = g.filter_bounds;
-    a.step = 1;
-    a.normal_squarings = dp.normal_squarings;
-    a.sigma_color = dp.sigma_color;
-    a.sigma_depth = dp.sigma_depth;
-    a.depth_eps = dp.depth_eps;
-    a.sigma_coverage = dp.sigma_coverage;
-    a.albedo_floor = dp.albedo_floor;
-    const dim3 grid((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH), block(256);
-    uint32_t e = 0;
-    HIPCHK(record(ctx->ev_dn[e++], st));
-    a.sig_in = nullptr;
-    if (d_moment) {  // signal and variance at once, where the variance pass would have left them
-        a.sig_out = sig[1];
-        hipLaunchKernelGGL(k_dn_prepare<true>, grid, block, 0, st, a);
-        HIPCHK(record(ctx->ev_dn[e++], st));
-    } else {
-        a.sig_out = sig[0];
-        hipLaunchKernelGGL(k_dn_prepare<false>, grid, block, 0, st, a);
-        HIPCHK(record(ctx->ev_dn[e++], st));
-        a.sig_in = sig[0];
-        a.sig_out = sig[1];
-        hipLaunchKernelGGL(k_dn_variance, grid, block, 0, st, a);
-    }
-    HIPCHK(record(ctx->ev_dn[e++], st));
-    int cur = 1;
-    for (uint32_t i = 0; i < dp.iterations; ++i) {
-        a.sig_in = sig[cur];
-        a.sig_out = sig[cur ^ 1];
-        a.step = 1u << i;
-        if (i == 0) hipLaunchKernelGGL(k_dn_atrous<2>, grid, block, 0, st, a);
-        else if (i == 1) hipLaunchKernelGGL(k_dn_atrous<4>, grid, block, 0, st, a);
-        else hipLaunchKernelGGL(k_dn_atrous<0>, grid, block, 0, st, a);
-        HIPCHK(record(ctx->ev_dn[e++], st));
-        cur ^= 1;
-    }
-    a.sig_in = sig[cur];
-    const size_t n_total = (size_t)g.total_width * g.total_height;
-    hipLaunchKernelGGL(k_dn_finalize, dim3((uint32_t)((n_total + 255) / 256)), block, 0, st, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(record(ctx->ev_dn[e++], st));
-    HIPCHK(hipEventSynchronize(ctx->ev_dn[e - 1].handle()));
-    for (double& t : ctx->dn_ms) t = 0.0;
-    double total = 0.0;
-    for (uint32_t k = 0; k + 1 < e; ++k) {
-        if (d_moment && k == 1) continue;  // no variance kernel ran between these two events
-        float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, ctx->ev_dn[k].handle(), ctx->ev_dn[k + 1].handle()));
-        // events 0..2 bracket prepare and variance, the last pair the finalise kernel
-        ctx->dn_ms[k + 2 == e ? 10 : k] = t;
-        total += t;
-    }
-    if (ms) *ms = total;
-    return NART_OK;
-}
-
-// What the stages over whole images (denoiser, reweighting, ranking) need of p without check_params.
-int check_image_size(nart_ctx* ctx, const nart_render_params* p) {
-    if (!p->image_width || !p->image_height || !(p->filter_width > 0.f))
-        return fail(ctx, NART_E_INVALID, "imageWidth, imageHeight and filterWidth must be > 0");
-    return NART_OK;
-}
-
-int check_sample_variance(nart_ctx* ctx, const nart_render_params* p) {
-    if (p->spp < 2) return fail(ctx, NART_E_INVALID, "sample variance needs spp >= 2");
-    return NART_OK;
-}
-
-// nart_hip_denoise (moment null) and nart_hip_denoise_moment: host images through the device.
-int denoise_host(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, const nart_pixel* beauty,
-                 const nart_pixel* albedo, const nart_pixel* normal, const nart_pixel* moment, nart_pixel* out,
-                 double* denoise_ms) {
-    nart_denoise_params d;
-    int rc = check_denoise(ctx, dp, d);
-    if (rc || (moment && (rc = check_sample_variance(ctx, p)))) return rc;
-    if (!ctx->subs.empty()) {  // on the first device
-        rc = denoise_host(ctx->subs[0], p, &d, beauty, albedo, normal, moment, out, denoise_ms);
-        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
-    }
-    if ((rc = check_image_size(ctx, p))) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const int n = moment ? 5 : 4;  // the inputs, then the denoised image
-    float* img[5];
-    if ((rc = denoise_images(ctx, g, img, n))) return rc;
-    const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
-    const nart_pixel* src[4] = {beauty, albedo, normal, moment};
-    for (int k = 0; k + 1 < n; ++k) HIPCHK(hipMemcpy(img[k], src[k], img_bytes, hipMemcpyHostToDevice));
-    if ((rc = denoise_device(ctx, p, d, img[0], img[1], img[2], moment ? img[3] : nullptr, img[n - 1], 0, denoise_ms)))
-        return rc;
-    HIPCHK(hipMemcpy(out, img[n - 1], img_bytes, hipMemcpyDeviceToHost));
-    return NART_OK;
-}
-
-// gp (null: the defaults) into out, or NART_E_INVALID.
-int check_guide(nart_ctx* ctx, const nart_guide_params* gp, nart_guide_params& out) {
-    out.max_follow = gp ? gp->max_follow : 8u;
-    if (out.max_follow > NART_GUIDE_MAX_FOLLOW) return fail(ctx, NART_E_INVALID, "max_follow must be 0..10");
-    return NART_OK;
-}
-
-// nart_hip_render_denoised and, with sample_variance, nart_hip_render_denoised_moment; with follow,
-// nart_hip_render_denoised_guides: the followed guides in the first-hit AOVs' place.
-int render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, bool sample_variance,
-                    nart_pixel* image, nart_pixel* out, nart_render_stats* stats, double* denoise_ms,
-                    const nart_guide_params* follow = nullptr) {
-    nart_denoise_params d;
-    int rc = check_denoise(ctx, dp, d);
-    if (rc || (sample_variance && (rc = check_sample_variance(ctx, p)))) return rc;
-    nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];  // the context that denoises
-    // beauty, both AOVs (and the moment image) into the first of its device images, the denoised image
-    // after them: nothing passes the host
-    FrameAsk ask(p->integrator);
-    if (follow) {
-        ask.guide[0] = ask.guide[1] = true;
-        ask.max_follow = follow->max_follow;
-    } else {
-        ask.aov[AOV_ALBEDO] = ask.aov[AOV_NORMAL] = true;
-    }
-    const OutputKind albedo = follow ? OutputKind::GuideAlbedo : OutputKind::Albedo;
-    const OutputKind normal = follow ? OutputKind::GuideNormal : OutputKind::Normal;
-    ask.moment = sample_variance;
-    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
-    const int n = sample_variance ? 5 : 4;
-    const FrameRequest rq(&c0->d_dn_img, (uint32_t)n);
-    if ((rc = render_frame(ctx, p, plan, rq, stats))) return rc;
-    RenderTimer timer(stats);  // render_ms covers the whole call
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const size_t img_bytes = (size_t)g.total_width * g.total_height * sizeof(nart_pixel);
-    float* img[5];
-    if ((rc = denoise_images(c0, g, img, n)) ||  // (sized by the frame: this lays them out)
-        (rc = denoise_device(c0, p, d, img[plan.find(OutputKind::Beauty)], img[plan.find(albedo)], img[plan.find(normal)],
-                             sample_variance ? img[plan.find(OutputKind::Moment)] : nullptr, img[n - 1], 0, denoise_ms)))
-        return c0 == ctx ? rc : fail(ctx, rc, c0->err);
-    HIPCHK(hipSetDevice(c0->device));
-    if (image) HIPCHK(hipMemcpy(image, img[plan.find(OutputKind::Beauty)], img_bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out, img[n - 1], img_bytes, hipMemcpyDeviceToHost));
-    return NART_OK;
-}
-
-// nart_hip_render_aovs (moment null) and nart_hip_render_moment.
-int render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_pixel* image, nart_pixel* albedo,
-                nart_pixel* normal, nart_pixel* moment, nart_render_stats* stats, double* aov_ms, double* moment_ms) {
-    if (aovs & ~(NART_AOV_ALBEDO | NART_AOV_NORMAL)) return fail(ctx, NART_E_INVALID, "unknown AOV bit");
-    if (((aovs & NART_AOV_ALBEDO) && !albedo) || ((aovs & NART_AOV_NORMAL) && !normal))
-        return fail(ctx, NART_E_INVALID, "an AOV is requested without its image buffer");
-    FrameAsk ask(p->integrator);
-    // the moment image needs the path kernel: with it the beauty is rendered even where it is not asked for
-    ask.beauty = image != nullptr || moment != nullptr;
-    ask.moment = moment != nullptr;
-    ask.aov[AOV_ALBEDO] = (aovs & NART_AOV_ALBEDO) != 0;
-    ask.aov[AOV_NORMAL] = (aovs & NART_AOV_NORMAL) != 0;
-    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
-    FrameRequest rq;
-    rq.to_host(plan, OutputKind::Beauty, image);
-    rq.to_host(plan, OutputKind::Albedo, albedo);
-    rq.to_host(plan, OutputKind::Normal, normal);
-    rq.to_host(plan, OutputKind::Moment, moment);
-    PassTimes times;
-    const int rc = render_frame(ctx, p, plan, rq, stats, &times);
-    if (aov_ms) *aov_ms = times.ms[PASS_FIRST_HIT];
-    if (moment_ms) *moment_ms = times.ms[PASS_MOMENT];
-    return rc;
-}
-
-// nart_hip_render_guides: render_aovs with the followed guides in the first-hit AOVs' place.
-int render_guides(nart_ctx* ctx, const nart_render_params* p, const nart_guide_params& gp, uint32_t aovs, nart_pixel* image,
-                  nart_pixel* albedo, nart_pixel* normal, nart_pixel* moment, nart_render_stats* stats, double* guide_ms) {
-    if (aovs & ~(NART_AOV_ALBEDO | NART_AOV_NORMAL)) return fail(ctx, NART_E_INVALID, "unknown AOV bit");
-    if (((aovs & NART_AOV_ALBEDO) && !albedo) || ((aovs & NART_AOV_NORMAL) && !normal))
-        return fail(ctx, NART_E_INVALID, "a guide is requested without its image buffer");
-    FrameAsk ask(p->integrator);
-    ask.beauty = image != nullptr || moment != nullptr;  // (the moment image needs the path kernel)
-    ask.moment = moment != nullptr;
-    ask.guide[0] = (aovs & NART_AOV_ALBEDO) != 0;
-    ask.guide[1] = (aovs & NART_AOV_NORMAL) != 0;
-    ask.max_follow = gp.max_follow;
-    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
-    FrameRequest rq;
-    rq.to_host(plan, OutputKind::Beauty, image);
-    rq.to_host(plan, OutputKind::GuideAlbedo, albedo);
-    rq.to_host(plan, OutputKind::GuideNormal, normal);
-    rq.to_host(plan, OutputKind::Moment, moment);
-    PassTimes times;
-    const int rc = render_frame(ctx, p, plan, rq, stats, &times);
-    if (guide_ms) *guide_ms = times.ms[PASS_GUIDE];
-    return rc;
-}
-
-// ---------------------------------------------------------------- firefly cascade (device/cascade.h)
-void cascade_defaults(nart_cascade_params* cp) {
-    cp->layers = 6;
-    cp->start = 1.f;
-    cp->base = 8.f;
-    cp->kappa = 2.f;
-}
-
-// cp (null: the defaults) into out and its levels into lv; the message of what is wrong, or null.
-const char* cascade_params_error(const nart_cascade_params* cp, nart_cascade_params& out, CascadeLevels& lv) {
-    if (cp) out = *cp;
-    else cascade_defaults(&out);
-    if (out.layers < 2 || out.layers > CASCADE_MAX_LAYERS) return "cascade layers must be in 2..8";
-    if (!std::isfinite(out.start) || !(out.start > 0.f)) return "cascade start must be finite and > 0";
-    if (!std::isfinite(out.base) || !(out.base > 1.f)) return "cascade base must be finite and > 1";
-    if (!std::isfinite(out.kappa) || !(out.kappa > 0.f)) return "cascade kappa must be finite and > 0";
-    lv.K = out.layers;
-    lv.base = out.base;
-    float b = out.start;
-    for (uint32_t j = 0; j < lv.K; ++j) {
-        if (!std::isfinite(b)) return "a cascade level is not finite";
-        if (j > 0 && !(b > lv.b[j - 1])) return "the cascade levels do not increase (start too small for base)";
-        lv.b[j] = b;
-        b = b * out.base;
-    }
-    return nullptr;
-}
-
-// The reweighting over device images on a single-device context: beauty, the K layer images back to
-// back, the robust image out; synchronous.  The time goes to ctx->cas_ms[1].
-int cascade_device(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params& cp, const CascadeLevels& lv,
-                   const float* d_beauty, const float* d_layers, float* d_out, hipStream_t st) {
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    CascadeReweightArgs a;
-    a.beauty = d_beauty;
-    a.layers = d_layers;
-    a.out = d_out;
-    a.W = p->image_width;
-    a.H = p->image_height;
-    a.totalW = g.total_width;
-    a.totalH = g.total_height;
-    a.fb = g.filter_bounds;
-    a.K = lv.K;
-    a.N = (float)p->spp;
-    a.kappa = cp.kappa;
-    for (uint32_t j = 0; j < CASCADE_MAX_LAYERS; ++j) a.b[j] = j < lv.K ? lv.b[j] : 0.f;
-    HIPCHK(record(ctx->ev_cas[0], st));
-    // the border stays zero: the kernel writes the cropped pixels only
-    HIPCHK(hipMemsetAsync(d_out, 0, (size_t)g.total_width * g.total_height * sizeof(nart_pixel), st));
-    const dim3 grid((a.W + CS_TW - 1) / CS_TW, (a.H + CS_TH - 1) / CS_TH), block(CS_TW * CS_TH);
-    hipLaunchKernelGGL(k_cascade_reweight, grid, block, (size_t)lv.K * CS_PLANE * sizeof(float), st, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(record(ctx->ev_cas[1], st));
-    HIPCHK(hipEventSynchronize(ctx->ev_cas[1].handle()));
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, ctx->ev_cas[0].handle(), ctx->ev_cas[1].handle()));
-    ctx->cas_ms[1] = t;
-    return NART_OK;
-}
-
-// The tile buffers a context keeps between whole frames grow with the number of outputs a frame
-// has.  A cascade or matte frame has up to twelve: what it made them grow by is given back when the
-// call returns, so that a later render finds the free memory (batch_slot_limit) it found before.
-struct TileGrowthGuard {
-    nart_ctx* ctx;
-    size_t gather_bytes;
-    std::vector<size_t> sub_bytes;
-    explicit TileGrowthGuard(nart_ctx* c) : ctx(c), gather_bytes(c->d_gather.bytes()) {
-        for (const Buf& b : c->sub_tiles) sub_bytes.push_back(b.bytes());
-    }
-    TileGrowthGuard(const TileGrowthGuard&) = delete;
-    ~TileGrowthGuard() {
-        if (ctx->d_gather.bytes() > gather_bytes) ctx->d_gather.release();
-        for (size_t d = 0; d < sub_bytes.size(); ++d)
-            if (ctx->sub_tiles[d].bytes() > sub_bytes[d]) ctx->sub_tiles[d].release();
-    }
-};
-
-int check_cascade_frame(nart_ctx* ctx, const nart_render_params* p) {
-    if (int rc = check_image_size(ctx, p)) return rc;
-    if (p->spp < 1) return fail(ctx, NART_E_INVALID, "the cascade needs spp >= 1");
-    return NART_OK;
-}
-
-// nart_hip_render_cascade: the beauty and the K layers through render_frame into device images of
-// the call, the reweighting on device 0 after them, then what the caller asked for to the host.
-int render_cascade(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params& cp, const CascadeLevels& lv,
-                   nart_pixel* image, nart_pixel* beauty, nart_pixel* layers, nart_render_stats* stats) {
-    nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];
-    ctx->cas_ms[0] = ctx->cas_ms[1] = 0.0;
-    TileGrowthGuard guard(ctx);
-    Buf imgs;  // the device images of the call, on device 0; freed on return
-    const uint32_t K = lv.K;
-    FrameAsk ask(p->integrator);
-    ask.cascade = lv;
-    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
-    const FrameRequest rq(&imgs, K + 2);  // the beauty, the layers, the robust image
-    PassTimes times;
-    int rc = render_frame(ctx, p, plan, rq, stats, &times);
-    ctx->cas_ms[0] = times.ms[PASS_CASCADE];
-    if (rc) return rc;
-    RenderTimer timer(stats);  // render_ms covers the whole call
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
-    // the plan's images back to back (the layers follow one another), the robust image after them
-    float* d_beauty = imgs.as<float>() + (size_t)plan.find(OutputKind::Beauty) * img_floats;
-    float* d_layers = imgs.as<float>() + (size_t)plan.find(OutputKind::Layer, 0) * img_floats;
-    float* d_out = imgs.as<float>() + (size_t)plan.n_outputs * img_floats;
-    if ((rc = cascade_device(c0, p, cp, lv, d_beauty, d_layers, d_out, 0))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
-    ctx->cas_ms[1] = c0->cas_ms[1];
-    HIPCHK(hipSetDevice(c0->device));
-    HIPCHK(hipMemcpy(image, d_out, img_bytes, hipMemcpyDeviceToHost));
-    if (beauty) HIPCHK(hipMemcpy(beauty, d_beauty, img_bytes, hipMemcpyDeviceToHost));
-    if (layers) HIPCHK(hipMemcpy(layers, d_layers, (size_t)K * img_bytes, hipMemcpyDeviceToHost));
-    return NART_OK;
-}
-
-// nart_hip_cascade_reweight: host images through the (first) device.
-int cascade_host(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params& cp, const CascadeLevels& lv,
-                 const nart_pixel* beauty, const nart_pixel* layers, nart_pixel* image) {
-    if (!ctx->subs.empty()) {
-        const int rc = cascade_host(ctx->subs[0], p, cp, lv, beauty, layers, image);
-        ctx->cas_ms[0] = 0.0;
-        ctx->cas_ms[1] = ctx->subs[0]->cas_ms[1];
-        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
-    }
-    ctx->cas_ms[0] = ctx->cas_ms[1] = 0.0;
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const uint32_t K = lv.K;
-    const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
-    Buf imgs;  // the beauty, the layers, the robust image; freed on return
-    if (int rc = reserve(ctx, imgs, ctx->device, (size_t)(K + 2) * img_bytes, "cascade images")) return rc;
-    float* d = imgs.as<float>();
-    float* d_out = d + (size_t)(K + 1) * img_floats;
-    HIPCHK(hipMemcpy(d, beauty, img_bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d + img_floats, layers, (size_t)K * img_bytes, hipMemcpyHostToDevice));
-    if (int rc = cascade_device(ctx, p, cp, lv, d, d + img_floats, d_out, 0)) return rc;
-    HIPCHK(hipMemcpy(image, d_out, img_bytes, hipMemcpyDeviceToHost));
-    return NART_OK;
-}
-
-// ---------------------------------------------------------------- first-hit ID mattes (device/matte.h)
-void matte_defaults(nart_matte_params* mp) {
-    mp->kind = NART_MATTE_MESH;
-    mp->ranks = 6;
-}
-
-// mp (null: the defaults) into out; the message of what is wrong, or null.
-const char* matte_params_error(const nart_matte_params* mp, nart_matte_params& out) {
-    if (mp) out = *mp;
-    else matte_defaults(&out);
-    if (out.kind != NART_MATTE_MESH && out.kind != NART_MATTE_MATERIAL) return "unknown matte id kind";
-    if (out.ranks < 2 || out.ranks > MATTE_MAX_RANKS || (out.ranks & 1u)) return "matte ranks must be even and in 2..8";
-    return nullptr;
-}
-
-// The ranking over device images on a single-device context: the P plane images back to back (null
-// with no ids), the R / 2 rank images out; synchronous.  The time goes to ctx->mat_ms[1].
-int matte_rank_device(nart_ctx* ctx, const nart_render_params* p, uint32_t n_ids, uint32_t R, const float* d_planes,
-                      float* d_ranks, hipStream_t st) {
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    MatteRankArgs a;
-    a.planes = d_planes;
-    a.out = d_ranks;
-    a.W = p->image_width;
-    a.H = p->image_height;
-    a.totalW = g.total_width;
-    a.totalH = g.total_height;
-    a.fb = g.filter_bounds;
-    a.n_ids = n_ids;
-    a.R = R;
-    HIPCHK(record(ctx->ev_mat[0], st));
-    // the border stays zero: the kernel writes the cropped pixels only
-    HIPCHK(hipMemsetAsync(d_ranks, 0, (size_t)(R / 2) * g.total_width * g.total_height * sizeof(nart_pixel), st));
-    const dim3 grid((a.W + MT_TW - 1) / MT_TW, (a.H + MT_TH - 1) / MT_TH), block(MT_LANES);
-    const size_t lds = (size_t)((n_ids + 3) / 4) * 4 * MT_LANES * sizeof(float);
-    hipLaunchKernelGGL(k_matte_rank, grid, block, lds, st, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(record(ctx->ev_mat[1], st));
-    HIPCHK(hipEventSynchronize(ctx->ev_mat[1].handle()));
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, ctx->ev_mat[0].handle(), ctx->ev_mat[1].handle()));
-    ctx->mat_ms[1] = t;
-    return NART_OK;
-}
-
-// nart_hip_render_mattes: the planes (and the beauty, if asked for) through render_frame into device
-// images of the call, the ranking on device 0 after them, then what the caller asked for to the host.
-// A scene without ids renders no plane: its ranks are empty.
-int render_mattes(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params& mp, nart_pixel* ranks,
-                  nart_pixel* image, nart_pixel* planes, nart_render_stats* stats) {
-    nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];
-    ctx->mat_ms[0] = ctx->mat_ms[1] = 0.0;
-    FrameAsk ask(p->integrator);
-    ask.beauty = image != nullptr;
-    ask.matte.on = true;
-    ask.matte.kind = mp.kind;
-    ask.matte.n_ids = mp.kind == NART_MATTE_MATERIAL ? c0->num_materials : c0->num_meshes;
-    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
-    if (plan.code) return fail(ctx, plan.code, plan.message);  // (before anything is allocated)
-    TileGrowthGuard guard(ctx);
-    Buf imgs;  // the device images of the call, on device 0; freed on return
-    const uint32_t n_ids = ask.matte.n_ids, P = ask.matte.planes(), R = mp.ranks;
-    const FrameRequest rq(&imgs, plan.n_outputs + R / 2);  // the beauty, the planes, the rank images
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
-    int rc = NART_OK;
-    if (plan.n_outputs) {
-        PassTimes times;
-        rc = render_frame(ctx, p, plan, rq, stats, &times);
-        ctx->mat_ms[0] = times.ms[PASS_MATTE];
-        if (rc) return rc;
-    } else {
-        if ((rc = check_params(c0, p))) return c0 == ctx ? rc : fail(ctx, rc, c0->err);
-        if ((rc = reserve(ctx, imgs, c0->device, (size_t)(R / 2) * img_bytes, "image"))) return rc;
-    }
-    RenderTimer timer(stats);  // render_ms covers the whole call
-    // the plan's images back to back (the planes follow one another), the rank images after them
-    float* d = imgs.as<float>();
-    float* d_planes = P ? d + (size_t)plan.find(OutputKind::Plane, 0) * img_floats : nullptr;
-    float* d_ranks = d + (size_t)plan.n_outputs * img_floats;
-    if ((rc = matte_rank_device(c0, p, n_ids, R, d_planes, d_ranks, 0)))
-        return c0 == ctx ? rc : fail(ctx, rc, c0->err);
-    ctx->mat_ms[1] = c0->mat_ms[1];
-    HIPCHK(hipSetDevice(c0->device));
-    HIPCHK(hipMemcpy(ranks, d_ranks, (size_t)(R / 2) * img_bytes, hipMemcpyDeviceToHost));
-    if (image) HIPCHK(hipMemcpy(image, d + (size_t)plan.find(OutputKind::Beauty) * img_floats, img_bytes, hipMemcpyDeviceToHost));
-    if (planes && P) HIPCHK(hipMemcpy(planes, d_planes, (size_t)P * img_bytes, hipMemcpyDeviceToHost));
-    return NART_OK;
-}
-
-// nart_hip_matte_rank: host planes through the (first) device.
-int matte_rank_host(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params& mp, uint32_t n_ids,
-                    const nart_pixel* planes, nart_pixel* ranks) {
-    if (!ctx->subs.empty()) {
-        const int rc = matte_rank_host(ctx->subs[0], p, mp, n_ids, planes, ranks);
-        ctx->mat_ms[0] = 0.0;
-        ctx->mat_ms[1] = ctx->subs[0]->mat_ms[1];
-        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
-    }
-    ctx->mat_ms[0] = ctx->mat_ms[1] = 0.0;
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const uint32_t P = (n_ids + 3) / 4, R = mp.ranks;
-    const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
-    Buf imgs;  // the planes, the rank images; freed on return
-    if (int rc = reserve(ctx, imgs, ctx->device, (size_t)(P + R / 2) * img_bytes, "matte images")) return rc;
-    float* d = imgs.as<float>();
-    float* d_ranks = d + (size_t)P * img_floats;
-    if (P) HIPCHK(hipMemcpy(d, planes, (size_t)P * img_bytes, hipMemcpyHostToDevice));
-    if (int rc = matte_rank_device(ctx, p, n_ids, R, P ? d : nullptr, d_ranks, 0)) return rc;
-    HIPCHK(hipMemcpy(ranks, d_ranks, (size_t)(R / 2) * img_bytes, hipMemcpyDeviceToHost));
-    return NART_OK;
-}
-
-// nart_hip_matte_extract: host rank images through the (first) device.
-int matte_extract_host(nart_ctx* ctx, const nart_render_params* p, const nart_matte_params& mp, const nart_pixel* ranks,
-                       uint64_t id_mask, nart_pixel* out) {
-    if (!ctx->subs.empty()) {
-        const int rc = matte_extract_host(ctx->subs[0], p, mp, ranks, id_mask, out);
-        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
-    }
-    HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
-    const uint32_t R = mp.ranks;
-    const size_t img_floats = (size_t)g.total_width * g.total_height * 5, img_bytes = img_floats * sizeof(float);
-    Buf imgs;  // the rank images, the matte; freed on return
-    if (int rc = reserve(ctx, imgs, ctx->device, (size_t)(R / 2 + 1) * img_bytes, "matte images")) return rc;
-    float* d = imgs.as<float>();
-    float* d_out = d + (size_t)(R / 2) * img_floats;
-    HIPCHK(hipMemcpy(d, ranks, (size_t)(R / 2) * img_bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(d_out, 0, img_bytes, 0));  // the border stays zero
-    MatteExtractArgs a;
-    a.ranks = d;
-    a.out = d_out;
-    a.W = p->image_width;
-    a.H = p->image_height;
-    a.totalW = g.total_width;
-    a.totalH = g.total_height;
-    a.fb = g.filter_bounds;
-    a.R = R;
-    a.mask = id_mask;
-    const uint64_t n = (uint64_t)a.W * a.H;
-    hipLaunchKernelGGL(k_matte_extract, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, 0, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, d_out, img_bytes, hipMemcpyDeviceToHost));
-    return NART_OK;
-}
+namespace {
 
 // Largest coordinate magnitude of the scene (triangles and camera position; at least 1): the scale
 // of the BVH box padding and of the octree margins (nart_hip_create, nart_hip_bvh_dump).
@@ -2789,7 +2287,7 @@ int nart_hip_scene_features_of(const nart_scene_blob* scene, uint32_t* features)
 
 int nart_hip_scene_features(const nart_ctx* ctx, uint32_t* features, uint32_t* build) {
     if (!ctx) return NART_E_INVALID;
-    const nart_ctx* c = ctx->subs.empty() ? ctx : ctx->subs[0];
+    const nart_ctx* c = first_device(ctx);
     if (features) *features = c->features;
     if (build) *build = c->fm_used;
     return NART_OK;
@@ -2821,22 +2319,18 @@ int nart_hip_render_buckets_async(nart_ctx* ctx, const nart_render_params* p, co
 int nart_hip_combine_async(nart_ctx* ctx, const nart_render_params* p, const nart_pixel* d_tiles, nart_pixel* d_image,
                            void* stream) {
     if (!ctx || !p || !d_tiles || !d_image) return NART_E_INVALID;
-    if (!ctx->subs.empty()) return nart_hip_combine_async(ctx->subs[0], p, d_tiles, d_image, stream);
+    if (!ctx->subs.empty()) return nart_hip_combine_async(first_device(ctx), p, d_tiles, d_image, stream);
     HIPCHK(hipSetDevice(ctx->device));
-    nart_session_geometry g;
-    nart_session_geometry_of(p, &g);
+    const ImageLayout layout(p);
+    const nart_session_geometry& g = layout.g;
     CombineArgs ca;
     ca.tiles = reinterpret_cast<const float*>(d_tiles);
     ca.image = reinterpret_cast<float*>(d_image);
-    ca.W = p->image_width;
-    ca.H = p->image_height;
+    layout.fill(ca);
     ca.B = p->bucket_size;
-    ca.fb = g.filter_bounds;
     ca.tile = g.tile_size;
     ca.nbx = g.n_buckets_x;
     ca.nby = g.n_buckets_y;
-    ca.totalW = g.total_width;
-    ca.totalH = g.total_height;
     uint64_t n = (uint64_t)g.total_width * g.total_height;
     hipLaunchKernelGGL(k_combine, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ca);
     HIPCHK(hipGetLastError());
@@ -2856,7 +2350,7 @@ int nart_hip_render_aovs(nart_ctx* ctx, const nart_render_params* p, uint32_t ao
     if (!ctx || !p) return NART_E_INVALID;
     if (!aovs && !image) return fail(ctx, NART_E_INVALID, "neither the beauty nor an AOV is requested");
     if (!aovs) return nart_hip_render(ctx, p, image, stats);
-    return render_aovs(ctx, p, aovs, image, albedo, normal, nullptr, stats, aov_ms, nullptr);
+    return render_aovs(ctx, p, nullptr, aovs, image, albedo, normal, nullptr, stats, aov_ms, nullptr);
 }
 
 int nart_hip_render_moment(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, nart_pixel* image,
@@ -2864,19 +2358,17 @@ int nart_hip_render_moment(nart_ctx* ctx, const nart_render_params* p, uint32_t 
                            double* aov_ms, double* moment_ms) {
     if (!ctx || !p) return NART_E_INVALID;
     if (!moment) return fail(ctx, NART_E_INVALID, "the moment image buffer is required");
-    return render_aovs(ctx, p, aovs, image, albedo, normal, moment, stats, aov_ms, moment_ms);
+    return render_aovs(ctx, p, nullptr, aovs, image, albedo, normal, moment, stats, aov_ms, moment_ms);
 }
 
 void nart_hip_adaptive_params_init(nart_adaptive_params* ap) {
-    if (ap) adaptive_defaults(ap);
+    if (ap) *ap = ADAPTIVE_DEFAULTS;
 }
 
 int nart_hip_adaptive_levels(const nart_adaptive_params* ap, uint32_t spp, uint32_t* levels, uint32_t* n) {
     if (!n) return NART_E_INVALID;
     nart_adaptive_params a;
-    if (ap) a = *ap;
-    else adaptive_defaults(&a);
-    if (adaptive_params_error(a, spp)) return NART_E_INVALID;
+    if (adaptive_params_error(ap, a, spp)) return NART_E_INVALID;
     const std::vector<uint32_t> l = adaptive_levels(a, spp);
     *n = (uint32_t)l.size();
     if (levels) std::copy(l.begin(), l.end(), levels);
@@ -2888,26 +2380,18 @@ int nart_hip_render_adaptive(nart_ctx* ctx, const nart_render_params* p, const n
                              uint32_t* bucket_spp, float* bucket_error, nart_render_stats* stats, double* adaptive_ms) {
     if (!ctx || !p) return NART_E_INVALID;
     if (adaptive_ms) *adaptive_ms = 0.0;
-    if (aovs & ~(NART_AOV_ALBEDO | NART_AOV_NORMAL)) return fail(ctx, NART_E_INVALID, "unknown AOV bit");
-    if (((aovs & NART_AOV_ALBEDO) && !albedo) || ((aovs & NART_AOV_NORMAL) && !normal))
-        return fail(ctx, NART_E_INVALID, "an AOV is requested without its image buffer");
+    if (const char* why = aov_request_error(aovs, albedo, normal)) return fail(ctx, NART_E_INVALID, why);
     AdaptiveRun run;
-    if (ap) run.ap = *ap;
-    else adaptive_defaults(&run.ap);
-    if (const char* why = adaptive_params_error(run.ap, p->spp)) return fail(ctx, NART_E_INVALID, why);
+    if (const char* why = adaptive_params_error(ap, run.ap, p->spp)) return fail(ctx, NART_E_INVALID, why);
     run.levels = adaptive_levels(run.ap, p->spp);
     FrameAsk ask(p->integrator);
     ask.adaptive = true;
     ask.moment = moment != nullptr;
-    ask.aov[AOV_ALBEDO] = (aovs & NART_AOV_ALBEDO) != 0;
-    ask.aov[AOV_NORMAL] = (aovs & NART_AOV_NORMAL) != 0;
+    ask_aovs(ask, aovs);
     const FramePlan plan = plan_frame(ask, PlanRules::Frame);
     FrameRequest rq;
     rq.adaptive = &run;
-    rq.to_host(plan, OutputKind::Beauty, image);
-    rq.to_host(plan, OutputKind::Albedo, albedo);
-    rq.to_host(plan, OutputKind::Normal, normal);
-    rq.to_host(plan, OutputKind::Moment, moment);
+    aovs_to_host(rq, plan, false, image, albedo, normal, moment);
     if (int rc = render_frame(ctx, p, plan, rq, stats)) return rc;
     if (bucket_spp) std::copy(run.spp.begin(), run.spp.end(), bucket_spp);
     if (bucket_error) std::copy(run.err.begin(), run.err.end(), bucket_error);
@@ -2916,7 +2400,7 @@ int nart_hip_render_adaptive(nart_ctx* ctx, const nart_render_params* p, const n
 }
 
 void nart_hip_cascade_defaults(nart_cascade_params* cp) {
-    if (cp) cascade_defaults(cp);
+    if (cp) *cp = CASCADE_DEFAULTS;
 }
 
 int nart_hip_cascade_levels(const nart_cascade_params* cp, float* levels, uint32_t* n) {
@@ -2935,7 +2419,7 @@ int nart_hip_render_cascade(nart_ctx* ctx, const nart_render_params* p, const na
     CascadeLevels lv;
     if (const char* why = cascade_params_error(cp, c, lv)) return fail(ctx, NART_E_INVALID, why);
     if (!ctx || !p || !image) return NART_E_INVALID;
-    if (int rc = check_cascade_frame(ctx, p)) return rc;
+    if (const char* why = check_cascade_frame(p)) return fail(ctx, NART_E_INVALID, why);
     return render_cascade(ctx, p, c, lv, image, beauty, layers, stats);
 }
 
@@ -2945,19 +2429,19 @@ int nart_hip_cascade_reweight(nart_ctx* ctx, const nart_render_params* p, const 
     CascadeLevels lv;
     if (const char* why = cascade_params_error(cp, c, lv)) return fail(ctx, NART_E_INVALID, why);
     if (!ctx || !p || !beauty || !layers || !image) return NART_E_INVALID;
-    if (int rc = check_cascade_frame(ctx, p)) return rc;
+    if (const char* why = check_cascade_frame(p)) return fail(ctx, NART_E_INVALID, why);
     return cascade_host(ctx, p, c, lv, beauty, layers, image);
 }
 
 int nart_hip_cascade_timings(const nart_ctx* ctx, double* cascade_ms, double* reweight_ms) {
     if (!ctx) return NART_E_INVALID;
     if (cascade_ms) *cascade_ms = ctx->cas_ms[0];
-    if (reweight_ms) *reweight_ms = ctx->cas_ms[1];
+    if (reweight_ms) *reweight_ms = first_device(ctx)->cas_ms[1];
     return NART_OK;
 }
 
 void nart_hip_matte_defaults(nart_matte_params* mp) {
-    if (mp) matte_defaults(mp);
+    if (mp) *mp = MATTE_DEFAULTS;
 }
 
 int nart_hip_matte_ids(const nart_scene_blob* scene, uint32_t kind, uint32_t* n_ids) {
@@ -2971,7 +2455,7 @@ int nart_hip_render_mattes(nart_ctx* ctx, const nart_render_params* p, const nar
     nart_matte_params m;
     if (const char* why = matte_params_error(mp, m)) return fail(ctx, NART_E_INVALID, why);
     if (!ctx || !p || !ranks) return NART_E_INVALID;
-    if (int rc = check_image_size(ctx, p)) return rc;
+    if (const char* why = check_image_size(p)) return fail(ctx, NART_E_INVALID, why);
     return render_mattes(ctx, p, m, ranks, image, planes, stats);
 }
 
@@ -2981,7 +2465,7 @@ int nart_hip_matte_rank(nart_ctx* ctx, const nart_render_params* p, const nart_m
     if (const char* why = matte_params_error(mp, m)) return fail(ctx, NART_E_INVALID, why);
     if (n_ids > MATTE_MAX_IDS) return fail(ctx, NART_E_INVALID, "n_ids must be <= 32");
     if (!ctx || !p || !ranks || (n_ids && !planes)) return NART_E_INVALID;
-    if (int rc = check_image_size(ctx, p)) return rc;
+    if (const char* why = check_image_size(p)) return fail(ctx, NART_E_INVALID, why);
     return matte_rank_host(ctx, p, m, n_ids, planes, ranks);
 }
 
@@ -2990,24 +2474,22 @@ int nart_hip_matte_extract(nart_ctx* ctx, const nart_render_params* p, const nar
     nart_matte_params m;
     if (const char* why = matte_params_error(mp, m)) return fail(ctx, NART_E_INVALID, why);
     if (!ctx || !p || !ranks || !out) return NART_E_INVALID;
-    if (int rc = check_image_size(ctx, p)) return rc;
+    if (const char* why = check_image_size(p)) return fail(ctx, NART_E_INVALID, why);
     return matte_extract_host(ctx, p, m, ranks, id_mask, out);
 }
 
 int nart_hip_matte_timings(const nart_ctx* ctx, double* matte_ms, double* rank_ms) {
     if (!ctx) return NART_E_INVALID;
     if (matte_ms) *matte_ms = ctx->mat_ms[0];
-    if (rank_ms) *rank_ms = ctx->mat_ms[1];
+    if (rank_ms) *rank_ms = first_device(ctx)->mat_ms[1];
     return NART_OK;
 }
 
 int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w,
                                 uint32_t h, float* out8, uint32_t* tri) {
     if (!ctx || !p || !out8) return NART_E_INVALID;
-    if (!ctx->subs.empty()) {  // per-sample debugging runs on the first device
-        const int rc = nart_hip_render_aov_samples(ctx->subs[0], p, x0, y0, w, h, out8, tri);
-        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
-    }
+    if (!ctx->subs.empty())  // per-sample debugging runs on the first device
+        return forwarded(ctx, nart_hip_render_aov_samples(first_device(ctx), p, x0, y0, w, h, out8, tri));
     int rc = check_params(ctx, p);
     if (rc) return rc;
     if (p->integrator == NART_INTEGRATOR_VOLUME)  // (frames: plan_frame's rule)
@@ -3029,7 +2511,7 @@ int nart_hip_render_aov_samples(nart_ctx* ctx, const nart_render_params* p, uint
 }
 
 void nart_hip_guide_defaults(nart_guide_params* gp) {
-    if (gp) gp->max_follow = 8;
+    if (gp) *gp = GUIDE_DEFAULTS;
 }
 
 int nart_hip_render_guides(nart_ctx* ctx, const nart_render_params* p, const nart_guide_params* gp, uint32_t aovs,
@@ -3037,9 +2519,9 @@ int nart_hip_render_guides(nart_ctx* ctx, const nart_render_params* p, const nar
                            nart_render_stats* stats, double* guide_ms) {
     if (!ctx || !p) return NART_E_INVALID;
     nart_guide_params g;
-    if (int rc = check_guide(ctx, gp, g)) return rc;
+    if (const char* why = guide_params_error(gp, g)) return fail(ctx, NART_E_INVALID, why);
     if (!aovs && !image && !moment) return fail(ctx, NART_E_INVALID, "neither the beauty, the moment image nor a guide is requested");
-    return render_guides(ctx, p, g, aovs, image, albedo, normal, moment, stats, guide_ms);
+    return render_aovs(ctx, p, &g, aovs, image, albedo, normal, moment, stats, guide_ms, nullptr);
 }
 
 int nart_hip_render_denoised_guides(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
@@ -3047,7 +2529,7 @@ int nart_hip_render_denoised_guides(nart_ctx* ctx, const nart_render_params* p, 
                                     nart_pixel* out, nart_render_stats* stats, double* denoise_ms) {
     if (!ctx || !p || !out) return NART_E_INVALID;
     nart_guide_params g;
-    if (int rc = check_guide(ctx, gp, g)) return rc;
+    if (const char* why = guide_params_error(gp, g)) return fail(ctx, NART_E_INVALID, why);
     return render_denoised(ctx, p, dp, sample_variance != 0, image, out, stats, denoise_ms, &g);
 }
 
@@ -3055,13 +2537,12 @@ int nart_hip_render_guide_samples(nart_ctx* ctx, const nart_render_params* p, co
                                   uint32_t y0, uint32_t w, uint32_t h, float* out8, float* seg8, uint32_t* tri,
                                   uint32_t* n_seg) {
     if (!ctx || !p || !out8) return NART_E_INVALID;
-    if (!ctx->subs.empty()) {  // per-sample debugging runs on the first device
-        const int rc = nart_hip_render_guide_samples(ctx->subs[0], p, gp, x0, y0, w, h, out8, seg8, tri, n_seg);
-        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
-    }
+    if (!ctx->subs.empty())  // per-sample debugging runs on the first device
+        return forwarded(ctx, nart_hip_render_guide_samples(first_device(ctx), p, gp, x0, y0, w, h, out8, seg8, tri, n_seg));
     nart_guide_params g;
-    int rc = check_guide(ctx, gp, g);
-    if (rc || (rc = check_params(ctx, p))) return rc;
+    if (const char* why = guide_params_error(gp, g)) return fail(ctx, NART_E_INVALID, why);
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
     if (p->integrator == NART_INTEGRATOR_VOLUME)  // (frames: plan_frame's rule)
         return fail(ctx, NART_E_UNSUPPORTED, "followed guides need surfaces: the volume integrator has none");
     if (!w || !h) return fail(ctx, NART_E_INVALID, "empty rect");
@@ -3095,7 +2576,7 @@ int nart_hip_render_guide_samples(nart_ctx* ctx, const nart_render_params* p, co
 }
 
 void nart_hip_denoise_params_init(nart_denoise_params* dp) {
-    if (dp) denoise_defaults(dp);
+    if (dp) *dp = DENOISE_DEFAULTS;
 }
 
 int nart_hip_denoise(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, const nart_pixel* beauty,
@@ -3126,7 +2607,7 @@ int nart_hip_render_denoised_moment(nart_ctx* ctx, const nart_render_params* p, 
 int nart_hip_denoise_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
                              double* finalize_ms) {
     if (!ctx) return NART_E_INVALID;
-    const nart_ctx* c0 = ctx->subs.empty() ? ctx : ctx->subs[0];
+    const nart_ctx* c0 = first_device(ctx);
     if (prepare_ms) *prepare_ms = c0->dn_ms[0];
     if (variance_ms) *variance_ms = c0->dn_ms[1];
     if (pass_ms)
@@ -3152,10 +2633,8 @@ int nart_hip_render_device(nart_ctx* ctx, const nart_render_params* p, const nar
 int nart_hip_render_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w,
                             uint32_t h, float* out) {
     if (!ctx || !p || !out) return NART_E_INVALID;
-    if (!ctx->subs.empty()) {  // per-sample debugging runs on the first device
-        const int rc = nart_hip_render_samples(ctx->subs[0], p, x0, y0, w, h, out);
-        return rc ? fail(ctx, rc, ctx->subs[0]->err) : NART_OK;
-    }
+    if (!ctx->subs.empty())  // per-sample debugging runs on the first device
+        return forwarded(ctx, nart_hip_render_samples(first_device(ctx), p, x0, y0, w, h, out));
     int rc = check_params(ctx, p);
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
@@ -3219,7 +2698,7 @@ int nart_hip_bvh_dump(const nart_scene_blob* blob, nart_bvh_dump_info* info, voi
 int nart_hip_context_bvh_dump(const nart_ctx* ctx, nart_bvh_dump_info* info, void* nodes, size_t nodes_cap,
                               float* tri_isect, size_t isect_cap, float* tri_perm, size_t perm_cap) {
     if (!ctx || !info) return NART_E_INVALID;
-    const nart_ctx* c = ctx->subs.empty() ? ctx : ctx->subs[0];
+    const nart_ctx* c = first_device(ctx);
     info->num_nodes = c->num_nodes;
     info->num_leaf_tris = c->num_leaf_tris;
     info->stack_depth = c->stack_depth;
@@ -3271,7 +2750,7 @@ int nart_hip_splat_thresholds(float filter_width, float* thr65) {
 
 int nart_hip_eval_sincos(nart_ctx* ctx, const float* x, uint32_t n, float* s, float* c) {
     if (!ctx || !x || !s || !c) return NART_E_INVALID;
-    if (!ctx->subs.empty()) return nart_hip_eval_sincos(ctx->subs[0], x, n, s, c);
+    if (!ctx->subs.empty()) return nart_hip_eval_sincos(first_device(ctx), x, n, s, c);
     HIPCHK(hipSetDevice(ctx->device));
     Buf bx, bs, bc;  // freed on return
     int rc = NART_OK;
@@ -3288,7 +2767,7 @@ int nart_hip_eval_sincos(nart_ctx* ctx, const float* x, uint32_t n, float* s, fl
 
 int nart_hip_context_bvh(const nart_ctx* ctx, nart_bvh_info* out, double* build_ms) {
     if (!ctx || !out) return NART_E_INVALID;
-    const nart_ctx* c = ctx->subs.empty() ? ctx : ctx->subs[0];
+    const nart_ctx* c = first_device(ctx);
     out->num_nodes = c->num_nodes;
     out->stack_depth = c->stack_depth;
     out->num_leaf_tris = c->num_leaf_tris;

@@ -148,3 +148,36 @@ def test_wrapping_rect_is_rejected(frame, glass_scene):
     after = r.render(p)
     assert _bits_equal(after, before) and _bits_equal(after, ref["plain"])
     r.close()
+
+
+def test_first_device_errors_reach_the_caller(gpu, glass_scene):
+    """Case 6: calls that a two-device context forwards to its first device and that fail there, after
+    the forward: the per-sample entry points with a rect ending one pixel beyond the total image, and
+    denoise with image_width = 0.  The caller's context reports the code and the very message a
+    single-device context gives, and both render as before."""
+    p = _params(glass_scene, 32, 24, 2)
+    g = nart_amd.session_geometry(p)
+    one = nart_amd.HipRenderer(glass_scene)
+    two = nart_amd.HipRenderer(glass_scene, devices=[0, 0])
+    before = one.render(p)
+    assert _bits_equal(two.render(p), before)
+    empty = p.copy()
+    empty.image_width = 0
+    ge = nart_amd.session_geometry(empty)
+    img = np.zeros((ge.total_height, ge.total_width, 5), np.float32)
+    calls = [("render_samples", lambda r: r.render_samples(p, g.total_width - 1, 0, 2, 1)),
+             ("render_aov_samples", lambda r: r.render_aov_samples(p, 0, g.total_height - 1, 1, 2)),
+             ("render_guide_samples", lambda r: r.render_guide_samples(p, g.total_width - 1, g.total_height - 1, 2, 2)),
+             ("denoise", lambda r: r.denoise(empty, img, img, img))]
+    for name, call in calls:
+        messages = []
+        for r in (one, two):
+            with pytest.raises(nart_amd.NartError) as e:
+                call(r)
+            assert e.value.code == -1, name  # NART_E_INVALID
+            messages.append(r._lib.nart_hip_last_error(r._ctx).decode())
+        print(name, messages)
+        assert messages[0] and messages[1] == messages[0], name
+    for r in (one, two):
+        assert _bits_equal(r.render(p), before)
+        r.close()
