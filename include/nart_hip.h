@@ -644,6 +644,69 @@ int nart_hip_render_guide_samples(nart_ctx* ctx, const nart_render_params* p, co
                                   uint32_t y0, uint32_t w, uint32_t h, float* out8, float* seg8, uint32_t* tri,
                                   uint32_t* n_seg);
 
+/* Light groups: the beauty split by light, one image per group of lights from a single render, so
+   that a light can be dimmed, tinted or switched off afterwards (nart_hip_light_mix) without tracing
+   a path again.
+
+   In PathIntegrator::Li_alpha radiance enters a sample's L at two places only: L += EstimateDirect(...)
+   * beta, whose two MIS terms both come from the one light the call drew, and L = Le of the one light
+   a camera ray escapes to.  Every term of L therefore belongs to exactly one light, and no RNG draw,
+   pdf, hit or alpha depends on a light's emission.
+
+   Inputs: group_of_light[n_lights], one entry per light of the scene in scene order, each < n_groups;
+   1 <= n_groups <= NART_LIGHT_GROUPS_MAX.
+   Per camera sample and group g the group record is {Lg.r, Lg.g, Lg.b, alpha}:
+     1. alpha is the sample's beauty alpha;
+     2. Lg starts at +0 and receives, in path order, exactly the terms the beauty's L receives whose
+        light is in group g, by the same operation: Lg = Lg + mul(muls(Led, numLights), beta_k) for a
+        shaded hit whose EstimateDirect drew a light of g (Led = ((0 + c1) + c2) over the unoccluded
+        terms, zero terms included), and Lg = Le when the camera ray escapes to a light of g (an
+        assignment, as in the reference);
+     3. terms of other groups are skipped, not multiplied by zero.
+   The group image is these records through the call's unchanged splat and tile combine: a full
+   nart_pixel image whose alpha and filter_weight_sum have the beauty's bits.
+   It is bit-identical to a render of the scene with every other light's intensity set to 0 wherever
+   that render forms no 0 * inf: there a zero-intensity light's term is 0 * numLights * beta_k, which is
+   +-0 (and leaves L's bits alone) unless beta_k is infinite or NaN, where it is NaN and the group image
+   is not.  A group image's own NaNs and infinities are the beauty's.  One group holding every light
+   gives the beauty bit for bit.
+
+   Mix: out = mix(groups, gains[n_groups][3]) over the totalW x totalH image; per pixel and channel c
+   of r, g, b:  acc = 0.f; for g ascending: acc = acc + gains[g][c] * I_g.contribution[c]  (float32,
+   unfused, in this order); alpha and filter_weight_sum are copied from I_0.  Gains must be finite.
+
+   On the device a light-group build of the ray-queue path kernel (k_render_rq with LG: the generic
+   two-wave build without priority lanes or speculative pairs, which hold a sample's result pending
+   and may drop it; small shards of a group frame run the plain schedule) accumulates the records in G
+   record arrays in global memory, 16 B per sample and group, held for the call (batches are sized for
+   28 + 16 G bytes per sample); the plan's splat then runs once per group, and k_light_mix
+   (device/lightgroup.h) mixes, one lane per pixel.  The counter pass has no light-group build: with
+   nart_hip_set_counters enabled a light-group render reports no work counts.
+
+   nart_hip_render_light_groups: groups receives the n_groups images back to back (required); image,
+   if non-null, the beauty, with the bits nart_hip_render gives.  Multi-device contexts gather the
+   group tiles with the beauty's gather.
+   nart_hip_light_mix: groups holds n_groups host images back to back; out receives the mix.
+   nart_hip_render_light_group_samples: debug / parity, as nart_hip_render_samples: the group records
+   of a rect in total-image coordinates into out[g][((y-y0)*w + (x-x0))*spp + s][4].
+   nart_hip_light_group_timings: device times of the last call's group splats and of the last mix.
+   NART_E_INVALID: a null ctx, p, map, groups, gains or out; n_groups outside 1..8; a map whose length
+   is not the scene's light count or that holds a value >= n_groups; a gain that is not finite; an
+   empty or out-of-range rect.  NART_E_UNSUPPORTED: the volume integrator; variant 3 or a BVH deeper
+   than the ray-queue kernel's LDS holds (k_render has no light-group build).  An error leaves the
+   context usable.  Not offered: light groups together with adaptive sampling, the cascade, the
+   mattes, AOVs, guides, the moment image or the denoiser in one call. */
+#define NART_LIGHT_GROUPS_MAX 8u
+int nart_hip_render_light_groups(nart_ctx* ctx, const nart_render_params* p, const uint32_t* group_of_light,
+                                 uint32_t n_lights, uint32_t n_groups, nart_pixel* groups, nart_pixel* image,
+                                 nart_render_stats* stats);
+int nart_hip_light_mix(nart_ctx* ctx, const nart_render_params* p, uint32_t n_groups, const float* gains,
+                       const nart_pixel* groups, nart_pixel* out);
+int nart_hip_render_light_group_samples(nart_ctx* ctx, const nart_render_params* p, const uint32_t* group_of_light,
+                                        uint32_t n_lights, uint32_t n_groups, uint32_t x0, uint32_t y0, uint32_t w,
+                                        uint32_t h, float* out);
+int nart_hip_light_group_timings(const nart_ctx* ctx, double* splat_ms, double* mix_ms);
+
 /* Multi-GPU building block: render the listed buckets (bucket id = by*nBucketsX + bx) into
    device-resident tiles d_tiles[i] (tile_size^2 nart_pixel each, same order as the list) on
    `stream` (a hipStream_t, may be 0).  bucket_ids is a host array.  Asynchronous w.r.t. the

@@ -81,6 +81,7 @@ SCHED = {"probe_queue": 0x1, "priority": 0x2, "spec_pairs": 0x4, "wave_groups": 
 FEATURES = {"lambert": 0x1, "specular": 0x2, "glass": 0x4, "glossy": 0x8, "plastic": 0x10, "disk": 0x20,
             "ring": 0x40, "environment": 0x80, "texture": 0x100, "normal_map": 0x200}
 FT_ALL = 0x3FF
+LIGHT_GROUPS_MAX = 8  # include/nart_hip.h NART_LIGHT_GROUPS_MAX
 
 
 class RenderStats(ctypes.Structure):
@@ -243,6 +244,13 @@ _HIP_SIGS = {
     "nart_hip_matte_extract": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(MatteParams), _P,
                                               ctypes.c_uint64, _P]),
     "nart_hip_matte_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_light_groups": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), _P, ctypes.c_uint32, ctypes.c_uint32,
+                                                    _P, _P, ctypes.POINTER(RenderStats)]),
+    "nart_hip_light_mix": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, _P, _P, _P]),
+    "nart_hip_render_light_group_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), _P, ctypes.c_uint32,
+                                                           ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                           ctypes.c_uint32, ctypes.c_uint32, _P]),
+    "nart_hip_light_group_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_aov_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, ctypes.c_uint32,
                                                    ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "nart_hip_denoise_params_init": (None, [ctypes.POINTER(DenoiseParams)]),
@@ -820,6 +828,76 @@ class HipRenderer:
         self._check(self._lib.nart_hip_matte_extract(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
                                                      rk.ctypes.data, mask & (2 ** 64 - 1), out.ctypes.data))
         return out
+
+    def _light_group_timings(self, out):
+        s, m = ctypes.c_double(), ctypes.c_double()
+        self._check(self._lib.nart_hip_light_group_timings(self._ctx, ctypes.byref(s), ctypes.byref(m)))
+        out["splat_ms"], out["mix_ms"] = s.value, m.value
+        return out
+
+    @staticmethod
+    def _light_group_map(groups):
+        """The group map as the ABI takes it: a uint32 array (None: null) and G = the largest group + 1."""
+        if groups is None:
+            return None, 0, 0
+        m = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        return m, len(m), int(m.max()) + 1 if len(m) else 0
+
+    def render_light_groups(self, p, groups, with_beauty=False, stats=None, n_groups=None):
+        """The beauty split by light from one render (nart_hip_render_light_groups; include/nart_hip.h
+        has the definition): groups[l] is the group of the scene's light l, G = max(groups) + 1 unless
+        n_groups says otherwise (at most 8).  Returns a dict with "groups", a (G, totalH, totalW, 5)
+        float32 array -- image g holds the radiance of the lights of group g, bit-identical to a render
+        with every other light's intensity at 0, alpha and filter weight sum the beauty's; "beauty"
+        (bit-identical to render()) if requested; "splat_ms", the device time of the group splats."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        m, n, G = self._light_group_map(groups)
+        G = G if n_groups is None else int(n_groups)
+        out = {"groups": np.empty((max(1, G),) + shape, np.float32)}
+        if with_beauty:
+            out["beauty"] = np.empty(shape, np.float32)
+        st = stats if stats is not None else RenderStats()
+        self._check(self._lib.nart_hip_render_light_groups(self._ctx, ctypes.byref(p), m.ctypes.data if m is not None else None,
+                                                           n, G, out["groups"].ctypes.data,
+                                                           out["beauty"].ctypes.data if with_beauty else None,
+                                                           ctypes.byref(st)))
+        out["groups"] = out["groups"][:G]
+        return self._light_group_timings(out)
+
+    def render_light_group_samples(self, p, groups, x0, y0, w, h, n_groups=None):
+        """Per-sample group records of a rect in total-image coordinates
+        (nart_hip_render_light_group_samples): (G, h, w, spp, 4) float32 = {Lg.rgb, alpha}."""
+        m, n, G = self._light_group_map(groups)
+        G = G if n_groups is None else int(n_groups)
+        out = np.empty((max(1, G), h, w, p.spp, 4), np.float32)
+        self._check(self._lib.nart_hip_render_light_group_samples(self._ctx, ctypes.byref(p),
+                                                                  m.ctypes.data if m is not None else None, n, G, x0, y0,
+                                                                  w, h, out.ctypes.data))
+        return out[:G]
+
+    def light_mix(self, p, images, gains):
+        """The mix of group images (nart_hip_light_mix): images a (G, totalH, totalW, 5) float32 array as
+        render_light_groups() returns it, gains one number per group or a (G, 3) array of r, g, b gains
+        (finite).  Returns the (totalH, totalW, 5) float32 image: per channel the sum over g ascending
+        of gains[g][c] * images[g][..., c] in float32, alpha and filter weight sum those of image 0."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        im = np.ascontiguousarray(images, dtype=np.float32)
+        if im.ndim != 4 or im.shape[1:] != shape:
+            raise ValueError("light_mix: images of shape %s, expected (G,) + %s" % (im.shape, shape))
+        G = im.shape[0]
+        k = np.asarray(gains, dtype=np.float32)
+        k = np.ascontiguousarray(np.repeat(k[:, None], 3, axis=1) if k.ndim == 1 else k)
+        if k.shape != (G, 3):
+            raise ValueError("light_mix: gains of shape %s, expected (%d,) or (%d, 3)" % (k.shape, G, G))
+        out = np.empty(shape, np.float32)
+        self._check(self._lib.nart_hip_light_mix(self._ctx, ctypes.byref(p), G, k.ctypes.data, im.ctypes.data, out.ctypes.data))
+        return out
+
+    def light_group_timings(self):
+        """Device times of the last light-group call: {"splat_ms", "mix_ms"}."""
+        return self._light_group_timings({})
 
     def render_aov_samples(self, p, x0, y0, w, h):
         """Per-sample AOV records of a rect in total-image coordinates (nart_hip_render_aov_samples):

@@ -175,6 +175,12 @@ struct RenderArgs {
     // gstack[gid * (stack_depth - stack_lds) + l - stack_lds]
     uint32_t stack_lds = 0;
     int2* gstack = nullptr;
+    // k_render_rq light-group build (LG; include/nart_hip.h, "Light groups"): n_groups record arrays
+    // with Lout's indexing, lgrp_stride records apart, all zero at the launch; the group of every light
+    uint32_t n_groups = 0;
+    const uint32_t* light_group = nullptr;
+    float4* Lgrp = nullptr;
+    unsigned long long lgrp_stride = 0;
 };
 
 // xorshift32 state after n draws (rng.h:38-40 applied n times)
@@ -1124,8 +1130,17 @@ __global__ __launch_bounds__(256) void k_aov(DScene S, RenderArgs A, const uint3
 // the bytes of this layout (rq_lds_bytes): path_layout.h.
 // PR = false (with WV = 3): the lean build proper.  PR = true keeps the small-shard schedule's code
 // (priority lanes, speculative pairs, raised issue priority) at three waves per SIMD.
-template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true>
+// LG (with FT_ALL, WV = 2, PR = false): the light-group build (include/nart_hip.h, "Light groups").
+// Every term that enters L belongs to one light -- the EstimateDirect term to the light the bounce
+// drew, the radiance a camera ray escapes to to the light that set the bound -- and goes, in the same
+// order, into the record of that light's group too.  The lane that owns a sample is the only writer
+// of its records, so they are accumulated in global memory (RenderArgs::Lgrp, zero at the launch)
+// with plain loads and stores and cost no register; the group of the light a bounce drew waits for
+// the shadow rays in the unused fourth word of the lane's result entry.  end_sample gives every
+// group record the sample's alpha.
+template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false>
 __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : NART_RENDER_WAVES)) void k_render_rq(DScene S, RenderArgs A) {
+    static_assert(!LG || (FM == FT_ALL && WV == 2 && !PR && !COUNT), "light groups: the generic two-wave build, no priority lanes");
     // priority lanes, speculative groups and raised issue priority: small-shard schedules only
     const uint32_t rq_prio = PR ? A.rq_prio : 0u, rq_pairs = PR ? A.rq_pairs : 0u;
     // a lean build whose shading needs more than Lambert lobes and area lights fits 168 VGPRs only
@@ -1289,12 +1304,26 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
     // a sample's result: written at once, or held by a pair lane until verified.  (Pairing an even
     // sample's result with the odd one after it as one 32-B store cut the writes 26.6 -> 11.1 GB
     // per C3 launch but ran 2.3 % slower, profiles/r05j_pair_writes_ab.log; retired in round 6.)
+    // LG: the current sample's record of group g; lg_add adds a term to it as L = add(L, t) adds it to L
+    auto lg_rec = [&](uint32_t g) { return A.Lgrp + ((uint64_t)g * A.lgrp_stride + soff + (uint64_t)s * sstr); };
+    auto lg_add = [&](uint32_t g, f3 t) {
+        float4* r = lg_rec(g);
+        float4 v = *r;
+        v.x = v.x + t.x;
+        v.y = v.y + t.y;
+        v.z = v.z + t.z;
+        *r = v;
+    };
+    auto lg_set = [&](uint32_t g, f3 t) { *lg_rec(g) = make_float4(t.x, t.y, t.z, 0.f); };
+    uint32_t ed_group = 0;  // LG: the group of the light the bounce shaded in this phase drew
     auto end_sample = [&](float4 v) {
         if (pm) {
             jres = v;
             jend = rng;
             jfl |= J_FIN;
         } else {
+            if (LG)
+                for (uint32_t g = 0; g < A.n_groups; ++g) lg_rec(g)->w = v.w;
             A.Lout[soff + (uint64_t)s * sstr] = v;
             if (COUNT) count_sample();
             ++s;
@@ -1335,7 +1364,9 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
                     f3 Led = F3(0.f, 0.f, 0.f);
                     if (use1 && r.y == 0u) Led = add(Led, c1);
                     if (use2 && r.z == 0u) Led = add(Led, c2);
-                    L = add(L, mul(muls(Led, nL), betak));
+                    const f3 term = mul(muls(Led, nL), betak);
+                    L = add(L, term);
+                    if (LG) lg_add(r.w, term);
                 }
                 if (ext_pending && r.x != NO_HIT) {
                     need_shade = true;
@@ -1346,6 +1377,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
                         // the camera ray, still in this lane's outbox entry of kind 0
                         const float4 ro = my_out[lane * 2], rd = my_out[lane * 2 + 1];
                         L = light_le(F3(ro.x, ro.y, ro.z), F3(rd.x, rd.y, rd.z));
+                        if (LG) lg_set(A.light_group[lwin], L);
                     }
                     end_sample(make_float4(L.x, L.y, L.z, alpha));
                 }
@@ -1570,7 +1602,10 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
                 const uint32_t g = gprim;
                 const float t = light_loop(ray.o, ray.d);
                 if (g == NO_HIT) {
-                    if (lightHit) L = light_le(ray.o, ray.d);
+                    if (lightHit) {
+                        L = light_le(ray.o, ray.d);
+                        if (LG) lg_set(A.light_group[lwin], L);
+                    }
                     end_sample(make_float4(L.x, L.y, L.z, alpha));
                     active = !pm && s < A.spp;
                     continue;
@@ -1659,6 +1694,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
                 }
                 betak = beta;
                 have_ed = true;
+                if (LG) ed_group = A.light_group[lsel];
                 // ---- continuation (pathintegrator.cpp:199-220)
                 float a = draw();
                 float b = draw();
@@ -1705,7 +1741,11 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
             } else {
                 // no query left (path ended, or ended at the bounce limit): the EstimateDirect
                 // term of this bounce, if any, is still owed
-                if (have_ed) L = add(L, mul(muls(F3(0.f, 0.f, 0.f), nL), betak));
+                if (have_ed) {
+                    const f3 term = mul(muls(F3(0.f, 0.f, 0.f), nL), betak);
+                    L = add(L, term);
+                    if (LG) lg_add(ed_group, term);
+                }
                 end_sample(make_float4(L.x, L.y, L.z, alpha));
             }
         }
@@ -1715,6 +1755,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
             if (newk & 1u) r0.x = RQ_PENDING;
             if (newk & 2u) r0.y = 2u;
             if (newk & 4u) r0.z = 2u;
+            if (LG) r0.w = ed_group;
             *my_res = r0;
         }
 #pragma unroll

@@ -1,6 +1,7 @@
 // The stages over whole images that follow a frame -- the denoiser, the firefly cascade's reweighting,
-// the ID mattes' ranking and extraction -- and the frames of the first-hit AOVs and followed guides;
-// included by render.hip after render_frame.  Every stage has the same two layers:
+// the ID mattes' ranking and extraction, the light groups' mix -- and the frames of the first-hit AOVs,
+// the followed guides and the light groups; included by render.hip after render_frame.  Every stage has
+// the same two layers:
 //   X_device   its kernels over images of a view (Images, render.hip), named by their positions in it;
 //   X_host     host images through the first device: upload, X_device, download (host_stage);
 //   render_X   a frame into device images of the first device, X_device over them there, and what the
@@ -397,6 +398,55 @@ int matte_extract_host(nart_ctx* ctx, const nart_render_params* p, const nart_ma
     Buf imgs;  // the rank images, the matte; freed on return
     return host_stage(ctx, p, imgs, "matte images", {{ranks, R / 2}}, out, 1,
                       [&](const Images& v) { return matte_extract_device(v, R, id_mask, 0, (int)R / 2, 0); });
+}
+
+// ---------------------------------------------------------------- light groups (device/lightgroup.h)
+// The mix over images of the view: the G group images back to back, the mixed image out; synchronous.
+// gains: [G][3].  The time goes to the view's context (lg_ms[1]).
+int light_mix_device(const Images& v, uint32_t G, const float* gains, int groups, int out, hipStream_t st) {
+    nart_ctx* ctx = v.ctx;
+    LightMixArgs a;
+    a.groups = v.at(groups);
+    a.out = v.at(out);
+    v.layout.fill(a);
+    a.G = G;
+    for (uint32_t g = 0; g < LIGHT_GROUPS_MAX; ++g)
+        for (uint32_t c = 0; c < 3; ++c) a.gains[g][c] = g < G ? gains[3 * g + c] : 0.f;
+    return timed(ctx, ctx->ev_mix, st, &ctx->lg_ms[1], [&]() -> int {
+        const uint64_t n = (uint64_t)a.totalW * a.totalH;  // every pixel, the border too
+        hipLaunchKernelGGL(k_light_mix, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
+        HIPCHK(hipGetLastError());
+        return NART_OK;
+    });
+}
+
+// nart_hip_light_mix.
+int light_mix_host(nart_ctx* ctx, const nart_render_params* p, uint32_t G, const float* gains, const nart_pixel* groups,
+                   nart_pixel* out) {
+    first_device(ctx)->lg_ms[1] = 0.0;  // (the mix's time is kept where it runs)
+    if (!ctx->subs.empty()) return forwarded(ctx, light_mix_host(first_device(ctx), p, G, gains, groups, out));
+    Buf imgs;  // the group images, the mixed image; freed on return
+    return host_stage(ctx, p, imgs, "light-group images", {{groups, G}}, out, 1,
+                      [&](const Images& v) { return light_mix_device(v, G, gains, 0, (int)G, 0); });
+}
+
+// nart_hip_render_light_groups: the beauty and the G group images.  map: the group of every light,
+// validated by the caller.
+int render_light_groups(nart_ctx* ctx, const nart_render_params* p, const uint32_t* map, uint32_t G, nart_pixel* groups,
+                        nart_pixel* image, nart_render_stats* stats) {
+    ctx->lg_ms[0] = 0.0;
+    FrameAsk ask(p->integrator);
+    ask.light_groups = G;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    if (plan.code) return fail(ctx, plan.code, plan.message);  // (before anything is allocated)
+    if (int rc = set_light_groups(ctx, map)) return rc;
+    TileGrowthGuard guard(ctx);
+    FrameRequest rq;
+    rq.to_host(plan, OutputKind::Beauty, image);
+    for (uint32_t g = 0; g < G; ++g) rq.dst[plan.find(OutputKind::LightGroup, g)] = groups + g * ImageLayout(p).img_floats / 5;
+    const int rc = render_frame(ctx, p, plan, rq, stats);
+    for (const nart_ctx* c : ctx->subs) ctx->lg_ms[0] = std::max(ctx->lg_ms[0], c->lg_ms[0]);  // the slowest device's
+    return rc;
 }
 
 }  // namespace

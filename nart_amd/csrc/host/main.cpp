@@ -43,6 +43,14 @@
 //                   nart_hip_render_denoised_guides): the first surface behind perfect mirrors and smooth
 //                   glass, at most N (0..10, default 8) interfaces deep.  Without --aovs or --denoise,
 //                   or together with --adaptive, --robust or --mattes: an error
+//   --light-groups each|a,b,c,..  also write every session's beauty split by light
+//                   (nart_hip_render_light_groups) to <out>.light.00.exr ...: `each` gives every light a
+//                   group of its own (at most 8 lights), the list the group of every light in scene
+//                   order (groups 0..7); <out>.exr is the same call's beauty.  Not offered together with
+//                   --adaptive, --robust, --mattes, --aovs, --denoise or --follow-specular: an error
+//   --light-gains k0,k1,..  with --light-groups: one gain per group; also write <out>.mix.exr, the sum of
+//                   the group images scaled by their gains (nart_hip_light_mix)
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -292,6 +300,53 @@ int main(int argc, char* argv[]) {
         return EXIT_FAILURE;
     }
     if (follow) gp.max_follow = (uint32_t)follow_arg;
+    // --light-groups each|a,b,..  and  --light-gains k0,k1,..
+    const char *groups_arg = nullptr, *gains_arg = nullptr;
+    if (!take_value_flag(args, "--light-groups", groups_arg) || !take_value_flag(args, "--light-gains", gains_arg))
+        return EXIT_FAILURE;
+    const bool light_groups = groups_arg != nullptr;
+    if (gains_arg && !light_groups) {
+        std::fprintf(stderr, "Error: --light-gains scales the light groups and needs --light-groups\n");
+        return EXIT_FAILURE;
+    }
+    if (light_groups && (adaptive_arg || robust || mattes || aovs || denoise || follow)) {
+        std::fprintf(stderr, "Error: --light-groups is not offered together with --adaptive, --robust, --mattes, --aovs, "
+                             "--denoise or --follow-specular\n");
+        return EXIT_FAILURE;
+    }
+    std::vector<uint32_t> group_of_light;  // empty: one group per light
+    std::vector<float> light_gains;        // [G][3], once the group count is known
+    std::vector<float> gain_list;
+    if (light_groups && std::strcmp(groups_arg, "each")) {
+        const std::string s(groups_arg);
+        for (size_t pos = 0; pos <= s.size();) {
+            size_t c = s.find(',', pos);
+            if (c == std::string::npos) c = s.size();
+            int v = 0;
+            if (!parse_int(s.substr(pos, c - pos).c_str(), v) || v < 0 || v >= (int)NART_LIGHT_GROUPS_MAX) {
+                std::fprintf(stderr, "Error: --light-groups %s: `each`, or a comma-separated list of groups in 0..7\n", groups_arg);
+                return EXIT_FAILURE;
+            }
+            group_of_light.push_back((uint32_t)v);
+            pos = c + 1;
+        }
+    }
+    if (gains_arg) {
+        const std::string s(gains_arg);
+        for (size_t pos = 0; pos <= s.size();) {
+            size_t c = s.find(',', pos);
+            if (c == std::string::npos) c = s.size();
+            const std::string t = s.substr(pos, c - pos);
+            char* end = nullptr;
+            const float v = std::strtof(t.c_str(), &end);
+            if (t.empty() || *end || !(v - v == 0.f)) {
+                std::fprintf(stderr, "Error: --light-gains %s: a comma-separated list of finite numbers\n", gains_arg);
+                return EXIT_FAILURE;
+            }
+            gain_list.push_back(v);
+            pos = c + 1;
+        }
+    }
     nart_adaptive_params ap;
     nart_hip_adaptive_params_init(&ap);
     if (adaptive) {
@@ -338,6 +393,27 @@ int main(int argc, char* argv[]) {
         std::fprintf(stderr, "Error: cannot create the HIP render context on %zu device(s) (%d)\n", devices.size(), rc);
         return EXIT_FAILURE;
     }
+    uint32_t n_groups = 0;
+    if (light_groups) {
+        const uint32_t n_lights = nart_scene_blob_of(scene)->num_lights;
+        if (group_of_light.empty()) {
+            if (n_lights > NART_LIGHT_GROUPS_MAX) {
+                std::fprintf(stderr, "Error: --light-groups each: the scene has %u lights, at most 8 groups are supported\n", n_lights);
+                return EXIT_FAILURE;
+            }
+            for (uint32_t l = 0; l < n_lights; ++l) group_of_light.push_back(l);
+        }
+        if (group_of_light.size() != n_lights) {
+            std::fprintf(stderr, "Error: --light-groups lists %zu lights, the scene has %u\n", group_of_light.size(), n_lights);
+            return EXIT_FAILURE;
+        }
+        for (uint32_t v : group_of_light) n_groups = std::max(n_groups, v + 1);
+        if (gains_arg && gain_list.size() != n_groups) {
+            std::fprintf(stderr, "Error: --light-gains lists %zu gains for %u groups\n", gain_list.size(), n_groups);
+            return EXIT_FAILURE;
+        }
+        for (float v : gain_list) light_gains.insert(light_gains.end(), 3, v);
+    }
     int k = 0;
     for (const nart_render_params& p : sessions) {
         auto start = std::chrono::high_resolution_clock::now();
@@ -351,7 +427,16 @@ int main(int argc, char* argv[]) {
         const bool mattes_after = mattes && (aovs || denoise);
         if (denoise) denoised.resize(image.size());
         std::vector<uint32_t> bucket_spp;
-        if (robust) {
+        std::vector<nart_pixel> group_imgs, mix_img;
+        if (light_groups) {
+            group_imgs.resize((size_t)n_groups * image.size());
+            rc = nart_hip_render_light_groups(ctx, &p, group_of_light.data(), (uint32_t)group_of_light.size(), n_groups,
+                                              group_imgs.data(), image.data(), nullptr);
+            if (rc == NART_OK && gains_arg) {
+                mix_img.resize(image.size());
+                rc = nart_hip_light_mix(ctx, &p, n_groups, light_gains.data(), group_imgs.data(), mix_img.data());
+            }
+        } else if (robust) {
             robust_img.resize(image.size());
             rc = nart_hip_render_cascade(ctx, &p, &cp, robust_img.data(), image.data(), nullptr, nullptr);
         } else if (mattes && !mattes_after) {
@@ -456,6 +541,9 @@ int main(int argc, char* argv[]) {
         for (uint32_t i = 0; mattes && i < mp.ranks / 2; ++i)
             extra.push_back({".matte.0" + std::to_string(i) + ".exr", matte_ranks.data() + (size_t)i * image.size()});
         if (mattes && matte_ids_arg) extra.push_back({".matte.exr", matte_img.data()});
+        for (uint32_t i = 0; i < (light_groups ? n_groups : 0u); ++i)
+            extra.push_back({".light.0" + std::to_string(i) + ".exr", group_imgs.data() + (size_t)i * image.size()});
+        if (light_groups && gains_arg) extra.push_back({".mix.exr", mix_img.data()});
         std::vector<nart_pixel> spp_img;
         if (adaptive) {
             // pixel (x, y) of the cropped image was traced by bucket (x / B, y / B)

@@ -32,6 +32,9 @@ struct PathBuildIn {
     bool has_env = false;        // the scene has an environment light
     Specialize specialize = Specialize::Lean;
     bool counters = false;  // the counter pass
+    // the light-group build (include/nart_hip.h, "Light groups"): always the generic two-wave build without
+    // priority lanes, on the ray-queue kernel only
+    bool light_groups = false;
     uint32_t bounces = 0;
     int variant = 0;  // 0: the ray-queue kernel where its LDS fits; 3: k_render
     uint32_t stack_depth = 1, num_nodes = 0;  // of the scene's BVH
@@ -47,8 +50,9 @@ struct BuildId {
     uint32_t fm = FT_ALL;
     int wv = 2;
     bool pr = true;
+    bool lg = false;  // the light-group build of k_render_rq
     bool operator==(const BuildId& o) const {
-        return ext == o.ext && count == o.count && env == o.env && fm == o.fm && wv == o.wv && pr == o.pr;
+        return ext == o.ext && count == o.count && env == o.env && fm == o.fm && wv == o.wv && pr == o.pr && lg == o.lg;
     }
 };
 
@@ -59,6 +63,7 @@ struct LdsLayout {
 
 struct PathBuild {
     const char* error = nullptr;  // a layout that cannot be launched (NART_E_INVALID)
+    bool unsupported = false;     // the error is a combination that has no kernel (NART_E_UNSUPPORTED)
     BuildId id;
     bool rq = false;             // the ray-queue kernel runs, else k_render
     uint32_t rq_block = 512;     // lanes of a ray-queue block
@@ -114,7 +119,17 @@ inline PathBuild plan_build(const PathBuildIn& in) {
     id.env = in.has_env;
     const uint32_t f = in.features;
     auto covers = [f](uint32_t m) { return (f & ~m) == 0u; };
-    if (in.specialize != Specialize::Off && !in.counters && in.bounces <= ILIST_REG) {
+    if (in.light_groups) {
+        // Priority lanes and speculative pairs hold a sample's result pending and may drop it: a group
+        // frame does without them (pr = false: small shards run the plain schedule) rather than make
+        // its G records droppable.  The counter pass has no light-group build: its counts are those of
+        // a plain render of the frame.
+        id.lg = true;
+        if (!b.rq) {
+            b.error = "light groups need the ray-queue kernel: not variant 3, nor a BVH deeper than its LDS holds";
+            b.unsupported = true;
+        }
+    } else if (in.specialize != Specialize::Off && !in.counters && in.bounces <= ILIST_REG) {
         if (!in.has_env && covers(FM_DIFFUSE)) id.fm = FM_DIFFUSE;
         else if (!in.has_env && covers(FM_GLASS)) id.fm = FM_GLASS;
         else if (in.has_env && covers(FM_ENVTEX)) id.fm = FM_ENVTEX;
@@ -123,7 +138,8 @@ inline PathBuild plan_build(const PathBuildIn& in) {
         // a path grows the dielectric list by at most one entry per bounce: the register list alone
         // serves bounces <= ILIST_REG; deeper ones (up to 32) spill it to the per-lane columns
         id.ext = in.bounces > ILIST_REG;
-        id.count = in.counters;
+        id.count = in.counters && !id.lg;
+        if (id.lg) id.pr = false;
     } else {
         // The lean three-waves-per-SIMD build (kernels.h WV = 3) for throughput-bound launches.  It raises
         // throughput (C3 whole frame, 16 rounds of resident waves: path kernels 276.6 -> ~241 ms; C4 4K
@@ -160,7 +176,7 @@ inline PathBuild plan_build(const PathBuildIn& in) {
     const size_t fixed = rq_lds_bytes(b.stack_lds, b.rq_block);
     b.rq_lds.nodes = staged_nodes(in.num_nodes, fixed, CU_LDS_BYTES);
     b.rq_lds.bytes = fixed + node_lds_bytes(b.rq_lds.nodes);
-    if (b.rq && (b.stack_lds < 1 || b.stack_lds > in.stack_depth || b.rq_lds.bytes > CU_LDS_BYTES))
+    if (!b.error && b.rq && (b.stack_lds < 1 || b.stack_lds > in.stack_depth || b.rq_lds.bytes > CU_LDS_BYTES))
         b.error = "ray-queue LDS layout out of range";
     return b;
 }

@@ -95,6 +95,28 @@ inline const char* matte_params_error(const nart_matte_params* in, nart_matte_pa
     return nullptr;
 }
 
+// ---------------------------------------------------------------- light groups
+// The group map of a light-group render: group_of_light[n_lights], one entry per light of the scene
+// (scene_lights), each below n_groups.
+inline const char* light_groups_error(const uint32_t* group_of_light, uint32_t n_lights, uint32_t scene_lights,
+                                      uint32_t n_groups) {
+    if (n_groups < 1 || n_groups > NART_LIGHT_GROUPS_MAX) return "n_groups must be 1..8";
+    if (!group_of_light) return "the light-group map is required";
+    if (n_lights != scene_lights) return "the light-group map must have one entry per light of the scene";
+    for (uint32_t l = 0; l < n_lights; ++l)
+        if (group_of_light[l] >= n_groups) return "a light's group must be < n_groups";
+    return nullptr;
+}
+
+// The mix of group images: gains[n_groups][3], finite.
+inline const char* light_mix_error(uint32_t n_groups, const float* gains, const void* groups, const void* out) {
+    if (n_groups < 1 || n_groups > NART_LIGHT_GROUPS_MAX) return "n_groups must be 1..8";
+    if (!gains || !groups || !out) return "the gains, the group images and the mixed image are required";
+    for (uint32_t i = 0; i < 3 * n_groups; ++i)
+        if (!std::isfinite(gains[i])) return "light-mix gains must be finite";
+    return nullptr;
+}
+
 // ---------------------------------------------------------------- what the stages need of p
 // What the stages over whole images (denoiser, reweighting, ranking) need of p without check_params.
 inline const char* check_image_size(const nart_render_params* p) {

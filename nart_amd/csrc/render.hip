@@ -22,6 +22,7 @@
 #include "device/denoise.h"
 #include "device/guide.h"
 #include "device/lbvh.h"
+#include "device/lightgroup.h"
 #include "device/matte.h"
 #include "device/volume.h"
 #include "host/bvh_build.h"
@@ -110,6 +111,12 @@ struct nart_ctx {
     double cas_ms[2] = {0.0, 0.0};
     double mat_ms[2] = {0.0, 0.0};
     uint32_t num_meshes = 0, num_materials = 0;  // the scene's: the id counts of the two matte kinds
+    // light groups: the group of every light, uploaded by the call (set_light_groups); events around a
+    // batch's group splats (render_buckets) and the mix (light_mix_device); the last call's times: group
+    // splats ([0] on the caller's context), mix ([1] on the first device's)
+    Buf d_light_group;
+    Event ev_lg[2], ev_mix[2];
+    double lg_ms[2] = {0.0, 0.0};
     // denoiser (denoise_device): work buffers over the cropped image, the four device images of
     // nart_hip_denoise / nart_hip_render_denoised (five with the moment image), events between its
     // kernels, the last run's times
@@ -869,10 +876,10 @@ void launch_primary(nart_ctx* ctx, const RenderArgs& pa, hipStream_t st) {
 // The template parameters are the kernel builds of `B.id` (dispatch_megakernel's table), `B` their LDS
 // layout (host/path_build.h plan_build); host/path_schedule.h plan_path decides the rest.
 // resident_k: resident blocks of k_render (dispatch_megakernel's occupancy query).
-template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true>
+template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false>
 int launch_render(nart_ctx* ctx, const RenderArgs& a_in, const PathBuild& B, uint32_t resident_k, hipStream_t st) {
     auto kern = k_render<EXT, COUNT, ENV>;
-    auto kern_rq = k_render_rq<EXT, COUNT, ENV, FM, WV, PR>;
+    auto kern_rq = k_render_rq<EXT, COUNT, ENV, FM, WV, PR, LG>;
     const uint32_t RQB = B.rq_block;
     RenderArgs a = a_in;
     int rc = EXT ? ensure_ilist(ctx, a) : NART_OK;
@@ -921,6 +928,7 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, const PathBuild& B, uin
     if (rc) return rc;
 
     if (!rq) {
+        if (LG) return fail(ctx, NART_E_UNSUPPORTED, "light groups need the ray-queue kernel");  // (plan_build refuses it first)
         hipLaunchKernelGGL(kern, dim3(plan.blocks), dim3(256), lds, st, ctx->scene, b);
         HIPCHK(hipGetLastError());
         return NART_OK;
@@ -947,9 +955,9 @@ struct BuildRow {
     BuildId id;
     RenderLauncher launch;
 };
-template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true>
+template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false>
 BuildRow build_row() {
-    return {BuildId{EXT, COUNT, ENV, FM, WV, PR}, launch_render<EXT, COUNT, ENV, FM, WV, PR>};
+    return {BuildId{EXT, COUNT, ENV, FM, WV, PR, LG}, launch_render<EXT, COUNT, ENV, FM, WV, PR, LG>};
 }
 
 int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
@@ -958,6 +966,7 @@ int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
     in.has_env = ctx->has_env;
     in.specialize = !ctx->specialize ? Specialize::Off : (ctx->lean ? Specialize::Lean : Specialize::On);
     in.counters = ctx->counters;
+    in.light_groups = a.n_groups != 0;
     in.bounces = a.bounces;
     in.variant = ctx->variant;
     in.stack_depth = ctx->stack_depth;
@@ -971,8 +980,9 @@ int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
     if (rc) return rc;
     read_build_knobs(in);
     const PathBuild B = plan_build(in);
-    if (B.error) return fail(ctx, NART_E_INVALID, B.error);
-    // every build plan_build can name (tests/test_path_build.py holds the same list).  The compiler emits
+    if (B.error) return fail(ctx, B.unsupported ? NART_E_UNSUPPORTED : NART_E_INVALID, B.error);
+    // every build plan_build can name (tests/test_path_build.py and test_path_build_lights.py hold the same
+    // list; new rows go at the end).  The compiler emits
     // the kernels in the order of the rows: keep it, and the gfx950 code object stays byte for byte the same
     static const BuildRow builds[] = {
         build_row<false, false, false, FM_DIFFUSE, 3, false>(),  // scene-specialised: lean, two waves per SIMD
@@ -989,6 +999,10 @@ int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
         build_row<false, false, false>(),
         build_row<true, true, false>(),
         build_row<true, false, false>(),
+        build_row<false, false, true, FT_ALL, 2, false, true>(),  // light groups: EXT x ENV
+        build_row<true, false, true, FT_ALL, 2, false, true>(),
+        build_row<false, false, false, FT_ALL, 2, false, true>(),
+        build_row<true, false, false, FT_ALL, 2, false, true>(),
     };
     for (const BuildRow& row : builds)
         if (row.id == B.id) return row.launch(ctx, a, B, in.resident_k, st);
@@ -1186,7 +1200,8 @@ int launch_latin(nart_ctx* ctx, const RenderArgs& ra, hipStream_t st) {
 // A plan (host/frame_plan.h) with its outputs' tile buffers: tiles[i] receives the splatted records of
 // plan.outputs[i], laid out like the beauty tiles, in the order of the bucket list rendered.
 static_assert(FRAME_MAX_LAYERS == CASCADE_MAX_LAYERS && FRAME_MAX_PLANES == MATTE_MAX_PLANES &&
-                  FRAME_MAX_MATTE_IDS == MATTE_MAX_IDS,
+                  FRAME_MAX_MATTE_IDS == MATTE_MAX_IDS && FRAME_MAX_LIGHT_GROUPS == LIGHT_GROUPS_MAX &&
+                  FRAME_MAX_LIGHT_GROUPS == NART_LIGHT_GROUPS_MAX,
               "frame_plan.h restates the device headers' limits");
 struct FrameTiles {
     FramePlan plan;
@@ -1468,6 +1483,10 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
     const size_t limit = batch_slot_limit(ctx, p->spp, frame.record_bytes);
     Buf layer_records;  // cascade: the second per-sample record buffer, 16 B per sample; freed on return
     Buf guide_records;  // both followed guides: the normal records, likewise
+    Buf group_records;  // light groups: G record arrays of the batch's samples, likewise
+    const uint32_t G = beauty ? frame.ask.light_groups : 0u;
+    if (G && !ctx->d_light_group) return fail(ctx, NART_E_INVALID, "no light-group map was set");
+    double group_ms = 0.0;
     const uint32_t tpx = g.tile_size * g.tile_size;
     nart_render_stats acc;  // this call's share, added to *stats at the end
     std::memset(&acc, 0, sizeof(acc));
@@ -1506,7 +1525,18 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         hipLaunchKernelGGL(k_slot_table, dim3(nbk), dim3(256), 0, st, ctx->d_bucket_base.as<uint32_t>(), nbk, nslots, p->spp,
                            ctx->d_slot_so.as<SlotSO>(), plan.skew);
         ctx->rows_pixel_major = plan.skew;
-        const RenderArgs ra = make_render_args(ctx, p, g, nslots, d_counters);
+        RenderArgs ra = make_render_args(ctx, p, g, nslots, d_counters);
+        const uint64_t ns = (uint64_t)nslots * p->spp;
+        if (G) {
+            // the group records start at +0: every sample's owner lane accumulates into them
+            if ((rc = reserve(ctx, group_records, ctx->device, (size_t)G * ns * sizeof(float4), "light-group records")))
+                return rc;
+            HIPCHK(hipMemsetAsync(group_records.as<void>(), 0, (size_t)G * ns * sizeof(float4), st));
+            ra.n_groups = G;
+            ra.light_group = ctx->d_light_group.as<uint32_t>();
+            ra.Lgrp = group_records.as<float4>();
+            ra.lgrp_stride = ns;
+        }
         HIPCHK(record(ctx->ev_latin0, st));
         rc = launch_latin(ctx, ra, st);
         if (rc) return rc;
@@ -1527,9 +1557,21 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         sa.n_buckets = nbk;
         if (beauty && (rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
         HIPCHK(record(ctx->ev_splat1, st));
-        const uint64_t ns = (uint64_t)nslots * p->spp;
         const dim3 rec_grid((uint32_t)((ns + 255) / 256)), rec_block(256);
         hipEvent_t last = ctx->ev_splat1.handle();
+        if (G) {
+            // the path kernel's own group records, each into its output's tiles by the beauty's splat
+            HIPCHK(record(ctx->ev_lg[0], st));
+            for (uint32_t o = 0; o < frame.n_outputs; ++o) {
+                const FrameOutput& w = frame.outputs[o];
+                if (w.kind != OutputKind::LightGroup) continue;
+                sa.Lout = group_records.as<float4>() + (size_t)w.index * ns;
+                sa.tiles = out.tiles[o] + (size_t)b0 * tpx * 5;
+                if ((rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
+            }
+            HIPCHK(record(ctx->ev_lg[1], st));
+            last = ctx->ev_lg[1].handle();
+        }
         for (uint32_t i = 0; i < frame.n_passes; ++i) {
             const PassKind pass = frame.passes[i];
             if (pass == PASS_CASCADE &&
@@ -1597,7 +1639,8 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
                 }
                 case OutputKind::GuideAlbedo: sa.Lout = ga.albedo; break;  // (filled at the start of the pass)
                 case OutputKind::GuideNormal: sa.Lout = ga.normal; break;
-                case OutputKind::Beauty: break;  // (no pass: pass_of)
+                case OutputKind::Beauty:
+                case OutputKind::LightGroup: break;  // (no pass: pass_of)
                 }
                 HIPCHK(hipGetLastError());
                 sa.tiles = out.tiles[o] + (size_t)b0 * tpx * 5;
@@ -1614,6 +1657,10 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             HIPCHK(hipEventElapsedTime(&ms, ctx->ev_pass[pass][0].handle(), ctx->ev_pass[pass][1].handle()));
             times->ms[pass] += ms;
         }
+        if (G) {
+            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_lg[0].handle(), ctx->ev_lg[1].handle()));
+            group_ms += ms;
+        }
         HIPCHK(hipEventElapsedTime(&ms, ctx->ev_path0.handle(), ctx->ev_path1.handle()));
         acc.kernel_ms += ms;
         if (ctx->primary_ran) {
@@ -1627,6 +1674,7 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         if (beauty) ++acc.kernel_launches;
         b0 = b1;
     }
+    if (G) ctx->lg_ms[0] = group_ms;
     if (stats) {
         acc.schedule = ctx->sched;
         acc.samples = counted * p->spp;
@@ -1982,6 +2030,16 @@ int rect_slots(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t
     ctx->rows_pixel_major = true;
     ra = make_render_args(ctx, p, g, n, counters);
     return NART_OK;
+}
+
+// The group of every light (validated by the caller: light_groups_error) onto every device of ctx,
+// for the light-group renders that follow (render_buckets reads it where the plan has groups).
+int set_light_groups(nart_ctx* ctx, const uint32_t* group_of_light) {
+    for (nart_ctx* c : ctx->subs)
+        if (int rc = set_light_groups(c, group_of_light)) return fail(ctx, rc, c->err);
+    if (!ctx->subs.empty()) return NART_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    return upload(ctx, ctx->d_light_group, group_of_light, ctx->scene.num_lights, "light groups");
 }
 
 }  // namespace
@@ -2482,6 +2540,60 @@ int nart_hip_matte_timings(const nart_ctx* ctx, double* matte_ms, double* rank_m
     if (!ctx) return NART_E_INVALID;
     if (matte_ms) *matte_ms = ctx->mat_ms[0];
     if (rank_ms) *rank_ms = first_device(ctx)->mat_ms[1];
+    return NART_OK;
+}
+
+int nart_hip_render_light_groups(nart_ctx* ctx, const nart_render_params* p, const uint32_t* group_of_light,
+                                 uint32_t n_lights, uint32_t n_groups, nart_pixel* groups, nart_pixel* image,
+                                 nart_render_stats* stats) {
+    if (!ctx || !p || !groups) return NART_E_INVALID;
+    if (const char* why = light_groups_error(group_of_light, n_lights, first_device(ctx)->scene.num_lights, n_groups))
+        return fail(ctx, NART_E_INVALID, why);
+    return render_light_groups(ctx, p, group_of_light, n_groups, groups, image, stats);
+}
+
+int nart_hip_light_mix(nart_ctx* ctx, const nart_render_params* p, uint32_t n_groups, const float* gains,
+                       const nart_pixel* groups, nart_pixel* out) {
+    if (!ctx || !p) return NART_E_INVALID;
+    if (const char* why = light_mix_error(n_groups, gains, groups, out)) return fail(ctx, NART_E_INVALID, why);
+    if (const char* why = check_image_size(p)) return fail(ctx, NART_E_INVALID, why);
+    return light_mix_host(ctx, p, n_groups, gains, groups, out);
+}
+
+int nart_hip_render_light_group_samples(nart_ctx* ctx, const nart_render_params* p, const uint32_t* group_of_light,
+                                        uint32_t n_lights, uint32_t n_groups, uint32_t x0, uint32_t y0, uint32_t w,
+                                        uint32_t h, float* out) {
+    if (!ctx || !p || !out) return NART_E_INVALID;
+    if (!ctx->subs.empty())  // per-sample debugging runs on the first device
+        return forwarded(ctx, nart_hip_render_light_group_samples(first_device(ctx), p, group_of_light, n_lights, n_groups,
+                                                                  x0, y0, w, h, out));
+    if (const char* why = light_groups_error(group_of_light, n_lights, ctx->scene.num_lights, n_groups))
+        return fail(ctx, NART_E_INVALID, why);
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    if (p->integrator == NART_INTEGRATOR_VOLUME)  // (frames: plan_frame's rule)
+        return fail(ctx, NART_E_UNSUPPORTED, "light groups need the path integrator: the volume integrator has no light-group build");
+    if (!w || !h) return fail(ctx, NART_E_INVALID, "empty rect");
+    if ((rc = set_light_groups(ctx, group_of_light)) || (rc = counter_buffer(ctx))) return rc;
+    RenderArgs ra;
+    if ((rc = rect_slots(ctx, p, x0, y0, w, h, ctx->d_counters.as<unsigned long long>(), ra))) return rc;
+    const size_t ns = (size_t)ra.n_slots * p->spp;
+    Buf records;  // the G record arrays; freed on return
+    if ((rc = reserve(ctx, records, ctx->device, n_groups * ns * sizeof(float4), "light-group records"))) return rc;
+    HIPCHK(hipMemsetAsync(records.as<void>(), 0, n_groups * ns * sizeof(float4), 0));
+    ra.n_groups = n_groups;
+    ra.light_group = ctx->d_light_group.as<uint32_t>();
+    ra.Lgrp = records.as<float4>();
+    ra.lgrp_stride = ns;
+    if ((rc = launch_latin(ctx, ra, 0)) || (rc = dispatch_render(ctx, ra, p->integrator, 0))) return rc;
+    HIPCHK(hipMemcpy(out, records.as<float4>(), n_groups * ns * sizeof(float4), hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+int nart_hip_light_group_timings(const nart_ctx* ctx, double* splat_ms, double* mix_ms) {
+    if (!ctx) return NART_E_INVALID;
+    if (splat_ms) *splat_ms = ctx->lg_ms[0];
+    if (mix_ms) *mix_ms = first_device(ctx)->lg_ms[1];
     return NART_OK;
 }
 
