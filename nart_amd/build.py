@@ -46,13 +46,23 @@ def _sources(*rel):
     return out
 
 
+# libnart_scene.so's own files under csrc/host; everything else under csrc feeds libnart_hip.so
+SCENE_SOURCES = ("host/scene_host.cpp", "host/json.h", "host/exr_piz.cpp", "host/exr_piz.h")
+
+
+def _hip_sources():
+    """What libnart_hip.so is built from under csrc: render.hip, device/ and host/ without the scene
+    library's files and the CLI (main.cpp links against the library)."""
+    other = set(_sources(*SCENE_SOURCES, "host/main.cpp"))
+    return [f for f in _sources("render.hip", "device", "host") if f not in other]
+
+
 def hip_source_sha():
     """sha256 (16 hex digits) of the sources of libnart_hip.so: ties a committed profile (e.g.
     profiles/pmc_latest.json's HBM traffic) to the kernel code it was measured on."""
     import hashlib
     h = hashlib.sha256()
-    for f in _sources("render.hip", "device", "host/bvh_build.cpp", "host/bvh_build.h", "host/multi_gpu.h",
-                      "host/path_schedule.h", "host/path_build.h", "host/image_stages.h"):
+    for f in _hip_sources():
         h.update(os.path.relpath(f, CSRC).encode())
         with open(f, "rb") as fh:
             h.update(fh.read())
@@ -62,8 +72,7 @@ def hip_source_sha():
 def build_scene_lib(force=False):
     os.makedirs(LIB, exist_ok=True)
     out = os.path.join(LIB, "libnart_scene.so")
-    srcs = _sources("host/scene_host.cpp", "host/json.h", "host/exr_piz.cpp", "host/exr_piz.h") + \
-        [os.path.join(REPO, "include", "nart_scene.h")]
+    srcs = _sources(*SCENE_SOURCES) + [os.path.join(REPO, "include", "nart_scene.h")]
     if not force and _newer(out, srcs):
         return out
     _run(["g++"] + COMMON + ["-shared", "-o", out, os.path.join(CSRC, "host", "scene_host.cpp"),
@@ -78,7 +87,7 @@ def hipcc():
 def build_hip_lib(force=False):
     scene = build_scene_lib()
     out = os.path.join(LIB, "libnart_hip.so")
-    srcs = _sources("render.hip", "device", "host") + [os.path.join(REPO, "include", "nart_hip.h"), scene]
+    srcs = _hip_sources() + [os.path.join(REPO, "include", "nart_hip.h"), scene]
     if not force and _newer(out, srcs):
         return out
     extra = os.environ.get("NART_HIP_DEFINES", "").split()  # development builds, e.g. -DNART_WAVEPROF

@@ -8,6 +8,7 @@
 
 #include "path.h"
 #include "queue_layout.h"  // RQ_*_BIT: the flag bits of queue entries
+#include "sample_layout.h"  // LATIN_*, NART_LATIN_PF, SPLAT_LUT_MAX, NART_SPLAT_NP: shared with the host's plans
 
 namespace nd {
 
@@ -371,8 +372,6 @@ struct LatinScratch {
     uint32_t *cx, *cy, *sx, *sy, *st;
     uint32_t n2;  // (spp + 1) / 2 word rows
 };
-#define LATIN_EMIT_SLOTS 16
-#define LATIN_ST_PAD (256 * 8 * 4)  // words read past the last block's states by k_latin_emit
 
 ND size_t latin_row(uint32_t g, uint32_t rows, uint32_t r, uint32_t lane) {
     return ((size_t)g * rows + r) * 64u + lane;
@@ -405,9 +404,6 @@ __global__ __launch_bounds__(256) void k_latin_draws(RenderArgs A, LatinScratch 
     const_cast<uint32_t*>(A.rng0)[slot] = rng;
 }
 
-#ifndef NART_LATIN_PF
-#define NART_LATIN_PF 16  // choice words (2 swaps each) loaded one batch ahead of their swaps
-#endif
 // BL lanes per block, each with its own u16 column of the block's [i][BL] LDS array.  BL = 80
 // where one 64-lane block per CU is all the LDS holds (640 < spp <= 1024: 128 KiB of 160 per 64
 // lanes): the 80-lane block fills the 160 KiB, and its second wave (16 lanes) runs its own swap
@@ -505,9 +501,6 @@ ND float latin_value(uint32_t k, uint32_t y, float inv) {
 // wave writes 4 rows x 16 neighbouring slots (128 B each in the bucket layout).  The index words
 // are loaded LATIN_EMIT_U rows ahead (the first batch before the LDS staging): with 2 blocks per
 // CU the kernel is otherwise bound by waiting on them.
-#ifndef LATIN_EMIT_U
-#define LATIN_EMIT_U 8
-#endif
 __global__ __launch_bounds__(256) void k_latin_emit(RenderArgs A, LatinScratch L) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_st[];  // [k][p]
     constexpr uint32_t P = LATIN_EMIT_SLOTS, RS = 256 / P, U = LATIN_EMIT_U;
@@ -1878,7 +1871,6 @@ struct SplatArgs {
     const float4* lut = nullptr;
     uint32_t lut_b0 = 0, lut_n = 0;
 };
-#define SPLAT_LUT_MAX 2048
 
 // a / b, or a * (1/b) when 1/b is an exact power of two (bit-identical, avoids the
 // correctly-rounded division sequence)

@@ -25,11 +25,14 @@
 #include "device/lightgroup.h"
 #include "device/matte.h"
 #include "device/volume.h"
+#include "host/bucket_batch.h"
 #include "host/bvh_build.h"
 #include "host/device_buf.h"
 #include "host/frame_plan.h"
+#include "host/latin_plan.h"
 #include "host/path_build.h"
 #include "host/path_schedule.h"
+#include "host/splat_plan.h"
 #include "host/stage_params.h"
 
 using namespace nd;
@@ -777,6 +780,11 @@ void read_build_knobs(PathBuildIn& in) {
 void read_volume_knobs(VolumeIn& in) {
     read_knobs({{"NART_VOL_SPARSE", &in.sparse}, {"NART_VOL_SPARSE_F", &in.sparse_f}, {"NART_VOL_SPARSE_ROUNDS", &in.sparse_rounds}});
 }
+void read_splat_knobs(SplatIn& in) {
+    read_knobs({{"NART_SKEW_BANDS", &in.skew_bands}});
+    const char* small = env_opt("NART_SPLAT_SMALL");  // a word, not a number
+    in.small_col4 = small && std::strcmp(small, "col4") == 0;
+}
 
 // What the scheduling steps of one launch_render share.
 using PathKernel = void (*)(DScene, RenderArgs);
@@ -1068,133 +1076,30 @@ int dispatch_render(nart_ctx* ctx, const RenderArgs& a, int integrator, hipStrea
     return dispatch_megakernel(ctx, a, st);
 }
 
-// Filter index of AddSample (render.cpp:43-49) as a function of d2 = distX^2 + distY^2:
-// fi(d2) = min(63, uint8(RN(RN(sqrt(d2)) / fw) * 64)).  sqrt and / are correctly rounded and the
-// scaling by 64 is exact, so below the uint8 wrap fi is a non-decreasing step function of d2 and
-// fi(d2) >= k  <=>  d2 >= thr[k].  thr[0] = 0, thr[64] = inf; thr[k] is found by bisection over the
-// float bit patterns with the same float operations.  A splat hit has |distX|, |distY| <= fw + 0.5,
-// so the thresholds are exact for every hit when RN(sqrt(2) (fw + 0.5) / fw) * 64 stays below 256
-// (fw > ~0.28); otherwise returns false and the splat keeps the direct computation.
-static uint32_t filter_index_host(float d2, float fw) {
-    volatile float dist = std::sqrt(d2);
-    volatile float q = dist / fw;
-    return std::min(63u, (uint32_t)(int32_t)(q * 64.f) & 0xFFu);
-}
-
-bool splat_thresholds(float fw, float thr[65]) {
-    if (!(fw > 0.f)) return false;
-    const float hmax = fw + 0.5f;
-    const double worst = std::sqrt(2.0 * (double)hmax * hmax) / fw * 64.0;
-    if (!(worst < 250.0)) return false;
-    const float d2max = 2.f * hmax * hmax * 1.001f;
-    uint32_t hi_bits;
-    std::memcpy(&hi_bits, &d2max, 4);
-    thr[0] = 0.f;
-    thr[64] = __builtin_inff();
-    for (uint32_t k = 1; k < 64; ++k) {
-        uint32_t lo = 0, hi = hi_bits;  // f(lo) < k <= f(hi) unless no hit reaches index k
-        if (filter_index_host(d2max, fw) < k) {
-            thr[k] = __builtin_inff();
-            continue;
-        }
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            float m;
-            std::memcpy(&m, &mid, 4);
-            if (filter_index_host(m, fw) >= k) hi = mid;
-            else lo = mid;
-        }
-        std::memcpy(&thr[k], &hi, 4);
-        if (filter_index_host(0.f, fw) >= k) thr[k] = 0.f;
-    }
-    return true;
-}
-
-// Filter weight by d2 cell for the splat (k_splat_col4<.., true>): cell c covers the floats whose
-// bits >> 16 equal b0 + c (128 cells per octave of d2).  Consecutive thresholds differ by at
-// least a factor (64/63)^2 = 1.03 > 1 + 1/128, so a cell holds at most one threshold t: the
-// filter index in the cell is base + (d2 >= t), base = fi(cell start).  Cell 0 lies wholly below
-// thr[1] (index 0 for every smaller d2 too); the last cell starts past thr[63] (index 63 beyond).
-// Stored per cell: {t (or inf), table[base], table[base + 1]}.  Returns false when the thresholds
-// do not apply (then the splat keeps the sqrt estimate) or a cell would hold two of them.
-bool splat_lut(const float thr[65], const float table[64], std::vector<float4>& lut, uint32_t& b0) {
-    uint32_t u1, u63;
-    std::memcpy(&u1, &thr[1], 4);
-    std::memcpy(&u63, &thr[63], 4);
-    if (!(thr[1] > 0.f) || !(thr[63] < __builtin_inff())) return false;
-    b0 = (u1 >> 16) - 1;
-    const uint32_t last = (u63 >> 16) + 1;
-    const uint32_t n = last - b0 + 1;
-    if (n > SPLAT_LUT_MAX) return false;
-    lut.assign(n, make_float4(0.f, 0.f, 0.f, 0.f));
-    for (uint32_t c = 0; c < n; ++c) {
-        const uint32_t lo = (b0 + c) << 16, hi = lo | 0xFFFFu;
-        float flo, fhi;
-        std::memcpy(&flo, &lo, 4);
-        std::memcpy(&fhi, &hi, 4);
-        uint32_t base = 0, inside = 0;
-        float t = __builtin_inff();
-        for (uint32_t k = 1; k < 64; ++k) {
-            if (thr[k] <= flo) base = k;
-            else if (thr[k] <= fhi) {
-                ++inside;
-                t = thr[k];
-            }
-        }
-        if (inside > 1) return false;
-        lut[c] = make_float4(t, table[std::min(base, 63u)], table[std::min(base + inside, 63u)], 0.f);
-    }
-    return true;
-}
-
-// LatinSquare per traced pixel: float arrays in LDS up to 256 spp, LDS index shuffles up to 1024
-// spp (scratch in Lout: 2*spp floats per lane of every launched block, within Lout's 4*spp per
-// slot once there are >= 64 slots), the global-memory variant beyond.
+// LatinSquare samples of the batch in `ra`, in the form and launch shapes of host/latin_plan.h plan_latin;
+// the three-kernel form's scratch arrays lie in ra.Lout, which the path kernel overwrites later.
 int launch_latin(nart_ctx* ctx, const RenderArgs& ra, hipStream_t st) {
-    // three-kernel form (k_latin_draws / _perm / _emit) when its scratch fits in Lout
-    const uint32_t groups = (ra.n_slots + 63) / 64;
-    LatinScratch ls;
-    ls.n2 = (ra.spp + 1) / 2;
-    // + padding rows per array: k_latin_perm / k_latin_emit load a batch of words ahead,
-    // unconditionally
-    const size_t words = (size_t)groups * 64 * ls.n2 + (size_t)std::max(NART_LATIN_PF, 2 * LATIN_EMIT_U * 16) * 64;
-    const size_t stw = (size_t)((ra.n_slots + LATIN_EMIT_SLOTS - 1) / LATIN_EMIT_SLOTS) * LATIN_EMIT_SLOTS * ra.spp +
-                       LATIN_ST_PAD;
-    const bool three = ra.spp >= 2 && ra.spp <= 1024 && (4 * words + stw) * 4 <= ctx->cap_samples * sizeof(float4) &&
-                       ra.spp > 64;  // C3 (256 spp): 6.7 -> 4.6 ms
-    if (three) {
-        uint32_t* base = reinterpret_cast<uint32_t*>(ra.Lout);
-        ls.cx = base;
-        ls.cy = base + words;
-        ls.sx = base + 2 * words;
-        ls.sy = base + 3 * words;
-        ls.st = base + 4 * words;
-        hipLaunchKernelGGL(k_latin_draws, dim3((ra.n_slots + 255) / 256), dim3(256), 0, st, ra, ls);
-        if ((size_t)ls.n2 * 4 * 128 > 160 * 1024)  // one 64-lane block per CU: 80 lanes fill its LDS
-            hipLaunchKernelGGL(k_latin_perm<80>, dim3((ra.n_slots + 79) / 80), dim3(80),
-                               (size_t)ls.n2 * 2 * 80 * sizeof(uint16_t), st, ra, ls);
-        else
-            hipLaunchKernelGGL(k_latin_perm<64>, dim3(groups), dim3(64), (size_t)ls.n2 * 2 * 64 * sizeof(uint16_t),
-                               st, ra, ls);
-        hipLaunchKernelGGL(k_latin_emit, dim3((ra.n_slots + LATIN_EMIT_SLOTS - 1) / LATIN_EMIT_SLOTS), dim3(256),
-                           (size_t)ra.spp * LATIN_EMIT_SLOTS * sizeof(uint32_t), st, ra, ls);
-        HIPCHK(hipGetLastError());
-        return NART_OK;
+    const LatinPlan lp = plan_latin(ra.n_slots, ra.spp, ctx->cap_samples * sizeof(float4));
+    auto launch = [&](auto kernel, const Grid& g, auto... args) {
+        hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(g.threads), g.lds, st, ra, args...);
+    };
+    switch (lp.form) {
+    case LatinForm::Three: {
+        uint32_t* const base = reinterpret_cast<uint32_t*>(ra.Lout);
+        const LatinScratch ls{base + lp.cx, base + lp.cy, base + lp.sx, base + lp.sy, base + lp.st, lp.n2};
+        launch(k_latin_draws, lp.draws, ls);
+        if (lp.perm_block == 80) launch(k_latin_perm<80>, lp.perm, ls);
+        else launch(k_latin_perm<64>, lp.perm, ls);
+        launch(k_latin_emit, lp.emit, ls);
+        break;
     }
-    // (k_latin_idx at <= 256 spp measured slower: C3 11.0 vs 6.6 ms; the three-kernel form 4.6)
-    if (ra.spp <= 256) {
-        size_t lds = (size_t)ra.spp * 2 * 64 * sizeof(float);
-        hipLaunchKernelGGL(k_latin_lds, dim3((ra.n_slots + 63) / 64), dim3(64), lds, st, ra);
-    } else if (ra.spp <= 1024 && ra.n_slots >= 64) {
-        size_t lds = (size_t)ra.spp * (ra.spp <= 512 ? 2 : 1) * 64 * sizeof(uint16_t);
-        hipLaunchKernelGGL(k_latin_idx, dim3((ra.n_slots + 63) / 64), dim3(64), lds, st, ra, (float*)ra.Lout);
-    } else {
-        hipLaunchKernelGGL(k_latin, dim3((ra.n_slots + 255) / 256), dim3(256), 0, st, ra);
+    case LatinForm::Lds: launch(k_latin_lds, lp.one); break;
+    case LatinForm::Idx: launch(k_latin_idx, lp.one, (float*)ra.Lout); break;
+    case LatinForm::Global: launch(k_latin, lp.one); break;
     }
     HIPCHK(hipGetLastError());
     return NART_OK;
 }
-
 
 // ---------------------------------------------------------------- first-hit AOVs
 // A plan (host/frame_plan.h) with its outputs' tile buffers: tiles[i] receives the splatted records of
@@ -1318,15 +1223,12 @@ RenderArgs make_render_args(const nart_ctx* ctx, const nart_render_params* p, co
     return ra;
 }
 
-// How a render_buckets call splats: the kernel (all bit-identical) and its launch shape, and the
+// How a render_buckets call splats: the kernel and sample layout (host/splat_plan.h plan_splat), and the
 // SplatArgs fields that hold for the whole call (the batch adds its buckets, samples and tiles).
+static_assert(sizeof(LutCell) == sizeof(float4), "the splat kernels read the filter cells as float4");
 struct SplatPlan {
     SplatArgs sa;
-    int mode = 0;         // 5 / 4 skewed time (rows / columns), 3 four tile pixels per lane, 1 / 0 one pixel per lane
-    bool skew = false;    // a pixel-major sample layout, for k_splat_skew (mode 4) or k_splat_rows (mode 5)
-    bool rows = false;    // k_splat_rows
-    uint32_t bands = 1;   // tile-row bands per bucket (k_splat_skew's NB)
-    size_t lut_bytes = 0;
+    SplatChoice choice;
 };
 
 // The splat of a call over n_buckets buckets; uploads the filter table, thresholds and LUT.
@@ -1339,115 +1241,65 @@ int plan_splat(nart_ctx* ctx, const nart_render_params* p, const nart_session_ge
     if (int rc = reserve(ctx, ctx->d_table, ctx->device, sizeof(table), "filter table")) return rc;
     float* const d_table = ctx->d_table.as<float>();
     HIPCHK(hipMemcpy(d_table, table, sizeof(table), hipMemcpyHostToDevice));
-    std::vector<float4> lut;
+    std::vector<LutCell> lut;
     uint32_t lut_b0 = 0;
     const bool lut_ok = thr_ok && splat_lut(table + 64, table, lut, lut_b0);
-    // skewed-time splat (k_splat_skew, pixel-major samples) where its preconditions hold, else
-    // k_splat_col4 / k_splat over the sample-major layout
-    // It runs one lane per tile column for ~W*B steps, so its time is one wave's latency once the
-    // launch has fewer than ~2 waves per SIMD: small shards keep k_splat_col4 (C5 1/8 shard:
-    // 54 ms skewed vs 23 ms col4; whole frame 72 vs 113 ms).  skew_min: waves per SIMD.
-    const uint32_t B = p->bucket_size, tile = B + 2 * g.filter_bounds;
-    const double skew_min = 2.0;
-    int n_cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    const double skew_waves = tile <= 64 ? (double)((n_buckets + 64 / tile - 1) / (64 / tile)) : 0.0;
-    // splat mode -1 (default): 4 where the launch is large enough, else 3; an explicit 4 forces it.
-    // Launches of 1-2 waves per SIMD split each bucket's tile rows into two bands (twice the waves
-    // for ~2/3 of the steps each): C5 1/2 shard 60 -> 49 ms (k_splat_col4: 62); a whole frame keeps
-    // one band (C5 73 vs 92 ms with two).  Below 1 wave per SIMD k_splat_col4 is faster (C5 1/4,
-    // 1/8 shards: 36 / 23 ms vs 41 / 37 with two bands; profiles/r03k_skew_band_ab.log).
-    // The two-band range is the volume integrator's only: for the path integrator the splat's
-    // gain at the C3 1/2 shard (17 -> 12.5 ms) is within the path kernels' run-to-run spread under
-    // the pixel-major layout (186-208 ms on one box; profiles/r03l_c3_half_shard_splat_ab.log).
-    const double skew_from = p->integrator == NART_INTEGRATOR_VOLUME ? 0.5 * skew_min : skew_min;
-    // Below that, k_splat_rows (mode 5: W lanes per tile column, five times k_splat_skew's
-    // parallelism, each sample still fetched once per bucket) unless NART_SPLAT_SMALL=col4
-    const char* ss = env_opt("NART_SPLAT_SMALL");
-    const int small_mode = ss && std::strcmp(ss, "col4") == 0 ? 3 : 5;
-    const int splat_mode =
-        ctx->splat_mode >= 0 ? ctx->splat_mode : (skew_waves >= skew_from * 4.0 * n_cus ? 4 : small_mode);
-    // NART_SKEW_BANDS (read per call): 1 or 2 forces the band count
-    const char* be = env_opt("NART_SKEW_BANDS");
-    const uint32_t skew_bands = be && std::atoi(be) > 0 ? (std::atoi(be) >= 2 ? 2u : 1u)
-                                                          : (skew_waves >= skew_min * 4.0 * n_cus ? 1u : 2u);
-    // skew: a pixel-major sample layout for k_splat_skew (mode 4) or k_splat_rows (mode 5)
-    const bool skew = splat_mode >= 4 && lut_ok && (B & (B - 1)) == 0 && B <= 32 && tile <= 64 &&
-                      g.filter_bounds >= 1 && g.filter_bounds <= 3;
-    const bool rows = skew && splat_mode == 5;
     if (lut_ok) {
         if (int rc = reserve(ctx, ctx->d_lut, ctx->device, SPLAT_LUT_MAX * sizeof(float4), "splat filter cells")) return rc;
         HIPCHK(hipMemcpy(ctx->d_lut.as<float4>(), lut.data(), lut.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
-    plan.mode = splat_mode;
-    plan.skew = skew;
-    plan.rows = rows;
-    plan.bands = skew_bands;
-    plan.lut_bytes = lut.size() * sizeof(float4);
+    int n_cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    SplatIn in;
+    in.mode = ctx->splat_mode;
+    in.volume = p->integrator == NART_INTEGRATOR_VOLUME;
+    in.B = p->bucket_size;
+    in.fb = g.filter_bounds;
+    in.tile = p->bucket_size + 2 * g.filter_bounds;
+    in.n_buckets = n_buckets;
+    in.n_cus = (uint32_t)n_cus;
+    in.lut_ok = lut_ok;
+    read_splat_knobs(in);
+    plan.choice = plan_splat(in);
+    const SplatScalars v = splat_scalars(p->filter_width, p->spp, p->bucket_size, g.filter_bounds, g.tile_size, g.n_buckets_x,
+                                         g.total_width, g.total_height, lut_b0, (uint32_t)lut.size());
     SplatArgs& sa = plan.sa;
     sa.table = d_table;
     sa.thr = thr_ok ? d_table + 64 : nullptr;
-    sa.idx_scale = 64.f / p->filter_width;
-    sa.spp = p->spp;
-    sa.B = p->bucket_size;
-    sa.fb = g.filter_bounds;
-    sa.tile = g.tile_size;
-    sa.nbx = g.n_buckets_x;
-    sa.totalW = g.total_width;
-    sa.totalH = g.total_height;
-    sa.fw = p->filter_width;
-    sa.invB = (B & (B - 1)) == 0 ? 1.f / (float)B : 0.f;
     sa.lut = lut_ok ? ctx->d_lut.as<const float4>() : nullptr;
-    sa.lut_b0 = lut_b0;
-    sa.lut_n = (uint32_t)lut.size();
-    int ex = 0;
-    sa.invFw = std::frexp(p->filter_width, &ex) == 0.5f ? 1.f / p->filter_width : 0.f;
+    sa.idx_scale = v.idx_scale;
+    sa.spp = v.spp, sa.B = v.B, sa.fb = v.fb, sa.tile = v.tile, sa.nbx = v.nbx, sa.totalW = v.totalW, sa.totalH = v.totalH;
+    sa.fw = v.fw, sa.invB = v.invB, sa.invFw = v.invFw;
+    sa.lut_b0 = v.lut_b0, sa.lut_n = v.lut_n;
     return NART_OK;
 }
 
-#ifndef NART_SPLAT_NP
-#define NART_SPLAT_NP 4
-#endif
 // sa.Lout into sa.tiles for the nbk buckets of a batch: the beauty, then each requested AOV's
-// records, by the same kernel.  Splat modes (all bit-identical): 5 / 4 skewed time, 3 four tile
-// pixels per lane (power-of-two buckets); 1 / 0 one tile pixel per lane with the threshold / direct
-// filter-index arithmetic (any bucket size; 2 selects 1 since the compare-only one-pixel kernel
-// was retired).
+// records, by the same kernel, launched as host/splat_plan.h splat_launch says.
 // MOM: the moment image's pass (kernels.h k_moment): the same kernel and launch shape.
 template <bool MOM>
 int launch_splat_as(nart_ctx* ctx, const SplatPlan& plan, const SplatArgs& sa, uint32_t nbk, hipStream_t st) {
-    const dim3 block(256);
-    if (plan.rows) {
-        ctx->sched |= NART_SCHED_SPLAT_ROWS;
-        const uint32_t U = sa.tile * (2 * sa.fb + 1), ub = std::max(1u, 512u / U);
-        const uint32_t threads = (ub * U + 63) / 64 * 64, nblk = (nbk + ub - 1) / ub;
-        const size_t lds = plan.lut_bytes + 2u * ub * sizeof(uint32_t);
-        if (sa.fb == 1) hipLaunchKernelGGL((k_splat_rows<1, MOM>), dim3(nblk), dim3(threads), lds, st, sa);
-        else if (sa.fb == 2) hipLaunchKernelGGL((k_splat_rows<2, MOM>), dim3(nblk), dim3(threads), lds, st, sa);
-        else hipLaunchKernelGGL((k_splat_rows<3, MOM>), dim3(nblk), dim3(threads), lds, st, sa);
-    } else if (plan.skew) {
-        ctx->sched |= NART_SCHED_SPLAT_SKEW;
-        const uint32_t nb = plan.bands;
-        const uint32_t pb = 64u / sa.tile, nblk = (nbk * nb + 4 * pb - 1) / (4 * pb);
-        const size_t lds = plan.lut_bytes + 8u * pb * sizeof(uint32_t);
-        const int fbk = (int)sa.fb * 2 + (int)nb - 1;
-        if (fbk == 2) hipLaunchKernelGGL((k_splat_skew<1, 1, MOM>), dim3(nblk), block, lds, st, sa);
-        else if (fbk == 3) hipLaunchKernelGGL((k_splat_skew<1, 2, MOM>), dim3(nblk), block, lds, st, sa);
-        else if (fbk == 4) hipLaunchKernelGGL((k_splat_skew<2, 1, MOM>), dim3(nblk), block, lds, st, sa);
-        else if (fbk == 5) hipLaunchKernelGGL((k_splat_skew<2, 2, MOM>), dim3(nblk), block, lds, st, sa);
-        else if (fbk == 6) hipLaunchKernelGGL((k_splat_skew<3, 1, MOM>), dim3(nblk), block, lds, st, sa);
-        else hipLaunchKernelGGL((k_splat_skew<3, 2, MOM>), dim3(nblk), block, lds, st, sa);
-    } else if (sa.thr && sa.invB != 0.f && plan.mode >= 3) {
-        const uint64_t n4 = (uint64_t)nbk * sa.tile * ((sa.tile + NART_SPLAT_NP - 1) / NART_SPLAT_NP);
-        const dim3 grid((uint32_t)((n4 + 255) / 256));
-        if (sa.lut) hipLaunchKernelGGL((k_splat_col4<NART_SPLAT_NP, true, MOM>), grid, block, 0, st, sa);
-        else hipLaunchKernelGGL((k_splat_col4<NART_SPLAT_NP, false, MOM>), grid, block, 0, st, sa);
-    } else {
-        const uint64_t nthreads = (uint64_t)nbk * sa.tile * sa.tile;
-        const dim3 grid((uint32_t)((nthreads + 255) / 256));
-        if (sa.thr && plan.mode >= 1) hipLaunchKernelGGL((k_splat<1, MOM>), grid, block, 0, st, sa);
-        else hipLaunchKernelGGL((k_splat<0, MOM>), grid, block, 0, st, sa);
+    const SplatLaunch l = splat_launch(plan.choice, sa.fb, sa.tile, sa.thr != nullptr, sa.invB != 0.f, sa.lut ? sa.lut_n : 0u, nbk);
+    using Kernel = void (*)(SplatArgs);
+    Kernel k = nullptr;
+    switch (l.kernel) {
+    case SplatKernel::Rows: {
+        static const Kernel rows[3] = {k_splat_rows<1, MOM>, k_splat_rows<2, MOM>, k_splat_rows<3, MOM>};
+        k = rows[l.fb - 1];
+        break;
     }
+    case SplatKernel::Skew: {
+        static const Kernel skew[3][2] = {{k_splat_skew<1, 1, MOM>, k_splat_skew<1, 2, MOM>},
+                                          {k_splat_skew<2, 1, MOM>, k_splat_skew<2, 2, MOM>},
+                                          {k_splat_skew<3, 1, MOM>, k_splat_skew<3, 2, MOM>}};
+        k = skew[l.fb - 1][l.bands - 1];
+        break;
+    }
+    case SplatKernel::Col4: k = l.lut ? k_splat_col4<NART_SPLAT_NP, true, MOM> : k_splat_col4<NART_SPLAT_NP, false, MOM>; break;
+    case SplatKernel::Pixel: k = l.thr ? k_splat<1, MOM> : k_splat<0, MOM>; break;
+    }
+    ctx->sched |= l.sched;
+    hipLaunchKernelGGL(k, dim3(l.blocks), dim3(l.threads), l.lds, st, sa);
     HIPCHK(hipGetLastError());
     return NART_OK;
 }
@@ -1456,12 +1308,94 @@ int launch_splat(nart_ctx* ctx, const SplatPlan& plan, const SplatArgs& sa, uint
     return moment ? launch_splat_as<true>(ctx, plan, sa, nbk, st) : launch_splat_as<false>(ctx, plan, sa, nbk, st);
 }
 
+// The per-sample records of output `w` for the ns samples of the batch in `ra`, which the splat then takes
+// into the output's tiles: one small kernel fills `records` from the beauty's records (ctx->d_L) or the
+// camera-ray hits (ctx->d_prim).  The guides' records were filled at the start of their pass (`ga`).
+// Returns the records to splat.
+int fill_records(nart_ctx* ctx, const FramePlan& frame, const FrameOutput& w, const RenderArgs& ra, const GuideArgs& ga,
+                 float4* records, uint64_t ns, hipStream_t st, const float4** filled) {
+    const dim3 grid((uint32_t)((ns + 255) / 256)), block(256);
+    *filled = records;
+    switch (w.kind) {
+    case OutputKind::Layer: {
+        const CascadeLevels& lv = frame.ask.cascade;
+        CascadeSplitArgs ca;
+        ca.L = ctx->d_L.as<float4>();
+        ca.out = records;
+        ca.n = ns;
+        ca.K = lv.K;
+        ca.b_first = lv.b[0];
+        ca.b_top = lv.b[lv.K - 1];
+        ca.base_m1 = lv.base - 1.f;
+        ca.j = w.index;
+        ca.b_prev = ca.j > 0 ? lv.b[ca.j - 1] : 0.f;
+        ca.b_cur = lv.b[ca.j];
+        ca.b_next = ca.j + 1 < lv.K ? lv.b[ca.j + 1] : 0.f;
+        hipLaunchKernelGGL(k_cascade_split, grid, block, 0, st, ca);
+        break;
+    }
+    case OutputKind::Moment: hipLaunchKernelGGL(k_moment, grid, block, 0, st, ctx->d_L.as<float4>(), ns); break;
+    case OutputKind::Albedo:
+    case OutputKind::Normal:
+        if (int rc = launch_aov(ctx, ra, w.kind == OutputKind::Albedo ? AOV_ALBEDO : AOV_NORMAL, records, st)) return rc;
+        break;
+    case OutputKind::Plane: {
+        MatteIdArgs ma;
+        ma.hit = ctx->d_prim.as<uint32_t>();
+        ma.tri_mesh = ctx->scene.tri_mesh;
+        ma.meshes = ctx->scene.meshes;
+        ma.out = ctx->d_L.as<float4>();
+        ma.n = ns;
+        ma.num_tris = ctx->scene.num_tris;
+        ma.num_meshes = ctx->num_meshes;
+        ma.kind = frame.ask.matte.kind;
+        ma.n_ids = frame.ask.matte.n_ids;
+        ma.q = w.index;
+        hipLaunchKernelGGL(k_matte_ids, grid, block, 0, st, ma);
+        break;
+    }
+    case OutputKind::GuideAlbedo: *filled = ga.albedo; break;
+    case OutputKind::GuideNormal: *filled = ga.normal; break;
+    case OutputKind::Beauty:
+    case OutputKind::LightGroup: break;  // (no pass: pass_of)
+    }
+    HIPCHK(hipGetLastError());
+    return NART_OK;
+}
+
+// The device times of a batch from its event pairs, once the last event recorded has been waited for:
+// the passes' into `times`, the light groups' splats into group_ms, the rest into acc.
+int read_batch_times(nart_ctx* ctx, const FramePlan& frame, bool groups, nart_render_stats& acc, PassTimes* times,
+                     double& group_ms) {
+    float ms = 0.f;
+    for (uint32_t i = 0; i < frame.n_passes && times; ++i) {
+        const PassKind pass = frame.passes[i];
+        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_pass[pass][0].handle(), ctx->ev_pass[pass][1].handle()));
+        times->ms[pass] += ms;
+    }
+    if (groups) {
+        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_lg[0].handle(), ctx->ev_lg[1].handle()));
+        group_ms += ms;
+    }
+    HIPCHK(hipEventElapsedTime(&ms, ctx->ev_path0.handle(), ctx->ev_path1.handle()));
+    acc.kernel_ms += ms;
+    if (ctx->primary_ran) {
+        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_path0.handle(), ctx->ev_primary.handle()));
+        acc.primary_ms += ms;
+    }
+    HIPCHK(hipEventElapsedTime(&ms, ctx->ev_path1.handle(), ctx->ev_splat1.handle()));
+    acc.splat_ms += ms;
+    HIPCHK(hipEventElapsedTime(&ms, ctx->ev_latin0.handle(), ctx->ev_path0.handle()));
+    acc.latin_ms += ms;
+    return NART_OK;
+}
+
 // Render a bucket list into device tiles (list order); p is validated by the caller (check_params).
 // Shared by all entry points.  After the path kernel and the beauty's splat each batch runs the
 // frame plan's passes (frame_plan.h PassKind, which gives their order and why): per output of the pass, one
-// small kernel fills a record buffer -- ctx->d_L, which the beauty splat has consumed by then, so no
-// extra per-sample memory; for the cascade a second record buffer, a temporary of this call -- and the
-// same splat kernel takes it into that output's tiles.  The guide pass fills the records of both its
+// small kernel fills a record buffer (fill_records) -- ctx->d_L, which the beauty splat has consumed by
+// then, so no extra per-sample memory; for the cascade a second record buffer, a temporary of this call --
+// and the same splat kernel takes it into that output's tiles.  The guide pass fills the records of both its
 // outputs by one k_guide launch at its start (the normal record in a temporary of this call where
 // both are asked for).  times: the passes' device times are added.
 int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* ids, uint32_t n, const FrameTiles& out,
@@ -1488,45 +1422,27 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
     if (G && !ctx->d_light_group) return fail(ctx, NART_E_INVALID, "no light-group map was set");
     double group_ms = 0.0;
     const uint32_t tpx = g.tile_size * g.tile_size;
+    const BucketGrid grid{p->bucket_size, g.n_buckets_x, g.total_width, g.total_height, p->image_width, p->image_height};
     nart_render_stats acc;  // this call's share, added to *stats at the end
     std::memset(&acc, 0, sizeof(acc));
     uint64_t counted = 0;
-    uint32_t b0 = 0;
     ctx->sched = 0;
     std::vector<uint32_t> xy, base;
-    while (b0 < n) {
-        // gather a batch of buckets whose traced pixels fit the slot budget
-        xy.clear();
-        base.clear();
-        uint32_t b1 = b0;
-        while (b1 < n) {
-            uint32_t id = ids[b1];
-            uint32_t bx = id % g.n_buckets_x, by = id / g.n_buckets_x;
-            uint32_t x0 = p->bucket_size * bx, y0 = p->bucket_size * by;
-            uint32_t x1 = std::min(p->bucket_size * (bx + 1), g.total_width);   // render.cpp:163-168
-            uint32_t y1 = std::min(p->bucket_size * (by + 1), g.total_height);
-            size_t cnt = (size_t)(x1 - x0) * (y1 - y0);
-            if (b1 > b0 && xy.size() + cnt > limit) break;
-            base.push_back((uint32_t)xy.size());
-            for (uint32_t y = y0; y < y1; ++y)
-                for (uint32_t x = x0; x < x1; ++x) {
-                    xy.push_back(x | (y << 16));
-                    if (x < p->image_width && y < p->image_height) ++counted;
-                }
-            ++b1;
-        }
+    for (uint32_t b0 = 0, b1; b0 < n; b0 = b1) {
+        // gather a batch of buckets whose traced pixels fit the slot budget, and upload it
+        b1 = gather_batch(grid, ids, b0, n, limit, xy, base, counted);
         const uint32_t nslots = (uint32_t)xy.size(), nbk = b1 - b0;
-        acc.traced_samples += (uint64_t)nslots * p->spp;
+        const uint64_t ns = (uint64_t)nslots * p->spp;
+        acc.traced_samples += ns;
         rc = ensure(ctx, nslots, p->spp, nbk);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(ctx->d_slot_xy.as<uint32_t>(), xy.data(), (size_t)nslots * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ctx->d_bucket_ids.as<uint32_t>(), ids + b0, (size_t)nbk * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ctx->d_bucket_base.as<uint32_t>(), base.data(), (size_t)nbk * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_slot_table, dim3(nbk), dim3(256), 0, st, ctx->d_bucket_base.as<uint32_t>(), nbk, nslots, p->spp,
-                           ctx->d_slot_so.as<SlotSO>(), plan.skew);
-        ctx->rows_pixel_major = plan.skew;
+                           ctx->d_slot_so.as<SlotSO>(), plan.choice.skew);
+        ctx->rows_pixel_major = plan.choice.skew;
         RenderArgs ra = make_render_args(ctx, p, g, nslots, d_counters);
-        const uint64_t ns = (uint64_t)nslots * p->spp;
         if (G) {
             // the group records start at +0: every sample's owner lane accumulates into them
             if ((rc = reserve(ctx, group_records, ctx->device, (size_t)G * ns * sizeof(float4), "light-group records")))
@@ -1537,6 +1453,7 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             ra.Lgrp = group_records.as<float4>();
             ra.lgrp_stride = ns;
         }
+        // LatinSquare, path kernel, the beauty's splat
         HIPCHK(record(ctx->ev_latin0, st));
         rc = launch_latin(ctx, ra, st);
         if (rc) return rc;
@@ -1557,7 +1474,6 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         sa.n_buckets = nbk;
         if (beauty && (rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
         HIPCHK(record(ctx->ev_splat1, st));
-        const dim3 rec_grid((uint32_t)((ns + 255) / 256)), rec_block(256);
         hipEvent_t last = ctx->ev_splat1.handle();
         if (G) {
             // the path kernel's own group records, each into its output's tiles by the beauty's splat
@@ -1572,6 +1488,7 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             HIPCHK(record(ctx->ev_lg[1], st));
             last = ctx->ev_lg[1].handle();
         }
+        // the frame plan's passes
         for (uint32_t i = 0; i < frame.n_passes; ++i) {
             const PassKind pass = frame.passes[i];
             if (pass == PASS_CASCADE &&
@@ -1585,7 +1502,6 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
                 return rc;
             HIPCHK(record(ctx->ev_pass[pass][0], st));
             float4* const records = (pass == PASS_CASCADE ? layer_records : ctx->d_L).as<float4>();
-            sa.Lout = records;
             GuideArgs ga;
             if (pass == PASS_GUIDE) {
                 ga.max_follow = frame.ask.max_follow;
@@ -1596,53 +1512,7 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             for (uint32_t o = 0; o < frame.n_outputs; ++o) {
                 const FrameOutput& w = frame.outputs[o];
                 if (pass_of(w.kind) != pass) continue;
-                switch (w.kind) {
-                case OutputKind::Layer: {
-                    const CascadeLevels& lv = frame.ask.cascade;
-                    CascadeSplitArgs ca;
-                    ca.L = ctx->d_L.as<float4>();
-                    ca.out = records;
-                    ca.n = ns;
-                    ca.K = lv.K;
-                    ca.b_first = lv.b[0];
-                    ca.b_top = lv.b[lv.K - 1];
-                    ca.base_m1 = lv.base - 1.f;
-                    ca.j = w.index;
-                    ca.b_prev = ca.j > 0 ? lv.b[ca.j - 1] : 0.f;
-                    ca.b_cur = lv.b[ca.j];
-                    ca.b_next = ca.j + 1 < lv.K ? lv.b[ca.j + 1] : 0.f;
-                    hipLaunchKernelGGL(k_cascade_split, rec_grid, rec_block, 0, st, ca);
-                    break;
-                }
-                case OutputKind::Moment:
-                    hipLaunchKernelGGL(k_moment, rec_grid, rec_block, 0, st, ctx->d_L.as<float4>(), ns);
-                    break;
-                case OutputKind::Albedo:
-                case OutputKind::Normal:
-                    if ((rc = launch_aov(ctx, ra, w.kind == OutputKind::Albedo ? AOV_ALBEDO : AOV_NORMAL, records, st)))
-                        return rc;
-                    break;
-                case OutputKind::Plane: {
-                    MatteIdArgs ma;
-                    ma.hit = ctx->d_prim.as<uint32_t>();
-                    ma.tri_mesh = ctx->scene.tri_mesh;
-                    ma.meshes = ctx->scene.meshes;
-                    ma.out = ctx->d_L.as<float4>();
-                    ma.n = ns;
-                    ma.num_tris = ctx->scene.num_tris;
-                    ma.num_meshes = ctx->num_meshes;
-                    ma.kind = frame.ask.matte.kind;
-                    ma.n_ids = frame.ask.matte.n_ids;
-                    ma.q = w.index;
-                    hipLaunchKernelGGL(k_matte_ids, rec_grid, rec_block, 0, st, ma);
-                    break;
-                }
-                case OutputKind::GuideAlbedo: sa.Lout = ga.albedo; break;  // (filled at the start of the pass)
-                case OutputKind::GuideNormal: sa.Lout = ga.normal; break;
-                case OutputKind::Beauty:
-                case OutputKind::LightGroup: break;  // (no pass: pass_of)
-                }
-                HIPCHK(hipGetLastError());
+                if ((rc = fill_records(ctx, frame, w, ra, ga, records, ns, st, &sa.Lout))) return rc;
                 sa.tiles = out.tiles[o] + (size_t)b0 * tpx * 5;
                 if ((rc = launch_splat(ctx, plan, sa, nbk, st, pass == PASS_MOMENT))) return rc;
             }
@@ -1651,28 +1521,8 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         }
         // one stream: waiting for the last event recorded is waiting for all of them
         HIPCHK(hipEventSynchronize(last));
-        float ms = 0.f;
-        for (uint32_t i = 0; i < frame.n_passes && times; ++i) {
-            const PassKind pass = frame.passes[i];
-            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_pass[pass][0].handle(), ctx->ev_pass[pass][1].handle()));
-            times->ms[pass] += ms;
-        }
-        if (G) {
-            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_lg[0].handle(), ctx->ev_lg[1].handle()));
-            group_ms += ms;
-        }
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_path0.handle(), ctx->ev_path1.handle()));
-        acc.kernel_ms += ms;
-        if (ctx->primary_ran) {
-            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_path0.handle(), ctx->ev_primary.handle()));
-            acc.primary_ms += ms;
-        }
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_path1.handle(), ctx->ev_splat1.handle()));
-        acc.splat_ms += ms;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_latin0.handle(), ctx->ev_path0.handle()));
-        acc.latin_ms += ms;
+        if ((rc = read_batch_times(ctx, frame, G != 0, acc, times, group_ms))) return rc;
         if (beauty) ++acc.kernel_launches;
-        b0 = b1;
     }
     if (G) ctx->lg_ms[0] = group_ms;
     if (stats) {
@@ -2021,8 +1871,7 @@ int rect_slots(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t
     if ((uint64_t)x0 + w > g.total_width || (uint64_t)y0 + h > g.total_height)
         return fail(ctx, NART_E_INVALID, "rect out of range");
     std::vector<uint32_t> xy;
-    for (uint32_t y = y0; y < y0 + h; ++y)
-        for (uint32_t x = x0; x < x0 + w; ++x) xy.push_back(x | (y << 16));
+    append_rect(xy, x0, y0, w, h);
     const uint32_t n = (uint32_t)xy.size();
     if (int rc = ensure(ctx, n, p->spp, 1)) return rc;
     HIPCHK(hipMemcpy(ctx->d_slot_xy.as<uint32_t>(), xy.data(), (size_t)n * 4, hipMemcpyHostToDevice));
@@ -2848,9 +2697,9 @@ int nart_hip_splat_lut(float filter_width, float* cells4, uint32_t* n_cells, uin
     if (!cells4 || !n_cells || !b0) return NART_E_INVALID;
     float table[64 + 65];
     nart_filter_table(table);
-    std::vector<float4> lut;
+    std::vector<LutCell> lut;
     if (!splat_thresholds(filter_width, table + 64) || !splat_lut(table + 64, table, lut, *b0)) return NART_E_INVALID;
-    std::memcpy(cells4, lut.data(), lut.size() * sizeof(float4));
+    std::memcpy(cells4, lut.data(), lut.size() * sizeof(LutCell));
     *n_cells = (uint32_t)lut.size();
     return NART_OK;
 }

@@ -401,6 +401,17 @@ def test_latin_square_high_spp(gpu, glass_scene, glass_oracle, spp):
         assert _bits_equal(g, o), _report(g, o)
 
 
+def test_latin_square_three_kernels_80_lane_blocks(gpu, glass_scene, glass_oracle):
+    """The three-kernel LatinSquare with k_latin_perm in 80-lane blocks (spp > 640) on a record buffer sized
+    for the batch itself: a 16x12 rectangle at 1,024 spp, for which tests/test_latin_plan.py asserts that
+    plan_latin gives this form (test_latin_square_high_spp reaches it only through the buffer its first
+    rectangle leaves behind).  192 slots: three 80-lane blocks, the last partly filled."""
+    p = _params(glass_scene, 64, 64, 1024, bounces=1)
+    g = nart_amd.HipRenderer(glass_scene).render_samples(p, 20, 20, 16, 12)
+    o = glass_oracle.render_samples(p, 20, 20, 16, 12)
+    assert _bits_equal(g, o), _report(g, o)
+
+
 def test_latin_square_high_spp_frame(gpu, glass_scene, glass_oracle):
     """Bucket layout at 512 spp (LDS-index LatinSquare, sample-major buckets, splat): framebuffer."""
     p = _params(glass_scene, 24, 20, 512, bounces=2)
