@@ -707,6 +707,72 @@ int nart_hip_render_light_group_samples(nart_ctx* ctx, const nart_render_params*
                                         uint32_t h, float* out);
 int nart_hip_light_group_timings(const nart_ctx* ctx, double* splat_ms, double* mix_ms);
 
+/* Depth cuts: the image at lower bounce limits from a single render -- direct against indirect light,
+   what the third bounce still adds, the limit at which the picture stops changing.
+
+   Lowering p->bounces and rendering again does not give that split.  A pixel's samples share one RNG
+   stream (RenderTile seeds once per pixel and hands the same rng to every Li_alpha), so a render with
+   a lower limit draws fewer numbers per sample and traces different paths from each pixel's second
+   sample on: "beauty minus a direct-only render" carries the noise of two renders and goes negative.
+   The cut images of one render share their paths.
+
+   Inputs: cuts[n_cuts], 1 <= n_cuts <= NART_DEPTH_CUTS_MAX, strictly ascending, 1 <= cuts[j] <=
+   p->bounces.  Per camera sample and cut d the record is {L_d.r, L_d.g, L_d.b, alpha}:
+     1. L_d holds the bits of L in PathIntegrator::Li_alpha at the moment its loop counter `bounce`
+        first equals d;
+     2. if the loop ends sooner -- by a miss, the bounce == 0 escape with L = Le, scatteringPdf <= 0,
+        roulette, or the limit -- L_d is the final L;
+     3. a stepped-through lower-priority interface is a bounce without a term;
+     4. alpha is the sample's alpha.  It is settled at bounce 0: the dielectric list is empty at the
+        camera, so a first hit is always valid.
+   A cut image is these records through the call's unchanged splat and tile combine: a full nart_pixel
+   image whose alpha and filter_weight_sum have the beauty's bits.  cuts[j] == p->bounces gives the
+   beauty bit for bit.  Per sample the records never decrease with the depth (every term is
+   non-negative and float addition is monotone), and the differences of neighbouring cut images are the
+   light each range of bounces added.
+
+   Yardstick: L_d is the result of the same loop stopped at d, started from the same RNG state, so a
+   render with bounces = d agrees exactly where the start state agrees: the whole frame at spp = 1, and
+   the first sample of every pixel at any spp.  Later samples of a pixel are not comparable to any
+   render with another bounce limit.
+
+   Layers: layers(cut_images[K], beauty) gives K + 1 images over the totalW x totalH image; per pixel
+   and channel of r, g, b:  layer_0 = I_0;  layer_j = I_j - I_{j-1};  layer_K = beauty - I_{K-1};  each
+   one float32 subtraction.  Alpha and filter_weight_sum are copied from the beauty.  With cuts = {1}
+   the layers are direct and indirect light.
+
+   On the device a depth-cut build of the ray-queue path kernel (k_render_rq with DC: the generic
+   two-wave build without priority lanes or speculative pairs, as for light groups) writes the records
+   into K record arrays in global memory, 16 B per sample and cut (batches are sized for 28 + 16 K
+   bytes per sample): the record of the cut equal to the kernel's bounce count where a bounce's
+   EstimateDirect term has been added, every deeper cut where the sample ends.  The plan's splat then
+   runs once per cut, and k_depth_layers (device/depthcut.h) subtracts, one lane per pixel.  The
+   counter pass has no depth-cut build.
+
+   nart_hip_render_depth_cuts: cut_images receives the n_cuts images back to back (required); image, if
+   non-null, the beauty, with the bits nart_hip_render gives.  Multi-device contexts gather the cut
+   tiles with the beauty's gather.
+   nart_hip_depth_layers: cut_images holds n_cuts host images back to back, beauty one; out receives
+   the n_cuts + 1 layers back to back.
+   nart_hip_render_depth_cut_samples: debug / parity, as nart_hip_render_samples: the cut records of a
+   rect in total-image coordinates into out[j][((y-y0)*w + (x-x0))*spp + s][4].
+   nart_hip_depth_cut_timings: device times of the last call's cut splats and of the last layers run.
+   NART_E_INVALID: a null ctx, p, cuts, cut_images, beauty or out; n_cuts outside 1..8; cuts that are
+   not strictly ascending; a cut of 0 or above p->bounces; an empty or out-of-range rect.
+   NART_E_UNSUPPORTED: the volume integrator; variant 3 or a BVH deeper than the ray-queue kernel's LDS
+   holds (k_render has no depth-cut build).  An error leaves the context usable.  Not offered: depth
+   cuts together with adaptive sampling, the cascade, the mattes, AOVs, guides, the moment image, light
+   groups or the denoiser in one call (denoising direct and indirect light separately is the obvious
+   next step). */
+#define NART_DEPTH_CUTS_MAX 8u
+int nart_hip_render_depth_cuts(nart_ctx* ctx, const nart_render_params* p, const uint32_t* cuts, uint32_t n_cuts,
+                               nart_pixel* cut_images, nart_pixel* image, nart_render_stats* stats);
+int nart_hip_depth_layers(nart_ctx* ctx, const nart_render_params* p, uint32_t n_cuts, const nart_pixel* cut_images,
+                          const nart_pixel* beauty, nart_pixel* out);
+int nart_hip_render_depth_cut_samples(nart_ctx* ctx, const nart_render_params* p, const uint32_t* cuts, uint32_t n_cuts,
+                                      uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float* out);
+int nart_hip_depth_cut_timings(const nart_ctx* ctx, double* splat_ms, double* layers_ms);
+
 /* Multi-GPU building block: render the listed buckets (bucket id = by*nBucketsX + bx) into
    device-resident tiles d_tiles[i] (tile_size^2 nart_pixel each, same order as the list) on
    `stream` (a hipStream_t, may be 0).  bucket_ids is a host array.  Asynchronous w.r.t. the

@@ -82,6 +82,7 @@ FEATURES = {"lambert": 0x1, "specular": 0x2, "glass": 0x4, "glossy": 0x8, "plast
             "ring": 0x40, "environment": 0x80, "texture": 0x100, "normal_map": 0x200}
 FT_ALL = 0x3FF
 LIGHT_GROUPS_MAX = 8  # include/nart_hip.h NART_LIGHT_GROUPS_MAX
+DEPTH_CUTS_MAX = 8  # include/nart_hip.h NART_DEPTH_CUTS_MAX
 
 
 class RenderStats(ctypes.Structure):
@@ -251,6 +252,13 @@ _HIP_SIGS = {
                                                            ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                            ctypes.c_uint32, ctypes.c_uint32, _P]),
     "nart_hip_light_group_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_depth_cuts": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), _P, ctypes.c_uint32, _P, _P,
+                                                  ctypes.POINTER(RenderStats)]),
+    "nart_hip_depth_layers": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, _P, _P, _P]),
+    "nart_hip_render_depth_cut_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), _P, ctypes.c_uint32,
+                                                         ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                         ctypes.c_uint32, _P]),
+    "nart_hip_depth_cut_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_aov_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, ctypes.c_uint32,
                                                    ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "nart_hip_denoise_params_init": (None, [ctypes.POINTER(DenoiseParams)]),
@@ -898,6 +906,75 @@ class HipRenderer:
     def light_group_timings(self):
         """Device times of the last light-group call: {"splat_ms", "mix_ms"}."""
         return self._light_group_timings({})
+
+    def _depth_cut_timings(self, out):
+        s, m = ctypes.c_double(), ctypes.c_double()
+        self._check(self._lib.nart_hip_depth_cut_timings(self._ctx, ctypes.byref(s), ctypes.byref(m)))
+        out["splat_ms"], out["layers_ms"] = s.value, m.value
+        return out
+
+    @staticmethod
+    def _depth_cut_list(cuts):
+        """The cuts as the ABI takes them: a uint32 array (None: null) and its length K."""
+        if cuts is None:
+            return None, 0
+        c = np.ascontiguousarray(cuts, dtype=np.uint32).reshape(-1)
+        return c, len(c)
+
+    def render_depth_cuts(self, p, cuts, with_beauty=False, stats=None, n_cuts=None):
+        """The image at lower bounce limits from one render (nart_hip_render_depth_cuts; include/nart_hip.h
+        has the definition): cuts is a strictly ascending list of at most 8 bounce limits in 1..p.bounces
+        (n_cuts overrides its length as the ABI sees it).  Returns a dict with "cuts", a
+        (K, totalH, totalW, 5) float32 array -- image j holds every sample's radiance as it stood when
+        the path had made cuts[j] bounces, alpha and filter weight sum the beauty's; a cut equal to
+        p.bounces is the beauty; "beauty" (bit-identical to render()) if requested; "splat_ms", the
+        device time of the cut splats."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        c, K = self._depth_cut_list(cuts)
+        K = K if n_cuts is None else int(n_cuts)
+        out = {"cuts": np.empty((max(1, K),) + shape, np.float32)}
+        if with_beauty:
+            out["beauty"] = np.empty(shape, np.float32)
+        st = stats if stats is not None else RenderStats()
+        self._check(self._lib.nart_hip_render_depth_cuts(self._ctx, ctypes.byref(p), c.ctypes.data if c is not None else None,
+                                                         K, out["cuts"].ctypes.data,
+                                                         out["beauty"].ctypes.data if with_beauty else None,
+                                                         ctypes.byref(st)))
+        out["cuts"] = out["cuts"][:K]
+        out["splat_ms"] = self._depth_cut_timings({})["splat_ms"]
+        return out
+
+    def render_depth_cut_samples(self, p, cuts, x0, y0, w, h, n_cuts=None):
+        """Per-sample cut records of a rect in total-image coordinates
+        (nart_hip_render_depth_cut_samples): (K, h, w, spp, 4) float32 = {L_d.rgb, alpha}."""
+        c, K = self._depth_cut_list(cuts)
+        K = K if n_cuts is None else int(n_cuts)
+        out = np.empty((max(1, K), h, w, p.spp, 4), np.float32)
+        self._check(self._lib.nart_hip_render_depth_cut_samples(self._ctx, ctypes.byref(p),
+                                                                c.ctypes.data if c is not None else None, K, x0, y0, w, h,
+                                                                out.ctypes.data))
+        return out[:K]
+
+    def depth_layers(self, p, cut_images, beauty):
+        """The layers between cut images (nart_hip_depth_layers): cut_images a (K, totalH, totalW, 5)
+        float32 array as render_depth_cuts() returns it, beauty the same call's beauty.  Returns the
+        (K + 1, totalH, totalW, 5) float32 layers: the first cut, the float32 differences of neighbouring
+        cuts, the beauty minus the last cut; alpha and filter weight sum those of the beauty."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        im = np.ascontiguousarray(cut_images, dtype=np.float32)
+        b = np.ascontiguousarray(beauty, dtype=np.float32)
+        if im.ndim != 4 or im.shape[1:] != shape or b.shape != shape:
+            raise ValueError("depth_layers: images of shape %s and %s, expected (K,) + %s and %s" % (im.shape, b.shape, shape, shape))
+        K = im.shape[0]
+        out = np.empty((K + 1,) + shape, np.float32)
+        self._check(self._lib.nart_hip_depth_layers(self._ctx, ctypes.byref(p), K, im.ctypes.data, b.ctypes.data, out.ctypes.data))
+        return out
+
+    def depth_cut_timings(self):
+        """Device times of the last depth-cut call: {"splat_ms", "layers_ms"}."""
+        return self._depth_cut_timings({})
 
     def render_aov_samples(self, p, x0, y0, w, h):
         """Per-sample AOV records of a rect in total-image coordinates (nart_hip_render_aov_samples):

@@ -182,6 +182,10 @@ struct RenderArgs {
     const uint32_t* light_group = nullptr;
     float4* Lgrp = nullptr;
     unsigned long long lgrp_stride = 0;
+    // k_render_rq depth-cut build (DC; include/nart_hip.h, "Depth cuts"): Lgrp, lgrp_stride and n_groups
+    // serve as the record arrays of the n_groups cuts (no memset: every record is written in full);
+    // cuts[j], strictly ascending in 1..bounces, is the bounce count of array j
+    uint32_t cuts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 // xorshift32 state after n draws (rng.h:38-40 applied n times)
@@ -1131,9 +1135,18 @@ __global__ __launch_bounds__(256) void k_aov(DScene S, RenderArgs A, const uint3
 // with plain loads and stores and cost no register; the group of the light a bounce drew waits for
 // the shadow rays in the unused fourth word of the lane's result entry.  end_sample gives every
 // group record the sample's alpha.
-template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false>
+// DC (with FT_ALL, WV = 2, PR = false, not with LG): the depth-cut build (include/nart_hip.h, "Depth
+// cuts").  `bounce` is incremented where a hit is shaded, and the EstimateDirect term of that hit
+// enters L once its shadow rays are back, so where step 1 has added the term (or found none owed: a
+// stepped-through interface) L is the reference's L at the moment its loop counter equals `bounce`:
+// the record of the cut equal to `bounce` takes it there.  Where the sample ends, every cut >= bounce
+// takes the final L and every cut the alpha.  The owning lane is the only writer of its records, as
+// for LG, and every record is written in full, so the arrays need not start at zero.
+template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false, bool DC = false>
 __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : NART_RENDER_WAVES)) void k_render_rq(DScene S, RenderArgs A) {
     static_assert(!LG || (FM == FT_ALL && WV == 2 && !PR && !COUNT), "light groups: the generic two-wave build, no priority lanes");
+    static_assert(!DC || (FM == FT_ALL && WV == 2 && !PR && !COUNT), "depth cuts: the generic two-wave build, no priority lanes");
+    static_assert(!(LG && DC), "light groups and depth cuts share the record arrays: one or the other");
     // priority lanes, speculative groups and raised issue priority: small-shard schedules only
     const uint32_t rq_prio = PR ? A.rq_prio : 0u, rq_pairs = PR ? A.rq_pairs : 0u;
     // a lean build whose shading needs more than Lambert lobes and area lights fits 168 VGPRs only
@@ -1309,6 +1322,12 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
     };
     auto lg_set = [&](uint32_t g, f3 t) { *lg_rec(g) = make_float4(t.x, t.y, t.z, 0.f); };
     uint32_t ed_group = 0;  // LG: the group of the light the bounce shaded in this phase drew
+    // DC: L now holds the terms of `bounce` bounces: the record of the cut equal to `bounce`, if any
+    auto dc_mark = [&]() {
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j)
+            if (j < A.n_groups && A.cuts[j] == bounce) *lg_rec(j) = make_float4(L.x, L.y, L.z, alpha);
+    };
     auto end_sample = [&](float4 v) {
         if (pm) {
             jres = v;
@@ -1317,6 +1336,15 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
         } else {
             if (LG)
                 for (uint32_t g = 0; g < A.n_groups; ++g) lg_rec(g)->w = v.w;
+            if (DC) {
+                // the loop ended at `bounce`: deeper cuts hold the final L; shallower ones have theirs
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j)
+                    if (j < A.n_groups) {
+                        if (A.cuts[j] >= bounce) *lg_rec(j) = v;
+                        else lg_rec(j)->w = v.w;
+                    }
+            }
             A.Lout[soff + (uint64_t)s * sstr] = v;
             if (COUNT) count_sample();
             ++s;
@@ -1361,6 +1389,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
                     L = add(L, term);
                     if (LG) lg_add(r.w, term);
                 }
+                if (DC) dc_mark();  // (a stepped-through interface too: a bounce without a term)
                 if (ext_pending && r.x != NO_HIT) {
                     need_shade = true;
                     hitg = r.x;

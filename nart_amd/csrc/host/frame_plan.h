@@ -14,9 +14,10 @@ namespace nd {
 constexpr uint32_t FRAME_MAX_LAYERS = 8, FRAME_MAX_PLANES = 8, FRAME_MAX_MATTE_IDS = 4 * FRAME_MAX_PLANES;
 // beauty, two first-hit AOVs, moment, layers, planes, two followed guides (a frame has layers or
 // planes, and first-hit AOVs or followed guides: at most twelve; a light-group frame the beauty and
-// its groups: at most nine)
+// its groups, a depth-cut frame the beauty and its cuts: at most nine)
 constexpr uint32_t FRAME_MAX_OUTPUTS = 4 + FRAME_MAX_LAYERS + FRAME_MAX_PLANES + 2;
 constexpr uint32_t FRAME_MAX_LIGHT_GROUPS = 8;  // include/nart_hip.h NART_LIGHT_GROUPS_MAX
+constexpr uint32_t FRAME_MAX_DEPTH_CUTS = 8;    // include/nart_hip.h NART_DEPTH_CUTS_MAX
 constexpr uint32_t FRAME_MAX_FOLLOW = 10;  // include/nart_hip.h NART_GUIDE_MAX_FOLLOW
 
 // The firefly cascade's levels (include/nart_hip.h, "Firefly cascade"): layer j takes the share of
@@ -45,12 +46,15 @@ struct FrameAsk {  // what the caller asks for
     bool guide[2] = {false, false};  // followed guides (include/nart_hip.h, "Followed guides"): albedo, normal
     uint32_t max_follow = 0;         // delta interfaces a guide chain follows, 0..FRAME_MAX_FOLLOW
     uint32_t light_groups = 0;       // G light groups (include/nart_hip.h, "Light groups"), 0: off
+    uint32_t depth_cuts = 0;         // K depth cuts (include/nart_hip.h, "Depth cuts"), 0: off
     explicit FrameAsk(uint32_t integrator_) : integrator(integrator_) {}
 };
 
 // One tile buffer (and image) of a render; index: j of cascade layer j, q of matte plane q, g of light
-// group g, else 0.
-enum class OutputKind : uint32_t { Beauty, Albedo, Normal, Moment, Layer, Plane, GuideAlbedo, GuideNormal, LightGroup };
+// group g, j of depth cut j, else 0.
+enum class OutputKind : uint32_t {
+    Beauty, Albedo, Normal, Moment, Layer, Plane, GuideAlbedo, GuideNormal, LightGroup, DepthCut
+};
 struct FrameOutput { OutputKind kind = OutputKind::Beauty; uint32_t index = 0; };
 
 // The passes of a batch after the path kernel and the beauty's splat, in the order they must run.
@@ -63,11 +67,13 @@ struct FrameOutput { OutputKind kind = OutputKind::Beauty; uint32_t index = 0; }
 //   PASS_GUIDE      k_guide traces every sample's chain once: the albedo record overwrites d_L, the
 //                   normal record goes to a second record buffer where both are asked for.
 enum PassKind : uint32_t { PASS_CASCADE, PASS_MOMENT, PASS_FIRST_HIT, PASS_MATTE, PASS_GUIDE, N_PASSES };
-// The pass that fills an output's records, by OutputKind; N_PASSES: the beauty and the light groups,
-// the path kernel's own.
+// The pass that fills an output's records, by OutputKind; N_PASSES: the beauty, the light groups
+// and the depth cuts, the path kernel's own.
 constexpr PassKind PASS_OF[8] = {N_PASSES,     PASS_FIRST_HIT, PASS_FIRST_HIT, PASS_MOMENT,
                                  PASS_CASCADE, PASS_MATTE,     PASS_GUIDE,     PASS_GUIDE};
-inline PassKind pass_of(OutputKind k) { return k == OutputKind::LightGroup ? N_PASSES : PASS_OF[(uint32_t)k]; }
+inline PassKind pass_of(OutputKind k) {
+    return k == OutputKind::LightGroup || k == OutputKind::DepthCut ? N_PASSES : PASS_OF[(uint32_t)k];
+}
 
 struct FramePlan {
     int code = NART_OK;  // not NART_OK: the first broken rule and its message; nothing else is set
@@ -75,14 +81,14 @@ struct FramePlan {
     FrameAsk ask{NART_INTEGRATOR_PATH};
     // Tile buffers and images in delivery order: beauty, albedo, normal, moment, then the layers or
     // the planes ascending, then the followed guides; a light-group frame: the beauty, then the groups
-    // ascending.  On-device delivery lays the images out back to back in this order.
+    // ascending; a depth-cut frame: the beauty, then the cuts ascending.  On-device delivery lays the images out back to back in this order.
     FrameOutput outputs[FRAME_MAX_OUTPUTS];
     uint32_t n_outputs = 0;
     PassKind passes[N_PASSES] = {};  // the passes that run, ascending
     uint32_t n_passes = 0;
     bool path_kernel = false;   // false: camera rays only (first-hit outputs without the beauty)
     // per-sample record memory beyond d_L (batch_slot_limit): the cascade's buffer, the second guide
-    // record's where both guides are asked for, or one record per light group
+    // record's where both guides are asked for, or one record per light group or depth cut
     uint32_t record_bytes = 0;
 
     int find(OutputKind kind, uint32_t index = 0) const {  // position in the list, or -1
@@ -138,6 +144,20 @@ inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
         why = "light groups need a uniform render: not adaptive sampling";
     } else if (a.light_groups && (a.cascade.K || a.matte.on || a.aov[0] || a.aov[1] || guides || a.moment)) {
         why = "light groups are not rendered with the cascade, the mattes, AOVs, guides or the moment image in one call";
+    } else if (a.depth_cuts > FRAME_MAX_DEPTH_CUTS) {
+        code = NART_E_INVALID;
+        why = "at most 8 depth cuts are supported";
+    } else if (a.depth_cuts && !a.beauty) {
+        code = NART_E_INVALID;
+        why = "depth cuts need the path kernel (the beauty)";
+    } else if (a.depth_cuts && a.integrator == NART_INTEGRATOR_VOLUME) {
+        why = "depth cuts need the path integrator: the volume integrator has no depth-cut build";
+    } else if (a.depth_cuts && a.adaptive) {
+        why = "depth cuts need a uniform render: not adaptive sampling";
+    } else if (a.depth_cuts &&
+               (a.cascade.K || a.matte.on || a.aov[0] || a.aov[1] || guides || a.moment || a.light_groups)) {
+        why = "depth cuts are not rendered with the cascade, the mattes, AOVs, guides, the moment image or light groups in "
+              "one call";
     }
     if (!why.empty()) {
         plan.code = code;
@@ -155,6 +175,7 @@ inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
     if (a.guide[0]) add(OutputKind::GuideAlbedo, 0);
     if (a.guide[1]) add(OutputKind::GuideNormal, 0);
     for (uint32_t g = 0; g < a.light_groups; ++g) add(OutputKind::LightGroup, g);
+    for (uint32_t j = 0; j < a.depth_cuts; ++j) add(OutputKind::DepthCut, j);
     // An adaptive render estimates a bucket's error from its moment tiles: every level runs the moment
     // pass, wanted or not (adaptive_level_ask).
     bool runs[N_PASSES + 1] = {};
@@ -165,6 +186,7 @@ inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
     plan.path_kernel = a.beauty;
     plan.record_bytes = (a.cascade.K || (a.guide[0] && a.guide[1])) ? 16 : 0;  // one float4 per sample
     if (a.light_groups) plan.record_bytes = 16 * a.light_groups;              // and per group
+    if (a.depth_cuts) plan.record_bytes = 16 * a.depth_cuts;                  // or per cut
     return plan;
 }
 

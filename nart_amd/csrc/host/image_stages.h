@@ -1,7 +1,7 @@
 // The stages over whole images that follow a frame -- the denoiser, the firefly cascade's reweighting,
-// the ID mattes' ranking and extraction, the light groups' mix -- and the frames of the first-hit AOVs,
-// the followed guides and the light groups; included by render.hip after render_frame.  Every stage has
-// the same two layers:
+// the ID mattes' ranking and extraction, the light groups' mix, the depth cuts' layers -- and the frames
+// of the first-hit AOVs, the followed guides, the light groups and the depth cuts; included by render.hip
+// after render_frame.  Every stage has the same two layers:
 //   X_device   its kernels over images of a view (Images, render.hip), named by their positions in it;
 //   X_host     host images through the first device: upload, X_device, download (host_stage);
 //   render_X   a frame into device images of the first device, X_device over them there, and what the
@@ -446,6 +446,53 @@ int render_light_groups(nart_ctx* ctx, const nart_render_params* p, const uint32
     for (uint32_t g = 0; g < G; ++g) rq.dst[plan.find(OutputKind::LightGroup, g)] = groups + g * ImageLayout(p).img_floats / 5;
     const int rc = render_frame(ctx, p, plan, rq, stats);
     for (const nart_ctx* c : ctx->subs) ctx->lg_ms[0] = std::max(ctx->lg_ms[0], c->lg_ms[0]);  // the slowest device's
+    return rc;
+}
+
+// ---------------------------------------------------------------- depth cuts (device/depthcut.h)
+// The layers over images of the view: the K cut images back to back, the beauty, the K + 1 layers out;
+// synchronous.  The time goes to the view's context (dc_ms[1]).
+int depth_layers_device(const Images& v, uint32_t K, int cuts, int beauty, int out, hipStream_t st) {
+    nart_ctx* ctx = v.ctx;
+    DepthLayersArgs a;
+    a.cuts = v.at(cuts);
+    a.beauty = v.at(beauty);
+    a.out = v.at(out);
+    v.layout.fill(a);
+    a.K = K;
+    return timed(ctx, ctx->ev_layers, st, &ctx->dc_ms[1], [&]() -> int {
+        const uint64_t n = (uint64_t)a.totalW * a.totalH;  // every pixel, the border too
+        hipLaunchKernelGGL(k_depth_layers, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
+        HIPCHK(hipGetLastError());
+        return NART_OK;
+    });
+}
+
+// nart_hip_depth_layers.
+int depth_layers_host(nart_ctx* ctx, const nart_render_params* p, uint32_t K, const nart_pixel* cuts, const nart_pixel* beauty,
+                      nart_pixel* out) {
+    first_device(ctx)->dc_ms[1] = 0.0;  // (the layers' time is kept where they run)
+    if (!ctx->subs.empty()) return forwarded(ctx, depth_layers_host(first_device(ctx), p, K, cuts, beauty, out));
+    Buf imgs;  // the cut images, the beauty, the layers; freed on return
+    return host_stage(ctx, p, imgs, "depth-cut images", {{cuts, K}, {beauty, 1}}, out, K + 1,
+                      [&](const Images& v) { return depth_layers_device(v, K, 0, (int)K, (int)K + 1, 0); });
+}
+
+// nart_hip_render_depth_cuts: the beauty and the K cut images.  cuts: validated by the caller.
+int render_depth_cuts(nart_ctx* ctx, const nart_render_params* p, const uint32_t* cuts, uint32_t K, nart_pixel* cut_images,
+                      nart_pixel* image, nart_render_stats* stats) {
+    ctx->dc_ms[0] = 0.0;
+    FrameAsk ask(p->integrator);
+    ask.depth_cuts = K;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    if (plan.code) return fail(ctx, plan.code, plan.message);  // (before anything is allocated)
+    set_depth_cuts(ctx, cuts, K);
+    TileGrowthGuard guard(ctx);
+    FrameRequest rq;
+    rq.to_host(plan, OutputKind::Beauty, image);
+    for (uint32_t j = 0; j < K; ++j) rq.dst[plan.find(OutputKind::DepthCut, j)] = cut_images + j * ImageLayout(p).img_floats / 5;
+    const int rc = render_frame(ctx, p, plan, rq, stats);
+    for (const nart_ctx* c : ctx->subs) ctx->dc_ms[0] = std::max(ctx->dc_ms[0], c->dc_ms[0]);  // the slowest device's
     return rc;
 }
 

@@ -50,6 +50,14 @@
 //                   --adaptive, --robust, --mattes, --aovs, --denoise or --follow-specular: an error
 //   --light-gains k0,k1,..  with --light-groups: one gain per group; also write <out>.mix.exr, the sum of
 //                   the group images scaled by their gains (nart_hip_light_mix)
+//   --depth-cuts d0,d1,..  also write every session's image at the bounce limits d0 < d1 < .. (at most 8,
+//                   each in 1..bounces) from the one render (nart_hip_render_depth_cuts) to
+//                   <out>.depth.NN.exr, NN the cut; <out>.exr is the same call's beauty.  Not offered
+//                   together with --light-groups, --adaptive, --robust, --mattes, --aovs, --denoise or
+//                   --follow-specular: an error
+//   --depth-layers  with --depth-cuts: also write <out>.layer.00.exr ... <out>.layer.0K.exr, the light each
+//                   range of bounces added (nart_hip_depth_layers): the first cut, the differences of
+//                   neighbouring cuts, the beauty minus the last cut
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -347,6 +355,37 @@ int main(int argc, char* argv[]) {
             pos = c + 1;
         }
     }
+    // --depth-cuts d0,d1,..  and  --depth-layers
+    const char* cuts_arg = nullptr;
+    if (!take_value_flag(args, "--depth-cuts", cuts_arg)) return EXIT_FAILURE;
+    const bool depth_layers = take_flag(args, "--depth-layers");
+    const bool depth_cuts = cuts_arg != nullptr;
+    if (depth_layers && !depth_cuts) {
+        std::fprintf(stderr, "Error: --depth-layers subtracts the depth cuts and needs --depth-cuts\n");
+        return EXIT_FAILURE;
+    }
+    if (depth_cuts && (light_groups || adaptive_arg || robust || mattes || aovs || denoise || follow)) {
+        std::fprintf(stderr, "Error: --depth-cuts is not offered together with --light-groups, --adaptive, --robust, --mattes, "
+                             "--aovs, --denoise or --follow-specular\n");
+        return EXIT_FAILURE;
+    }
+    std::vector<uint32_t> cuts;
+    if (depth_cuts) {
+        const std::string s(cuts_arg);
+        for (size_t pos = 0; pos <= s.size();) {
+            size_t c = s.find(',', pos);
+            if (c == std::string::npos) c = s.size();
+            int v = 0;
+            if (!parse_int(s.substr(pos, c - pos).c_str(), v) || v < 1 || (!cuts.empty() && (uint32_t)v <= cuts.back()) ||
+                cuts.size() == NART_DEPTH_CUTS_MAX) {
+                std::fprintf(stderr, "Error: --depth-cuts %s: a comma-separated, strictly ascending list of at most 8 bounce "
+                                     "limits, each at least 1\n", cuts_arg);
+                return EXIT_FAILURE;
+            }
+            cuts.push_back((uint32_t)v);
+            pos = c + 1;
+        }
+    }
     nart_adaptive_params ap;
     nart_hip_adaptive_params_init(&ap);
     if (adaptive) {
@@ -387,6 +426,11 @@ int main(int argc, char* argv[]) {
     }
     std::vector<nart_render_params> sessions(n);
     nart_load_sessions(args[1], &params, sessions.data(), n);
+    for (const nart_render_params& p : sessions)
+        if (depth_cuts && cuts.back() > p.bounces) {
+            std::fprintf(stderr, "Error: --depth-cuts %s: a session's bounce limit is %u\n", cuts_arg, p.bounces);
+            return EXIT_FAILURE;
+        }
     nart_ctx* ctx = nullptr;
     int rc = nart_hip_create_multi(nart_scene_blob_of(scene), devices.data(), (int)devices.size(), &ctx);
     if (rc != NART_OK) {
@@ -427,8 +471,15 @@ int main(int argc, char* argv[]) {
         const bool mattes_after = mattes && (aovs || denoise);
         if (denoise) denoised.resize(image.size());
         std::vector<uint32_t> bucket_spp;
-        std::vector<nart_pixel> group_imgs, mix_img;
-        if (light_groups) {
+        std::vector<nart_pixel> group_imgs, mix_img, cut_imgs, layer_imgs;
+        if (depth_cuts) {
+            cut_imgs.resize(cuts.size() * image.size());
+            rc = nart_hip_render_depth_cuts(ctx, &p, cuts.data(), (uint32_t)cuts.size(), cut_imgs.data(), image.data(), nullptr);
+            if (rc == NART_OK && depth_layers) {
+                layer_imgs.resize((cuts.size() + 1) * image.size());
+                rc = nart_hip_depth_layers(ctx, &p, (uint32_t)cuts.size(), cut_imgs.data(), image.data(), layer_imgs.data());
+            }
+        } else if (light_groups) {
             group_imgs.resize((size_t)n_groups * image.size());
             rc = nart_hip_render_light_groups(ctx, &p, group_of_light.data(), (uint32_t)group_of_light.size(), n_groups,
                                               group_imgs.data(), image.data(), nullptr);
@@ -544,6 +595,11 @@ int main(int argc, char* argv[]) {
         for (uint32_t i = 0; i < (light_groups ? n_groups : 0u); ++i)
             extra.push_back({".light.0" + std::to_string(i) + ".exr", group_imgs.data() + (size_t)i * image.size()});
         if (light_groups && gains_arg) extra.push_back({".mix.exr", mix_img.data()});
+        auto two = [](uint32_t v) { return (v < 10 ? "0" : "") + std::to_string(v); };
+        for (size_t i = 0; depth_cuts && i < cuts.size(); ++i)
+            extra.push_back({".depth." + two(cuts[i]) + ".exr", cut_imgs.data() + i * image.size()});
+        for (size_t i = 0; depth_layers && i <= cuts.size(); ++i)
+            extra.push_back({".layer." + two((uint32_t)i) + ".exr", layer_imgs.data() + i * image.size()});
         std::vector<nart_pixel> spp_img;
         if (adaptive) {
             // pixel (x, y) of the cropped image was traced by bucket (x / B, y / B)

@@ -117,6 +117,19 @@ inline const char* light_mix_error(uint32_t n_groups, const float* gains, const 
     return nullptr;
 }
 
+// ---------------------------------------------------------------- depth cuts
+// The cuts of a depth-cut render: cuts[n_cuts], strictly ascending, each in 1..bounces.
+inline const char* depth_cuts_error(const uint32_t* cuts, uint32_t n_cuts, uint32_t bounces) {
+    if (n_cuts < 1 || n_cuts > NART_DEPTH_CUTS_MAX) return "n_cuts must be 1..8";
+    if (!cuts) return "the depth cuts are required";
+    for (uint32_t j = 0; j < n_cuts; ++j) {
+        if (cuts[j] < 1) return "a depth cut must be at least 1";
+        if (cuts[j] > bounces) return "a depth cut must not exceed the bounce limit";
+        if (j && cuts[j] <= cuts[j - 1]) return "depth cuts must be strictly ascending";
+    }
+    return nullptr;
+}
+
 // ---------------------------------------------------------------- what the stages need of p
 // What the stages over whole images (denoiser, reweighting, ranking) need of p without check_params.
 inline const char* check_image_size(const nart_render_params* p) {

@@ -20,6 +20,7 @@
 #include "device/adaptive.h"
 #include "device/cascade.h"
 #include "device/denoise.h"
+#include "device/depthcut.h"
 #include "device/guide.h"
 #include "device/lbvh.h"
 #include "device/lightgroup.h"
@@ -120,6 +121,12 @@ struct nart_ctx {
     Buf d_light_group;
     Event ev_lg[2], ev_mix[2];
     double lg_ms[2] = {0.0, 0.0};
+    // depth cuts: the cuts of the call (set_depth_cuts; they travel in the kernel arguments), n_depth_cuts
+    // of them; their splats share ev_lg; events around the layers (depth_layers_device); the last call's
+    // times: cut splats ([0] on the caller's context), layers ([1] on the first device's)
+    uint32_t depth_cuts[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_depth_cuts = 0;
+    Event ev_layers[2];
+    double dc_ms[2] = {0.0, 0.0};
     // denoiser (denoise_device): work buffers over the cropped image, the four device images of
     // nart_hip_denoise / nart_hip_render_denoised (five with the moment image), events between its
     // kernels, the last run's times
@@ -884,10 +891,10 @@ void launch_primary(nart_ctx* ctx, const RenderArgs& pa, hipStream_t st) {
 // The template parameters are the kernel builds of `B.id` (dispatch_megakernel's table), `B` their LDS
 // layout (host/path_build.h plan_build); host/path_schedule.h plan_path decides the rest.
 // resident_k: resident blocks of k_render (dispatch_megakernel's occupancy query).
-template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false>
+template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false, bool DC = false>
 int launch_render(nart_ctx* ctx, const RenderArgs& a_in, const PathBuild& B, uint32_t resident_k, hipStream_t st) {
     auto kern = k_render<EXT, COUNT, ENV>;
-    auto kern_rq = k_render_rq<EXT, COUNT, ENV, FM, WV, PR, LG>;
+    auto kern_rq = k_render_rq<EXT, COUNT, ENV, FM, WV, PR, LG, DC>;
     const uint32_t RQB = B.rq_block;
     RenderArgs a = a_in;
     int rc = EXT ? ensure_ilist(ctx, a) : NART_OK;
@@ -937,6 +944,7 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, const PathBuild& B, uin
 
     if (!rq) {
         if (LG) return fail(ctx, NART_E_UNSUPPORTED, "light groups need the ray-queue kernel");  // (plan_build refuses it first)
+        if (DC) return fail(ctx, NART_E_UNSUPPORTED, "depth cuts need the ray-queue kernel");    // (likewise)
         hipLaunchKernelGGL(kern, dim3(plan.blocks), dim3(256), lds, st, ctx->scene, b);
         HIPCHK(hipGetLastError());
         return NART_OK;
@@ -963,9 +971,9 @@ struct BuildRow {
     BuildId id;
     RenderLauncher launch;
 };
-template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false>
+template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false, bool DC = false>
 BuildRow build_row() {
-    return {BuildId{EXT, COUNT, ENV, FM, WV, PR, LG}, launch_render<EXT, COUNT, ENV, FM, WV, PR, LG>};
+    return {BuildId{EXT, COUNT, ENV, FM, WV, PR, LG, DC}, launch_render<EXT, COUNT, ENV, FM, WV, PR, LG, DC>};
 }
 
 int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
@@ -974,7 +982,8 @@ int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
     in.has_env = ctx->has_env;
     in.specialize = !ctx->specialize ? Specialize::Off : (ctx->lean ? Specialize::Lean : Specialize::On);
     in.counters = ctx->counters;
-    in.light_groups = a.n_groups != 0;
+    in.depth_cuts = a.n_groups != 0 && a.cuts[0] != 0;  // (the record arrays are the cuts' where cuts are given)
+    in.light_groups = a.n_groups != 0 && !in.depth_cuts;
     in.bounces = a.bounces;
     in.variant = ctx->variant;
     in.stack_depth = ctx->stack_depth;
@@ -989,8 +998,8 @@ int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
     read_build_knobs(in);
     const PathBuild B = plan_build(in);
     if (B.error) return fail(ctx, B.unsupported ? NART_E_UNSUPPORTED : NART_E_INVALID, B.error);
-    // every build plan_build can name (tests/test_path_build.py and test_path_build_lights.py hold the same
-    // list; new rows go at the end).  The compiler emits
+    // every build plan_build can name (tests/test_path_build.py, test_path_build_lights.py and
+    // test_path_build_depth.py hold the same list; new rows go at the end).  The compiler emits
     // the kernels in the order of the rows: keep it, and the gfx950 code object stays byte for byte the same
     static const BuildRow builds[] = {
         build_row<false, false, false, FM_DIFFUSE, 3, false>(),  // scene-specialised: lean, two waves per SIMD
@@ -1011,6 +1020,10 @@ int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
         build_row<true, false, true, FT_ALL, 2, false, true>(),
         build_row<false, false, false, FT_ALL, 2, false, true>(),
         build_row<true, false, false, FT_ALL, 2, false, true>(),
+        build_row<false, false, true, FT_ALL, 2, false, false, true>(),  // depth cuts: EXT x ENV
+        build_row<true, false, true, FT_ALL, 2, false, false, true>(),
+        build_row<false, false, false, FT_ALL, 2, false, false, true>(),
+        build_row<true, false, false, FT_ALL, 2, false, false, true>(),
     };
     for (const BuildRow& row : builds)
         if (row.id == B.id) return row.launch(ctx, a, B, in.resident_k, st);
@@ -1106,7 +1119,8 @@ int launch_latin(nart_ctx* ctx, const RenderArgs& ra, hipStream_t st) {
 // plan.outputs[i], laid out like the beauty tiles, in the order of the bucket list rendered.
 static_assert(FRAME_MAX_LAYERS == CASCADE_MAX_LAYERS && FRAME_MAX_PLANES == MATTE_MAX_PLANES &&
                   FRAME_MAX_MATTE_IDS == MATTE_MAX_IDS && FRAME_MAX_LIGHT_GROUPS == LIGHT_GROUPS_MAX &&
-                  FRAME_MAX_LIGHT_GROUPS == NART_LIGHT_GROUPS_MAX,
+                  FRAME_MAX_LIGHT_GROUPS == NART_LIGHT_GROUPS_MAX && FRAME_MAX_DEPTH_CUTS == DEPTH_CUTS_MAX &&
+                  FRAME_MAX_DEPTH_CUTS == NART_DEPTH_CUTS_MAX && sizeof(RenderArgs::cuts) == 4 * DEPTH_CUTS_MAX,
               "frame_plan.h restates the device headers' limits");
 struct FrameTiles {
     FramePlan plan;
@@ -1357,14 +1371,15 @@ int fill_records(nart_ctx* ctx, const FramePlan& frame, const FrameOutput& w, co
     case OutputKind::GuideAlbedo: *filled = ga.albedo; break;
     case OutputKind::GuideNormal: *filled = ga.normal; break;
     case OutputKind::Beauty:
-    case OutputKind::LightGroup: break;  // (no pass: pass_of)
+    case OutputKind::LightGroup:
+    case OutputKind::DepthCut: break;  // (no pass: pass_of)
     }
     HIPCHK(hipGetLastError());
     return NART_OK;
 }
 
 // The device times of a batch from its event pairs, once the last event recorded has been waited for:
-// the passes' into `times`, the light groups' splats into group_ms, the rest into acc.
+// the passes' into `times`, the light groups' or depth cuts' splats into group_ms, the rest into acc.
 int read_batch_times(nart_ctx* ctx, const FramePlan& frame, bool groups, nart_render_stats& acc, PassTimes* times,
                      double& group_ms) {
     float ms = 0.f;
@@ -1417,9 +1432,13 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
     const size_t limit = batch_slot_limit(ctx, p->spp, frame.record_bytes);
     Buf layer_records;  // cascade: the second per-sample record buffer, 16 B per sample; freed on return
     Buf guide_records;  // both followed guides: the normal records, likewise
-    Buf group_records;  // light groups: G record arrays of the batch's samples, likewise
+    Buf group_records;  // light groups or depth cuts: R record arrays of the batch's samples, likewise
     const uint32_t G = beauty ? frame.ask.light_groups : 0u;
     if (G && !ctx->d_light_group) return fail(ctx, NART_E_INVALID, "no light-group map was set");
+    // depth cuts: the K cuts of the call (set_depth_cuts); they share the groups' arrays, splats and events
+    const uint32_t K = beauty && !G ? frame.ask.depth_cuts : 0u;
+    if (K && ctx->n_depth_cuts != K) return fail(ctx, NART_E_INVALID, "no depth cuts were set");
+    const uint32_t R = G ? G : K;
     double group_ms = 0.0;
     const uint32_t tpx = g.tile_size * g.tile_size;
     const BucketGrid grid{p->bucket_size, g.n_buckets_x, g.total_width, g.total_height, p->image_width, p->image_height};
@@ -1443,16 +1462,21 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
                            ctx->d_slot_so.as<SlotSO>(), plan.choice.skew);
         ctx->rows_pixel_major = plan.choice.skew;
         RenderArgs ra = make_render_args(ctx, p, g, nslots, d_counters);
-        if (G) {
-            // the group records start at +0: every sample's owner lane accumulates into them
-            if ((rc = reserve(ctx, group_records, ctx->device, (size_t)G * ns * sizeof(float4), "light-group records")))
+        if (R) {
+            if ((rc = reserve(ctx, group_records, ctx->device, (size_t)R * ns * sizeof(float4),
+                              G ? "light-group records" : "depth-cut records")))
                 return rc;
-            HIPCHK(hipMemsetAsync(group_records.as<void>(), 0, (size_t)G * ns * sizeof(float4), st));
-            ra.n_groups = G;
-            ra.light_group = ctx->d_light_group.as<uint32_t>();
+            ra.n_groups = R;
             ra.Lgrp = group_records.as<float4>();
             ra.lgrp_stride = ns;
         }
+        if (G) {
+            // the group records start at +0: every sample's owner lane accumulates into them
+            HIPCHK(hipMemsetAsync(group_records.as<void>(), 0, (size_t)G * ns * sizeof(float4), st));
+            ra.light_group = ctx->d_light_group.as<uint32_t>();
+        }
+        // (the cut records need no memset: the owner lane writes every one in full)
+        for (uint32_t j = 0; j < K; ++j) ra.cuts[j] = ctx->depth_cuts[j];
         // LatinSquare, path kernel, the beauty's splat
         HIPCHK(record(ctx->ev_latin0, st));
         rc = launch_latin(ctx, ra, st);
@@ -1475,12 +1499,12 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         if (beauty && (rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
         HIPCHK(record(ctx->ev_splat1, st));
         hipEvent_t last = ctx->ev_splat1.handle();
-        if (G) {
-            // the path kernel's own group records, each into its output's tiles by the beauty's splat
+        if (R) {
+            // the path kernel's own group or cut records, each into its output's tiles by the beauty's splat
             HIPCHK(record(ctx->ev_lg[0], st));
             for (uint32_t o = 0; o < frame.n_outputs; ++o) {
                 const FrameOutput& w = frame.outputs[o];
-                if (w.kind != OutputKind::LightGroup) continue;
+                if (w.kind != (G ? OutputKind::LightGroup : OutputKind::DepthCut)) continue;
                 sa.Lout = group_records.as<float4>() + (size_t)w.index * ns;
                 sa.tiles = out.tiles[o] + (size_t)b0 * tpx * 5;
                 if ((rc = launch_splat(ctx, plan, sa, nbk, st))) return rc;
@@ -1521,10 +1545,11 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         }
         // one stream: waiting for the last event recorded is waiting for all of them
         HIPCHK(hipEventSynchronize(last));
-        if ((rc = read_batch_times(ctx, frame, G != 0, acc, times, group_ms))) return rc;
+        if ((rc = read_batch_times(ctx, frame, R != 0, acc, times, group_ms))) return rc;
         if (beauty) ++acc.kernel_launches;
     }
     if (G) ctx->lg_ms[0] = group_ms;
+    if (K) ctx->dc_ms[0] = group_ms;
     if (stats) {
         acc.schedule = ctx->sched;
         acc.samples = counted * p->spp;
@@ -1889,6 +1914,14 @@ int set_light_groups(nart_ctx* ctx, const uint32_t* group_of_light) {
     if (!ctx->subs.empty()) return NART_OK;
     HIPCHK(hipSetDevice(ctx->device));
     return upload(ctx, ctx->d_light_group, group_of_light, ctx->scene.num_lights, "light groups");
+}
+
+// The cuts (validated by the caller: depth_cuts_error) onto every device's context of ctx, for the
+// depth-cut renders that follow (render_buckets hands them to the path kernel in its arguments).
+void set_depth_cuts(nart_ctx* ctx, const uint32_t* cuts, uint32_t K) {
+    for (nart_ctx* c : ctx->subs) set_depth_cuts(c, cuts, K);
+    for (uint32_t j = 0; j < DEPTH_CUTS_MAX; ++j) ctx->depth_cuts[j] = j < K ? cuts[j] : 0u;
+    ctx->n_depth_cuts = K;
 }
 
 }  // namespace
@@ -2443,6 +2476,55 @@ int nart_hip_light_group_timings(const nart_ctx* ctx, double* splat_ms, double* 
     if (!ctx) return NART_E_INVALID;
     if (splat_ms) *splat_ms = ctx->lg_ms[0];
     if (mix_ms) *mix_ms = first_device(ctx)->lg_ms[1];
+    return NART_OK;
+}
+
+int nart_hip_render_depth_cuts(nart_ctx* ctx, const nart_render_params* p, const uint32_t* cuts, uint32_t n_cuts,
+                               nart_pixel* cut_images, nart_pixel* image, nart_render_stats* stats) {
+    if (!ctx || !p || !cut_images) return NART_E_INVALID;
+    if (const char* why = depth_cuts_error(cuts, n_cuts, p->bounces)) return fail(ctx, NART_E_INVALID, why);
+    return render_depth_cuts(ctx, p, cuts, n_cuts, cut_images, image, stats);
+}
+
+int nart_hip_depth_layers(nart_ctx* ctx, const nart_render_params* p, uint32_t n_cuts, const nart_pixel* cut_images,
+                          const nart_pixel* beauty, nart_pixel* out) {
+    if (!ctx || !p) return NART_E_INVALID;
+    if (n_cuts < 1 || n_cuts > NART_DEPTH_CUTS_MAX) return fail(ctx, NART_E_INVALID, "n_cuts must be 1..8");
+    if (!cut_images || !beauty || !out) return fail(ctx, NART_E_INVALID, "the cut images, the beauty and the layers are required");
+    if (const char* why = check_image_size(p)) return fail(ctx, NART_E_INVALID, why);
+    return depth_layers_host(ctx, p, n_cuts, cut_images, beauty, out);
+}
+
+int nart_hip_render_depth_cut_samples(nart_ctx* ctx, const nart_render_params* p, const uint32_t* cuts, uint32_t n_cuts,
+                                      uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float* out) {
+    if (!ctx || !p || !out) return NART_E_INVALID;
+    if (!ctx->subs.empty())  // per-sample debugging runs on the first device
+        return forwarded(ctx, nart_hip_render_depth_cut_samples(first_device(ctx), p, cuts, n_cuts, x0, y0, w, h, out));
+    if (const char* why = depth_cuts_error(cuts, n_cuts, p->bounces)) return fail(ctx, NART_E_INVALID, why);
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    if (p->integrator == NART_INTEGRATOR_VOLUME)  // (frames: plan_frame's rule)
+        return fail(ctx, NART_E_UNSUPPORTED, "depth cuts need the path integrator: the volume integrator has no depth-cut build");
+    if (!w || !h) return fail(ctx, NART_E_INVALID, "empty rect");
+    if ((rc = counter_buffer(ctx))) return rc;
+    RenderArgs ra;
+    if ((rc = rect_slots(ctx, p, x0, y0, w, h, ctx->d_counters.as<unsigned long long>(), ra))) return rc;
+    const size_t ns = (size_t)ra.n_slots * p->spp;
+    Buf records;  // the K record arrays; freed on return
+    if ((rc = reserve(ctx, records, ctx->device, n_cuts * ns * sizeof(float4), "depth-cut records"))) return rc;
+    ra.n_groups = n_cuts;
+    for (uint32_t j = 0; j < n_cuts; ++j) ra.cuts[j] = cuts[j];
+    ra.Lgrp = records.as<float4>();
+    ra.lgrp_stride = ns;
+    if ((rc = launch_latin(ctx, ra, 0)) || (rc = dispatch_render(ctx, ra, p->integrator, 0))) return rc;
+    HIPCHK(hipMemcpy(out, records.as<float4>(), n_cuts * ns * sizeof(float4), hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+int nart_hip_depth_cut_timings(const nart_ctx* ctx, double* splat_ms, double* layers_ms) {
+    if (!ctx) return NART_E_INVALID;
+    if (splat_ms) *splat_ms = ctx->dc_ms[0];
+    if (layers_ms) *layers_ms = first_device(ctx)->dc_ms[1];
     return NART_OK;
 }
 
