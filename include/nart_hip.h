@@ -795,8 +795,60 @@ int nart_hip_render_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t
    renders.  Slower; used to compute algorithmic bytes per sample. */
 int nart_hip_set_counters(nart_ctx* ctx, int enable);
 
-/* Device self-test: glibc-equivalent sinf/cosf over n inputs (parity of the device libm). */
+/* Device self-test: glibc-equivalent sinf/cosf over n inputs (parity of the device libm).  The
+   general entry is nart_hip_eval (NART_EVAL_SINCOS computes the same values). */
 int nart_hip_eval_sincos(nart_ctx* ctx, const float* x, uint32_t n, float* sin_out, float* cos_out);
+
+/* Device probe (test hook, never launched by a render): one device function of the render path
+   on n caller-supplied inputs, one lane per input.  in and out hold n records of NART_EVAL_WORDS
+   (16) floats each; integer fields (u32) travel as their bits; input words an op does not name are
+   ignored and output words it does not name are 0.
+
+     op                       in                                        out
+     ACOSF ATANF LOGF         0 x                                       0 f(x)
+     LOGF_LDS                 0 x     (logf through the volume kernel's LDS table)   0 logf(x)
+     ATAN2F                   0 y, 1 x                                  0 atan2f(y, x)
+     SINCOS                   0 x                                       0 sinf(x), 1 cosf(x)
+     F2U32 F2U8               0 f                                       0 u32 result
+     GMOD                     0 a, 1 b                                  0 a - b * floor(a / b)
+     GFRACT                   0 x                                       0 x - floor(x)
+     RNG_FLOAT                0 u32 state                               0 value, 1 u32 state after
+     RNG_INT                  0 u32 state, 1 u32 max                    0 u32 value, 1 u32 state after
+     SAMPLE_DISK              0-1 sample                                0-1 point
+     SAMPLE_RING              0-1 sample, 2 inner                       0-1 point, 2 pdf
+     SAMPLE_COSHEMI           0-1 sample                                0-2 direction, 3 pdf
+     SAMPLE_SPHERE            0-1 sample                                0-2 direction
+     SAMPLE_WH                0-1 sample, 2 alpha, 3 u32 diel (0/1), 4-6 wo      0-2 wh
+     FRESNEL                  0 eta_o, 1 eta_i, 2 cos_theta             0 Fr
+     BXDF_F                   shading record, 12-14 wi                  0-2 f
+     BXDF_PDF                 shading record, 12-14 wi                  0 pdf
+     BXDF_F_PDF               shading record, 12-14 wi                  0-2 f, 3 pdf
+     BXDF_SAMPLE_F            shading record, 12 s1, 13-14 sample       0-2 f, 3-5 wi, 6 pdf, 7 u32 flags,
+                                                                        8 alpha_i (-1 where not written)
+
+   Shading record: 0 u32 packed = type (bits 0-7: 0 Lambert, 1 specular, 2 specular dielectric,
+   3 dielectric, 4 Torrance-Sparrow) | uap << 8 (use alpha_prime) | incoming flags << 16 (8 bits, the
+   reference's uint8_t; BXDF_SAMPLE_F only); 1-3 rho; 4 tau (the lobe's tau is (tau, tau / 2, tau / 4):
+   three distinct channels from one word); 5 eta; 6 alpha_0; 7 alpha_prime; 8 eta_outer; 9-11 wo.
+
+   fm: the path kernel's feature mask (NART_FT_*) that BXDF_F_PDF and BXDF_SAMPLE_F are compiled
+   for: NART_FT_ALL, or one of NART_FT_LAMBERT, _SPECULAR, _GLASS, _GLOSSY, _PLASTIC (per BxDF kind
+   the narrowest mask that creates it; give such a build only the kinds its mask creates).  The other
+   ops ignore the build but fm must still be one of these.
+   NART_E_INVALID: a null pointer, an unknown op, any other fm, n above NART_EVAL_MAX_N (1 GiB of
+   records each way; the block count stays far from 32 bits).  n == 0: NART_OK, nothing launched.
+   Multi-device contexts run it on their first device. */
+#define NART_EVAL_WORDS 16
+#define NART_EVAL_MAX_N (1u << 24)
+enum {
+    NART_EVAL_ACOSF = 0, NART_EVAL_ATANF = 1, NART_EVAL_ATAN2F = 2, NART_EVAL_LOGF = 3, NART_EVAL_LOGF_LDS = 4,
+    NART_EVAL_SINCOS = 5, NART_EVAL_F2U32 = 6, NART_EVAL_F2U8 = 7, NART_EVAL_GMOD = 8, NART_EVAL_GFRACT = 9,
+    NART_EVAL_RNG_FLOAT = 10, NART_EVAL_RNG_INT = 11, NART_EVAL_SAMPLE_DISK = 12, NART_EVAL_SAMPLE_RING = 13,
+    NART_EVAL_SAMPLE_COSHEMI = 14, NART_EVAL_SAMPLE_SPHERE = 15, NART_EVAL_SAMPLE_WH = 16, NART_EVAL_FRESNEL = 17,
+    NART_EVAL_BXDF_F = 18, NART_EVAL_BXDF_PDF = 19, NART_EVAL_BXDF_F_PDF = 20, NART_EVAL_BXDF_SAMPLE_F = 21,
+    NART_EVAL_N_OPS = 22
+};
+int nart_hip_eval(nart_ctx* ctx, uint32_t op, uint32_t fm, const float* in, uint32_t n, float* out);
 
 /* Splat filter-index thresholds (host only, no device): thr65[k] = the least d2 whose AddSample
    filter index (render.cpp:43-49) is >= k.  NART_E_INVALID when filter_width is too small for

@@ -81,6 +81,16 @@ SCHED = {"probe_queue": 0x1, "priority": 0x2, "spec_pairs": 0x4, "wave_groups": 
 FEATURES = {"lambert": 0x1, "specular": 0x2, "glass": 0x4, "glossy": 0x8, "plastic": 0x10, "disk": 0x20,
             "ring": 0x40, "environment": 0x80, "texture": 0x100, "normal_map": 0x200}
 FT_ALL = 0x3FF
+# device probe ops (include/nart_hip.h NART_EVAL_*; HipRenderer.eval, oracle.eval)
+EVAL_OPS = {"acosf": 0, "atanf": 1, "atan2f": 2, "logf": 3, "logf_lds": 4, "sincos": 5, "f2u32": 6, "f2u8": 7,
+            "gmod": 8, "gfract": 9, "rng_float": 10, "rng_int": 11, "uniform_sample_disk": 12,
+            "uniform_sample_ring": 13, "cosine_sample_hemisphere": 14, "uniform_sample_sphere": 15,
+            "sample_wh": 16, "fresnel": 17, "bxdf_f": 18, "bxdf_pdf": 19, "bxdf_f_pdf": 20, "bxdf_sample_f": 21}
+EVAL_WORDS = 16  # floats per probe record (NART_EVAL_WORDS)
+# the feature masks the probe's templated ops are built for, with the BxDF kinds each creates
+# (path.h create_bsdf: 0 Lambert, 1 specular, 2 specular dielectric, 3 dielectric, 4 Torrance-Sparrow)
+EVAL_MASKS = {"all": (FT_ALL, (0, 1, 2, 3, 4)), "lambert": (0x1, (0,)), "specular": (0x2, (1, 4)),
+              "glass": (0x4, (2, 3)), "glossy": (0x8, (1, 4)), "plastic": (0x10, (0, 1, 4))}
 LIGHT_GROUPS_MAX = 8  # include/nart_hip.h NART_LIGHT_GROUPS_MAX
 DEPTH_CUTS_MAX = 8  # include/nart_hip.h NART_DEPTH_CUTS_MAX
 
@@ -290,6 +300,7 @@ _HIP_SIGS = {
                                                ctypes.c_uint32, ctypes.c_uint32, _P]),
     "nart_hip_set_counters": (ctypes.c_int, [_P, ctypes.c_int]),
     "nart_hip_eval_sincos": (ctypes.c_int, [_P, _P, ctypes.c_uint32, _P, _P]),
+    "nart_hip_eval": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, _P, ctypes.c_uint32, _P]),
     "nart_hip_set_variant": (ctypes.c_int, [_P, ctypes.c_int]),
     "nart_hip_set_splat_mode": (ctypes.c_int, [_P, ctypes.c_int]),
     "nart_hip_set_specialize": (ctypes.c_int, [_P, ctypes.c_int]),
@@ -1118,6 +1129,19 @@ class HipRenderer:
         c = np.empty_like(x)
         self._check(self._lib.nart_hip_eval_sincos(self._ctx, x.ctypes.data, len(x), s.ctypes.data, c.ctypes.data))
         return s, c
+
+    def eval(self, op, inputs, fm=None):
+        """Device probe (nart_hip_eval): one device function of the render path on caller-supplied
+        inputs.  op: a name or number of EVAL_OPS; inputs: (n, 16) float32 records, integer fields as
+        their bits (include/nart_hip.h documents the fields per op); fm: the feature mask bxdf_f_pdf
+        and bxdf_sample_f are built for (an EVAL_MASKS mask; None: FT_ALL).  Returns (n, 16) float32."""
+        x = np.ascontiguousarray(inputs, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != EVAL_WORDS:
+            raise ValueError("probe inputs must be (n, %d) float32 records, got %r" % (EVAL_WORDS, x.shape))
+        out = np.zeros_like(x)
+        self._check(self._lib.nart_hip_eval(self._ctx, EVAL_OPS[op] if isinstance(op, str) else int(op),
+                                            FT_ALL if fm is None else int(fm), x.ctypes.data, len(x), out.ctypes.data))
+        return out
 
     def close(self):
         if self._ctx:

@@ -7,7 +7,8 @@
 //    -fhip-fp32-correctly-rounded-divide-sqrt) and no FMA contraction (-ffp-contract=off);
 //  * sinf/cosf are glibc 2.35's algorithm (sysdeps/ieee754/flt-32/s_sinf.c, s_cosf.c,
 //    sincosf.h: double-precision range reduction + polynomials), verified bit-exact against
-//    the host libm over every float in [-7, 7] (tests/test_libm_parity.py).
+//    the host libm over every float in [-120, 120] (tests/test_libm_parity.py; the device build
+//    in tests/test_gpu_probe.py).
 //
 // Third-party notices.  The sinf/cosf/logf ports restate algorithms and constant tables of the
 // GNU C Library 2.35 (sysdeps/ieee754/flt-32; those files are Copyright (C) 2017-2022 Free
@@ -96,26 +97,33 @@ NHD SinCosT sincos_table(int k) {
     return t;
 }
 NHD uint32_t abstop12(float x) { return (__builtin_bit_cast(uint32_t, x) >> 20) & 0x7ff; }
+// (every a + b * c of glibc's polynomial and reduction code is one fused multiply-add here: see reduce_fast)
 NHD float sinf_poly(double x, double x2, const SinCosT* p, int n) {
     if ((n & 1) == 0) {
         double x3 = x * x2;
-        double s1 = p->s2 + x2 * p->s3;
+        double s1 = __builtin_fma(x2, p->s3, p->s2);
         double x7 = x3 * x2;
-        double s = x + x3 * p->s1;
-        return (float)(s + x7 * s1);
+        double s = __builtin_fma(x3, p->s1, x);
+        return (float)__builtin_fma(x7, s1, s);
     }
     double x4 = x2 * x2;
-    double c2 = p->c3 + x2 * p->c4;
-    double c1 = p->c0 + x2 * p->c1;
+    double c2 = __builtin_fma(x2, p->c4, p->c3);
+    double c1 = __builtin_fma(x2, p->c1, p->c0);
     double x6 = x4 * x2;
-    double c = c1 + x4 * p->c2;
-    return (float)(c + x6 * c2);
+    double c = __builtin_fma(x4, p->c2, c1);
+    return (float)__builtin_fma(x6, c2, c);
 }
 NHD double reduce_fast(double x, const SinCosT* p, int* np) {
     double r = x * p->hpi_inv;
     int n = ((int32_t)r + 0x800000) >> 24;
     *np = n;
-    return x - n * p->hpi;
+    // Fused multiply-adds, as the glibc build that x86-64 hosts with FMA run is contracted (the sinf /
+    // cosf ifunc variants, like logf's below).  It matters here: next to a multiple of pi/2 the
+    // difference cancels, and the rounding of n * hpi alone then shows in the float result.  Unfused,
+    // 34 of the 2.25e9 floats in [-120, 120] differed from the host by an ulp (the first at 11 pi / 2;
+    // none in [-7, 7], where the render path's angles lie); with this step fused none does, whether
+    // the polynomials are fused as well (as they are, and as the host runs them) or not.
+    return __builtin_fma(-(double)n, p->hpi, x);
 }
 // sinf and cosf of one argument (glibc's sinf / cosf / sincosf share this reduction), without
 // branches: a wave whose lanes fall on both sides of glibc's |y| < pi/4 test used to run both

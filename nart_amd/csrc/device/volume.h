@@ -20,6 +20,24 @@ ND f3 uniform_sample_sphere(f2 smp) {  // sampling.cpp:33-45 (pdf unused by the 
     return F3(sinTheta * cosPhi, sinTheta * sinPhi, cosTheta);
 }
 
+// glibc logf's (invc, logc) table in LDS: one LDS read per logf instead of a 16-way select of
+// double pairs (~80 VALU instructions).  logf_lds_stage fills tab[16] from the block's first 16
+// lanes (a __syncthreads() must follow before glibc_logf_lds reads it).
+ND void logf_lds_stage(double2* tab) {
+    if (threadIdx.x < 16) {
+        double invc, logc;
+        logf_table((int)threadIdx.x, invc, logc);
+        tab[threadIdx.x] = make_double2(invc, logc);
+    }
+}
+ND float glibc_logf_lds(float x, const double2* tab) {
+    return glibc_logf_with(x, [&](int i, double& invc, double& logc) {
+        const double2 e = tab[i];
+        invc = e.x;
+        logc = e.y;
+    });
+}
+
 NHD float dg_at(const DMedium& m, const float* dens, uint32_t x, uint32_t y, uint32_t z) {  // media.cpp:3-7
     return dens[(m.rx * m.ry * z) + (m.rx * y) + x];
 }
@@ -185,14 +203,8 @@ template <bool COUNT, int WV>
 __global__ __launch_bounds__(256, WV) void k_render_volume_sm(DScene S, RenderArgs A) {
     // A.lds_nodes != 0: the density grid (that many floats) is staged in LDS
     extern __shared__ float s_dens[];
-    // glibc logf's (invc, logc) table: one LDS read per tentative collision instead of a
-    // 16-way select of double pairs (~80 VALU instructions)
     __shared__ double2 s_logf[16];
-    if (threadIdx.x < 16) {
-        double invc, logc;
-        logf_table((int)threadIdx.x, invc, logc);
-        s_logf[threadIdx.x] = make_double2(invc, logc);
-    }
+    logf_lds_stage(s_logf);
     // the medium stays in the kernel arguments (a local copy with its density pointer swapped
     // lived in scratch memory: every field read in the loop was a scratch load)
     const float* dens = S.medium.density;
@@ -353,11 +365,7 @@ __global__ __launch_bounds__(256, WV) void k_render_volume_sm(DScene S, RenderAr
             float isig = m.inv_maj[0];
 #pragma unroll
             for (int j = 1; j < 8; ++j) isig = (int)sidx == j ? m.inv_maj[j] : isig;
-            const float lg = -glibc_logf_with(1.f - rng_float(rng), [&](int i, double& invc, double& logc) {
-                const double2 e = s_logf[i];
-                invc = e.x;
-                logc = e.y;
-            });
+            const float lg = -glibc_logf_lds(1.f - rng_float(rng), s_logf);
             float t;
             if (sp2) t = tMin + lg * isig;
             else t = tMin + lg / sigma;

@@ -25,6 +25,7 @@
 #include "device/lbvh.h"
 #include "device/lightgroup.h"
 #include "device/matte.h"
+#include "device/probe.h"
 #include "device/volume.h"
 #include "host/bucket_batch.h"
 #include "host/bvh_build.h"
@@ -2805,6 +2806,24 @@ int nart_hip_eval_sincos(nart_ctx* ctx, const float* x, uint32_t n, float* s, fl
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(s, ds, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(c, dc, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+int nart_hip_eval(nart_ctx* ctx, uint32_t op, uint32_t fm, const float* in, uint32_t n, float* out) {
+    if (!ctx || !in || !out || op >= NART_EVAL_N_OPS || !probe_fm_ok(fm) || n > NART_EVAL_MAX_N) return NART_E_INVALID;
+    if (!n) return NART_OK;
+    if (!ctx->subs.empty()) return nart_hip_eval(first_device(ctx), op, fm, in, n, out);
+    HIPCHK(hipSetDevice(ctx->device));
+    Buf bi, bo;  // freed on return
+    int rc = NART_OK;
+    const size_t bytes = (size_t)n * NART_EVAL_WORDS * sizeof(float);
+    for (Buf* b : {&bi, &bo})
+        if ((rc = reserve(ctx, *b, ctx->device, bytes, "probe records"))) return rc;
+    float *const di = bi.as<float>(), *const dout = bo.as<float>();
+    HIPCHK(hipMemcpy(di, in, bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_probe, dim3((n + 255) / 256), dim3(256), 0, 0, op, fm, di, n, dout);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
     return NART_OK;
 }
 

@@ -1912,3 +1912,129 @@ void oracle_trace(const oracle_scene* s, const float* o, const float* d, float t
     out[2] = bg;
     memcpy(&out[3], &bf.tMax, 4);
 }
+
+/* ---------------------------------------------------------------- probe (oracle_eval) */
+typedef struct {
+    bxdf_t b;
+    int uap;
+    uint8_t flags;
+    float eta_outer, s1;
+    v3 wo, wi;
+    v2 sample;
+} eval_shade_t;
+static inline uint32_t f2bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+static inline float bits2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+/* the shading record of nart_hip_eval (include/nart_hip.h) */
+static eval_shade_t eval_shade_in(const float* in, int sampled) {
+    eval_shade_t p;
+    memset(&p, 0, sizeof(p));
+    uint32_t w = f2bits(in[0]);
+    p.b.type = (int)(w & 0xFFu);
+    p.uap = (int)((w >> 8) & 1u);
+    p.flags = (uint8_t)((w >> 16) & 0xFFu);
+    p.b.rho = V3(in[1], in[2], in[3]);
+    p.b.tau = V3(in[4], in[4] * 0.5f, in[4] * 0.25f);
+    p.b.eta = in[5];
+    p.b.alpha_0 = in[6];
+    p.b.alpha_prime = in[7];
+    p.eta_outer = in[8];
+    p.wo = V3(in[9], in[10], in[11]);
+    if (sampled) {
+        p.s1 = in[12];
+        p.sample = V2(in[13], in[14]);
+    } else {
+        p.wi = V3(in[12], in[13], in[14]);
+    }
+    return p;
+}
+
+/* One function of the restatement on n caller-supplied inputs: the ops and the 16-float records of
+   nart_hip_eval (include/nart_hip.h).  The libm ops call the libm this library links (the
+   reference's glm::acos / atan / log / sin / cos); BXDF_F_PDF is (bxdf_f, bxdf_pdf): the reference
+   has no fused form.  Returns 0, or -1 for an unknown op or a null pointer. */
+int oracle_eval(uint32_t op, const float* in, uint32_t n, float* out) {
+    if (!in || !out || op >= NART_EVAL_N_OPS) return -1;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* x = in + (size_t)i * NART_EVAL_WORDS;
+        float* y = out + (size_t)i * NART_EVAL_WORDS;
+        for (int k = 0; k < NART_EVAL_WORDS; ++k) y[k] = 0.f;
+        switch (op) {
+            case NART_EVAL_ACOSF: y[0] = acosf(x[0]); break;
+            case NART_EVAL_ATANF: y[0] = atanf(x[0]); break;
+            case NART_EVAL_ATAN2F: y[0] = atan2f(x[0], x[1]); break;
+            case NART_EVAL_LOGF:
+            case NART_EVAL_LOGF_LDS: y[0] = logf(x[0]); break;
+            case NART_EVAL_SINCOS: y[0] = sinf(x[0]); y[1] = cosf(x[0]); break;
+            case NART_EVAL_F2U32: y[0] = bits2f(f2u32(x[0])); break;
+            case NART_EVAL_F2U8: y[0] = bits2f((uint32_t)f2u8(x[0])); break;
+            case NART_EVAL_GMOD: y[0] = gmod(x[0], x[1]); break;
+            case NART_EVAL_GFRACT: y[0] = gfract(x[0]); break;
+            case NART_EVAL_RNG_FLOAT: {
+                rng_t r = {f2bits(x[0])};
+                y[0] = rng_float(&r);
+                y[1] = bits2f(r.y);
+                break;
+            }
+            case NART_EVAL_RNG_INT: {
+                rng_t r = {f2bits(x[0])};
+                y[0] = bits2f(rng_int(&r, f2bits(x[1])));
+                y[1] = bits2f(r.y);
+                break;
+            }
+            case NART_EVAL_SAMPLE_DISK: {
+                v2 d = uniform_sample_disk(V2(x[0], x[1]));
+                y[0] = d.x; y[1] = d.y;
+                break;
+            }
+            case NART_EVAL_SAMPLE_RING: {
+                float pdf;
+                v2 d = uniform_sample_ring(V2(x[0], x[1]), &pdf, x[2]);
+                y[0] = d.x; y[1] = d.y; y[2] = pdf;
+                break;
+            }
+            case NART_EVAL_SAMPLE_COSHEMI: {
+                float pdf;
+                v3 d = cosine_sample_hemisphere(V2(x[0], x[1]), &pdf);
+                y[0] = d.x; y[1] = d.y; y[2] = d.z; y[3] = pdf;
+                break;
+            }
+            case NART_EVAL_SAMPLE_SPHERE: {
+                v3 d = uniform_sample_sphere(V2(x[0], x[1]));
+                y[0] = d.x; y[1] = d.y; y[2] = d.z;
+                break;
+            }
+            case NART_EVAL_SAMPLE_WH: {
+                v3 wh = sample_wh(V3(x[4], x[5], x[6]), x[2], V2(x[0], x[1]), f2bits(x[3]) != 0u);
+                y[0] = wh.x; y[1] = wh.y; y[2] = wh.z;
+                break;
+            }
+            case NART_EVAL_FRESNEL: y[0] = fresnel(x[0], x[1], x[2]); break;
+            case NART_EVAL_BXDF_F:
+            case NART_EVAL_BXDF_PDF:
+            case NART_EVAL_BXDF_F_PDF: {
+                eval_shade_t p = eval_shade_in(x, 0);
+                if (op != NART_EVAL_BXDF_PDF) {
+                    v3 f = bxdf_f(&p.b, p.wo, p.wi, p.uap, p.eta_outer);
+                    y[0] = f.x; y[1] = f.y; y[2] = f.z;
+                }
+                if (op != NART_EVAL_BXDF_F)
+                    y[op == NART_EVAL_BXDF_PDF ? 0 : 3] = bxdf_pdf(&p.b, p.wo, p.wi, p.uap, p.eta_outer);
+                break;
+            }
+            case NART_EVAL_BXDF_SAMPLE_F: {
+                eval_shade_t p = eval_shade_in(x, 1);
+                v3 wi = V3(0.f, 0.f, 0.f);
+                float pdf = 0.f, alpha_i = -1.f;
+                uint8_t flags = p.flags;
+                v3 f = bxdf_sample_f(&p.b, p.wo, &wi, p.s1, p.sample, &pdf, &flags, &alpha_i, p.uap, p.eta_outer);
+                y[0] = f.x; y[1] = f.y; y[2] = f.z;
+                y[3] = wi.x; y[4] = wi.y; y[5] = wi.z;
+                y[6] = pdf;
+                y[7] = bits2f((uint32_t)flags);
+                y[8] = alpha_i;
+                break;
+            }
+        }
+    }
+    return 0;
+}

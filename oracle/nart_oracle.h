@@ -18,6 +18,7 @@
 #define NART_ORACLE_H
 
 #include "../include/nart_scene.h"
+#include "../include/nart_hip.h" /* declarations only: the NART_EVAL_* ops and record layout of oracle_eval */
 
 #ifdef __cplusplus
 extern "C" {
@@ -68,6 +69,13 @@ void oracle_latin_square(uint32_t seed, uint32_t spp, float* out_xy, uint32_t* r
 float oracle_fresnel(float eta_o, float eta_i, float cos_theta);
 /* BinarySearch (util.cpp:4-20) as the environment light's CDF inversion uses it. */
 uint32_t oracle_binary_search(float value, const float* v, uint32_t start, uint32_t end);
+/* One function of the restatement (fresnel, bxdf_f / bxdf_pdf / bxdf_sample_f, sample_wh, the
+   sampling functions, the rng, f2u32 / f2u8, gmod / gfract) or of the linked libm (acosf, atanf,
+   atan2f, logf, sinf / cosf) on n caller-supplied inputs.  op and the 16-float records in and out are
+   those of the device probe nart_hip_eval (NART_EVAL_*, include/nart_hip.h), of which this is the
+   CPU side; BXDF_F_PDF answers (bxdf_f, bxdf_pdf), LOGF_LDS answers logf.  0, or -1 for an unknown
+   op or a null pointer. */
+int oracle_eval(uint32_t op, const float* in, uint32_t n, float* out);
 /* Test statistic: the longest nested-dielectric list a path of this process reached (reset: zero it). */
 uint32_t oracle_max_list(int reset);
 

@@ -84,6 +84,7 @@ def lib():
         _lib.oracle_camera_ray.argtypes = [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                            ctypes.c_float, ctypes.c_float, P, P]
         _lib.oracle_trace.argtypes = [P, P, P, ctypes.c_float, P]
+        _lib.oracle_eval.argtypes = [ctypes.c_uint32, P, ctypes.c_uint32, P]
     return _lib
 
 
@@ -163,6 +164,19 @@ def latin_square(seed, spp):
 
 def fresnel(eta_o, eta_i, c):
     return lib().oracle_fresnel(eta_o, eta_i, c)
+
+
+def eval(op, inputs):  # noqa: A001  (the counterpart of HipRenderer.eval)
+    """One function of the restatement on caller-supplied inputs (oracle_eval): op a name or number
+    of nart_amd.EVAL_OPS, inputs (n, 16) float32 records (include/nart_hip.h).  Returns (n, 16)."""
+    from nart_amd import EVAL_OPS
+    x = np.ascontiguousarray(inputs, np.float32)
+    assert x.ndim == 2 and x.shape[1] == 16, x.shape
+    out = np.zeros_like(x)
+    rc = lib().oracle_eval(EVAL_OPS[op] if isinstance(op, str) else int(op), x.ctypes.data, len(x), out.ctypes.data)
+    if rc:
+        raise RuntimeError("oracle_eval failed: %d" % rc)
+    return out
 
 
 def camera_ray(orc, W, H, x, y, u, v):

@@ -10,10 +10,12 @@
 int main(int argc, char** argv) {
     unsigned stride = argc > 1 ? (unsigned)std::atoi(argv[1]) : 1;
     float lim = argc > 2 ? std::atof(argv[2]) : 7.0f;
+    float from = argc > 3 ? std::atof(argv[3]) : 0.0f;  // sweep [from, lim] (a window at stride 1)
     unsigned long n = 0, bad = 0;
-    unsigned top;
+    unsigned top, first;
     std::memcpy(&top, &lim, 4);
-    for (unsigned b = 0; b <= top; b += stride) {
+    std::memcpy(&first, &from, 4);
+    for (unsigned b = first; b <= top; b += stride) {
         float x;
         std::memcpy(&x, &b, 4);
         for (int sgn = 0; sgn < 2; ++sgn) {

@@ -49,6 +49,42 @@ def test_hip_create_without_gpu_fails_cleanly(built, glass_scene):
         raise AssertionError("render context created without a GPU")
 
 
+def test_eval_validates_its_arguments(built):
+    """nart_hip_eval without a device: a null context, input or output, an unknown op and a feature mask the
+    probe is not built for are NART_E_INVALID before anything touches a GPU, n == 0 included (with a
+    context: test_gpu_probe.py).  The Python names number the ops as the header does, and the oracle's
+    side refuses the same unknown op."""
+    import numpy as np
+    import oracle
+    lib = nart_amd.api.hip_lib()
+    x = np.zeros((2, nart_amd.EVAL_WORDS), np.float32)
+    y = np.full((2, nart_amd.EVAL_WORDS), 5.0, np.float32)
+    fake = ctypes.c_void_p(x.ctypes.data)  # never dereferenced: every call below fails on another argument
+    ok_fm = [fm for fm, _ in nart_amd.EVAL_MASKS.values()]
+    assert sorted(ok_fm) == [0x1, 0x2, 0x4, 0x8, 0x10, nart_amd.FT_ALL]
+    for n in (0, 2):
+        for fm in ok_fm:
+            assert lib.nart_hip_eval(None, 0, fm, x.ctypes.data, n, y.ctypes.data) == -1
+        assert lib.nart_hip_eval(fake, 0, nart_amd.FT_ALL, None, n, y.ctypes.data) == -1
+        assert lib.nart_hip_eval(fake, 0, nart_amd.FT_ALL, x.ctypes.data, n, None) == -1
+        assert lib.nart_hip_eval(fake, len(nart_amd.EVAL_OPS), nart_amd.FT_ALL, x.ctypes.data, n, y.ctypes.data) == -1
+        assert lib.nart_hip_eval(fake, 0xFFFFFFFF, nart_amd.FT_ALL, x.ctypes.data, n, y.ctypes.data) == -1
+        for fm in (0, 0x3, 0x6, 0x20, 0x3FE, 0x400, 0x7FF, 0xFFFFFFFF):
+            assert lib.nart_hip_eval(fake, 0, fm, x.ctypes.data, n, y.ctypes.data) == -1, fm
+    for n in ((1 << 24) + 1, 0xFFFFFF01, 0xFFFFFFFF):  # above NART_EVAL_MAX_N; the last two would wrap the block count
+        assert lib.nart_hip_eval(fake, 0, nart_amd.FT_ALL, x.ctypes.data, n, y.ctypes.data) == -1, n
+    assert np.all(y == 5.0)
+    header = open(os.path.join(REPO, "include", "nart_hip.h")).read()
+    enum = dict((k.lower(), int(v)) for k, v in re.findall(r"NART_EVAL_(\w+) = (\d+)", header))
+    assert enum.pop("n_ops") == len(nart_amd.EVAL_OPS) and enum.pop("words", 16) == nart_amd.EVAL_WORDS
+    assert "#define NART_EVAL_MAX_N (1u << 24)" in header
+    short = {"sample_disk": "uniform_sample_disk", "sample_ring": "uniform_sample_ring",
+             "sample_coshemi": "cosine_sample_hemisphere", "sample_sphere": "uniform_sample_sphere"}
+    assert {short.get(k, k): v for k, v in enum.items()} == nart_amd.EVAL_OPS
+    assert oracle.lib().oracle_eval(len(nart_amd.EVAL_OPS), x.ctypes.data, 2, y.ctypes.data) == -1
+    assert oracle.lib().oracle_eval(0, None, 2, y.ctypes.data) == -1 and np.all(y == 5.0)
+
+
 def test_splat_thresholds_reproduce_filter_index(built):
     """The splat's filter index from d2 thresholds equals AddSample's
     uint8((sqrt(d2) / fw) * 64) clamped to 63 (render.cpp:43-49), float32 throughout."""
