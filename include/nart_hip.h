@@ -773,6 +773,61 @@ int nart_hip_render_depth_cut_samples(nart_ctx* ctx, const nart_render_params* p
                                       uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float* out);
 int nart_hip_depth_cut_timings(const nart_ctx* ctx, double* splat_ms, double* layers_ms);
 
+/* Cost image: per-pixel ray, hit and traversal counts of a render -- where its time goes.
+
+   A shard's time is set by its costliest pixels' serial sample chains; the whole-frame totals of the
+   counter pass (nart_hip_set_counters) do not say where those pixels are.  For every traced camera
+   sample the cost record is four uint32 (nart_cost_pixel):
+     rays_extend  closest-hit queries of the sample, as nart_render_stats::rays_extend: the camera ray
+                  when p->bounces > 0, plus one per continued bounce;
+     rays_shadow  occlusion queries of EstimateDirect actually traced, as nart_render_stats::rays_shadow
+                  (the device skips a query whose term is exactly zero);
+     hits         shaded hits, as nart_render_stats::bounces;
+     steps        BVH node visits plus triangle tests of the sample's own extension and shadow rays, as
+                  nart_render_stats::node_visits + tri_tests count them, from the start of a ray's
+                  traversal until it resolves, whichever lane traces it.
+   The cost grid is the sum of a pixel's records over its p->spp samples, (grid_h, grid_w) nart_cost_pixel,
+   on the grid of traced pixels: grid_w = min(bucket_size * n_buckets_x, total_width), grid_h likewise --
+   the x, y range of RenderTile's loops, the rows and columns beyond the cropped window included
+   (nart_hip_cost_grid).  grid_w * grid_h * spp is nart_render_stats::traced_samples.  Per sample:
+   1 <= rays_extend <= bounces (bounces > 0), rays_extend - 1 <= hits <= rays_extend, rays_shadow <= 2 hits.
+
+   Every word depends on the scene and the session only, not on the schedule.  A cost frame runs the
+   cost build of the ray-queue path kernel (k_render_rq with CS: the generic two-wave build without
+   priority lanes or speculative pairs, as for light groups and depth cuts, so no traced work is
+   dropped) and no k_primary: the camera rays are traced by the path kernel too, so every ray of a
+   sample goes through the single-ray traversal and packet traversal, whose steps are a wave's union,
+   never enters `steps`.  The owning lane writes one 16-byte record per sample (batches are sized for
+   28 + 16 bytes per sample); k_cost_reduce (device/cost.h) sums a slot's records into the grid once per
+   batch.  The beauty of a cost render has the bits nart_hip_render gives.  With nart_hip_set_counters
+   enabled a cost render reports no work counts: the grid holds them.
+
+   nart_hip_cost_grid: the grid's size for p; host only.
+   nart_hip_render_cost: cost receives the grid (required); beauty, if non-null, the beauty.  On a
+   multi-device context every device reduces its own buckets into its own zeroed grid and the host adds
+   them: each pixel is non-zero on exactly one device.
+   nart_hip_render_cost_samples: debug / parity, as nart_hip_render_samples: the records of a rect in
+   total-image coordinates (which are the grid's) into records[((y-y0)*w + (x-x0))*spp + s][4].
+   nart_hip_cost_image: a grid as a nart_pixel image the EXR writer and finalize() take unchanged: grid
+   pixel (x, y) goes to image pixel (y + fb, x + fb) as {float(rays_extend), float(rays_shadow),
+   float(hits), float(steps), float(spp)} (round to nearest even); grid pixels outside the total image
+   are dropped and the rest of the image is zero, so finalize() gives per-sample means over the cropped
+   window.
+   nart_hip_cost_timings: device times of the last cost render's reduces and of the last image run.
+   NART_E_INVALID: a null ctx, p, cost, image or records; an empty or out-of-range rect.
+   NART_E_UNSUPPORTED: the volume integrator; variant 3 or a BVH deeper than the ray-queue kernel's LDS
+   holds (k_render has no cost build).  An error leaves the context usable.  Not offered: the cost image
+   together with adaptive sampling, the cascade, the mattes, AOVs, guides, the moment image, light groups,
+   depth cuts or the denoiser in one call. */
+typedef struct nart_cost_pixel { uint32_t rays_extend, rays_shadow, hits, steps; } nart_cost_pixel;
+int nart_hip_cost_grid(const nart_render_params* p, uint32_t* width, uint32_t* height);
+int nart_hip_render_cost(nart_ctx* ctx, const nart_render_params* p, nart_cost_pixel* cost, nart_pixel* beauty,
+                         nart_render_stats* stats);
+int nart_hip_render_cost_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w,
+                                 uint32_t h, uint32_t* records);
+int nart_hip_cost_image(nart_ctx* ctx, const nart_render_params* p, const nart_cost_pixel* cost, nart_pixel* image);
+int nart_hip_cost_timings(nart_ctx* ctx, double* reduce_ms, double* image_ms);
+
 /* Multi-GPU building block: render the listed buckets (bucket id = by*nBucketsX + bx) into
    device-resident tiles d_tiles[i] (tile_size^2 nart_pixel each, same order as the list) on
    `stream` (a hipStream_t, may be 0).  bucket_ids is a host array.  Asynchronous w.r.t. the

@@ -269,6 +269,13 @@ _HIP_SIGS = {
                                                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                          ctypes.c_uint32, _P]),
     "nart_hip_depth_cut_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_cost_grid": (ctypes.c_int, [ctypes.POINTER(RenderParams), ctypes.POINTER(ctypes.c_uint32),
+                                          ctypes.POINTER(ctypes.c_uint32)]),
+    "nart_hip_render_cost": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), _P, _P, ctypes.POINTER(RenderStats)]),
+    "nart_hip_render_cost_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, ctypes.c_uint32,
+                                                    ctypes.c_uint32, ctypes.c_uint32, _P]),
+    "nart_hip_cost_image": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), _P, _P]),
+    "nart_hip_cost_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_aov_samples": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, ctypes.c_uint32,
                                                    ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "nart_hip_denoise_params_init": (None, [ctypes.POINTER(DenoiseParams)]),
@@ -408,6 +415,16 @@ def session_geometry(p):
     g = SessionGeometry()
     scene_lib().nart_session_geometry_of(ctypes.byref(p), ctypes.byref(g))
     return g
+
+
+def cost_grid(p):
+    """(grid_h, grid_w) of the cost grid of p (nart_hip_cost_grid): the traced pixels, x and y below
+    min(bucket_size * n_buckets, total size)."""
+    w, h = ctypes.c_uint32(), ctypes.c_uint32()
+    rc = hip_lib().nart_hip_cost_grid(ctypes.byref(p), ctypes.byref(w), ctypes.byref(h))
+    if rc:
+        raise NartError(rc, "cost_grid: invalid parameters")
+    return h.value, w.value
 
 
 def filter_table():
@@ -986,6 +1003,56 @@ class HipRenderer:
     def depth_cut_timings(self):
         """Device times of the last depth-cut call: {"splat_ms", "layers_ms"}."""
         return self._depth_cut_timings({})
+
+    def cost_timings(self):
+        """Device times of the last cost call: {"reduce_ms", "image_ms"}."""
+        r, m = ctypes.c_double(), ctypes.c_double()
+        self._check(self._lib.nart_hip_cost_timings(self._ctx, ctypes.byref(r), ctypes.byref(m)))
+        return {"reduce_ms": r.value, "image_ms": m.value}
+
+    def render_cost(self, p, with_beauty=False, stats=None, cost=True):
+        """Per-pixel ray, hit and traversal counts of a render (nart_hip_render_cost; include/nart_hip.h,
+        "Cost image", has the definition).  Returns a dict with "cost", the (grid_h, grid_w, 4) uint32
+        grid of {extension rays, shadow rays, shaded hits, traversal steps} summed over each traced
+        pixel's samples (cost_grid(p) gives its shape); "beauty" (bit-identical to render()) if requested;
+        "totals", the four sums over the grid as Python ints; "buckets", the (n_buckets_y, n_buckets_x, 4)
+        uint64 sums over each bucket's pixels; "reduce_ms", the device time of the reduces.  cost=False
+        passes a null grid (the ABI's error)."""
+        g = session_geometry(p)
+        gh, gw = cost_grid(p)
+        out = {"cost": np.zeros((gh, gw, 4), np.uint32)}
+        if with_beauty:
+            out["beauty"] = np.empty((g.total_height, g.total_width, PIXEL_FLOATS), np.float32)
+        st = stats if stats is not None else RenderStats()
+        self._check(self._lib.nart_hip_render_cost(self._ctx, ctypes.byref(p), out["cost"].ctypes.data if cost else None,
+                                                   out["beauty"].ctypes.data if with_beauty else None, ctypes.byref(st)))
+        c = out["cost"]
+        out["totals"] = tuple(int(v) for v in c.reshape(-1, 4).sum(axis=0, dtype=np.uint64))
+        B = p.bucket_size
+        edges_y, edges_x = np.arange(0, gh, B), np.arange(0, gw, B)
+        rows = np.add.reduceat(c.astype(np.uint64), edges_y, axis=0)
+        out["buckets"] = np.add.reduceat(rows, edges_x, axis=1)
+        out["reduce_ms"] = self.cost_timings()["reduce_ms"]
+        return out
+
+    def render_cost_samples(self, p, x0, y0, w, h):
+        """Per-sample cost records of a rect in total-image coordinates, which are the cost grid's
+        (nart_hip_render_cost_samples): (h, w, spp, 4) uint32."""
+        out = np.zeros((h, w, p.spp, 4), np.uint32)
+        self._check(self._lib.nart_hip_render_cost_samples(self._ctx, ctypes.byref(p), x0, y0, w, h, out.ctypes.data))
+        return out
+
+    def cost_image(self, p, cost):
+        """A cost grid as a (totalH, totalW, 5) float32 image (nart_hip_cost_image): grid pixel (x, y) at
+        (y + fb, x + fb) as {the four counts as float32, spp}, zero elsewhere, so that finalize() gives the
+        per-sample means over the cropped window and write_exr() takes it unchanged."""
+        g = session_geometry(p)
+        c = np.ascontiguousarray(cost, dtype=np.uint32)
+        if c.shape != cost_grid(p) + (4,):
+            raise ValueError("cost_image: grid of shape %s, expected %s" % (c.shape, cost_grid(p) + (4,)))
+        out = np.empty((g.total_height, g.total_width, PIXEL_FLOATS), np.float32)
+        self._check(self._lib.nart_hip_cost_image(self._ctx, ctypes.byref(p), c.ctypes.data, out.ctypes.data))
+        return out
 
     def render_aov_samples(self, p, x0, y0, w, h):
         """Per-sample AOV records of a rect in total-image coordinates (nart_hip_render_aov_samples):

@@ -186,6 +186,10 @@ struct RenderArgs {
     // serve as the record arrays of the n_groups cuts (no memset: every record is written in full);
     // cuts[j], strictly ascending in 1..bounces, is the bounce count of array j
     uint32_t cuts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // k_render_rq cost build (CS; include/nart_hip.h, "Cost image"): one record per sample with Lout's
+    // indexing, {extension rays, shadow rays, shaded hits, traversal steps} (no memset: the owning lane
+    // writes every record in full where the sample ends)
+    uint4* cost_rec = nullptr;
 };
 
 // xorshift32 state after n draws (rng.h:38-40 applied n times)
@@ -1142,11 +1146,26 @@ __global__ __launch_bounds__(256) void k_aov(DScene S, RenderArgs A, const uint3
 // the record of the cut equal to `bounce` takes it there.  Where the sample ends, every cut >= bounce
 // takes the final L and every cut the alpha.  The owning lane is the only writer of its records, as
 // for LG, and every record is written in full, so the arrays need not start at zero.
-template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false, bool DC = false>
+// CS (with FT_ALL, WV = 2, PR = false, not with LG or DC): the cost build (include/nart_hip.h, "Cost
+// image").  The owning lane keeps the sample's path counts in the registers COUNT keeps them in (j_ext,
+// j_sh, j_bounce, grown at the same three sites) and its traversal steps in a fourth, and stores the four
+// as one uint4 where the sample ends (RenderArgs::cost_rec): every record is written in full, the arrays
+// need not start at zero, and there is no global atomic.  The steps of a ray -- trav_step's node visits
+// plus triangle tests, counted by the lane that traces it from trav_begin on -- are added, where the ray
+// resolves, to the fourth word of its owner's result entry in LDS (no ray kind writes that word; only
+// LG uses it otherwise).  Up to three rays of one owner can resolve in one step on three lanes, so the
+// add is an LDS atomic; the owner drains the word where it reads its results.  With no priority lanes
+// and no speculative pairs no work is dropped, and the host launches no k_primary for this build, so
+// every ray of a sample runs through trav_step and the record depends on the sample alone.
+template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false, bool DC = false,
+          bool CS = false>
 __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : NART_RENDER_WAVES)) void k_render_rq(DScene S, RenderArgs A) {
     static_assert(!LG || (FM == FT_ALL && WV == 2 && !PR && !COUNT), "light groups: the generic two-wave build, no priority lanes");
     static_assert(!DC || (FM == FT_ALL && WV == 2 && !PR && !COUNT), "depth cuts: the generic two-wave build, no priority lanes");
     static_assert(!(LG && DC), "light groups and depth cuts share the record arrays: one or the other");
+    static_assert(!CS || (FM == FT_ALL && WV == 2 && !PR && !COUNT), "cost image: the generic two-wave build, no priority lanes");
+    static_assert(!(CS && (LG || DC)), "the cost build runs alone: it uses the result entry's fourth word, as LG does");
+    constexpr bool PC = COUNT || CS;  // the sample's path counts are kept
     // priority lanes, speculative groups and raised issue priority: small-shard schedules only
     const uint32_t rq_prio = PR ? A.rq_prio : 0u, rq_pairs = PR ? A.rq_pairs : 0u;
     // a lean build whose shading needs more than Lambert lobes and area lights fits 168 VGPRs only
@@ -1244,6 +1263,8 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
     // totals are per accepted sample and do not depend on the schedule (cnt, the traversal work, is
     // added by whichever lane traces a ray and does include dropped speculation)
     uint32_t j_ext = 0, j_sh = 0, j_bounce = 0;
+    uint32_t j_steps = 0;  // CS: traversal steps of the sample's rays, drained from the result entry
+    if (CS) my_res->w = 0u;
     auto count_sample = [&]() {
         n_ext += j_ext;
         n_sh += j_sh;
@@ -1347,13 +1368,14 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
             }
             A.Lout[soff + (uint64_t)s * sstr] = v;
             if (COUNT) count_sample();
+            if (CS) A.cost_rec[soff + (uint64_t)s * sstr] = make_uint4(j_ext, j_sh, j_bounce, j_steps);
             ++s;
         }
     };
     auto queue_ext = [&](f3 o, f3 d) {
         put_ray(0, o, d, light_loop(o, d));
         ext_pending = true;
-        if (COUNT) ++j_ext;
+        if (PC) ++j_ext;
     };
 
     bool raised = false;  // this wave runs at a raised issue priority (A.rq_setprio)
@@ -1377,6 +1399,11 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
             const uint4 r = *my_res;
             if ((!ext_pending || r.x != RQ_PENDING) && (!use1 || r.y != 2u) && (!use2 || r.z != 2u)) {
                 waiting = false;
+                if (CS) {
+                    // the steps of the rays that are back: into the sample's count, the word cleared
+                    j_steps += r.w;
+                    my_res->w = 0u;
+                }
                 if (jfl & J_DOOM) {
                     jfl = 0;  // a dropped speculative job: its rays are back, nothing to keep
                 } else {
@@ -1573,7 +1600,8 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
         //    a hit is to be shaded, a ray is queued or the pixel is done.
         while (active) {
             nd = 0;
-            if (COUNT) j_ext = j_sh = j_bounce = 0;
+            if (PC) j_ext = j_sh = j_bounce = 0;
+            if (CS) j_steps = 0;
             // pixel-major rows (stride 1): samples and camera hits are read in pairs, the odd one
             // kept for the lane's next sample -- each read of a line the lane's neighbours do not
             // share then serves two samples
@@ -1645,7 +1673,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
         }
         // 3. shade the hits (pathintegrator.cpp:185-246)
         if (need_shade) {
-            if (COUNT) ++j_bounce;  // shaded hit (nart_hip.h nart_render_stats::bounces)
+            if (PC) ++j_bounce;  // shaded hit (nart_hip.h nart_render_stats::bounces)
             const float4 ro = my_out[lane * 2], rd = my_out[lane * 2 + 1];
             const Ray cur = make_ray(F3(ro.x, ro.y, ro.z), F3(rd.x, rd.y, rd.z));
             Isect is;
@@ -1755,7 +1783,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
                 }
             }
             ++bounce;
-            if (COUNT) j_sh += (use1 ? 1u : 0u) + (use2 ? 1u : 0u);
+            if (PC) j_sh += (use1 ? 1u : 0u) + (use2 ? 1u : 0u);
             ext_pending = false;
             if (cont && bounce < A.bounces) queue_ext(no, nd);
             if (newk) {
@@ -1837,6 +1865,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
                     const float4 a = my_out[(kind * 64 + owner) * 2], b = my_out[(kind * 64 + owner) * 2 + 1];
                     tr = make_ray(F3(a.x, a.y, a.z), F3(b.x, b.y, b.z));
                     trav_begin(S, tr, a.w, kind != 0u, tq);
+                    if (CS) cnt.nodes = cnt.tris = 0u;  // the ray's own steps
                     tracing = true;
                 }
                 const uint32_t took = min((uint32_t)__popcll(mn), avp + avn);
@@ -1847,7 +1876,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
             bool fin = false;
             if (tracing) {
                 fin = !S.geometry_visible;  // one-chunk scenes render no geometry (Q14)
-                if (!fin) fin = trav_step<COUNT, ENV, SHORT>(S, tr, tq, sc, gstk, stride, cnt, s_nodes, nl, (int)sk);
+                if (!fin) fin = trav_step<PC, ENV, SHORT>(S, tr, tq, sc, gstk, stride, cnt, s_nodes, nl, (int)sk);
             }
             if (fin) {
                 tracing = false;
@@ -1858,6 +1887,7 @@ __global__ __launch_bounds__(RQ_BLOCK_OF(COUNT, WV), COUNT ? 1 : (WV == 3 ? 3 : 
                                       bt, bg, cnt);
                 uint32_t* rw = reinterpret_cast<uint32_t*>(s_res + wv * 64 + (tid8 & 63u));
                 const uint32_t kind = tid8 >> 6;
+                if (CS) atomicAdd(rw + 3, cnt.nodes + cnt.tris);  // (LDS; the owner reads it in the next path phase)
                 rw[kind] = kind == 0u ? bg : (bg != NO_HIT ? 1u : 0u);
             }
             // priority rays all resolved and a priority lane waits on its results: shade it now (ending

@@ -47,6 +47,9 @@ struct FrameAsk {  // what the caller asks for
     uint32_t max_follow = 0;         // delta interfaces a guide chain follows, 0..FRAME_MAX_FOLLOW
     uint32_t light_groups = 0;       // G light groups (include/nart_hip.h, "Light groups"), 0: off
     uint32_t depth_cuts = 0;         // K depth cuts (include/nart_hip.h, "Depth cuts"), 0: off
+    // the cost image (include/nart_hip.h, "Cost image"): a per-pixel grid of counts next to the beauty.
+    // Not a tile image: no output of the list, no pass, no splat, combine or gather
+    bool cost = false;
     explicit FrameAsk(uint32_t integrator_) : integrator(integrator_) {}
 };
 
@@ -88,7 +91,8 @@ struct FramePlan {
     uint32_t n_passes = 0;
     bool path_kernel = false;   // false: camera rays only (first-hit outputs without the beauty)
     // per-sample record memory beyond d_L (batch_slot_limit): the cascade's buffer, the second guide
-    // record's where both guides are asked for, or one record per light group or depth cut
+    // record's where both guides are asked for, one record per light group or depth cut, or the cost
+    // record
     uint32_t record_bytes = 0;
 
     int find(OutputKind kind, uint32_t index = 0) const {  // position in the list, or -1
@@ -158,6 +162,17 @@ inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
                (a.cascade.K || a.matte.on || a.aov[0] || a.aov[1] || guides || a.moment || a.light_groups)) {
         why = "depth cuts are not rendered with the cascade, the mattes, AOVs, guides, the moment image or light groups in "
               "one call";
+    } else if (a.cost && !a.beauty) {
+        code = NART_E_INVALID;
+        why = "the cost image needs the path kernel (the beauty)";
+    } else if (a.cost && a.integrator == NART_INTEGRATOR_VOLUME) {
+        why = "the cost image needs the path integrator: the volume integrator has no cost build";
+    } else if (a.cost && a.adaptive) {
+        why = "the cost image needs a uniform render: not adaptive sampling";
+    } else if (a.cost && (a.cascade.K || a.matte.on || a.aov[0] || a.aov[1] || guides || a.moment || a.light_groups ||
+                          a.depth_cuts)) {
+        why = "the cost image is not rendered with the cascade, the mattes, AOVs, guides, the moment image, light groups or "
+              "depth cuts in one call";
     }
     if (!why.empty()) {
         plan.code = code;
@@ -187,6 +202,7 @@ inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
     plan.record_bytes = (a.cascade.K || (a.guide[0] && a.guide[1])) ? 16 : 0;  // one float4 per sample
     if (a.light_groups) plan.record_bytes = 16 * a.light_groups;              // and per group
     if (a.depth_cuts) plan.record_bytes = 16 * a.depth_cuts;                  // or per cut
+    if (a.cost) plan.record_bytes = 16;                                       // one uint4 per sample
     return plan;
 }
 

@@ -1,7 +1,7 @@
 // The stages over whole images that follow a frame -- the denoiser, the firefly cascade's reweighting,
-// the ID mattes' ranking and extraction, the light groups' mix, the depth cuts' layers -- and the frames
-// of the first-hit AOVs, the followed guides, the light groups and the depth cuts; included by render.hip
-// after render_frame.  Every stage has the same two layers:
+// the ID mattes' ranking and extraction, the light groups' mix, the depth cuts' layers, the cost grid's
+// image -- and the frames of the first-hit AOVs, the followed guides, the light groups, the depth cuts and
+// the cost image; included by render.hip after render_frame.  Every stage has the same two layers:
 //   X_device   its kernels over images of a view (Images, render.hip), named by their positions in it;
 //   X_host     host images through the first device: upload, X_device, download (host_stage);
 //   render_X   a frame into device images of the first device, X_device over them there, and what the
@@ -494,6 +494,100 @@ int render_depth_cuts(nart_ctx* ctx, const nart_render_params* p, const uint32_t
     const int rc = render_frame(ctx, p, plan, rq, stats);
     for (const nart_ctx* c : ctx->subs) ctx->dc_ms[0] = std::max(ctx->dc_ms[0], c->dc_ms[0]);  // the slowest device's
     return rc;
+}
+
+// ---------------------------------------------------------------- cost image (device/cost.h)
+// The grid of traced pixels of p (include/nart_hip.h, "Cost image"): RenderTile's x, y range.
+void cost_grid_of(const nart_render_params* p, uint32_t* w, uint32_t* h) {
+    nart_session_geometry g;
+    nart_session_geometry_of(p, &g);
+    *w = std::min(p->bucket_size * g.n_buckets_x, g.total_width);
+    *h = std::min(p->bucket_size * g.n_buckets_y, g.total_height);
+}
+
+// A host cost grid into image `out` of the view; synchronous.  The time goes to the view's context
+// (cost_ms[1]).
+int cost_image_device(const Images& v, const nart_render_params* p, const nart_cost_pixel* cost, int out, hipStream_t st) {
+    nart_ctx* ctx = v.ctx;
+    CostImageArgs a;
+    cost_grid_of(p, &a.grid_w, &a.grid_h);
+    const size_t n = (size_t)a.grid_w * a.grid_h;
+    Buf grid;  // the grid on the device; freed on return
+    if (int rc = reserve(ctx, grid, ctx->device, n * sizeof(uint4), "cost grid")) return rc;
+    HIPCHK(hipMemcpy(grid.as<void>(), cost, n * sizeof(uint4), hipMemcpyHostToDevice));
+    a.grid = grid.as<uint4>();
+    a.out = v.at(out);
+    a.spp = p->spp;
+    v.layout.fill(a);
+    if (int rc = v.zero_async(out, 1, st)) return rc;
+    return timed(ctx, ctx->ev_cost_img, st, &ctx->cost_ms[1], [&]() -> int {
+        hipLaunchKernelGGL(k_cost_image, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, a);
+        HIPCHK(hipGetLastError());
+        return NART_OK;
+    });
+}
+
+// nart_hip_cost_image.
+int cost_image_host(nart_ctx* ctx, const nart_render_params* p, const nart_cost_pixel* cost, nart_pixel* image) {
+    first_device(ctx)->cost_ms[1] = 0.0;  // (the image's time is kept where it runs)
+    if (!ctx->subs.empty()) return forwarded(ctx, cost_image_host(first_device(ctx), p, cost, image));
+    Buf imgs;  // the image; freed on return
+    return host_stage(ctx, p, imgs, "cost image", {}, image, 1,
+                      [&](const Images& v) { return cost_image_device(v, p, cost, 0, 0); });
+}
+
+// A cost frame's grid on one device's context: sized for p and zero (every device of a multi-device
+// context reduces its own buckets into its own grid).
+int cost_grid_begin(nart_ctx* ctx, uint32_t gw, uint32_t gh) {
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)gw * gh * sizeof(uint4);
+    if (int rc = reserve(ctx, ctx->d_cost_grid, ctx->device, bytes, "cost grid")) return rc;
+    HIPCHK(hipMemset(ctx->d_cost_grid.as<void>(), 0, bytes));
+    ctx->cost_grid_w = gw;
+    ctx->cost_grid_h = gh;
+    return NART_OK;
+}
+
+// nart_hip_render_cost: the beauty (if asked for) and the cost grid.  The devices' grids are added on
+// the host: every pixel is non-zero on exactly one of them.
+int render_cost(nart_ctx* ctx, const nart_render_params* p, nart_cost_pixel* cost, nart_pixel* image,
+                nart_render_stats* stats) {
+    ctx->cost_ms[0] = 0.0;
+    FrameAsk ask(p->integrator);
+    ask.cost = true;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    if (plan.code) return fail(ctx, plan.code, plan.message);  // (before anything is allocated)
+    int rc = forwarded(ctx, check_params(first_device(ctx), p));
+    if (rc) return rc;
+    uint32_t gw = 0, gh = 0;
+    cost_grid_of(p, &gw, &gh);
+    std::vector<nart_ctx*> devs = ctx->subs;
+    if (devs.empty()) devs.push_back(ctx);
+    for (nart_ctx* c : devs)
+        if ((rc = cost_grid_begin(c, gw, gh))) return c == ctx ? rc : fail(ctx, rc, c->err);
+    TileGrowthGuard guard(ctx);
+    FrameRequest rq;
+    rq.to_host(plan, OutputKind::Beauty, image);
+    if ((rc = render_frame(ctx, p, plan, rq, stats))) return rc;
+    const size_t n = (size_t)gw * gh;
+    std::vector<nart_cost_pixel> part(devs.size() > 1 ? n : 0);
+    for (size_t d = 0; d < devs.size(); ++d) {
+        nart_ctx* c = devs[d];
+        nart_cost_pixel* dst = d ? part.data() : cost;
+        if (hipSetDevice(c->device) != hipSuccess ||
+            hipMemcpy(dst, c->d_cost_grid.as<void>(), n * sizeof(uint4), hipMemcpyDeviceToHost) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, NART_E_HIP, "copy cost grid");
+        }
+        for (size_t i = 0; d && i < n; ++i) {
+            cost[i].rays_extend += dst[i].rays_extend;
+            cost[i].rays_shadow += dst[i].rays_shadow;
+            cost[i].hits += dst[i].hits;
+            cost[i].steps += dst[i].steps;
+        }
+        ctx->cost_ms[0] = std::max(ctx->cost_ms[0], c->cost_ms[0]);  // the slowest device's
+    }
+    return NART_OK;
 }
 
 }  // namespace

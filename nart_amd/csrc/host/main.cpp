@@ -58,6 +58,13 @@
 //   --depth-layers  with --depth-cuts: also write <out>.layer.00.exr ... <out>.layer.0K.exr, the light each
 //                   range of bounces added (nart_hip_depth_layers): the first cut, the differences of
 //                   neighbouring cuts, the beauty minus the last cut
+//   --cost          also write every session's cost image (nart_hip_render_cost, nart_hip_cost_image) to
+//                   <out>.cost.exr: RGBA the per-sample means of extension rays, shadow rays, shaded hits
+//                   and traversal steps (BVH node visits plus triangle tests) of every pixel of the
+//                   cropped window, in half precision -- a mean above 65504 is written as inf -- and
+//                   print the four totals; <out>.exr is the same call's beauty.  Not offered together
+//                   with --depth-cuts, --light-groups, --adaptive, --robust, --mattes, --aovs, --denoise
+//                   or --follow-specular: an error
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -386,6 +393,13 @@ int main(int argc, char* argv[]) {
             pos = c + 1;
         }
     }
+    // --cost
+    const bool cost = take_flag(args, "--cost");
+    if (cost && (depth_cuts || light_groups || adaptive_arg || robust || mattes || aovs || denoise || follow)) {
+        std::fprintf(stderr, "Error: --cost is not offered together with --depth-cuts, --light-groups, --adaptive, --robust, "
+                             "--mattes, --aovs, --denoise or --follow-specular\n");
+        return EXIT_FAILURE;
+    }
     nart_adaptive_params ap;
     nart_hip_adaptive_params_init(&ap);
     if (adaptive) {
@@ -471,8 +485,28 @@ int main(int argc, char* argv[]) {
         const bool mattes_after = mattes && (aovs || denoise);
         if (denoise) denoised.resize(image.size());
         std::vector<uint32_t> bucket_spp;
-        std::vector<nart_pixel> group_imgs, mix_img, cut_imgs, layer_imgs;
-        if (depth_cuts) {
+        std::vector<nart_pixel> group_imgs, mix_img, cut_imgs, layer_imgs, cost_img;
+        if (cost) {
+            uint32_t gw = 0, gh = 0;
+            rc = nart_hip_cost_grid(&p, &gw, &gh);
+            std::vector<nart_cost_pixel> grid((size_t)gw * gh);
+            if (rc == NART_OK) rc = nart_hip_render_cost(ctx, &p, grid.data(), image.data(), nullptr);
+            if (rc == NART_OK) {
+                cost_img.resize(image.size());
+                rc = nart_hip_cost_image(ctx, &p, grid.data(), cost_img.data());
+            }
+            if (rc == NART_OK) {
+                unsigned long long t[4] = {0, 0, 0, 0};
+                for (const nart_cost_pixel& c : grid) {
+                    t[0] += c.rays_extend;
+                    t[1] += c.rays_shadow;
+                    t[2] += c.hits;
+                    t[3] += c.steps;
+                }
+                std::printf("Cost: %llu extension rays, %llu shadow rays, %llu shaded hits, %llu traversal steps\n", t[0], t[1],
+                            t[2], t[3]);
+            }
+        } else if (depth_cuts) {
             cut_imgs.resize(cuts.size() * image.size());
             rc = nart_hip_render_depth_cuts(ctx, &p, cuts.data(), (uint32_t)cuts.size(), cut_imgs.data(), image.data(), nullptr);
             if (rc == NART_OK && depth_layers) {
@@ -600,6 +634,7 @@ int main(int argc, char* argv[]) {
             extra.push_back({".depth." + two(cuts[i]) + ".exr", cut_imgs.data() + i * image.size()});
         for (size_t i = 0; depth_layers && i <= cuts.size(); ++i)
             extra.push_back({".layer." + two((uint32_t)i) + ".exr", layer_imgs.data() + i * image.size()});
+        if (cost) extra.push_back({".cost.exr", cost_img.data()});
         std::vector<nart_pixel> spp_img;
         if (adaptive) {
             // pixel (x, y) of the cropped image was traced by bucket (x / B, y / B)

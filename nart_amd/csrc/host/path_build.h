@@ -37,6 +37,8 @@ struct PathBuildIn {
     bool light_groups = false;
     // the depth-cut build (include/nart_hip.h, "Depth cuts"): the light groups' rule
     bool depth_cuts = false;
+    // the cost build (include/nart_hip.h, "Cost image"): the light groups' rule
+    bool cost = false;
     uint32_t bounces = 0;
     int variant = 0;  // 0: the ray-queue kernel where its LDS fits; 3: k_render
     uint32_t stack_depth = 1, num_nodes = 0;  // of the scene's BVH
@@ -54,9 +56,10 @@ struct BuildId {
     bool pr = true;
     bool lg = false;  // the light-group build of k_render_rq
     bool dc = false;  // the depth-cut build of k_render_rq
+    bool cs = false;  // the cost build of k_render_rq
     bool operator==(const BuildId& o) const {
         return ext == o.ext && count == o.count && env == o.env && fm == o.fm && wv == o.wv && pr == o.pr && lg == o.lg &&
-               dc == o.dc;
+               dc == o.dc && cs == o.cs;
     }
 };
 
@@ -141,6 +144,15 @@ inline PathBuild plan_build(const PathBuildIn& in) {
             b.error = "depth cuts need the ray-queue kernel: not variant 3, nor a BVH deeper than its LDS holds";
             b.unsupported = true;
         }
+    } else if (in.cost) {
+        // As for light groups: work that may be dropped (a doomed speculative job's rays) would enter the
+        // traversal steps, which must depend on the sample alone, and the counter pass has no cost build:
+        // its records are the counts.
+        id.cs = true;
+        if (!b.rq) {
+            b.error = "the cost image needs the ray-queue kernel: not variant 3, nor a BVH deeper than its LDS holds";
+            b.unsupported = true;
+        }
     } else if (in.specialize != Specialize::Off && !in.counters && in.bounces <= ILIST_REG) {
         if (!in.has_env && covers(FM_DIFFUSE)) id.fm = FM_DIFFUSE;
         else if (!in.has_env && covers(FM_GLASS)) id.fm = FM_GLASS;
@@ -150,8 +162,8 @@ inline PathBuild plan_build(const PathBuildIn& in) {
         // a path grows the dielectric list by at most one entry per bounce: the register list alone
         // serves bounces <= ILIST_REG; deeper ones (up to 32) spill it to the per-lane columns
         id.ext = in.bounces > ILIST_REG;
-        id.count = in.counters && !id.lg && !id.dc;
-        if (id.lg || id.dc) id.pr = false;
+        id.count = in.counters && !id.lg && !id.dc && !id.cs;
+        if (id.lg || id.dc || id.cs) id.pr = false;
     } else {
         // The lean three-waves-per-SIMD build (kernels.h WV = 3) for throughput-bound launches.  It raises
         // throughput (C3 whole frame, 16 rounds of resident waves: path kernels 276.6 -> ~241 ms; C4 4K

@@ -19,6 +19,7 @@
 #include "../../include/nart_hip.h"
 #include "device/adaptive.h"
 #include "device/cascade.h"
+#include "device/cost.h"
 #include "device/denoise.h"
 #include "device/depthcut.h"
 #include "device/guide.h"
@@ -128,6 +129,14 @@ struct nart_ctx {
     uint32_t depth_cuts[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_depth_cuts = 0;
     Event ev_layers[2];
     double dc_ms[2] = {0.0, 0.0};
+    // cost image: the grid of traced pixels a cost frame reduces its batches' records into (uint4 per
+    // pixel, sized and zeroed by render_cost at the start of the frame, one per device), its size; events
+    // around a batch's reduce (render_buckets) and around k_cost_image (cost_image_device); the last
+    // call's times: reduce ([0] on the caller's context), image ([1] on the first device's)
+    Buf d_cost_grid;
+    uint32_t cost_grid_w = 0, cost_grid_h = 0;
+    Event ev_cost[2], ev_cost_img[2];
+    double cost_ms[2] = {0.0, 0.0};
     // denoiser (denoise_device): work buffers over the cropped image, the four device images of
     // nart_hip_denoise / nart_hip_render_denoised (five with the moment image), events between its
     // kernels, the last run's times
@@ -892,10 +901,11 @@ void launch_primary(nart_ctx* ctx, const RenderArgs& pa, hipStream_t st) {
 // The template parameters are the kernel builds of `B.id` (dispatch_megakernel's table), `B` their LDS
 // layout (host/path_build.h plan_build); host/path_schedule.h plan_path decides the rest.
 // resident_k: resident blocks of k_render (dispatch_megakernel's occupancy query).
-template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false, bool DC = false>
+template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false, bool DC = false,
+          bool CS = false>
 int launch_render(nart_ctx* ctx, const RenderArgs& a_in, const PathBuild& B, uint32_t resident_k, hipStream_t st) {
     auto kern = k_render<EXT, COUNT, ENV>;
-    auto kern_rq = k_render_rq<EXT, COUNT, ENV, FM, WV, PR, LG, DC>;
+    auto kern_rq = k_render_rq<EXT, COUNT, ENV, FM, WV, PR, LG, DC, CS>;
     const uint32_t RQB = B.rq_block;
     RenderArgs a = a_in;
     int rc = EXT ? ensure_ilist(ctx, a) : NART_OK;
@@ -916,8 +926,10 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, const PathBuild& B, uin
     uint32_t resident_rq = 1;
     if (rq && (rc = resident_blocks(ctx, (const void*)kern_rq, RQB, lds_rq, &resident_rq))) return rc;
 
+    // (a cost frame leaves the camera rays to the path kernel: k_primary's packets would count a wave's
+    // union of steps, not the ray's own)
     const PathLaunchIn in{a.n_slots, resident_k, resident_rq * (RQB / 256), RQB, WV, PR, ENV, rq, FM != FT_ALL,
-                          (bool)ctx->d_prim && a.cost == nullptr};
+                          (bool)ctx->d_prim && a.cost == nullptr && !CS};
     const PathSchedule plan = plan_path(in, read_sched_knobs());
     if (plan.error) return fail(ctx, NART_E_INVALID, plan.error);
     ctx->sched |= plan.sched;
@@ -946,6 +958,7 @@ int launch_render(nart_ctx* ctx, const RenderArgs& a_in, const PathBuild& B, uin
     if (!rq) {
         if (LG) return fail(ctx, NART_E_UNSUPPORTED, "light groups need the ray-queue kernel");  // (plan_build refuses it first)
         if (DC) return fail(ctx, NART_E_UNSUPPORTED, "depth cuts need the ray-queue kernel");    // (likewise)
+        if (CS) return fail(ctx, NART_E_UNSUPPORTED, "the cost image needs the ray-queue kernel");  // (likewise)
         hipLaunchKernelGGL(kern, dim3(plan.blocks), dim3(256), lds, st, ctx->scene, b);
         HIPCHK(hipGetLastError());
         return NART_OK;
@@ -972,9 +985,10 @@ struct BuildRow {
     BuildId id;
     RenderLauncher launch;
 };
-template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false, bool DC = false>
+template <bool EXT, bool COUNT, bool ENV, uint32_t FM = FT_ALL, int WV = 2, bool PR = true, bool LG = false, bool DC = false,
+          bool CS = false>
 BuildRow build_row() {
-    return {BuildId{EXT, COUNT, ENV, FM, WV, PR, LG, DC}, launch_render<EXT, COUNT, ENV, FM, WV, PR, LG, DC>};
+    return {BuildId{EXT, COUNT, ENV, FM, WV, PR, LG, DC, CS}, launch_render<EXT, COUNT, ENV, FM, WV, PR, LG, DC, CS>};
 }
 
 int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
@@ -985,6 +999,7 @@ int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
     in.counters = ctx->counters;
     in.depth_cuts = a.n_groups != 0 && a.cuts[0] != 0;  // (the record arrays are the cuts' where cuts are given)
     in.light_groups = a.n_groups != 0 && !in.depth_cuts;
+    in.cost = a.cost_rec != nullptr;
     in.bounces = a.bounces;
     in.variant = ctx->variant;
     in.stack_depth = ctx->stack_depth;
@@ -999,8 +1014,8 @@ int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
     read_build_knobs(in);
     const PathBuild B = plan_build(in);
     if (B.error) return fail(ctx, B.unsupported ? NART_E_UNSUPPORTED : NART_E_INVALID, B.error);
-    // every build plan_build can name (tests/test_path_build.py, test_path_build_lights.py and
-    // test_path_build_depth.py hold the same list; new rows go at the end).  The compiler emits
+    // every build plan_build can name (tests/test_path_build.py, test_path_build_lights.py,
+    // test_path_build_depth.py and test_path_build_cost.py hold the same list; new rows go at the end).  The compiler emits
     // the kernels in the order of the rows: keep it, and the gfx950 code object stays byte for byte the same
     static const BuildRow builds[] = {
         build_row<false, false, false, FM_DIFFUSE, 3, false>(),  // scene-specialised: lean, two waves per SIMD
@@ -1025,6 +1040,10 @@ int dispatch_megakernel(nart_ctx* ctx, const RenderArgs& a, hipStream_t st) {
         build_row<true, false, true, FT_ALL, 2, false, false, true>(),
         build_row<false, false, false, FT_ALL, 2, false, false, true>(),
         build_row<true, false, false, FT_ALL, 2, false, false, true>(),
+        build_row<false, false, true, FT_ALL, 2, false, false, false, true>(),  // cost image: EXT x ENV
+        build_row<true, false, true, FT_ALL, 2, false, false, false, true>(),
+        build_row<false, false, false, FT_ALL, 2, false, false, false, true>(),
+        build_row<true, false, false, FT_ALL, 2, false, false, false, true>(),
     };
     for (const BuildRow& row : builds)
         if (row.id == B.id) return row.launch(ctx, a, B, in.resident_k, st);
@@ -1440,6 +1459,14 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
     const uint32_t K = beauty && !G ? frame.ask.depth_cuts : 0u;
     if (K && ctx->n_depth_cuts != K) return fail(ctx, NART_E_INVALID, "no depth cuts were set");
     const uint32_t R = G ? G : K;
+    // cost image: the batch's cost records, and the grid of this device they are reduced into
+    Buf cost_records;  // one uint4 per sample of the batch; freed on return
+    const bool CS = beauty && frame.ask.cost;
+    if (CS && (!ctx->d_cost_grid || ctx->d_cost_grid.bytes() < (size_t)ctx->cost_grid_w * ctx->cost_grid_h * sizeof(uint4) ||
+               ctx->cost_grid_w != std::min(p->bucket_size * g.n_buckets_x, g.total_width) ||
+               ctx->cost_grid_h != std::min(p->bucket_size * g.n_buckets_y, g.total_height)))
+        return fail(ctx, NART_E_INVALID, "no cost grid was set");
+    double cost_ms = 0.0;
     double group_ms = 0.0;
     const uint32_t tpx = g.tile_size * g.tile_size;
     const BucketGrid grid{p->bucket_size, g.n_buckets_x, g.total_width, g.total_height, p->image_width, p->image_height};
@@ -1478,6 +1505,11 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         }
         // (the cut records need no memset: the owner lane writes every one in full)
         for (uint32_t j = 0; j < K; ++j) ra.cuts[j] = ctx->depth_cuts[j];
+        if (CS) {
+            // (no memset: the owner lane writes every record in full)
+            if ((rc = reserve(ctx, cost_records, ctx->device, ns * sizeof(uint4), "cost records"))) return rc;
+            ra.cost_rec = cost_records.as<uint4>();
+        }
         // LatinSquare, path kernel, the beauty's splat
         HIPCHK(record(ctx->ev_latin0, st));
         rc = launch_latin(ctx, ra, st);
@@ -1513,6 +1545,23 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
             HIPCHK(record(ctx->ev_lg[1], st));
             last = ctx->ev_lg[1].handle();
         }
+        if (CS) {
+            // the batch's cost records summed per slot into the grid (every pixel belongs to one batch)
+            CostReduceArgs ca;
+            ca.records = cost_records.as<uint4>();
+            ca.slot_xy = ctx->d_slot_xy.as<uint32_t>();
+            ca.slot_so = ctx->d_slot_so.as<SlotSO>();
+            ca.grid = ctx->d_cost_grid.as<uint4>();
+            ca.n_slots = nslots;
+            ca.spp = p->spp;
+            ca.grid_w = ctx->cost_grid_w;
+            ca.grid_h = ctx->cost_grid_h;
+            HIPCHK(record(ctx->ev_cost[0], st));
+            hipLaunchKernelGGL(k_cost_reduce, dim3((nslots + 255) / 256), dim3(256), 0, st, ca);
+            HIPCHK(hipGetLastError());
+            HIPCHK(record(ctx->ev_cost[1], st));
+            last = ctx->ev_cost[1].handle();
+        }
         // the frame plan's passes
         for (uint32_t i = 0; i < frame.n_passes; ++i) {
             const PassKind pass = frame.passes[i];
@@ -1547,10 +1596,16 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         // one stream: waiting for the last event recorded is waiting for all of them
         HIPCHK(hipEventSynchronize(last));
         if ((rc = read_batch_times(ctx, frame, R != 0, acc, times, group_ms))) return rc;
+        if (CS) {
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, ctx->ev_cost[0].handle(), ctx->ev_cost[1].handle()));
+            cost_ms += ms;
+        }
         if (beauty) ++acc.kernel_launches;
     }
     if (G) ctx->lg_ms[0] = group_ms;
     if (K) ctx->dc_ms[0] = group_ms;
+    if (CS) ctx->cost_ms[0] = cost_ms;
     if (stats) {
         acc.schedule = ctx->sched;
         acc.samples = counted * p->spp;
@@ -2526,6 +2581,56 @@ int nart_hip_depth_cut_timings(const nart_ctx* ctx, double* splat_ms, double* la
     if (!ctx) return NART_E_INVALID;
     if (splat_ms) *splat_ms = ctx->dc_ms[0];
     if (layers_ms) *layers_ms = first_device(ctx)->dc_ms[1];
+    return NART_OK;
+}
+
+int nart_hip_cost_grid(const nart_render_params* p, uint32_t* width, uint32_t* height) {
+    if (!p || !width || !height) return NART_E_INVALID;
+    if (check_image_size(p) || !p->bucket_size) return NART_E_INVALID;
+    cost_grid_of(p, width, height);
+    return NART_OK;
+}
+
+int nart_hip_render_cost(nart_ctx* ctx, const nart_render_params* p, nart_cost_pixel* cost, nart_pixel* beauty,
+                         nart_render_stats* stats) {
+    if (!ctx || !p) return NART_E_INVALID;
+    if (!cost) return fail(ctx, NART_E_INVALID, "the cost grid is required");
+    return render_cost(ctx, p, cost, beauty, stats);
+}
+
+int nart_hip_render_cost_samples(nart_ctx* ctx, const nart_render_params* p, uint32_t x0, uint32_t y0, uint32_t w,
+                                 uint32_t h, uint32_t* records) {
+    if (!ctx || !p || !records) return NART_E_INVALID;
+    if (!ctx->subs.empty())  // per-sample debugging runs on the first device
+        return forwarded(ctx, nart_hip_render_cost_samples(first_device(ctx), p, x0, y0, w, h, records));
+    int rc = check_params(ctx, p);
+    if (rc) return rc;
+    if (p->integrator == NART_INTEGRATOR_VOLUME)  // (frames: plan_frame's rule)
+        return fail(ctx, NART_E_UNSUPPORTED, "the cost image needs the path integrator: the volume integrator has no cost build");
+    if (!w || !h) return fail(ctx, NART_E_INVALID, "empty rect");
+    if ((rc = counter_buffer(ctx))) return rc;
+    RenderArgs ra;
+    if ((rc = rect_slots(ctx, p, x0, y0, w, h, ctx->d_counters.as<unsigned long long>(), ra))) return rc;
+    const size_t ns = (size_t)ra.n_slots * p->spp;
+    Buf rec;  // the record array; freed on return
+    if ((rc = reserve(ctx, rec, ctx->device, ns * sizeof(uint4), "cost records"))) return rc;
+    ra.cost_rec = rec.as<uint4>();
+    if ((rc = launch_latin(ctx, ra, 0)) || (rc = dispatch_render(ctx, ra, p->integrator, 0))) return rc;
+    HIPCHK(hipMemcpy(records, rec.as<uint4>(), ns * sizeof(uint4), hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+int nart_hip_cost_image(nart_ctx* ctx, const nart_render_params* p, const nart_cost_pixel* cost, nart_pixel* image) {
+    if (!ctx || !p) return NART_E_INVALID;
+    if (!cost || !image) return fail(ctx, NART_E_INVALID, "the cost grid and the image are required");
+    if (const char* why = check_image_size(p)) return fail(ctx, NART_E_INVALID, why);
+    return cost_image_host(ctx, p, cost, image);
+}
+
+int nart_hip_cost_timings(nart_ctx* ctx, double* reduce_ms, double* image_ms) {
+    if (!ctx) return NART_E_INVALID;
+    if (reduce_ms) *reduce_ms = ctx->cost_ms[0];
+    if (image_ms) *image_ms = first_device(ctx)->cost_ms[1];
     return NART_OK;
 }
 
