@@ -905,6 +905,45 @@ enum {
 };
 int nart_hip_eval(nart_ctx* ctx, uint32_t op, uint32_t fm, const float* in, uint32_t n, float* out);
 
+/* Device trace probe (test hook, never launched by a render): n caller-supplied rays against the
+   context's own device scene (its BVH, permuted triangle records and octree tables), each answered by
+   one of the render kernels' traversal entry points, one lane per ray, 256-lane blocks.
+
+   in: n records of NART_TRACE_IN_WORDS (8) words: 0-2 origin, 3 tmax, 4-6 direction (used as given,
+   not normalised), 7 u32 query kind (NART_TRACE_CLOSEST, NART_TRACE_ANY).
+   out: n records of NART_TRACE_OUT_WORDS (32) u32 words:
+     0      closest: the winning scene triangle or NART_TRACE_NO_HIT; any: 1 (a hit exists) or 0
+     1      closest: the bits of t (tmax on a miss); any: 0
+     2-5    with count != 0 the lane's TraceCounters: nodes, triangle tests, exact octree ancestor
+            checks, octree replays; else 0
+     6-25   closest hit only (else 0): the Isect that fill_isect produces, as float bits: 6-8 p,
+            9-11 gn, 12-14 sn, 15-17 dpds, 18-20 dpdt, 21-22 st; u32 23 meshID, 24 priority, 25 material
+     26-31  0
+
+   variant: which entry point answers.
+     NART_TRACE_PLAIN     traverse<>, no node in LDS (k_guide, k_primary's per-lane form); LDS: their stack
+     NART_TRACE_LDS       traverse<> over the top nodes staged by stage_nodes (k_render); LDS: k_render's layout
+     NART_TRACE_STEP      trav_begin / trav_step / oc_resolve as k_render_rq runs them, nodes staged
+     NART_TRACE_STEP_ROT  ... with the rotated node quarters of the environment-light builds
+     NART_TRACE_PACKET    traverse_packet, one wave per 64 consecutive records (closest queries only;
+                          the last wave may be partial); LDS: k_primary_px's wave stacks
+   sk (the STEP variants; the others ignore it): 0 = the whole stack in LDS (the two-wave builds); 1 ..
+   stack_depth = the lean build's short stack, sk levels in LDS and the rest in a per-thread global
+   column.  The staged node count is what a 256-lane ray-queue block with that stack would stage.
+
+   NART_E_INVALID: a null pointer, an unknown variant, sk above the context's stack depth, n above
+   NART_EVAL_MAX_N, a query kind other than the two, an any-hit record under NART_TRACE_PACKET.  n == 0: NART_OK, nothing launched.  Multi-device contexts run it on their first device. */
+#define NART_TRACE_IN_WORDS 8
+#define NART_TRACE_OUT_WORDS 32
+#define NART_TRACE_NO_HIT 0xFFFFFFFFu
+enum { NART_TRACE_CLOSEST = 0, NART_TRACE_ANY = 1 };
+enum {
+    NART_TRACE_PLAIN = 0, NART_TRACE_LDS = 1, NART_TRACE_STEP = 2, NART_TRACE_STEP_ROT = 3, NART_TRACE_PACKET = 4,
+    NART_TRACE_N_VARIANTS = 5
+};
+int nart_hip_trace(nart_ctx* ctx, uint32_t variant, uint32_t sk, int count, const float* in, uint32_t n,
+                   uint32_t* out);
+
 /* Splat filter-index thresholds (host only, no device): thr65[k] = the least d2 whose AddSample
    filter index (render.cpp:43-49) is >= k.  NART_E_INVALID when filter_width is too small for
    them (the splat then evaluates sqrt and division per pair). */

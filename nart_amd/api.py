@@ -87,6 +87,22 @@ EVAL_OPS = {"acosf": 0, "atanf": 1, "atan2f": 2, "logf": 3, "logf_lds": 4, "sinc
             "uniform_sample_ring": 13, "cosine_sample_hemisphere": 14, "uniform_sample_sphere": 15,
             "sample_wh": 16, "fresnel": 17, "bxdf_f": 18, "bxdf_pdf": 19, "bxdf_f_pdf": 20, "bxdf_sample_f": 21}
 EVAL_WORDS = 16  # floats per probe record (NART_EVAL_WORDS)
+# nart_hip_trace (include/nart_hip.h): the traversal entry point that answers, and its records
+TRACE_VARIANTS = {"plain": 0, "lds": 1, "step": 2, "step_rot": 3, "packet": 4}
+TRACE_IN_WORDS, TRACE_OUT_WORDS, TRACE_NO_HIT = 8, 32, 0xFFFFFFFF
+TRACE_CLOSEST, TRACE_ANY = 0, 1
+
+
+def trace_rays(o, d, tmax=np.inf, kind=TRACE_CLOSEST):
+    """(n, 8) float32 records of nart_hip_trace / oracle_trace_n from origins and directions (n, 3),
+    tmax and query kind (scalars or (n,))."""
+    o = np.asarray(o, np.float32).reshape(-1, 3)
+    r = np.zeros((len(o), TRACE_IN_WORDS), np.float32)
+    r[:, 0:3] = o
+    r[:, 3] = np.asarray(tmax, np.float32)
+    r[:, 4:7] = np.asarray(d, np.float32).reshape(-1, 3)
+    r[:, 7] = np.broadcast_to(np.asarray(kind, np.uint32), (len(o),)).copy().view(np.float32)
+    return r
 # the feature masks the probe's templated ops are built for, with the BxDF kinds each creates
 # (path.h create_bsdf: 0 Lambert, 1 specular, 2 specular dielectric, 3 dielectric, 4 Torrance-Sparrow)
 EVAL_MASKS = {"all": (FT_ALL, (0, 1, 2, 3, 4)), "lambert": (0x1, (0,)), "specular": (0x2, (1, 4)),
@@ -308,6 +324,7 @@ _HIP_SIGS = {
     "nart_hip_set_counters": (ctypes.c_int, [_P, ctypes.c_int]),
     "nart_hip_eval_sincos": (ctypes.c_int, [_P, _P, ctypes.c_uint32, _P, _P]),
     "nart_hip_eval": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, _P, ctypes.c_uint32, _P]),
+    "nart_hip_trace": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, _P, ctypes.c_uint32, _P]),
     "nart_hip_set_variant": (ctypes.c_int, [_P, ctypes.c_int]),
     "nart_hip_set_splat_mode": (ctypes.c_int, [_P, ctypes.c_int]),
     "nart_hip_set_specialize": (ctypes.c_int, [_P, ctypes.c_int]),
@@ -1208,6 +1225,20 @@ class HipRenderer:
         out = np.zeros_like(x)
         self._check(self._lib.nart_hip_eval(self._ctx, EVAL_OPS[op] if isinstance(op, str) else int(op),
                                             FT_ALL if fm is None else int(fm), x.ctypes.data, len(x), out.ctypes.data))
+        return out
+
+    def trace(self, rays, variant="plain", sk=0, count=False):
+        """Device trace probe (nart_hip_trace): caller-supplied rays against this context's device scene,
+        answered by one of the render kernels' traversal entry points.  rays: (n, 8) float32 records
+        (trace_rays builds them); variant: a name or number of TRACE_VARIANTS; sk: the STEP variants'
+        LDS stack levels (0: the whole stack); count: also return the lanes' traversal counters.
+        Returns (n, 32) uint32 records (include/nart_hip.h documents the words)."""
+        x = np.ascontiguousarray(rays, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != TRACE_IN_WORDS:
+            raise ValueError("trace rays must be (n, %d) float32 records, got %r" % (TRACE_IN_WORDS, x.shape))
+        out = np.zeros((len(x), TRACE_OUT_WORDS), np.uint32)
+        self._check(self._lib.nart_hip_trace(self._ctx, TRACE_VARIANTS[variant] if isinstance(variant, str) else int(variant),
+                                             int(sk), 1 if count else 0, x.ctypes.data, len(x), out.ctypes.data))
         return out
 
     def close(self):

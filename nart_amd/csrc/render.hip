@@ -27,6 +27,7 @@
 #include "device/lightgroup.h"
 #include "device/matte.h"
 #include "device/probe.h"
+#include "device/trace_probe.h"
 #include "device/volume.h"
 #include "host/bucket_batch.h"
 #include "host/bvh_build.h"
@@ -2929,6 +2930,71 @@ int nart_hip_eval(nart_ctx* ctx, uint32_t op, uint32_t fm, const float* in, uint
     hipLaunchKernelGGL(k_probe, dim3((n + 255) / 256), dim3(256), 0, 0, op, fm, di, n, dout);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+int nart_hip_trace(nart_ctx* ctx, uint32_t variant, uint32_t sk, int count, const float* in, uint32_t n, uint32_t* out) {
+    if (!ctx || !in || !out || variant >= NART_TRACE_N_VARIANTS || n > NART_EVAL_MAX_N) return NART_E_INVALID;
+    if (!ctx->subs.empty()) return nart_hip_trace(first_device(ctx), variant, sk, count, in, n, out);
+    const bool step = variant == NART_TRACE_STEP || variant == NART_TRACE_STEP_ROT;
+    if (step && sk > ctx->stack_depth) return NART_E_INVALID;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t kind;
+        std::memcpy(&kind, in + (size_t)i * NART_TRACE_IN_WORDS + 7, 4);
+        if (kind > NART_TRACE_ANY || (kind == NART_TRACE_ANY && variant == NART_TRACE_PACKET)) return NART_E_INVALID;
+    }
+    if (!n) return NART_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    Buf bi, bo, bg;  // freed on return
+    int rc = NART_OK;
+    const size_t bytes_in = (size_t)n * NART_TRACE_IN_WORDS * 4, bytes_out = (size_t)n * NART_TRACE_OUT_WORDS * 4;
+    if ((rc = reserve(ctx, bi, ctx->device, bytes_in, "trace probe rays"))) return rc;
+    if ((rc = reserve(ctx, bo, ctx->device, bytes_out, "trace probe records"))) return rc;
+    const uint32_t depth = ctx->stack_depth, grid = (n + 255) / 256;
+    TraceProbeArgs P;
+    P.in = bi.as<float>();
+    P.out = bo.as<uint32_t>();
+    P.n = n;
+    P.stack_depth = depth;
+    // LDS as the render launch of the same entry point sizes it: the per-lane stack alone (k_guide,
+    // k_primary), k_render's layout, a 256-lane ray-queue block's stack and staged nodes, the wave stacks
+    size_t lds = (size_t)depth * 256 * 8;
+    const void* kern = nullptr;
+    if (variant == NART_TRACE_PLAIN || variant == NART_TRACE_LDS) {
+        if (variant == NART_TRACE_LDS) {
+            const LdsLayout l = k_render_layout(depth, ctx->num_nodes);
+            P.lds_nodes = l.nodes;
+            lds = l.bytes;
+        }
+        kern = count ? (const void*)k_trace_probe<true> : (const void*)k_trace_probe<false>;
+    } else if (step) {
+        const bool rot = variant == NART_TRACE_STEP_ROT, sh = sk != 0;
+        const uint32_t lv = sh ? sk : depth;
+        P.sk = lv;
+        P.lds_nodes = staged_nodes(ctx->num_nodes, rq_lds_bytes(lv, 256), CU_LDS_BYTES);
+        lds = (size_t)lv * 256 * 8 + node_lds_bytes(P.lds_nodes);
+        if (sh && lv < depth) {
+            if ((rc = reserve(ctx, bg, ctx->device, (size_t)grid * 256 * (depth - lv) * sizeof(int2), "trace probe stack columns")))
+                return rc;
+            P.gstack = bg.as<int2>();
+        }
+        const void* tab[2][2][2] = {
+            {{(const void*)k_trace_probe_step<false, false, false>, (const void*)k_trace_probe_step<false, false, true>},
+             {(const void*)k_trace_probe_step<false, true, false>, (const void*)k_trace_probe_step<false, true, true>}},
+            {{(const void*)k_trace_probe_step<true, false, false>, (const void*)k_trace_probe_step<true, false, true>},
+             {(const void*)k_trace_probe_step<true, true, false>, (const void*)k_trace_probe_step<true, true, true>}}};
+        kern = tab[count ? 1 : 0][rot ? 1 : 0][sh ? 1 : 0];
+    } else {
+        lds = (size_t)depth * 4 * sizeof(uint4);
+        kern = count ? (const void*)k_trace_probe_packet<true> : (const void*)k_trace_probe_packet<false>;
+    }
+    if (lds > (size_t)160 * 1024) return fail(ctx, NART_E_UNSUPPORTED, "trace probe LDS layout out of range");
+    HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipMemcpy(bi.as<float>(), in, bytes_in, hipMemcpyHostToDevice));
+    void* args[] = {(void*)&ctx->scene, (void*)&P};
+    HIPCHK(hipLaunchKernel(kern, dim3(grid), dim3(256), args, lds, 0));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, bo.as<uint32_t>(), bytes_out, hipMemcpyDeviceToHost));
     return NART_OK;
 }
 

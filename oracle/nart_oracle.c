@@ -165,6 +165,7 @@ typedef struct { /* Intersection (geometry.h:29-51) */
     float tMin, tMax;
     uint32_t meshID;
     uint32_t priority;
+    uint32_t tri; /* not a member of Intersection: the triangle Chunk::Intersect accepted last (oracle_trace_n) */
 } isect_t;
 static inline void isect_init(isect_t* i) {
     memset(i, 0, sizeof(*i));
@@ -176,11 +177,15 @@ static inline void isect_init(isect_t* i) {
 }
 static inline v3 tv(const float* a) { return V3(a[0], a[1], a[2]); }
 
+/* oracle_trace_n only (never set while a render runs): a second search in which a NaN plane distance is
+   rejected, to show whether the NaN decided the reference's answer */
+static int g_reject_nan = 0;
 static int triangle_intersect(const nart_triangle* T, const ray_t* ray, isect_t* is) { /* geometry.cpp:32-115 */
     v3 v0 = tv(T->v0), v1 = tv(T->v1), v2_ = tv(T->v2);
     v3 n = cross3(sub3(v1, v0), sub3(v2_, v0));
     float t = (dot3(v0, n) - dot3(ray->o, n)) / dot3(ray->d, n);
     if (t <= is->tMin || t >= is->tMax) return 0;
+    if (g_reject_nan && t != t) return 0;
     v3 p0 = sub3(v0, ray->o), p1 = sub3(v1, ray->o), p2 = sub3(v2_, ray->o);
     uint8_t M = ray->major;
     uint8_t m0 = (uint8_t)(M + 1);
@@ -445,6 +450,7 @@ static int chunk_intersect(const oracle_scene* s, const chunk_t* c, const ray_t*
             is->mat = (int32_t)m->material;
             is->meshID = s->tri_mesh[g];
             is->priority = m->priority;
+            is->tri = g;
         }
     }
     return hit;
@@ -1865,6 +1871,7 @@ uint32_t oracle_binary_search(float value, const float* v, uint32_t start, uint3
 }
 
 /* ---------------------------------------------------------------- debugging aids (tests/tools only) */
+static inline uint32_t f2bits_(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 /* Camera ray of pixel (x, y) with image sample (u, v) (pinholecamera.cpp:9-40). */
 void oracle_camera_ray(const oracle_scene* s, uint32_t W, uint32_t H, uint32_t x, uint32_t y, float u, float v,
                        float* o, float* d) {
@@ -1911,6 +1918,130 @@ void oracle_trace(const oracle_scene* s, const float* o, const float* d, float t
     }
     out[2] = bg;
     memcpy(&out[3], &bf.tMax, 4);
+}
+
+/* A hit before the ray enters its triangle's bounds, or on a ray that misses them (bounds grown by 2^-12 of
+   the coordinates involved): the ray lies in the triangle's plane, its 0 / 0 came out as a quotient of
+   roundings, and the edge test (which sees the triangle edge-on) passed. */
+static int trace_ghost(const nart_triangle* T, const ray_t* r, float t) {
+    const double tt = (double)t;
+    const float oo[3] = {r->o.x, r->o.y, r->o.z}, dd[3] = {r->d.x, r->d.y, r->d.z};
+    double te = 0.0, tx = INFINITY;
+    for (int k = 0; k < 3; ++k) {
+        double lo = gmin(gmin(T->v0[k], T->v1[k]), T->v2[k]), hi = gmax(gmax(T->v0[k], T->v1[k]), T->v2[k]);
+        const double slack = (fabs(lo) + fabs(hi) + fabs((double)oo[k]) + fabs(tt * dd[k])) * 0x1p-12;
+        lo -= slack;
+        hi += slack;
+        if (dd[k] == 0.f) {
+            if (oo[k] < lo || oo[k] > hi) tx = -1.0;
+            continue;
+        }
+        double s0 = (lo - oo[k]) / dd[k], s1 = (hi - oo[k]) / dd[k];
+        if (s0 > s1) { double x_ = s0; s0 = s1; s1 = x_; }
+        if (s0 > te) te = s0;
+        if (s1 < tx) tx = s1;
+    }
+    return te > tx || tt < te;
+}
+/* oracle_trace over n rays (nart_oracle.h): the CPU side of the device probe nart_hip_trace. */
+static int cmp_bits(const void* a, const void* b) {
+    uint32_t x = *(const uint32_t*)a, y = *(const uint32_t*)b;
+    return x < y ? -1 : (x > y ? 1 : 0);
+}
+int oracle_trace_n(const oracle_scene* s, const float* in, uint32_t n, uint32_t* out) {
+    if (!s || !in || !out) return -1;
+    const uint32_t nt = s->blob->num_triangles;
+    heap_t q = {0, 0, 0};
+    uint32_t* acc = (uint32_t*)malloc((size_t)(nt ? nt : 1) * sizeof(uint32_t));
+    if (!acc) return -1;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* x = in + (size_t)i * NART_TRACE_IN_WORDS;
+        uint32_t* y = out + (size_t)i * NART_TRACE_OUT_WORDS;
+        memset(y, 0, NART_TRACE_OUT_WORDS * sizeof(uint32_t));
+        const float tmax = x[3];
+        uint32_t kind;
+        memcpy(&kind, &x[7], 4);
+        ray_t r = make_ray(V3(x[0], x[1], x[2]), V3(x[4], x[5], x[6]));
+        /* the reference's search, tMax preset as the light loop presets it */
+        isect_t is;
+        isect_init(&is);
+        is.tMax = tmax;
+        const int hit = bvh_intersect(s, &r, &is, &q);
+        /* every triangle on its own against the preset tMax: the classes, and the strictly closest */
+        uint32_t flags = 0, na = 0;
+        isect_t bf;
+        isect_init(&bf);
+        bf.tMax = tmax;
+        uint32_t bg = 0xFFFFFFFFu;
+        for (uint32_t g = 0; g < nt; ++g) {
+            const nart_triangle* T = &s->blob->triangles[g];
+            v3 v0 = tv(T->v0), v1 = tv(T->v1), v2_ = tv(T->v2);
+            v3 nn = cross3(sub3(v1, v0), sub3(v2_, v0));
+            float t = (dot3(v0, nn) - dot3(r.o, nn)) / dot3(r.d, nn);
+            isect_t t1;
+            isect_init(&t1);
+            t1.tMax = tmax;
+            const int a = triangle_intersect(T, &r, &t1);
+            if (t != t) {
+                flags |= ORACLE_TRACE_NAN;
+                if (a) { /* Chunk::Intersect goes on with tMax = NaN: the search's answer can change */
+                    flags |= ORACLE_TRACE_NAN_ACCEPTED;
+                    for (int k = 0; k < 3; ++k) {
+                        float lo = gmin(gmin(T->v0[k], T->v1[k]), T->v2[k]), hi = gmax(gmax(T->v0[k], T->v1[k]), T->v2[k]);
+                        float ok = k == 0 ? r.o.x : (k == 1 ? r.o.y : r.o.z);
+                        if (ok < lo || ok > hi) flags |= ORACLE_TRACE_NAN_OUTSIDE;
+                    }
+                }
+                continue;
+            }
+            if (!a) continue;
+            if (trace_ghost(T, &r, t1.tMax)) flags |= ORACLE_TRACE_GHOST;
+            acc[na++] = f2bits_(t1.tMax);
+            if (t1.tMax < bf.tMax) {
+                bf = t1;
+                bg = g;
+            }
+        }
+        qsort(acc, na, sizeof(uint32_t), cmp_bits);
+        for (uint32_t k = 1; k < na; ++k)
+            if (acc[k] == acc[k - 1]) {
+                flags |= ORACLE_TRACE_TIE;
+                if (acc[k] == f2bits_(bf.tMax)) flags |= ORACLE_TRACE_TIE_CLOSEST;
+            }
+        const uint32_t og = hit ? is.tri : 0xFFFFFFFFu;
+        if (hit && trace_ghost(&s->blob->triangles[is.tri], &r, is.tMax)) flags |= ORACLE_TRACE_GHOST_WINS;
+        if (flags & ORACLE_TRACE_NAN_ACCEPTED) { /* did the NaN decide the answer?  the same search without it */
+            isect_t is2;
+            isect_init(&is2);
+            is2.tMax = tmax;
+            g_reject_nan = 1;
+            const int hit2 = bvh_intersect(s, &r, &is2, &q);
+            g_reject_nan = 0;
+            if (hit2 != hit || (hit && (is2.tri != is.tri || f2bits_(is2.tMax) != f2bits_(is.tMax)))) flags |= ORACLE_TRACE_NAN_DECIDES;
+            if (hit2 && !hit) flags |= ORACLE_TRACE_NAN_HIDES;
+            if (hit2 && trace_ghost(&s->blob->triangles[is2.tri], &r, is2.tMax)) flags |= ORACLE_TRACE_GHOST_WINS;
+        }
+        if (og != bg || (hit && f2bits_(is.tMax) != f2bits_(bf.tMax))) flags |= ORACLE_TRACE_NOT_BRUTE;
+        y[2] = flags;
+        y[3] = bg;
+        y[4] = f2bits_(bf.tMax);
+        if (kind) { /* any hit: the closest-hit search with tMax preset finds something */
+            y[0] = hit ? 1u : 0u;
+            continue;
+        }
+        y[0] = og;
+        y[1] = f2bits_(is.tMax);
+        if (!hit) continue;
+        const float f[17] = {is.p.x, is.p.y, is.p.z, is.gn.x, is.gn.y, is.gn.z, is.sn.x, is.sn.y, is.sn.z,
+                             is.dpds.x, is.dpds.y, is.dpds.z, is.dpdt.x, is.dpdt.y, is.dpdt.z, is.st.x, is.st.y};
+        memcpy(&y[6], f, sizeof(f));
+        y[23] = is.meshID;
+        y[24] = is.priority;
+        y[25] = (uint32_t)is.mat;
+    }
+    free(acc);
+    free(q.e);
+    return 0;
 }
 
 /* ---------------------------------------------------------------- probe (oracle_eval) */

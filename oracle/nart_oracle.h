@@ -76,6 +76,28 @@ uint32_t oracle_binary_search(float value, const float* v, uint32_t start, uint3
    CPU side; BXDF_F_PDF answers (bxdf_f, bxdf_pdf), LOGF_LDS answers logf.  0, or -1 for an unknown
    op or a null pointer. */
 int oracle_eval(uint32_t op, const float* in, uint32_t n, float* out);
+/* oracle_trace over n rays: the CPU side of the device probe nart_hip_trace, whose records these are
+   (include/nart_hip.h: NART_TRACE_IN_WORDS words in -- origin, tMax, direction, query kind -- and
+   NART_TRACE_OUT_WORDS words out per ray).  Out: 0 the triangle the reference octree returns or
+   0xFFFFFFFF (any-hit: 1 when the search with tMax preset finds a hit, else 0), 1 the bits of its t
+   (the preset tMax on a miss; any-hit: 0), 2 the ORACLE_TRACE_* class flags, 3-4 the strictly closest
+   triangle over all triangles and the bits of its t (brute force; lowest index on a tie), 6-25 the
+   isect_t fields of a closest hit in the probe's order (zero on a miss and for any-hit).
+   0, or -1 for a null pointer. */
+#define ORACLE_TRACE_NAN 1u           /* some triangle's plane distance is NaN (0/0) */
+#define ORACLE_TRACE_TIE 2u           /* two triangles the ray hits (each tested alone) have bit-equal t */
+#define ORACLE_TRACE_NOT_BRUTE 4u     /* the octree's answer is not the brute-force closest hit */
+#define ORACLE_TRACE_TIE_CLOSEST 8u   /* ... and that t is the closest one */
+#define ORACLE_TRACE_NAN_ACCEPTED 16u /* a NaN-plane triangle passes Triangle::Intersect (edge test included) */
+#define ORACLE_TRACE_NAN_OUTSIDE 32u  /* ... and the ray's origin lies outside that triangle's bounds */
+#define ORACLE_TRACE_GHOST 64u        /* a triangle passes with a t before the ray enters its bounds (grown by 2^-12 of the
+                                         coordinates involved), or on a ray that misses them: the ray lies in its plane and
+                                         t is a quotient of two roundings */
+#define ORACLE_TRACE_GHOST_WINS 128u  /* the search's own answer (with or without the NaN triangles) is such a hit */
+#define ORACLE_TRACE_NAN_DECIDES 256u /* the same search with NaN plane distances rejected answers differently: a NaN
+                                         triangle shares the winner's chunk */
+#define ORACLE_TRACE_NAN_HIDES 512u   /* ... it finds a hit where the reference's search finds none */
+int oracle_trace_n(const oracle_scene* s, const float* in, uint32_t n, uint32_t* out);
 /* Test statistic: the longest nested-dielectric list a path of this process reached (reset: zero it). */
 uint32_t oracle_max_list(int reset);
 

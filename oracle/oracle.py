@@ -85,6 +85,7 @@ def lib():
                                            ctypes.c_float, ctypes.c_float, P, P]
         _lib.oracle_trace.argtypes = [P, P, P, ctypes.c_float, P]
         _lib.oracle_eval.argtypes = [ctypes.c_uint32, P, ctypes.c_uint32, P]
+        _lib.oracle_trace_n.argtypes = [P, P, ctypes.c_uint32, P]
     return _lib
 
 
@@ -196,6 +197,25 @@ def trace(orc, o, d, tmax=float("inf")):
     t0 = np.array([out[1]], np.int32).view(np.float32)[0]
     t1 = np.array([out[3]], np.int32).view(np.float32)[0]
     return out[0], float(t0), out[2], float(t1)
+
+
+# class flags of trace_n (nart_oracle.h ORACLE_TRACE_*)
+TRACE_NAN, TRACE_TIE, TRACE_NOT_BRUTE, TRACE_TIE_CLOSEST, TRACE_NAN_ACCEPTED, TRACE_NAN_OUTSIDE, TRACE_GHOST = 1, 2, 4, 8, 16, 32, 64
+TRACE_GHOST_WINS, TRACE_NAN_DECIDES, TRACE_NAN_HIDES = 128, 256, 512
+
+
+def trace_n(orc, rays):
+    """oracle_trace over (n, 8) float32 ray records (nart_amd.trace_rays): (n, 32) uint32 records laid
+    out as the device probe's (HipRenderer.trace) -- word 0 the reference octree's triangle, 1 the bits
+    of t, 6-25 the isect_t fields -- with the class flags in word 2 and the brute-force closest hit in
+    words 3-4 (nart_oracle.h)."""
+    x = np.ascontiguousarray(rays, np.float32)
+    assert x.ndim == 2 and x.shape[1] == 8, x.shape
+    out = np.zeros((len(x), 32), np.uint32)
+    rc = lib().oracle_trace_n(orc._h, x.ctypes.data, len(x), out.ctypes.data)
+    if rc:
+        raise RuntimeError("oracle_trace_n failed: %d" % rc)
+    return out
 
 
 def max_list_length(reset=False):

@@ -49,6 +49,33 @@ def test_hip_create_without_gpu_fails_cleanly(built, glass_scene):
         raise AssertionError("render context created without a GPU")
 
 
+def test_trace_validates_its_arguments(built):
+    """nart_hip_trace without a device: a null context, input or output, an unknown variant and a record
+    count above the cap are NART_E_INVALID before anything touches the context or a GPU (with a context:
+    test_gpu_trace.py).  The Python names number the variants and size the records as the header does."""
+    import numpy as np
+    lib = nart_amd.api.hip_lib()
+    x = np.zeros((2, nart_amd.TRACE_IN_WORDS), np.float32)
+    y = np.full((2, nart_amd.TRACE_OUT_WORDS), 5, np.uint32)
+    fake = ctypes.c_void_p(x.ctypes.data)  # never dereferenced: every call below fails on another argument
+    for n in (0, 2):
+        assert lib.nart_hip_trace(None, 0, 0, 0, x.ctypes.data, n, y.ctypes.data) == -1
+        assert lib.nart_hip_trace(fake, 0, 0, 0, None, n, y.ctypes.data) == -1
+        assert lib.nart_hip_trace(fake, 0, 0, 0, x.ctypes.data, n, None) == -1
+        assert lib.nart_hip_trace(fake, len(nart_amd.TRACE_VARIANTS), 0, 0, x.ctypes.data, n, y.ctypes.data) == -1
+        assert lib.nart_hip_trace(fake, 0xFFFFFFFF, 0, 0, x.ctypes.data, n, y.ctypes.data) == -1
+    for n in ((1 << 24) + 1, 0xFFFFFFFF):
+        assert lib.nart_hip_trace(fake, 0, 0, 0, x.ctypes.data, n, y.ctypes.data) == -1, n
+    assert np.all(y == 5)
+    header = open(os.path.join(REPO, "include", "nart_hip.h")).read()
+    enum = dict((k.lower(), int(v)) for k, v in re.findall(r"NART_TRACE_(\w+) = (\d+)", header))
+    assert enum.pop("n_variants") == len(nart_amd.TRACE_VARIANTS)
+    assert (enum.pop("closest"), enum.pop("any")) == (nart_amd.TRACE_CLOSEST, nart_amd.TRACE_ANY)
+    assert enum == nart_amd.TRACE_VARIANTS
+    words = dict(re.findall(r"#define NART_TRACE_(\w+)_WORDS (\d+)", header))
+    assert (int(words["IN"]), int(words["OUT"])) == (nart_amd.TRACE_IN_WORDS, nart_amd.TRACE_OUT_WORDS)
+
+
 def test_eval_validates_its_arguments(built):
     """nart_hip_eval without a device: a null context, input or output, an unknown op and a feature mask the
     probe is not built for are NART_E_INVALID before anything touches a GPU, n == 0 included (with a

@@ -11,7 +11,9 @@ a property of the scene alone.  This test evaluates it, with the reference's flo
 suite and the bench render: no triangle has zero area and no triangle plane contains the camera, so no camera ray can produce a
 NaN plane distance in these scenes.  (Secondary rays start at biased hit points and would need
 an exactly zero dot(d, n) as well, for a direction drawn from a continuous distribution; the
-device already replays the octree for every NaN it does see -- octree.h.)"""
+device already replays the octree for every NaN it does see -- octree.h.)  tests/test_gpu_trace.py traces
+rays designed to produce these NaNs on the device and sets aside, by an oracle-side criterion
+(trace_cases.set_aside), only those of this case."""
 import numpy as np
 import pytest
 
