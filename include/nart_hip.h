@@ -762,8 +762,8 @@ int nart_hip_light_group_timings(const nart_ctx* ctx, double* splat_ms, double* 
    NART_E_UNSUPPORTED: the volume integrator; variant 3 or a BVH deeper than the ray-queue kernel's LDS
    holds (k_render has no depth-cut build).  An error leaves the context usable.  Not offered: depth
    cuts together with adaptive sampling, the cascade, the mattes, AOVs, guides, the moment image, light
-   groups or the denoiser in one call (denoising direct and indirect light separately is the obvious
-   next step). */
+   groups or the denoiser in one call (the layers are denoised separately, with shared guides, by
+   nart_hip_render_denoised_depth_layers and nart_hip_denoise_parts: "Denoised parts" below). */
 #define NART_DEPTH_CUTS_MAX 8u
 int nart_hip_render_depth_cuts(nart_ctx* ctx, const nart_render_params* p, const uint32_t* cuts, uint32_t n_cuts,
                                nart_pixel* cut_images, nart_pixel* image, nart_render_stats* stats);
@@ -772,6 +772,73 @@ int nart_hip_depth_layers(nart_ctx* ctx, const nart_render_params* p, uint32_t n
 int nart_hip_render_depth_cut_samples(nart_ctx* ctx, const nart_render_params* p, const uint32_t* cuts, uint32_t n_cuts,
                                       uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float* out);
 int nart_hip_depth_cut_timings(const nart_ctx* ctx, double* splat_ms, double* layers_ms);
+
+/* Denoised parts: the light groups or the depth layers of a render, each denoised on its own, with one
+   set of guides for all of them (no reference counterpart).
+
+   A group image that is re-gained in comp is as noisy as the beauty was, and direct light (hard shadow
+   edges, low variance) and indirect light (smooth, noisy) want different luminance weights: one
+   variance for their sum blurs the edge or keeps the noise.  So the parts are denoised one by one.
+
+   Definition: n_parts part images, 1 <= n_parts <= NART_DENOISE_PARTS_MAX (8 light groups, or the 9
+   layers of 8 depth cuts), one albedo and one normal image.  For every k, out[k] has the bits of
+   nart_hip_denoise over (parts[k], albedo, normal) with the same parameters: the filter above run on
+   part k alone.  That holds for every n_parts, every chunking (below), every image size, and for pixels
+   that are invalid, empty or outside the crop; a pixel may be invalid in one part and valid in another.
+   Only the spatial variance estimate is offered: the sample-variance mode would need a second-moment
+   image per part.
+
+   Factorisation: the weight of a tap is w_n * f(d_g + d_l) ("Guide terms" above), and w_n and d_g -- the
+   normal dot product and its squarings, the depth division, the coverage division -- are the guides'
+   alone.  The kernels (device/denoise_parts.h) prepare guide, cov, slope and a_d once, and signal, alpha
+   and validity per part; a launch then takes a chunk of 1..4 parts, computes w_n and d_g once per tap,
+   and per part d_l, f, the weight and the sums, with the operations and the order written above.  In
+   the variance pass u = w_n * f(d_g) is shared and su, sl, sl2 are per part, because an invalid tap is
+   skipped per part.  NART_DN_PARTS_CHUNK = 1..4 forces the chunk size (0 or unset: the measured choice
+   per n_parts, host/denoise_parts_plan.h); it changes no bit.
+
+   Sum: per pixel of the total image and channel of r, g, b,  sum = ((out_0 + out_1) + out_2) + ...  in
+   float32, starting from out_0 itself (no 0 is added, so -0 stays); alpha and filter_weight_sum are
+   out_0's.
+
+   nart_hip_denoise_parts: host images; parts and out hold n_parts images back to back; sum, if non-null,
+   receives the sum.  One upload, the stage, one download.  denoise_ms: the device time of the stage.
+   nart_hip_render_denoised_light_groups: as nart_hip_render_light_groups, and denoises the n_groups group
+   images: denoised receives them back to back (required); optional: sum, their sum; groups, the noisy
+   group images; image, the noisy beauty -- these two with the bits nart_hip_render_light_groups gives.
+   nart_hip_light_mix takes the denoised groups unchanged.
+   nart_hip_render_denoised_depth_layers: as nart_hip_render_depth_cuts, then the n_cuts + 1 layers on the
+   device, and denoises them: denoised receives them back to back (required); optional: sum; layers, the
+   noisy layers, with the bits of nart_hip_depth_layers over nart_hip_render_depth_cuts; image, the beauty.
+   gp null: the first-hit AOVs are the guides; non-null: the followed guides, as
+   nart_hip_render_denoised_guides.
+   Both whole-frame calls render two frames of the existing kinds back to back -- the light-group or
+   depth-cut frame, then a frame without beauty that asks for both AOVs (or both followed guides): camera
+   rays only, no path kernel -- into device images of the first device, and run the stage there; nothing
+   but what the caller asked for passes the host.  All device images and work buffers are temporaries of
+   the call.  stats describe the first frame and the stage; multi-device contexts gather as before and
+   denoise on their first device.
+   nart_hip_denoise_parts_timings: device times (ms) of the last parts denoise, kernel by kernel and
+   summed over the chunks: prepare, variance, the passes (pass_ms[8]), finalise, the sum; and guides_ms,
+   the render_ms of the last whole-frame call's guides frame.  Any pointer may be null.
+   NART_E_INVALID: a null ctx, p or required image; n_parts outside 1..9; whatever nart_hip_denoise,
+   nart_hip_render_light_groups, nart_hip_render_depth_cuts and nart_guide_params reject.
+   NART_E_UNSUPPORTED: the volume integrator; what the light-group and depth-cut builds refuse.  An error
+   leaves the context usable. */
+#define NART_DENOISE_PARTS_MAX 9u
+int nart_hip_denoise_parts(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, uint32_t n_parts,
+                           const nart_pixel* parts, const nart_pixel* albedo, const nart_pixel* normal, nart_pixel* out,
+                           nart_pixel* sum, double* denoise_ms);
+int nart_hip_render_denoised_light_groups(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                                          const nart_guide_params* gp, const uint32_t* group_of_light, uint32_t n_lights,
+                                          uint32_t n_groups, nart_pixel* denoised, nart_pixel* sum, nart_pixel* groups,
+                                          nart_pixel* image, nart_render_stats* stats, double* denoise_ms);
+int nart_hip_render_denoised_depth_layers(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                                          const nart_guide_params* gp, const uint32_t* cuts, uint32_t n_cuts,
+                                          nart_pixel* denoised, nart_pixel* sum, nart_pixel* layers, nart_pixel* image,
+                                          nart_render_stats* stats, double* denoise_ms);
+int nart_hip_denoise_parts_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
+                                   double* finalize_ms, double* sum_ms, double* guides_ms);
 
 /* Cost image: per-pixel ray, hit and traversal counts of a render -- where its time goes.
 

@@ -314,6 +314,16 @@ _HIP_SIGS = {
                                                      _P, _P, _P, _P]),
     "nart_hip_denoise_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_denoise_parts": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams), ctypes.c_uint32,
+                                              _P, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_denoised_light_groups": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams),
+                                                             ctypes.POINTER(GuideParams), _P, ctypes.c_uint32,
+                                                             ctypes.c_uint32, _P, _P, _P, _P, ctypes.POINTER(RenderStats),
+                                                             ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_denoised_depth_layers": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams),
+                                                             ctypes.POINTER(GuideParams), _P, ctypes.c_uint32, _P, _P, _P, _P,
+                                                             ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_denoise_parts_timings": (ctypes.c_int, [_P] + [ctypes.POINTER(ctypes.c_double)] * 6),
     "nart_hip_render_device": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(_P),
                                               ctypes.POINTER(RenderStats)]),
     "nart_hip_render_buckets_async": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(ctypes.c_uint32),
@@ -1180,6 +1190,90 @@ class HipRenderer:
         self._check(self._lib.nart_hip_denoise_timings(self._ctx, ctypes.byref(a), ctypes.byref(b), passes,
                                                        ctypes.byref(c)))
         return {"prepare": a.value, "variance": b.value, "passes": list(passes), "finalize": c.value}
+
+    def denoise_parts(self, p, parts, albedo, normal, params=None, with_sum=False):
+        """Denoise K host part images that share their guides (nart_hip_denoise_parts; include/nart_hip.h,
+        "Denoised parts"): parts a (K, totalH, totalW, 5) float32 array, 1 <= K <= 9 -- light groups as
+        render_light_groups() returns them, or layers as depth_layers() does -- albedo and normal as
+        render_aovs() returns them; params a DenoiseParams (None: the defaults).  Returns the
+        (K, totalH, totalW, 5) denoised parts, image k with the bits of denoise(p, parts[k], albedo, normal,
+        params); with_sum=True returns (denoised, sum), the sum being ((d_0 + d_1) + d_2) + ... per r, g, b
+        with the alpha and filter weight sum of d_0."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        im = np.ascontiguousarray(parts, dtype=np.float32)
+        a, n = (np.ascontiguousarray(x, dtype=np.float32) for x in (albedo, normal))
+        if im.ndim != 4 or im.shape[1:] != shape or a.shape != shape or n.shape != shape:
+            raise ValueError("denoise_parts: images of shape %s, %s and %s, expected (K,) + %s and %s twice" % (
+                im.shape, a.shape, n.shape, shape, shape))
+        K = im.shape[0]
+        out = np.empty((max(1, K),) + shape, np.float32)
+        total = np.empty(shape, np.float32) if with_sum else None
+        self._check(self._lib.nart_hip_denoise_parts(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None, K,
+                                                     im.ctypes.data, a.ctypes.data, n.ctypes.data, out.ctypes.data,
+                                                     total.ctypes.data if with_sum else None, None))
+        return (out[:K], total) if with_sum else out[:K]
+
+    def _denoised_parts_call(self, p, entry, head, K, noisy_name, params, guides, with_sum, with_noisy, with_beauty, stats):
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        out = {"denoised": np.empty((max(1, K),) + shape, np.float32)}
+        if with_sum:
+            out["sum"] = np.empty(shape, np.float32)
+        if with_noisy:
+            out[noisy_name] = np.empty((max(1, K),) + shape, np.float32)
+        if with_beauty:
+            out["beauty"] = np.empty(shape, np.float32)
+        ptr = lambda name: out[name].ctypes.data if name in out else None
+        st = stats if stats is not None else RenderStats()
+        ms = ctypes.c_double()
+        self._check(entry(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
+                          ctypes.byref(guides) if guides is not None else None, *head, ptr("denoised"), ptr("sum"),
+                          ptr(noisy_name), ptr("beauty"), ctypes.byref(st), ctypes.byref(ms)))
+        for name in ("denoised", noisy_name):
+            if name in out:
+                out[name] = out[name][:K]
+        out["denoise_ms"] = ms.value
+        out["guides_ms"] = self.denoise_parts_timings()["guides_ms"]
+        return out
+
+    def render_denoised_light_groups(self, p, groups, params=None, guides=None, with_sum=True, with_groups=False,
+                                     with_beauty=False, stats=None, n_groups=None):
+        """render_light_groups() and the group images denoised one by one with shared guides, on the device
+        (nart_hip_render_denoised_light_groups): a dict with "denoised", (G, totalH, totalW, 5), image g with
+        the bits of denoise() over group g and the AOVs of render_aovs(); "sum" of the denoised groups;
+        "groups" and "beauty", the noisy images with render_light_groups()'s bits, if requested;
+        "denoise_ms", the device time of the stage; "guides_ms", the render time of the guides frame.
+        guides: a GuideParams selects the followed guides (as render_denoised).  light_mix() takes
+        "denoised" as it takes "groups"."""
+        m, n, G = self._light_group_map(groups)
+        G = G if n_groups is None else int(n_groups)
+        head = (m.ctypes.data if m is not None else None, n, G)
+        return self._denoised_parts_call(p, self._lib.nart_hip_render_denoised_light_groups, head, G, "groups", params, guides,
+                                         with_sum, with_groups, with_beauty, stats)
+
+    def render_denoised_depth_layers(self, p, cuts, params=None, guides=None, with_sum=True, with_layers=False,
+                                     with_beauty=False, stats=None, n_cuts=None):
+        """render_depth_cuts(), depth_layers() and the K + 1 layers denoised one by one with shared guides, on
+        the device (nart_hip_render_denoised_depth_layers): a dict with "denoised", (K + 1, totalH, totalW, 5);
+        "sum" of the denoised layers; "layers" (the noisy layers, depth_layers()'s bits) and "beauty" if
+        requested; "denoise_ms" and "guides_ms" as render_denoised_light_groups()."""
+        c, K = self._depth_cut_list(cuts)
+        K = K if n_cuts is None else int(n_cuts)
+        head = (c.ctypes.data if c is not None else None, K)
+        return self._denoised_parts_call(p, self._lib.nart_hip_render_denoised_depth_layers, head, min(K, 8) + 1, "layers",
+                                         params, guides, with_sum, with_layers, with_beauty, stats)
+
+    def denoise_parts_timings(self):
+        """Device times (ms) of the last parts denoise, summed over its chunks, and the render time of the
+        last whole-frame call's guides frame (nart_hip_denoise_parts_timings): {"prepare", "variance",
+        "passes": [8], "finalize", "sum", "guides_ms"}."""
+        v = [ctypes.c_double() for _ in range(5)]
+        passes = (ctypes.c_double * 8)()
+        self._check(self._lib.nart_hip_denoise_parts_timings(self._ctx, ctypes.byref(v[0]), ctypes.byref(v[1]), passes,
+                                                             ctypes.byref(v[2]), ctypes.byref(v[3]), ctypes.byref(v[4])))
+        return {"prepare": v[0].value, "variance": v[1].value, "passes": list(passes), "finalize": v[2].value,
+                "sum": v[3].value, "guides_ms": v[4].value}
 
     def render_device(self, p, stats=None):
         """Whole session, image left on the (first) device: returns its device address (totalH x

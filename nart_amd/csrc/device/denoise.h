@@ -55,9 +55,75 @@ __device__ __forceinline__ bool dn_finite(float a) { return dn_abs(a) < __builti
 __device__ __forceinline__ float dn_lum(const float4& s) { return (0.2126f * s.x + 0.7152f * s.y) + 0.0722f * s.z; }
 
 // Mean depth over hit samples of total-image pixel ti: normal.w / albedo.a, 0 for an empty pixel.
-__device__ __forceinline__ float dn_depth(const DnArgs& a, size_t ti) {
+// (Args: DnArgs, or the parts' DnpArgs of denoise_parts.h, which names the same fields.)
+template <class Args>
+__device__ __forceinline__ float dn_depth(const Args& a, size_t ti) {
     const float hs = a.albedo[ti * 5 + 3];
     return hs > 0.f ? a.normal[ti * 5 + 3] / hs : 0.f;
+}
+
+// c = P.rgba / P.w of a nart_pixel, 0 if P.w <= 0.
+__device__ __forceinline__ void dn_mean(const float* P, float c[4]) {
+    c[0] = c[1] = c[2] = c[3] = 0.f;
+    if (P[4] > 0.f)
+        for (int k = 0; k < 4; ++k) c[k] = P[k] / P[4];
+}
+
+// What prepare takes from the albedo and normal images alone, for cropped pixel (x, y) = total-image
+// pixel ti: the guide g = {n.xyz, z}, cov, the demodulation albedo ce.xyz = a_d (ce.w is left alone)
+// (dn_guides), and the depth slope around a pixel of depth z (dn_slope).
+template <class Args>
+__device__ __forceinline__ void dn_guides(const Args& a, size_t ti, float4& g, float& cov, float4& ce) {
+    const float* A = a.albedo + ti * 5;
+    const float* N = a.normal + ti * 5;
+    float al[3] = {0.f, 0.f, 0.f};
+    cov = 0.f;
+    if (A[4] > 0.f) {
+        for (int k = 0; k < 3; ++k) al[k] = A[k] / A[4];
+        cov = A[3] / A[4];
+    }
+    const float hs = A[3];
+    g = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (hs > 0.f) {
+        g.w = N[3] / hs;
+        if (g.w != 0.f) {
+            g.x = N[0] / hs;
+            g.y = N[1] / hs;
+            g.z = N[2] / hs;
+        } else {
+            g.w = 0.f;  // -0 -> +0
+        }
+    }
+    const float miss = 1.f - cov;
+    ce.x = dn_max(al[0] + miss, a.albedo_floor);
+    ce.y = dn_max(al[1] + miss, a.albedo_floor);
+    ce.z = dn_max(al[2] + miss, a.albedo_floor);
+}
+
+// Depth slope: per axis the smaller one-sided |dz| (the one available at a border, 0 on a
+// single-pixel axis).
+template <class Args>
+__device__ __forceinline__ float dn_slope(const Args& a, uint32_t x, uint32_t y, size_t ti, float z) {
+    float sx = 0.f, sy = 0.f;
+    if (a.W > 1) {
+        const float dl = x > 0 ? dn_abs(z - dn_depth(a, ti - 1)) : 0.f;
+        const float dr = x + 1 < a.W ? dn_abs(dn_depth(a, ti + 1) - z) : 0.f;
+        sx = x == 0 ? dr : (x + 1 == a.W ? dl : dn_min(dl, dr));
+    }
+    if (a.H > 1) {
+        const float du = y > 0 ? dn_abs(z - dn_depth(a, ti - a.totalW)) : 0.f;
+        const float dd = y + 1 < a.H ? dn_abs(dn_depth(a, ti + a.totalW) - z) : 0.f;
+        sy = y == 0 ? dd : (y + 1 == a.H ? du : dn_min(du, dd));
+    }
+    return sx + sy;
+}
+
+// A pixel whose c.rgb has a non-finite component is invalid: signal {0, 0, 0, -1}; a valid one's is
+// {c.rgb / a_d, v}.
+__device__ __forceinline__ bool dn_valid(const float c[4]) { return dn_finite(c[0]) && dn_finite(c[1]) && dn_finite(c[2]); }
+__device__ __forceinline__ float4 dn_invalid_signal() { return make_float4(0.f, 0.f, 0.f, -1.f); }
+__device__ __forceinline__ float4 dn_signal(const float c[4], const float4& ad, float v) {
+    return make_float4(c[0] / ad.x, c[1] / ad.y, c[2] / ad.z, v);
 }
 
 // Sample variance of the demodulated luminance from the second-moment pixel M (include/nart_hip.h,
@@ -92,56 +158,21 @@ __global__ void __launch_bounds__(256) k_dn_prepare(DnArgs a) {
     if (x >= a.W || y >= a.H) return;
     const size_t ti = (size_t)(y + a.fb) * a.totalW + (x + a.fb);
     const size_t i = (size_t)y * a.W + x;
-    const float* B = a.beauty + ti * 5;
-    const float* A = a.albedo + ti * 5;
-    const float* N = a.normal + ti * 5;
-    float c[4] = {0.f, 0.f, 0.f, 0.f};
-    if (B[4] > 0.f)
-        for (int k = 0; k < 4; ++k) c[k] = B[k] / B[4];
-    float al[3] = {0.f, 0.f, 0.f}, cov = 0.f;
-    if (A[4] > 0.f) {
-        for (int k = 0; k < 3; ++k) al[k] = A[k] / A[4];
-        cov = A[3] / A[4];
-    }
-    const float hs = A[3];
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (hs > 0.f) {
-        g.w = N[3] / hs;
-        if (g.w != 0.f) {
-            g.x = N[0] / hs;
-            g.y = N[1] / hs;
-            g.z = N[2] / hs;
-        } else {
-            g.w = 0.f;  // -0 -> +0
-        }
-    }
-    const float miss = 1.f - cov;
-    float4 ce;
-    ce.x = dn_max(al[0] + miss, a.albedo_floor);
-    ce.y = dn_max(al[1] + miss, a.albedo_floor);
-    ce.z = dn_max(al[2] + miss, a.albedo_floor);
+    float c[4];
+    dn_mean(a.beauty + ti * 5, c);
+    float4 g, ce;
+    float cov;
+    dn_guides(a, ti, g, cov, ce);
     ce.w = c[3];
-    const bool valid = dn_finite(c[0]) && dn_finite(c[1]) && dn_finite(c[2]);
-    float4 s = make_float4(0.f, 0.f, 0.f, -1.f);
-    if (valid) s = make_float4(c[0] / ce.x, c[1] / ce.y, c[2] / ce.z, MOMENT ? dn_sample_variance(a.moment + ti * 5, c, ce) : 0.f);
-    // depth slope: per axis the smaller one-sided |dz| (the one available at a border, 0 on a
-    // single-pixel axis)
-    float sx = 0.f, sy = 0.f;
-    if (a.W > 1) {
-        const float dl = x > 0 ? dn_abs(g.w - dn_depth(a, ti - 1)) : 0.f;
-        const float dr = x + 1 < a.W ? dn_abs(dn_depth(a, ti + 1) - g.w) : 0.f;
-        sx = x == 0 ? dr : (x + 1 == a.W ? dl : dn_min(dl, dr));
-    }
-    if (a.H > 1) {
-        const float du = y > 0 ? dn_abs(g.w - dn_depth(a, ti - a.totalW)) : 0.f;
-        const float dd = y + 1 < a.H ? dn_abs(dn_depth(a, ti + a.totalW) - g.w) : 0.f;
-        sy = y == 0 ? dd : (y + 1 == a.H ? du : dn_min(du, dd));
-    }
+    const bool valid = dn_valid(c);
+    float4 s = dn_invalid_signal();
+    if (valid) s = dn_signal(c, ce, MOMENT ? dn_sample_variance(a.moment + ti * 5, c, ce) : 0.f);
+    const float slope = dn_slope(a, x, y, ti, g.w);
     a.guide[i] = g;
     a.cov[i] = cov;
     a.sig_out[i] = s;
     a.centre[i] = ce;
-    a.slope[i] = sx + sy;
+    a.slope[i] = slope;
 }
 
 // A block's view of the per-tap records: its tile plus R pixels of halo in LDS (R > 0), or global
@@ -184,20 +215,34 @@ struct DnView {
     __device__ __forceinline__ float cov(int x, int y) const { return R > 0 ? lc[idx(x, y)] : a.cov[idx(x, y)]; }
 };
 
-// w_n * f(d_g + d_l) of a tap that is not the centre (include/nart_hip.h, "Guide terms").
-__device__ __forceinline__ float dn_tap_weight(const DnArgs& a, const float4& gp, float covp, float slope_p,
-                                               const float4& gq, float covq, float cheb, float d_l) {
-    float wn = 1.f;
+// The weight of a tap that is not the centre (include/nart_hip.h, "Guide terms"), in two halves.
+// The guide half: w_n and d_g, which the guides alone decide (the same for every image filtered with
+// them: denoise_parts.h computes them once per tap for several).
+template <class Args>
+__device__ __forceinline__ void dn_tap_guide(const Args& a, const float4& gp, float covp, float slope_p, const float4& gq,
+                                             float covq, float cheb, float& wn, float& dg) {
+    wn = 1.f;
     if (!(gp.w == 0.f && gq.w == 0.f)) {
         const float dot = (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z;
         wn = dn_min(1.f, dn_max(0.f, dot));
         for (uint32_t k = 0; k < a.normal_squarings; ++k) wn = wn * wn;
     }
     const float dz = dn_abs(gp.w - gq.w) / ((a.sigma_depth * (slope_p * cheb) + a.depth_eps * dn_max(gp.w, gq.w)) + 1e-30f);
-    const float dg = dz + dn_abs(covp - covq) / a.sigma_coverage;
+    dg = dz + dn_abs(covp - covq) / a.sigma_coverage;
+}
+
+// The falloff half: w_n * f(d_g + d_l).
+__device__ __forceinline__ float dn_tap_falloff(float wn, float dg, float d_l) {
     const float t = dn_max(0.f, 1.f - (dg + d_l) * 0.125f);
     const float t2 = t * t, t4 = t2 * t2;
     return wn * (t4 * t4);
+}
+
+__device__ __forceinline__ float dn_tap_weight(const DnArgs& a, const float4& gp, float covp, float slope_p,
+                                               const float4& gq, float covq, float cheb, float d_l) {
+    float wn, dg;
+    dn_tap_guide(a, gp, covp, slope_p, gq, covq, cheb, wn, dg);
+    return dn_tap_falloff(wn, dg, d_l);
 }
 
 __global__ void __launch_bounds__(256) k_dn_variance(DnArgs a) {

@@ -8,6 +8,8 @@
 //              caller asked for to the host (frame_stage).
 // The denoiser's images and work buffers are the context's, kept between calls; the cascade's and the
 // mattes' images are temporaries of the call.  The parameters' rules are host/stage_params.h's.
+// The parts denoise (light groups or depth layers denoised one by one with shared guides) is the one
+// stage over two frames: the parts' frame and a guides frame, both into temporaries of the call.
 #pragma once
 
 namespace {
@@ -494,6 +496,206 @@ int render_depth_cuts(nart_ctx* ctx, const nart_render_params* p, const uint32_t
     const int rc = render_frame(ctx, p, plan, rq, stats);
     for (const nart_ctx* c : ctx->subs) ctx->dc_ms[0] = std::max(ctx->dc_ms[0], c->dc_ms[0]);  // the slowest device's
     return rc;
+}
+
+// ---------------------------------------------------------------- denoised parts (device/denoise_parts.h)
+// One chunk of C parts, first + c the part of slot c: variance, the passes (LDS tiles for steps 1 and 2,
+// global reads beyond), finalise, an event after each (slot[e]: the time of dnp_ms the interval ending at
+// event e counts towards).  sig[0][k]: part k's prepared signal; sig[1][k]: its ping-pong partner.
+template <int C>
+int dnp_chunk(nart_ctx* ctx, DnpArgs a, uint32_t first, const nart_denoise_params& dp, float4* (&sig)[2][DNP_MAX_PARTS],
+              float* const* alpha, float* const* out, hipStream_t st, uint32_t& e, uint8_t* slot) {
+    const dim3 grid((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH), block(256);
+    a.n = C;
+    int cur = 0;
+    auto point = [&](int in) {
+        for (int c = 0; c < C; ++c) {
+            a.sig_in[c] = sig[in][first + c];
+            a.sig_out[c] = sig[in ^ 1][first + c];
+            a.alpha[c] = alpha[first + c];
+            a.out[c] = out[first + c];
+        }
+    };
+    point(cur);
+    a.step = 1;
+    hipLaunchKernelGGL(k_dnp_variance<C>, grid, block, 0, st, a);
+    slot[e] = 1;
+    HIPCHK(record(ctx->ev_dnp[e++], st));
+    cur ^= 1;
+    for (uint32_t i = 0; i < dp.iterations; ++i) {
+        point(cur);
+        a.step = 1u << i;
+        if (i == 0) hipLaunchKernelGGL((k_dnp_atrous<2, C>), grid, block, 0, st, a);
+        else if (i == 1) hipLaunchKernelGGL((k_dnp_atrous<4, C>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_dnp_atrous<0, C>), grid, block, 0, st, a);
+        slot[e] = (uint8_t)(2 + i);
+        HIPCHK(record(ctx->ev_dnp[e++], st));
+        cur ^= 1;
+    }
+    point(cur);
+    const size_t n_total = (size_t)a.totalW * a.totalH;
+    hipLaunchKernelGGL(k_dnp_finalize, dim3((uint32_t)((n_total + 255) / 256)), block, 0, st, a);
+    HIPCHK(hipGetLastError());
+    slot[e] = 10;
+    HIPCHK(record(ctx->ev_dnp[e++], st));
+    return NART_OK;
+}
+
+// Denoise K part images of the layout with shared guides, on ctx's device (current): prepare once, the
+// chunks of the plan (host/denoise_parts_plan.h; NART_DN_PARTS_CHUNK forces their size), and with `sum`
+// the sum of the outputs; synchronous.  sum may be one of the part images (they are consumed by
+// prepare), not an output.  The work buffers are temporaries of the call.  ms: device time.
+int denoise_parts_device(nart_ctx* ctx, const ImageLayout& layout, const nart_denoise_params& dp, uint32_t K,
+                         const float* const* parts, const float* albedo, const float* normal, float* const* out, float* sum,
+                         hipStream_t st, double* ms) {
+    const char* knob = env_opt("NART_DN_PARTS_CHUNK");
+    const PartsPlan plan = plan_denoise_parts(K, knob && *knob ? (uint32_t)std::max(0, std::atoi(knob)) : 0u);
+    const size_t npx = (size_t)layout.W * layout.H;
+    // float4: guide, a_d, signal x 2 per part; then float: cov, slope, alpha per part
+    Buf work;  // freed on return
+    const size_t n4 = 2 + 2 * (size_t)K, n1 = 2 + (size_t)K;
+    if (int rc = reserve(ctx, work, ctx->device, npx * (n4 * sizeof(float4) + n1 * sizeof(float)), "denoised parts work buffers"))
+        return rc;
+    float4* f4 = work.as<float4>();
+    float* f1 = reinterpret_cast<float*>(f4 + n4 * npx);
+    float4* sig[2][DNP_MAX_PARTS] = {};
+    float* alpha[DNP_MAX_PARTS] = {};
+    DnpArgs a = {};
+    a.albedo = albedo;
+    a.normal = normal;
+    a.guide = f4;
+    a.ad = f4 + npx;
+    a.cov = f1;
+    a.slope = f1 + npx;
+    for (uint32_t k = 0; k < K; ++k) {
+        sig[0][k] = f4 + (2 + k) * npx;
+        sig[1][k] = f4 + (2 + K + k) * npx;
+        alpha[k] = f1 + (2 + k) * npx;
+        a.part[k] = parts[k];
+        a.sig_out[k] = sig[0][k];
+        a.alpha[k] = alpha[k];
+    }
+    layout.fill(a);
+    a.n = K;
+    a.step = 1;
+    a.normal_squarings = dp.normal_squarings;
+    a.sigma_color = dp.sigma_color;
+    a.sigma_depth = dp.sigma_depth;
+    a.depth_eps = dp.depth_eps;
+    a.sigma_coverage = dp.sigma_coverage;
+    a.albedo_floor = dp.albedo_floor;
+    const dim3 grid((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH), block(256);
+    uint32_t e = 0;
+    uint8_t slot[sizeof(ctx->ev_dnp) / sizeof(ctx->ev_dnp[0])] = {};
+    HIPCHK(record(ctx->ev_dnp[e++], st));
+    hipLaunchKernelGGL(k_dnp_prepare, grid, block, 0, st, a);
+    HIPCHK(hipGetLastError());
+    slot[e] = 0;
+    HIPCHK(record(ctx->ev_dnp[e++], st));
+    for (uint32_t k = 0; k < K; ++k) a.part[k] = nullptr, a.sig_out[k] = nullptr, a.alpha[k] = nullptr;
+    for (uint32_t j = 0; j < plan.n_chunks; ++j) {
+        int rc = NART_OK;
+        switch (plan.size[j]) {
+            case 1: rc = dnp_chunk<1>(ctx, a, plan.first[j], dp, sig, alpha, out, st, e, slot); break;
+            case 2: rc = dnp_chunk<2>(ctx, a, plan.first[j], dp, sig, alpha, out, st, e, slot); break;
+            case 3: rc = dnp_chunk<3>(ctx, a, plan.first[j], dp, sig, alpha, out, st, e, slot); break;
+            default: rc = dnp_chunk<4>(ctx, a, plan.first[j], dp, sig, alpha, out, st, e, slot); break;
+        }
+        if (rc) return rc;
+    }
+    if (sum) {
+        PartsSumArgs s = {};
+        for (uint32_t k = 0; k < K; ++k) s.in[k] = out[k];
+        s.out = sum;
+        s.n = K;
+        s.n_pixels = (uint64_t)a.totalW * a.totalH;
+        hipLaunchKernelGGL(k_parts_sum, dim3((uint32_t)((s.n_pixels + 255) / 256)), block, 0, st, s);
+        HIPCHK(hipGetLastError());
+        slot[e] = 11;
+        HIPCHK(record(ctx->ev_dnp[e++], st));
+    }
+    HIPCHK(hipEventSynchronize(ctx->ev_dnp[e - 1].handle()));
+    for (double& t : ctx->dnp_ms) t = 0.0;
+    double total = 0.0;
+    for (uint32_t k = 1; k < e; ++k) {
+        float t = 0.f;
+        HIPCHK(hipEventElapsedTime(&t, ctx->ev_dnp[k - 1].handle(), ctx->ev_dnp[k].handle()));
+        ctx->dnp_ms[slot[k]] += t;
+        total += t;
+    }
+    if (ms) *ms = total;
+    return NART_OK;
+}
+
+// nart_hip_denoise_parts: the K parts, the albedo, the normal, the K denoised images after them; the sum
+// takes the place of part 0, which prepare has consumed by then.  d: validated by the caller.
+int denoise_parts_host(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params& d, uint32_t K,
+                       const nart_pixel* parts, const nart_pixel* albedo, const nart_pixel* normal, nart_pixel* out,
+                       nart_pixel* sum, double* denoise_ms) {
+    if (!ctx->subs.empty())
+        return forwarded(ctx, denoise_parts_host(first_device(ctx), p, d, K, parts, albedo, normal, out, sum, denoise_ms));
+    if (const char* why = check_image_size(p)) return fail(ctx, NART_E_INVALID, why);
+    Buf imgs;  // freed on return
+    return host_stage(ctx, p, imgs, "denoised parts images", {{parts, K}, {albedo, 1}, {normal, 1}}, out, K,
+                      [&](const Images& v) {
+                          const float* in[DNP_MAX_PARTS] = {};
+                          float* o[DNP_MAX_PARTS] = {};
+                          for (uint32_t k = 0; k < K; ++k) in[k] = v.at(k), o[k] = v.at(K + 2 + k);
+                          int rc = denoise_parts_device(v.ctx, v.layout, d, K, in, v.at(K), v.at(K + 1), o, sum ? v.at(0) : nullptr,
+                                                        0, denoise_ms);
+                          if (!rc && sum) rc = v.download(0, sum);
+                          return rc;
+                      });
+}
+
+// nart_hip_render_denoised_light_groups (n_cuts 0: `plan` a light-group frame of K groups) and
+// nart_hip_render_denoised_depth_layers (`plan` a depth-cut frame of n_cuts cuts, K = n_cuts + 1 layers):
+// two frames back to back into device images of the first device -- the parts' frame, then the guides'
+// frame (no beauty: camera rays only; follow: the followed guides in the first-hit AOVs' place) -- then
+// the layers, the parts denoise and what the caller asked for to the host.  All images are temporaries
+// of the call.  The group map or the cuts are set, and everything validated, by the caller.  stats: the
+// parts' frame and the stage; the guides frame's render_ms goes to ctx->dnp_guides_ms.
+int render_denoised_parts(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params& d,
+                          const nart_guide_params* follow, const FramePlan& plan, uint32_t n_cuts, uint32_t K,
+                          nart_pixel* denoised, nart_pixel* sum, nart_pixel* noisy, nart_pixel* image, nart_render_stats* stats,
+                          double* denoise_ms) {
+    nart_ctx* c0 = first_device(ctx);
+    ctx->dnp_guides_ms = 0.0;
+    FrameAsk gask(p->integrator);
+    gask.beauty = false;
+    ask_aovs(gask, NART_AOV_ALBEDO | NART_AOV_NORMAL, follow);
+    const FramePlan gplan = plan_frame(gask, PlanRules::Frame);
+    if (plan.code) return fail(ctx, plan.code, plan.message);  // (before anything is allocated)
+    if (gplan.code) return fail(ctx, gplan.code, gplan.message);
+    TileGrowthGuard guard(ctx);
+    Buf imgs, gimgs;  // the device images of the call, on device 0; freed on return
+    const uint32_t L = plan.n_outputs, O = L + (n_cuts ? K : 0), n_images = O + K + 1;
+    if (int rc = render_frame(ctx, p, plan, FrameRequest(&imgs, n_images), stats)) return rc;
+    nart_render_stats gstats = {};
+    if (int rc = render_frame(ctx, p, gplan, FrameRequest(&gimgs, 2), &gstats)) return rc;
+    ctx->dnp_guides_ms = gstats.render_ms;
+    RenderTimer timer(stats);
+    Images v(c0, p), gv(c0, p);
+    int rc = v.in(imgs, n_images, "image");  // (sized by the frames: this lays them out)
+    if (!rc) rc = gv.in(gimgs, 2, "image");
+    const int b = plan.find(OutputKind::Beauty);
+    if (!rc && n_cuts) rc = depth_layers_device(v, n_cuts, plan.find(OutputKind::DepthCut, 0), b, (int)L, 0);
+    const float* in[DNP_MAX_PARTS] = {};
+    float* o[DNP_MAX_PARTS] = {};
+    for (uint32_t k = 0; k < K; ++k) {
+        in[k] = n_cuts ? v.at(L + k) : v.at(plan.find(OutputKind::LightGroup, k));
+        o[k] = v.at(O + k);
+    }
+    if (!rc)
+        rc = denoise_parts_device(c0, v.layout, d, K, in, gv.at(gplan.find(follow ? OutputKind::GuideAlbedo : OutputKind::Albedo)),
+                                  gv.at(gplan.find(follow ? OutputKind::GuideNormal : OutputKind::Normal)), o,
+                                  sum ? v.at(O + K) : nullptr, 0, denoise_ms);
+    if (!rc) rc = v.download(O, denoised, K);
+    if (!rc && sum) rc = v.download(O + K, sum);
+    for (uint32_t k = 0; k < K && !rc && noisy; ++k)
+        rc = v.download(n_cuts ? L + k : plan.find(OutputKind::LightGroup, k), noisy + k * (v.layout.img_floats / 5));
+    if (!rc && image) rc = v.download(b, image);
+    return forwarded(ctx, rc);
 }
 
 // ---------------------------------------------------------------- cost image (device/cost.h)

@@ -58,6 +58,16 @@
 //   --depth-layers  with --depth-cuts: also write <out>.layer.00.exr ... <out>.layer.0K.exr, the light each
 //                   range of bounces added (nart_hip_depth_layers): the first cut, the differences of
 //                   neighbouring cuts, the beauty minus the last cut
+//   --denoise-parts  with --light-groups or --depth-cuts: also denoise the group images or the depth layers
+//                   one by one with shared guides (default parameters) and write them to
+//                   <out>.light.NN.denoised.exr or <out>.layer.NN.denoised.exr, and their sum to
+//                   <out>.denoised.exr; with --light-gains also <out>.mix.denoised.exr, the denoised groups
+//                   through nart_hip_light_mix.  The light groups take one call
+//                   (nart_hip_render_denoised_light_groups); the depth cuts, whose cut images are written
+//                   too, nart_hip_render_depth_cuts, nart_hip_depth_layers, a guides-only render and
+//                   nart_hip_denoise_parts: the same images.  The noisy layers are written only with
+//                   --depth-layers.  --follow-specular [N] next to it selects the followed guides.  Without
+//                   --light-groups or --depth-cuts: an error
 //   --cost          also write every session's cost image (nart_hip_render_cost, nart_hip_cost_image) to
 //                   <out>.cost.exr: RGBA the per-sample means of extension rays, shadow rays, shaded hits
 //                   and traversal steps (BVH node visits plus triangle tests) of every pixel of the
@@ -234,6 +244,7 @@ int main(int argc, char* argv[]) {
     const bool aovs = take_flag(args, "--aovs");
     const bool denoise = take_flag(args, "--denoise");
     const bool sample_variance = take_flag(args, "--sample-variance");
+    const bool denoise_parts = take_flag(args, "--denoise-parts");
     if (sample_variance && !denoise) {
         std::fprintf(stderr, "Error: --sample-variance selects the denoiser's variance input and needs --denoise\n");
         return EXIT_FAILURE;
@@ -302,7 +313,7 @@ int main(int argc, char* argv[]) {
     nart_hip_guide_defaults(&gp);
     float follow_arg = (float)gp.max_follow;
     const bool follow = take_optional_value_flag(args, "--follow-specular", follow_arg);
-    if (follow && !aovs && !denoise) {
+    if (follow && !aovs && !denoise && !denoise_parts) {
         std::fprintf(stderr, "Error: --follow-specular selects the guides of --aovs and --denoise and needs one of them\n");
         return EXIT_FAILURE;
     }
@@ -324,7 +335,7 @@ int main(int argc, char* argv[]) {
         std::fprintf(stderr, "Error: --light-gains scales the light groups and needs --light-groups\n");
         return EXIT_FAILURE;
     }
-    if (light_groups && (adaptive_arg || robust || mattes || aovs || denoise || follow)) {
+    if (light_groups && (adaptive_arg || robust || mattes || aovs || denoise || (follow && !denoise_parts))) {
         std::fprintf(stderr, "Error: --light-groups is not offered together with --adaptive, --robust, --mattes, --aovs, "
                              "--denoise or --follow-specular\n");
         return EXIT_FAILURE;
@@ -371,7 +382,7 @@ int main(int argc, char* argv[]) {
         std::fprintf(stderr, "Error: --depth-layers subtracts the depth cuts and needs --depth-cuts\n");
         return EXIT_FAILURE;
     }
-    if (depth_cuts && (light_groups || adaptive_arg || robust || mattes || aovs || denoise || follow)) {
+    if (depth_cuts && (light_groups || adaptive_arg || robust || mattes || aovs || denoise || (follow && !denoise_parts))) {
         std::fprintf(stderr, "Error: --depth-cuts is not offered together with --light-groups, --adaptive, --robust, --mattes, "
                              "--aovs, --denoise or --follow-specular\n");
         return EXIT_FAILURE;
@@ -392,6 +403,11 @@ int main(int argc, char* argv[]) {
             cuts.push_back((uint32_t)v);
             pos = c + 1;
         }
+    }
+    if (denoise_parts && !light_groups && !depth_cuts) {
+        std::fprintf(stderr, "Error: --denoise-parts denoises the light groups or the depth layers and needs --light-groups or "
+                             "--depth-cuts\n");
+        return EXIT_FAILURE;
     }
     // --cost
     const bool cost = take_flag(args, "--cost");
@@ -485,7 +501,8 @@ int main(int argc, char* argv[]) {
         const bool mattes_after = mattes && (aovs || denoise);
         if (denoise) denoised.resize(image.size());
         std::vector<uint32_t> bucket_spp;
-        std::vector<nart_pixel> group_imgs, mix_img, cut_imgs, layer_imgs, cost_img;
+        std::vector<nart_pixel> group_imgs, mix_img, cut_imgs, layer_imgs, cost_img, part_imgs, parts_sum, parts_mix;
+        const nart_guide_params* parts_gp = follow ? &gp : nullptr;
         if (cost) {
             uint32_t gw = 0, gh = 0;
             rc = nart_hip_cost_grid(&p, &gw, &gh);
@@ -509,14 +526,40 @@ int main(int argc, char* argv[]) {
         } else if (depth_cuts) {
             cut_imgs.resize(cuts.size() * image.size());
             rc = nart_hip_render_depth_cuts(ctx, &p, cuts.data(), (uint32_t)cuts.size(), cut_imgs.data(), image.data(), nullptr);
-            if (rc == NART_OK && depth_layers) {
+            if (rc == NART_OK && (depth_layers || denoise_parts)) {
                 layer_imgs.resize((cuts.size() + 1) * image.size());
                 rc = nart_hip_depth_layers(ctx, &p, (uint32_t)cuts.size(), cut_imgs.data(), image.data(), layer_imgs.data());
             }
+            if (rc == NART_OK && denoise_parts) {
+                // the guides alone (camera rays only), then the layers through the parts denoise
+                albedo.resize(image.size());
+                normal.resize(image.size());
+                rc = follow ? nart_hip_render_guides(ctx, &p, &gp, NART_AOV_ALBEDO | NART_AOV_NORMAL, nullptr, albedo.data(),
+                                                     normal.data(), nullptr, nullptr, nullptr)
+                            : nart_hip_render_aovs(ctx, &p, NART_AOV_ALBEDO | NART_AOV_NORMAL, nullptr, albedo.data(),
+                                                   normal.data(), nullptr, nullptr);
+                part_imgs.resize(layer_imgs.size());
+                parts_sum.resize(image.size());
+                if (rc == NART_OK)
+                    rc = nart_hip_denoise_parts(ctx, &p, nullptr, (uint32_t)cuts.size() + 1, layer_imgs.data(), albedo.data(),
+                                                normal.data(), part_imgs.data(), parts_sum.data(), nullptr);
+            }
         } else if (light_groups) {
             group_imgs.resize((size_t)n_groups * image.size());
-            rc = nart_hip_render_light_groups(ctx, &p, group_of_light.data(), (uint32_t)group_of_light.size(), n_groups,
-                                              group_imgs.data(), image.data(), nullptr);
+            if (denoise_parts) {
+                part_imgs.resize(group_imgs.size());
+                parts_sum.resize(image.size());
+                rc = nart_hip_render_denoised_light_groups(ctx, &p, nullptr, parts_gp, group_of_light.data(),
+                                                           (uint32_t)group_of_light.size(), n_groups, part_imgs.data(),
+                                                           parts_sum.data(), group_imgs.data(), image.data(), nullptr, nullptr);
+                if (rc == NART_OK && gains_arg) {
+                    parts_mix.resize(image.size());
+                    rc = nart_hip_light_mix(ctx, &p, n_groups, light_gains.data(), part_imgs.data(), parts_mix.data());
+                }
+            } else {
+                rc = nart_hip_render_light_groups(ctx, &p, group_of_light.data(), (uint32_t)group_of_light.size(), n_groups,
+                                                  group_imgs.data(), image.data(), nullptr);
+            }
             if (rc == NART_OK && gains_arg) {
                 mix_img.resize(image.size());
                 rc = nart_hip_light_mix(ctx, &p, n_groups, light_gains.data(), group_imgs.data(), mix_img.data());
@@ -634,6 +677,14 @@ int main(int argc, char* argv[]) {
             extra.push_back({".depth." + two(cuts[i]) + ".exr", cut_imgs.data() + i * image.size()});
         for (size_t i = 0; depth_layers && i <= cuts.size(); ++i)
             extra.push_back({".layer." + two((uint32_t)i) + ".exr", layer_imgs.data() + i * image.size()});
+        if (denoise_parts) {
+            const size_t n_parts = light_groups ? n_groups : cuts.size() + 1;
+            for (size_t i = 0; i < n_parts; ++i)
+                extra.push_back({std::string(light_groups ? ".light." : ".layer.") + two((uint32_t)i) + ".denoised.exr",
+                                 part_imgs.data() + i * image.size()});
+            extra.push_back({".denoised.exr", parts_sum.data()});
+            if (light_groups && gains_arg) extra.push_back({".mix.denoised.exr", parts_mix.data()});
+        }
         if (cost) extra.push_back({".cost.exr", cost_img.data()});
         std::vector<nart_pixel> spp_img;
         if (adaptive) {

@@ -130,6 +130,22 @@ inline const char* depth_cuts_error(const uint32_t* cuts, uint32_t n_cuts, uint3
     return nullptr;
 }
 
+// ---------------------------------------------------------------- denoised parts
+// A parts denoise (include/nart_hip.h, "Denoised parts"): n_parts images in 1..9; images_given: every
+// image the call requires is there; dp (null: the defaults) into d; follow (null: the first-hit AOVs are
+// the guides) into g.  The rules in this order: the count, the images, the denoiser's, the guides'.
+// The whole-frame calls check their group map or their cuts first (light_groups_error, depth_cuts_error)
+// and hand in the number of parts those give.
+inline const char* denoise_parts_error(uint32_t n_parts, bool images_given, const nart_denoise_params* dp,
+                                       nart_denoise_params& d, const nart_guide_params* follow, nart_guide_params& g) {
+    d = dp ? *dp : DENOISE_DEFAULTS;
+    g = follow ? *follow : GUIDE_DEFAULTS;
+    if (n_parts < 1 || n_parts > NART_DENOISE_PARTS_MAX) return "n_parts must be 1..9";
+    if (!images_given) return "the part images, the guide images and the denoised images are required";
+    if (const char* why = denoise_params_error(dp, d)) return why;
+    return follow ? guide_params_error(follow, g) : nullptr;
+}
+
 // ---------------------------------------------------------------- what the stages need of p
 // What the stages over whole images (denoiser, reweighting, ranking) need of p without check_params.
 inline const char* check_image_size(const nart_render_params* p) {

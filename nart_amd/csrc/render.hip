@@ -21,6 +21,7 @@
 #include "device/cascade.h"
 #include "device/cost.h"
 #include "device/denoise.h"
+#include "device/denoise_parts.h"
 #include "device/depthcut.h"
 #include "device/guide.h"
 #include "device/lbvh.h"
@@ -31,6 +32,7 @@
 #include "device/volume.h"
 #include "host/bucket_batch.h"
 #include "host/bvh_build.h"
+#include "host/denoise_parts_plan.h"
 #include "host/device_buf.h"
 #include "host/frame_plan.h"
 #include "host/latin_plan.h"
@@ -144,6 +146,14 @@ struct nart_ctx {
     Buf d_dn, d_dn_img;
     Event ev_dn[12];
     double dn_ms[11] = {};  // prepare, variance, passes 0..7, finalise
+    // denoised parts (denoise_parts_device): events between its kernels (prepare, then per chunk the
+    // variance, up to 8 passes and finalise, then the sum); the last run's times on the first device's
+    // context: prepare, variance, passes 0..7, finalise, sum, each summed over the chunks; on the
+    // caller's context the render_ms of the last whole-frame call's guides frame.  Its work buffers
+    // and images are temporaries of the call.
+    Event ev_dnp[2 + 9 * 10 + 1];
+    double dnp_ms[12] = {};
+    double dnp_guides_ms = 0.0;
     uint32_t sched = 0;        // NART_SCHED_* bits of the current render (nart_render_stats::schedule)
     // path-kernel scheduling buffers (ensure_queue, ensure_ilist, ensure_gstack; launch_render,
     // dispatch_volume): the queue group shares a capacity counted in queue entries
@@ -2763,6 +2773,75 @@ int nart_hip_denoise_timings(const nart_ctx* ctx, double* prepare_ms, double* va
     if (pass_ms)
         for (int k = 0; k < 8; ++k) pass_ms[k] = c0->dn_ms[2 + k];
     if (finalize_ms) *finalize_ms = c0->dn_ms[10];
+    return NART_OK;
+}
+
+int nart_hip_denoise_parts(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, uint32_t n_parts,
+                           const nart_pixel* parts, const nart_pixel* albedo, const nart_pixel* normal, nart_pixel* out,
+                           nart_pixel* sum, double* denoise_ms) {
+    if (!ctx || !p) return NART_E_INVALID;
+    nart_denoise_params d;
+    nart_guide_params g;
+    if (const char* why = denoise_parts_error(n_parts, parts && albedo && normal && out, dp, d, nullptr, g))
+        return fail(ctx, NART_E_INVALID, why);
+    return denoise_parts_host(ctx, p, d, n_parts, parts, albedo, normal, out, sum, denoise_ms);
+}
+
+int nart_hip_render_denoised_light_groups(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                                          const nart_guide_params* gp, const uint32_t* group_of_light, uint32_t n_lights,
+                                          uint32_t n_groups, nart_pixel* denoised, nart_pixel* sum, nart_pixel* groups,
+                                          nart_pixel* image, nart_render_stats* stats, double* denoise_ms) {
+    if (!ctx || !p) return NART_E_INVALID;
+    if (const char* why = light_groups_error(group_of_light, n_lights, first_device(ctx)->scene.num_lights, n_groups))
+        return fail(ctx, NART_E_INVALID, why);
+    nart_denoise_params d;
+    nart_guide_params g;
+    if (const char* why = denoise_parts_error(n_groups, denoised != nullptr, dp, d, gp, g)) return fail(ctx, NART_E_INVALID, why);
+    ctx->lg_ms[0] = 0.0;
+    FrameAsk ask(p->integrator);
+    ask.light_groups = n_groups;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    if (plan.code) return fail(ctx, plan.code, plan.message);  // (before anything is uploaded)
+    if (int rc = set_light_groups(ctx, group_of_light)) return rc;
+    const int rc = render_denoised_parts(ctx, p, d, gp ? &g : nullptr, plan, 0, n_groups, denoised, sum, groups, image, stats,
+                                         denoise_ms);
+    for (const nart_ctx* c : ctx->subs) ctx->lg_ms[0] = std::max(ctx->lg_ms[0], c->lg_ms[0]);  // the slowest device's
+    return rc;
+}
+
+int nart_hip_render_denoised_depth_layers(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                                          const nart_guide_params* gp, const uint32_t* cuts, uint32_t n_cuts,
+                                          nart_pixel* denoised, nart_pixel* sum, nart_pixel* layers, nart_pixel* image,
+                                          nart_render_stats* stats, double* denoise_ms) {
+    if (!ctx || !p) return NART_E_INVALID;
+    if (const char* why = depth_cuts_error(cuts, n_cuts, p->bounces)) return fail(ctx, NART_E_INVALID, why);
+    nart_denoise_params d;
+    nart_guide_params g;
+    if (const char* why = denoise_parts_error(n_cuts + 1, denoised != nullptr, dp, d, gp, g))
+        return fail(ctx, NART_E_INVALID, why);
+    ctx->dc_ms[0] = first_device(ctx)->dc_ms[1] = 0.0;
+    FrameAsk ask(p->integrator);
+    ask.depth_cuts = n_cuts;
+    const FramePlan plan = plan_frame(ask, PlanRules::Frame);
+    if (plan.code) return fail(ctx, plan.code, plan.message);
+    set_depth_cuts(ctx, cuts, n_cuts);
+    const int rc = render_denoised_parts(ctx, p, d, gp ? &g : nullptr, plan, n_cuts, n_cuts + 1, denoised, sum, layers, image,
+                                         stats, denoise_ms);
+    for (const nart_ctx* c : ctx->subs) ctx->dc_ms[0] = std::max(ctx->dc_ms[0], c->dc_ms[0]);  // the slowest device's
+    return rc;
+}
+
+int nart_hip_denoise_parts_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
+                                   double* finalize_ms, double* sum_ms, double* guides_ms) {
+    if (!ctx) return NART_E_INVALID;
+    const nart_ctx* c0 = first_device(ctx);
+    if (prepare_ms) *prepare_ms = c0->dnp_ms[0];
+    if (variance_ms) *variance_ms = c0->dnp_ms[1];
+    if (pass_ms)
+        for (int k = 0; k < 8; ++k) pass_ms[k] = c0->dnp_ms[2 + k];
+    if (finalize_ms) *finalize_ms = c0->dnp_ms[10];
+    if (sum_ms) *sum_ms = c0->dnp_ms[11];
+    if (guides_ms) *guides_ms = ctx->dnp_guides_ms;
     return NART_OK;
 }
 
