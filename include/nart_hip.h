@@ -644,6 +644,123 @@ int nart_hip_render_guide_samples(nart_ctx* ctx, const nart_render_params* p, co
                                   uint32_t y0, uint32_t w, uint32_t h, float* out8, float* seg8, uint32_t* tri,
                                   uint32_t* n_seg);
 
+/* Half buffers: the beauty's samples split by the parity of their index into two images from a single
+   render, after Rousselle, Knaus and Zwicker, "Adaptive Rendering with Non-Local Means Filtering"
+   (2012), and Bitterli et al., "Nonlinearly Weighted First-order Regression for Denoising Monte Carlo
+   Renderings" (2016).  Two images of independent halves of the samples are what cross-filtering
+   denoisers and error estimates start from: the difference of the halves estimates the noise of their
+   average without assuming independent samples within a pixel (ours are Latin-square stratified).
+
+   Half image h (0 or 1), a nart_pixel image laid out as the beauty:
+       contribution      { sum w r, sum w g, sum w b, sum w } over the (sample, pixel) pairs of the
+                         beauty's splat whose sample index i has i mod 2 == h, in the beauty's order
+       filter_weight_sum the beauty's: sum w over all samples, with the beauty's bits
+   i is the sample's index 0..spp-1 in its pixel's sequence: the s of nart_hip_render_samples.  The
+   half's mean is rgb / contribution[3], normalised by its own weights; finalize and the EXR writer
+   divide by filter_weight_sum as for any image, so that the two written halves add up to the beauty
+   up to rounding.  At spp 1 half 0 has the beauty's rgb bits and half 1 is zero but for
+   filter_weight_sum.
+
+   On the device k_half_split (device/halves.h) runs once per half per batch after the beauty's splat
+   and before any other pass overwrites the per-sample records: a sample of parity h writes
+   {L.r, L.g, L.b, 1} (the colour copied: a non-finite colour reaches exactly one half), every other
+   sample {0, 0, 0, 0}, into a second record buffer of 16 B per sample held for the call only; the
+   plan's splat then takes it into the half's tiles, unchanged (adding the zero records changes no
+   bit of a finite sum).
+
+   nart_hip_render_halves: image, half_a (h = 0) and half_b (h = 1) are required; aovs selects the
+   albedo and normal images (NART_AOV_ALBEDO, NART_AOV_NORMAL) as nart_hip_render_aovs does, and with
+   gp non-null they hold the followed guides of nart_hip_render_guides.  The beauty, the AOVs and the
+   guides have the bits those entry points give.  halves_ms, if non-null, receives the device time of
+   the splits and the half splats.  The volume integrator is supported where aovs is 0.  Multi-device
+   contexts gather the half tiles with the beauty's gather.
+   NART_E_INVALID: a null ctx, p, image, half_a or half_b, an unknown AOV bit, a bit without its
+   buffer, max_follow > 10.  NART_E_UNSUPPORTED: AOVs or guides with the volume integrator.  An error
+   leaves the context usable.  Not offered: half buffers together with the moment image, adaptive
+   sampling, the cascade, the mattes, light groups, depth cuts or the cost image in one call. */
+int nart_hip_render_halves(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, const nart_guide_params* gp,
+                           nart_pixel* image, nart_pixel* albedo, nart_pixel* normal, nart_pixel* half_a, nart_pixel* half_b,
+                           nart_render_stats* stats, double* halves_ms);
+
+/* Cross-filtered denoising: the a-trous denoiser above over the two half buffers, each half filtered
+   with colour weights taken from the other half, after Rousselle et al. 2012 and Bitterli et al. 2016
+   (see "Half buffers").  The plain denoiser compares lum(s_p) and lum(s_q) of the signal it averages:
+   a pixel that is bright by chance rejects its neighbours and survives.  Here the noise of the
+   weights is independent of the noise they average, and the difference of the two filtered halves
+   estimates the error of their average.
+
+   Everything is float32 + - * / sqrt and comparisons in the order below, built without contraction;
+   tests/denoise_cross_py.py restates it.  Sums start at 0 and run over dy then dx, ascending, as the
+   plain denoiser's do; min, max, lum, the guide terms w_n, d_g and the falloff f are the plain
+   denoiser's ("Guide terms").  H_h is half image h, p a pixel of the cropped window.
+
+   Prepare.  The guide {n, z}, the coverage, a_d, the depth slope and alpha are what the plain
+   denoiser's prepare computes from the albedo, normal and beauty images.
+       c_h = H_h.rgb / H_h[3]                 per half, by its own weight sum
+       valid(p): H_0[3] > 0 and H_1[3] > 0 and all six components of c_0, c_1 finite
+       s_h = c_h / a_d                         per channel
+       d   = lum(s_0) - lum(s_1)
+       v   = 0.5f * (d * d)                    the initial variance of both halves
+   v is the one-sample estimate of the variance of one half's luminance (the two halves have equal
+   variance and d has twice it), so that den = sigma_color * sqrt(v) stands against a tap difference
+   of variance 2 v as in the plain denoiser.  An invalid pixel is {0, 0, 0, -1} in both halves.
+
+   Variance.  For a valid p, over the taps q of the 7x7 window that lie in the image and are valid:
+       u = 1 at the centre, else w_n * f(d_g + 0)
+       su = su + u;  sv = sv + u * v(q)        v(p) <- sv / su, for both halves
+   An invalid pixel stays as it is.
+
+   A-trous pass at step 2^i, for every p (valid or not), both halves at once.  With o = 1 - h:
+       vb_h   = sum over the 3x3 taps (clamped coordinates) of k * max(v_h(q), 0), k = {1/4, 1/2, 1/4}^2
+       den_h  = sigma_color * sqrt(vb_o) + 1e-6f, lp_h = lum(s_o(p))     where half o is valid at p
+   For each tap q = p + step * (ix, iy), ix, iy in -2..2, inside the image, with a valid half:
+       (w_n, d_g) once per tap, with cheb = step * max(|ix|, |iy|)       (not at the centre)
+       for h = 0, 1 where half h is valid at q:
+           d_l = |lp_h - lum(s_o(q))| / den_h   where half o is valid at p and at q, else 0
+           w   = h_x * h_y at the centre, else (h_x * h_y) * (w_n * f(d_g + d_l))
+           sw_h += w;  s_h' += w * s_h(q) per channel;  sv_h += (w * w) * v_h(q)
+       s_h(p) <- s_h' / sw_h,  v_h(p) <- sv_h / (sw_h * sw_h)     where sw_h > 0, else half h is invalid at p
+   The colour distance of half h comes from the other half, and den_h from the variance of the half
+   whose colours are compared.
+
+   Finalize.  Cropped pixels, per channel c:
+       out_c = ((s_0c + s_1c) * 0.5f) * a_d_c                         out   = {out.rgb, alpha, 1}
+       t     = ((s_0c - s_1c) * 0.5f) * a_d_c;  e_c = t * t           error = {e.rgb, alpha, 1}
+   A pixel with an invalid half gets the beauty's mean (0 where its weight sum is <= 0) and error 0.
+   Border pixels are zero in both images.  e_c is a one-degree-of-freedom estimate per pixel of the
+   squared error of out_c: average it over a neighbourhood before use.
+
+   The order is symmetric in the halves: + and * commute, d and t only change sign before they are
+   squared, and each half's sums see the other half's values in the same places.  Swapping half_a and
+   half_b leaves both images bit-equal.  With identical halves d = 0 and v = 0 throughout, s_0 = s_1,
+   the error is exactly 0 and out.rgb has the bits of the plain denoiser's prepare, a-trous passes
+   and finalise run with variance 0 (no variance kernel) on a beauty whose mean is the halves'.
+
+   On the device (device/denoise_cross.h) k_dnx_prepare, k_dnx_variance, k_dnx_atrous<R> and
+   k_dnx_finalize run on 32 x 8 tiles with the plain denoiser's LDS halo scheme (two signals, one
+   guide and the coverage per staged pixel: 52 B, at most 40 x 16 pixels); the guide half of a tap
+   weight is computed once for both halves.
+
+   nart_hip_denoise_cross: host images in, as nart_hip_denoise: the two halves and the beauty of
+   nart_hip_render_halves, the albedo and normal images (first-hit or followed); out receives the
+   denoised image and error, if non-null, the error image.  dp null: the defaults of
+   nart_hip_denoise_params_init, which are not changed.  denoise_ms: the device time.
+   nart_hip_render_denoised_cross: renders the halves and the AOVs (gp non-null: the followed
+   guides) and filters them on the device; nothing but out, error and, if non-null, image (the beauty)
+   passes the host.  The images equal nart_hip_denoise_cross fed with nart_hip_render_halves' images.
+   nart_hip_denoise_cross_timings: as nart_hip_denoise_timings, of the last cross call.
+   NART_E_INVALID: a null ctx, p or required image, p->spp < 2 (a half would be empty), the parameter
+   errors of nart_hip_denoise, max_follow > 10.  NART_E_UNSUPPORTED (nart_hip_render_denoised_cross):
+   the volume integrator (the guides need surfaces).  An error leaves the context usable. */
+int nart_hip_denoise_cross(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, const nart_pixel* half_a,
+                           const nart_pixel* half_b, const nart_pixel* beauty, const nart_pixel* albedo,
+                           const nart_pixel* normal, nart_pixel* out, nart_pixel* error, double* denoise_ms);
+int nart_hip_render_denoised_cross(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                                   const nart_guide_params* gp, nart_pixel* out, nart_pixel* error, nart_pixel* image,
+                                   nart_render_stats* stats, double* denoise_ms);
+int nart_hip_denoise_cross_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
+                                   double* finalize_ms);
+
 /* Light groups: the beauty split by light, one image per group of lights from a single render, so
    that a light can be dimmed, tinted or switched off afterwards (nart_hip_light_mix) without tracing
    a path again.

@@ -8,7 +8,7 @@ from .api import (HIP_SYMBOLS, PIXEL_FLOATS, SCENE_SYMBOLS, HipRenderer, bvh_inf
                   hip_lib, load_sessions, parse_args, read_exr, scene_lib, session_geometry, shard_buckets,
                   write_exr, DenoiseParams, sample_variance, AdaptiveParams, adaptive_levels, spp_image,
                   CascadeParams, cascade_levels, MatteParams, matte_ids, GuideParams, LIGHT_GROUPS_MAX,
-                  DEPTH_CUTS_MAX, EVAL_OPS, EVAL_WORDS, EVAL_MASKS, FT_ALL, cost_grid,
+                  DEPTH_CUTS_MAX, EVAL_OPS, EVAL_WORDS, EVAL_MASKS, FT_ALL, cost_grid, half_mean,
                   TRACE_VARIANTS, TRACE_IN_WORDS, TRACE_OUT_WORDS, TRACE_NO_HIT, TRACE_CLOSEST, TRACE_ANY, trace_rays)
 
 __all__ = ["HipRenderer", "bvh_info", "bvh_dump", "NartError", "NativeLibraryMissing", "RenderParams", "RenderStats", "Scene",
@@ -16,5 +16,5 @@ __all__ = ["HipRenderer", "bvh_info", "bvh_dump", "NartError", "NativeLibraryMis
            "write_exr", "hip_lib", "scene_lib", "session_geometry", "PIXEL_FLOATS", "HIP_SYMBOLS", "SCENE_SYMBOLS",
            "DenoiseParams", "sample_variance", "AdaptiveParams", "adaptive_levels", "spp_image",
            "CascadeParams", "cascade_levels", "MatteParams", "matte_ids", "GuideParams", "LIGHT_GROUPS_MAX",
-           "DEPTH_CUTS_MAX", "EVAL_OPS", "EVAL_WORDS", "EVAL_MASKS", "FT_ALL", "cost_grid",
+           "DEPTH_CUTS_MAX", "EVAL_OPS", "EVAL_WORDS", "EVAL_MASKS", "FT_ALL", "cost_grid", "half_mean",
            "TRACE_VARIANTS", "TRACE_IN_WORDS", "TRACE_OUT_WORDS", "TRACE_NO_HIT", "TRACE_CLOSEST", "TRACE_ANY", "trace_rays"]

@@ -248,6 +248,9 @@ _HIP_SIGS = {
     "nart_hip_render_moment": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, _P, _P, _P, _P,
                                               ctypes.POINTER(RenderStats), ctypes.POINTER(ctypes.c_double),
                                               ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_halves": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.c_uint32, ctypes.POINTER(GuideParams),
+                                              _P, _P, _P, _P, _P, ctypes.POINTER(RenderStats),
+                                              ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_adaptive_params_init": (None, [ctypes.POINTER(AdaptiveParams)]),
     "nart_hip_adaptive_levels": (ctypes.c_int, [ctypes.POINTER(AdaptiveParams), ctypes.c_uint32,
                                                 ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
@@ -314,6 +317,13 @@ _HIP_SIGS = {
                                                      _P, _P, _P, _P]),
     "nart_hip_denoise_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_denoise_cross": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams), _P, _P, _P, _P,
+                                              _P, _P, _P, ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_render_denoised_cross": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams),
+                                                      ctypes.POINTER(GuideParams), _P, _P, _P, ctypes.POINTER(RenderStats),
+                                                      ctypes.POINTER(ctypes.c_double)]),
+    "nart_hip_denoise_cross_timings": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                      ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_denoise_parts": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams), ctypes.c_uint32,
                                               _P, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_double)]),
     "nart_hip_render_denoised_light_groups": (ctypes.c_int, [_P, ctypes.POINTER(RenderParams), ctypes.POINTER(DenoiseParams),
@@ -1113,6 +1123,31 @@ class HipRenderer:
         out["guide_ms"] = ms.value
         return out
 
+    def render_halves(self, p, albedo=False, normal=False, guides=None, stats=None):
+        """Half buffers (nart_hip_render_halves; include/nart_hip.h has the definition): the beauty and
+        the images of its samples of even and of odd index, from one render.  Returns a dict with
+        "beauty" (bit-identical to render()), "halves" ((2, totalH, totalW, 5) float32: half h holds
+        {sum w r, sum w g, sum w b, sum w} over its own samples and the beauty's filter weight sum;
+        half_mean() gives its mean), the requested "albedo" / "normal" images -- the first-hit AOVs of
+        render_aovs(), or with guides a GuideParams the followed guides of render_guides() -- and
+        "halves_ms", the device time of the splits and the half splats."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        out = {"beauty": np.empty(shape, np.float32), "halves": np.empty((2,) + shape, np.float32)}
+        for name, want in (("albedo", albedo), ("normal", normal)):
+            if want:
+                out[name] = np.empty(shape, np.float32)
+        ptr = lambda name: out[name].ctypes.data if name in out else None
+        st = stats if stats is not None else RenderStats()
+        ms = ctypes.c_double()
+        mask = (AOV_ALBEDO if albedo else 0) | (AOV_NORMAL if normal else 0)
+        self._check(self._lib.nart_hip_render_halves(self._ctx, ctypes.byref(p), mask,
+                                                     ctypes.byref(guides) if guides is not None else None, ptr("beauty"),
+                                                     ptr("albedo"), ptr("normal"), out["halves"][0].ctypes.data,
+                                                     out["halves"][1].ctypes.data, ctypes.byref(st), ctypes.byref(ms)))
+        out["halves_ms"] = ms.value
+        return out
+
     def render_guide_samples(self, p, x0, y0, w, h, params=None):
         """Per-sample guide chains of a rect in total-image coordinates (nart_hip_render_guide_samples),
         M = max_follow + 1: a dict with "rec" (h, w, spp, 8) float32 = {albedo record, normal record},
@@ -1189,6 +1224,59 @@ class HipRenderer:
         passes = (ctypes.c_double * 8)()
         self._check(self._lib.nart_hip_denoise_timings(self._ctx, ctypes.byref(a), ctypes.byref(b), passes,
                                                        ctypes.byref(c)))
+        return {"prepare": a.value, "variance": b.value, "passes": list(passes), "finalize": c.value}
+
+    def denoise_cross(self, p, half_a, half_b, beauty, albedo, normal, params=None, with_error=True):
+        """Cross-filtered denoising of host images (nart_hip_denoise_cross; include/nart_hip.h,
+        "Cross-filtered denoising"): half_a, half_b and beauty as render_halves() returns them, albedo
+        and normal as render_aovs() or render_guides() do; params a DenoiseParams (None: the defaults).
+        Each half is filtered with colour weights taken from the other.  Returns a dict with "denoised",
+        the average of the two filtered halves ({rgb, alpha, 1} in the cropped window, zero in the
+        border), "error" unless with_error=False ({e.rgb, alpha, 1}: per channel the squared half
+        difference of the filtered halves, a one-sample estimate of the squared error of "denoised")
+        and "denoise_ms".  p.spp >= 2."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        src = [np.ascontiguousarray(a, dtype=np.float32) for a in (half_a, half_b, beauty, albedo, normal)]
+        for a in src:
+            if a.shape != shape:
+                raise ValueError("denoise_cross: image of shape %s, expected %s" % (a.shape, shape))
+        out = {"denoised": np.empty(shape, np.float32)}
+        if with_error:
+            out["error"] = np.empty(shape, np.float32)
+        ms = ctypes.c_double()
+        self._check(self._lib.nart_hip_denoise_cross(self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
+                                                     *[a.ctypes.data for a in src], out["denoised"].ctypes.data,
+                                                     out["error"].ctypes.data if with_error else None, ctypes.byref(ms)))
+        out["denoise_ms"] = ms.value
+        return out
+
+    def render_denoised_cross(self, p, params=None, beauty=True, stats=None, guides=None):
+        """Render the beauty, its two half buffers and both first-hit AOVs (guides a GuideParams: the
+        followed guides) and cross-denoise them on the device (nart_hip_render_denoised_cross): a dict
+        with "denoised", "error", "beauty" (bit-identical to render(); only if requested) and
+        "denoise_ms".  The images are denoise_cross()'s over render_halves()' images.  p.spp >= 2."""
+        g = session_geometry(p)
+        shape = (g.total_height, g.total_width, PIXEL_FLOATS)
+        out = {"denoised": np.empty(shape, np.float32), "error": np.empty(shape, np.float32)}
+        if beauty:
+            out["beauty"] = np.empty(shape, np.float32)
+        st = stats if stats is not None else RenderStats()
+        ms = ctypes.c_double()
+        self._check(self._lib.nart_hip_render_denoised_cross(
+            self._ctx, ctypes.byref(p), ctypes.byref(params) if params else None,
+            ctypes.byref(guides) if guides is not None else None, out["denoised"].ctypes.data, out["error"].ctypes.data,
+            out["beauty"].ctypes.data if beauty else None, ctypes.byref(st), ctypes.byref(ms)))
+        out["denoise_ms"] = ms.value
+        return out
+
+    def denoise_cross_timings(self):
+        """Device times (ms) of the last cross denoise, kernel by kernel (nart_hip_denoise_cross_timings):
+        {"prepare", "variance", "passes": [8], "finalize"}."""
+        a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        passes = (ctypes.c_double * 8)()
+        self._check(self._lib.nart_hip_denoise_cross_timings(self._ctx, ctypes.byref(a), ctypes.byref(b), passes,
+                                                             ctypes.byref(c)))
         return {"prepare": a.value, "variance": b.value, "passes": list(passes), "finalize": c.value}
 
     def denoise_parts(self, p, parts, albedo, normal, params=None, with_sum=False):
@@ -1397,6 +1485,14 @@ def spp_image(p, bucket_spp):
     b = np.ascontiguousarray(bucket_spp, np.uint32).reshape(g.n_buckets_y, g.n_buckets_x)
     B = p.bucket_size
     return np.repeat(np.repeat(b, B, axis=0), B, axis=1)[:p.image_height, :p.image_width].copy()
+
+
+def half_mean(half):
+    """The mean colour of a half buffer of render_halves(), normalised by the half's own weights:
+    (..., 3) float32 rgb / contribution[3], and 0 where the half holds no sample."""
+    h = np.ascontiguousarray(half, np.float32)
+    with np.errstate(all="ignore"):
+        return np.where((h[..., 3] > 0)[..., None], h[..., :3] / h[..., 3:4], np.float32(0)).astype(np.float32)
 
 
 def sample_variance(p, beauty, moment):

@@ -14,7 +14,8 @@ namespace nd {
 constexpr uint32_t FRAME_MAX_LAYERS = 8, FRAME_MAX_PLANES = 8, FRAME_MAX_MATTE_IDS = 4 * FRAME_MAX_PLANES;
 // beauty, two first-hit AOVs, moment, layers, planes, two followed guides (a frame has layers or
 // planes, and first-hit AOVs or followed guides: at most twelve; a light-group frame the beauty and
-// its groups, a depth-cut frame the beauty and its cuts: at most nine)
+// its groups, a depth-cut frame the beauty and its cuts: at most nine; a half-buffer frame the beauty,
+// two AOVs or guides and the two halves: five)
 constexpr uint32_t FRAME_MAX_OUTPUTS = 4 + FRAME_MAX_LAYERS + FRAME_MAX_PLANES + 2;
 constexpr uint32_t FRAME_MAX_LIGHT_GROUPS = 8;  // include/nart_hip.h NART_LIGHT_GROUPS_MAX
 constexpr uint32_t FRAME_MAX_DEPTH_CUTS = 8;    // include/nart_hip.h NART_DEPTH_CUTS_MAX
@@ -50,13 +51,16 @@ struct FrameAsk {  // what the caller asks for
     // the cost image (include/nart_hip.h, "Cost image"): a per-pixel grid of counts next to the beauty.
     // Not a tile image: no output of the list, no pass, no splat, combine or gather
     bool cost = false;
+    // the half buffers (include/nart_hip.h, "Half buffers"): the beauty's samples of even and of odd
+    // index, each into a tile image of its own
+    bool halves = false;
     explicit FrameAsk(uint32_t integrator_) : integrator(integrator_) {}
 };
 
 // One tile buffer (and image) of a render; index: j of cascade layer j, q of matte plane q, g of light
-// group g, j of depth cut j, else 0.
+// group g, j of depth cut j, else 0.  HalfA: the samples of even index, HalfB: of odd index.
 enum class OutputKind : uint32_t {
-    Beauty, Albedo, Normal, Moment, Layer, Plane, GuideAlbedo, GuideNormal, LightGroup, DepthCut
+    Beauty, Albedo, Normal, Moment, Layer, Plane, GuideAlbedo, GuideNormal, LightGroup, DepthCut, HalfA, HalfB
 };
 struct FrameOutput { OutputKind kind = OutputKind::Beauty; uint32_t index = 0; };
 
@@ -68,13 +72,19 @@ struct FrameOutput { OutputKind kind = OutputKind::Beauty; uint32_t index = 0; }
 //   PASS_FIRST_HIT  k_aov overwrites d_L from the camera-ray hits (d_prim), one AOV at a time;
 //   PASS_MATTE      k_matte_ids overwrites d_L from the same hits, one plane at a time;
 //   PASS_GUIDE      k_guide traces every sample's chain once: the albedo record overwrites d_L, the
-//                   normal record goes to a second record buffer where both are asked for.
-enum PassKind : uint32_t { PASS_CASCADE, PASS_MOMENT, PASS_FIRST_HIT, PASS_MATTE, PASS_GUIDE, N_PASSES };
+//                   normal record goes to a second record buffer where both are asked for;
+//   PASS_HALVES     reads the Li_alpha records in d_L like the cascade (k_half_split into a second
+//                   record buffer, one half at a time).  It runs first among a frame's passes, though it
+//                   has the largest value: N_PASSES is also pass_of's "no pass" and stays what it was,
+//                   so the new pass takes the next value after it.
+enum PassKind : uint32_t { PASS_CASCADE, PASS_MOMENT, PASS_FIRST_HIT, PASS_MATTE, PASS_GUIDE, N_PASSES, PASS_HALVES };
+constexpr uint32_t PASS_SLOTS = PASS_HALVES + 1;  // what is indexed by PassKind has this many entries
 // The pass that fills an output's records, by OutputKind; N_PASSES: the beauty, the light groups
 // and the depth cuts, the path kernel's own.
 constexpr PassKind PASS_OF[8] = {N_PASSES,     PASS_FIRST_HIT, PASS_FIRST_HIT, PASS_MOMENT,
                                  PASS_CASCADE, PASS_MATTE,     PASS_GUIDE,     PASS_GUIDE};
 inline PassKind pass_of(OutputKind k) {
+    if (k == OutputKind::HalfA || k == OutputKind::HalfB) return PASS_HALVES;
     return k == OutputKind::LightGroup || k == OutputKind::DepthCut ? N_PASSES : PASS_OF[(uint32_t)k];
 }
 
@@ -84,15 +94,16 @@ struct FramePlan {
     FrameAsk ask{NART_INTEGRATOR_PATH};
     // Tile buffers and images in delivery order: beauty, albedo, normal, moment, then the layers or
     // the planes ascending, then the followed guides; a light-group frame: the beauty, then the groups
-    // ascending; a depth-cut frame: the beauty, then the cuts ascending.  On-device delivery lays the images out back to back in this order.
+    // ascending; a depth-cut frame: the beauty, then the cuts ascending; the two halves come after the
+    // followed guides.  On-device delivery lays the images out back to back in this order.
     FrameOutput outputs[FRAME_MAX_OUTPUTS];
     uint32_t n_outputs = 0;
-    PassKind passes[N_PASSES] = {};  // the passes that run, ascending
+    PassKind passes[PASS_SLOTS] = {};  // the passes that run: the halves' first, the others ascending
     uint32_t n_passes = 0;
     bool path_kernel = false;   // false: camera rays only (first-hit outputs without the beauty)
     // per-sample record memory beyond d_L (batch_slot_limit): the cascade's buffer, the second guide
-    // record's where both guides are asked for, one record per light group or depth cut, or the cost
-    // record
+    // record's where both guides are asked for, one record per light group or depth cut, the cost
+    // record, or the halves' buffer (free again when the guide pass runs: the two share the 16 bytes)
     uint32_t record_bytes = 0;
 
     int find(OutputKind kind, uint32_t index = 0) const {  // position in the list, or -1
@@ -173,6 +184,14 @@ inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
                           a.depth_cuts)) {
         why = "the cost image is not rendered with the cascade, the mattes, AOVs, guides, the moment image, light groups or "
               "depth cuts in one call";
+    } else if (a.halves && !a.beauty) {
+        code = NART_E_INVALID;
+        why = "the half buffers need the path kernel (the beauty)";
+    } else if (a.halves && a.adaptive) {
+        why = "the half buffers need a uniform render: not adaptive sampling";
+    } else if (a.halves && (a.moment || a.cascade.K || a.matte.on || a.light_groups || a.depth_cuts || a.cost)) {
+        why = "the half buffers are not rendered with the moment image, the cascade, the mattes, light groups, depth cuts or "
+              "the cost image in one call";
     }
     if (!why.empty()) {
         plan.code = code;
@@ -189,17 +208,20 @@ inline FramePlan plan_frame(const FrameAsk& a, PlanRules rules) {
     for (uint32_t q = 0; q < a.matte.planes(); ++q) add(OutputKind::Plane, q);
     if (a.guide[0]) add(OutputKind::GuideAlbedo, 0);
     if (a.guide[1]) add(OutputKind::GuideNormal, 0);
+    if (a.halves) add(OutputKind::HalfA, 0);
+    if (a.halves) add(OutputKind::HalfB, 0);
     for (uint32_t g = 0; g < a.light_groups; ++g) add(OutputKind::LightGroup, g);
     for (uint32_t j = 0; j < a.depth_cuts; ++j) add(OutputKind::DepthCut, j);
     // An adaptive render estimates a bucket's error from its moment tiles: every level runs the moment
     // pass, wanted or not (adaptive_level_ask).
-    bool runs[N_PASSES + 1] = {};
+    bool runs[PASS_SLOTS] = {};
     runs[PASS_MOMENT] = a.adaptive;
     for (uint32_t i = 0; i < plan.n_outputs; ++i) runs[pass_of(plan.outputs[i].kind)] = true;
+    if (runs[PASS_HALVES]) plan.passes[plan.n_passes++] = PASS_HALVES;  // before anything overwrites Li_alpha
     for (uint32_t k = 0; k < N_PASSES; ++k)
         if (runs[k]) plan.passes[plan.n_passes++] = (PassKind)k;
     plan.path_kernel = a.beauty;
-    plan.record_bytes = (a.cascade.K || (a.guide[0] && a.guide[1])) ? 16 : 0;  // one float4 per sample
+    plan.record_bytes = (a.cascade.K || a.halves || (a.guide[0] && a.guide[1])) ? 16 : 0;  // one float4 per sample
     if (a.light_groups) plan.record_bytes = 16 * a.light_groups;              // and per group
     if (a.depth_cuts) plan.record_bytes = 16 * a.depth_cuts;                  // or per cut
     if (a.cost) plan.record_bytes = 16;                                       // one uint4 per sample

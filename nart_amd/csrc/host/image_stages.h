@@ -104,6 +104,53 @@ int render_aovs(nart_ctx* ctx, const nart_render_params* p, const nart_guide_par
     return rc;
 }
 
+// The tile buffers a context keeps between whole frames grow with the number of outputs a frame
+// has.  A cascade or matte frame has up to twelve, a half-buffer frame five: what it made them grow by is given back when the
+// call returns, so that a later render finds the free memory (batch_slot_limit) it found before.
+struct TileGrowthGuard {
+    nart_ctx* ctx;
+    size_t gather_bytes;
+    std::vector<size_t> sub_bytes;
+    explicit TileGrowthGuard(nart_ctx* c) : ctx(c), gather_bytes(c->d_gather.bytes()) {
+        for (const Buf& b : c->sub_tiles) sub_bytes.push_back(b.bytes());
+    }
+    TileGrowthGuard(const TileGrowthGuard&) = delete;
+    ~TileGrowthGuard() {
+        if (ctx->d_gather.bytes() > gather_bytes) ctx->d_gather.release();
+        for (size_t d = 0; d < sub_bytes.size(); ++d)
+            if (ctx->sub_tiles[d].bytes() > sub_bytes[d]) ctx->sub_tiles[d].release();
+    }
+};
+
+// ---------------------------------------------------------------- half buffers (device/halves.h)
+// The ask of a half-buffer frame: the beauty, its two halves, and the AOVs of `aovs` (the followed
+// guides with `follow`).
+FrameAsk halves_ask(const nart_render_params* p, uint32_t aovs, const nart_guide_params* follow) {
+    FrameAsk ask(p->integrator);
+    ask.halves = true;
+    ask_aovs(ask, aovs, follow);
+    return ask;
+}
+
+// nart_hip_render_halves.  halves_ms: the split and the two half splats.
+int render_halves(nart_ctx* ctx, const nart_render_params* p, const nart_guide_params* follow, uint32_t aovs, nart_pixel* image,
+                  nart_pixel* albedo, nart_pixel* normal, nart_pixel* half_a, nart_pixel* half_b, nart_render_stats* stats,
+                  double* halves_ms) {
+    if (halves_ms) *halves_ms = 0.0;
+    TileGrowthGuard guard(ctx);
+    if (!image || !half_a || !half_b) return fail(ctx, NART_E_INVALID, "the half buffers need the beauty's and both halves' image buffers");
+    if (const char* why = aov_request_error(aovs, albedo, normal, follow != nullptr)) return fail(ctx, NART_E_INVALID, why);
+    const FramePlan plan = plan_frame(halves_ask(p, aovs, follow), PlanRules::Frame);
+    FrameRequest rq;
+    aovs_to_host(rq, plan, follow != nullptr, image, albedo, normal, nullptr);
+    rq.to_host(plan, OutputKind::HalfA, half_a);
+    rq.to_host(plan, OutputKind::HalfB, half_b);
+    PassTimes times;
+    const int rc = render_frame(ctx, p, plan, rq, stats, &times);
+    if (halves_ms) *halves_ms = times.ms[PASS_HALVES];
+    return rc;
+}
+
 // ---------------------------------------------------------------- denoiser (device/denoise.h)
 // Denoise images of the view: prepare, variance, the a-trous passes (LDS tiles for steps 1 and 2,
 // global reads beyond), finalise; synchronous.  ms: device time.  moment >= 0: the sample-variance
@@ -235,6 +282,136 @@ int render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoi
     });
 }
 
+// ---------------------------------------------------------------- cross-filtered denoiser (device/denoise_cross.h)
+// Cross-denoise images of the view: prepare, variance, the a-trous passes over both halves (LDS tiles
+// for steps 1 and 2, global reads beyond), finalise; synchronous.  error < 0: no error image.  The work
+// buffers are temporaries of the call.  ms: device time.
+int denoise_cross_device(const Images& v, const nart_denoise_params& dp, int half_a, int half_b, int beauty, int albedo,
+                         int normal, int out, int error, hipStream_t st, double* ms) {
+    nart_ctx* ctx = v.ctx;
+    const size_t npx = (size_t)v.layout.W * v.layout.H;
+    // guide, centre, signal x 2 halves x 2 (float4 each), then cov and slope
+    Buf work;  // freed on return
+    if (int rc = reserve(ctx, work, ctx->device, npx * (6 * sizeof(float4) + 2 * sizeof(float)), "cross denoiser work buffers"))
+        return rc;
+    float4* f4 = work.as<float4>();
+    float4* sig[2][2] = {{f4 + 2 * npx, f4 + 3 * npx}, {f4 + 4 * npx, f4 + 5 * npx}};  // [ping-pong][half]
+    DnxArgs a;
+    a.half[0] = v.at(half_a);
+    a.half[1] = v.at(half_b);
+    a.beauty = v.at(beauty);
+    a.albedo = v.at(albedo);
+    a.normal = v.at(normal);
+    a.out = v.at(out);
+    a.error = error >= 0 ? v.at(error) : nullptr;
+    a.guide = f4;
+    a.centre = f4 + npx;
+    a.cov = reinterpret_cast<float*>(f4 + 6 * npx);
+    a.slope = a.cov + npx;
+    v.layout.fill(a);
+    a.step = 1;
+    a.normal_squarings = dp.normal_squarings;
+    a.sigma_color = dp.sigma_color;
+    a.sigma_depth = dp.sigma_depth;
+    a.depth_eps = dp.depth_eps;
+    a.sigma_coverage = dp.sigma_coverage;
+    a.albedo_floor = dp.albedo_floor;
+    auto use = [&a, &sig](int in, int out_) {
+        for (int h = 0; h < 2; ++h) {
+            a.sig_in[h] = in < 0 ? nullptr : sig[in][h];
+            a.sig_out[h] = out_ < 0 ? nullptr : sig[out_][h];
+        }
+    };
+    const dim3 grid((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH), block(256);
+    uint32_t e = 0;
+    HIPCHK(record(ctx->ev_dnx[e++], st));
+    use(-1, 0);
+    hipLaunchKernelGGL(k_dnx_prepare, grid, block, 0, st, a);
+    HIPCHK(record(ctx->ev_dnx[e++], st));
+    use(0, 1);
+    hipLaunchKernelGGL(k_dnx_variance, grid, block, 0, st, a);
+    HIPCHK(record(ctx->ev_dnx[e++], st));
+    int cur = 1;
+    for (uint32_t i = 0; i < dp.iterations; ++i) {
+        use(cur, cur ^ 1);
+        a.step = 1u << i;
+        if (i == 0) hipLaunchKernelGGL(k_dnx_atrous<2>, grid, block, 0, st, a);
+        else if (i == 1) hipLaunchKernelGGL(k_dnx_atrous<4>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_dnx_atrous<0>, grid, block, 0, st, a);
+        HIPCHK(record(ctx->ev_dnx[e++], st));
+        cur ^= 1;
+    }
+    use(cur, -1);
+    const size_t n_total = (size_t)a.totalW * a.totalH;
+    hipLaunchKernelGGL(k_dnx_finalize, dim3((uint32_t)((n_total + 255) / 256)), block, 0, st, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(record(ctx->ev_dnx[e++], st));
+    HIPCHK(hipEventSynchronize(ctx->ev_dnx[e - 1].handle()));
+    for (double& t : ctx->dnx_ms) t = 0.0;
+    double total = 0.0;
+    for (uint32_t k = 0; k + 1 < e; ++k) {
+        float t = 0.f;
+        HIPCHK(hipEventElapsedTime(&t, ctx->ev_dnx[k].handle(), ctx->ev_dnx[k + 1].handle()));
+        // events 0..2 bracket prepare and variance, the last pair the finalise kernel
+        ctx->dnx_ms[k + 2 == e ? 10 : k] = t;
+        total += t;
+    }
+    if (ms) *ms = total;
+    return NART_OK;
+}
+
+// dp (null: the defaults) into d for a call that cross-denoises: two halves need two samples.
+int check_denoise_cross(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, nart_denoise_params& d) {
+    const char* why = denoise_params_error(dp, d);
+    if (!why && p->spp < 2) why = "cross-filtered denoising needs spp >= 2: a half buffer of its own for each half";
+    return why ? fail(ctx, NART_E_INVALID, why) : NART_OK;
+}
+
+// nart_hip_denoise_cross.  The images are temporaries of the call: the five inputs, the denoised image and
+// the error image.
+int denoise_cross_host(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, const nart_pixel* half_a,
+                       const nart_pixel* half_b, const nart_pixel* beauty, const nart_pixel* albedo, const nart_pixel* normal,
+                       nart_pixel* out, nart_pixel* error, double* denoise_ms) {
+    nart_denoise_params d;
+    if (int rc = check_denoise_cross(ctx, p, dp, d)) return rc;
+    if (!ctx->subs.empty())
+        return forwarded(ctx, denoise_cross_host(first_device(ctx), p, &d, half_a, half_b, beauty, albedo, normal, out, error,
+                                                 denoise_ms));
+    if (const char* why = check_image_size(p)) return fail(ctx, NART_E_INVALID, why);
+    Buf imgs;  // freed on return
+    Images v(ctx, p);
+    if (int rc = v.in(imgs, 7, "cross denoiser images")) return rc;
+    const nart_pixel* in[5] = {half_a, half_b, beauty, albedo, normal};
+    for (size_t i = 0; i < 5; ++i)
+        if (int rc = v.upload(i, in[i])) return rc;
+    if (int rc = denoise_cross_device(v, d, 0, 1, 2, 3, 4, 5, error ? 6 : -1, 0, denoise_ms)) return rc;
+    if (int rc = v.download(5, out)) return rc;
+    return error ? v.download(6, error) : NART_OK;
+}
+
+// nart_hip_render_denoised_cross: the beauty, the AOVs or followed guides and the two halves into device
+// images of the first device, the denoised and the error image after them: nothing passes the host.
+int render_denoised_cross(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                          const nart_guide_params* follow, nart_pixel* out, nart_pixel* error, nart_pixel* image,
+                          nart_render_stats* stats, double* denoise_ms) {
+    nart_denoise_params d;
+    if (int rc = check_denoise_cross(ctx, p, dp, d)) return rc;
+    const FramePlan plan = plan_frame(halves_ask(p, NART_AOV_ALBEDO | NART_AOV_NORMAL, follow), PlanRules::Frame);
+    TileGrowthGuard guard(ctx);
+    Buf imgs;  // freed on return
+    const uint32_t n = 7;
+    return frame_stage(ctx, p, plan, imgs, n, stats, nullptr, [&](const Images& v) {
+        const int b = plan.find(OutputKind::Beauty);
+        int rc = denoise_cross_device(v, d, plan.find(OutputKind::HalfA), plan.find(OutputKind::HalfB), b,
+                                      plan.find(follow ? OutputKind::GuideAlbedo : OutputKind::Albedo),
+                                      plan.find(follow ? OutputKind::GuideNormal : OutputKind::Normal), 5, 6, 0, denoise_ms);
+        if (!rc && image) rc = v.download(b, image);
+        if (!rc) rc = v.download(5, out);
+        if (!rc) rc = v.download(6, error);
+        return rc;
+    });
+}
+
 // ---------------------------------------------------------------- firefly cascade (device/cascade.h)
 // The reweighting over images of the view: the beauty, the K layer images back to back, the robust
 // image out; synchronous.  The time goes to the view's context (cas_ms[1]).
@@ -259,24 +436,6 @@ int cascade_device(const Images& v, const nart_cascade_params& cp, const Cascade
         return NART_OK;
     });
 }
-
-// The tile buffers a context keeps between whole frames grow with the number of outputs a frame
-// has.  A cascade or matte frame has up to twelve: what it made them grow by is given back when the
-// call returns, so that a later render finds the free memory (batch_slot_limit) it found before.
-struct TileGrowthGuard {
-    nart_ctx* ctx;
-    size_t gather_bytes;
-    std::vector<size_t> sub_bytes;
-    explicit TileGrowthGuard(nart_ctx* c) : ctx(c), gather_bytes(c->d_gather.bytes()) {
-        for (const Buf& b : c->sub_tiles) sub_bytes.push_back(b.bytes());
-    }
-    TileGrowthGuard(const TileGrowthGuard&) = delete;
-    ~TileGrowthGuard() {
-        if (ctx->d_gather.bytes() > gather_bytes) ctx->d_gather.release();
-        for (size_t d = 0; d < sub_bytes.size(); ++d)
-            if (ctx->sub_tiles[d].bytes() > sub_bytes[d]) ctx->sub_tiles[d].release();
-    }
-};
 
 // nart_hip_render_cascade: the beauty and the K layers, the robust image after them.
 int render_cascade(nart_ctx* ctx, const nart_render_params* p, const nart_cascade_params& cp, const CascadeLevels& lv,

@@ -75,6 +75,21 @@
 //                   print the four totals; <out>.exr is the same call's beauty.  Not offered together
 //                   with --depth-cuts, --light-groups, --adaptive, --robust, --mattes, --aovs, --denoise
 //                   or --follow-specular: an error
+//   --halves        also write every session's half buffers (nart_hip_render_halves) to <out>.half.0.exr and
+//                   <out>.half.1.exr: the samples of even and of odd index, each divided by the beauty's
+//                   filter weight sum, so that the two files add up to <out>.exr, the same call's beauty.
+//                   With --aovs (and --follow-specular [N]) the AOVs or followed guides are the same
+//                   call's.  Not offered together with --denoise, --denoise-parts, --adaptive, --robust,
+//                   --mattes, --light-groups, --depth-cuts or --cost: an error
+//   --denoise-cross  also write every session's cross-filtered denoised image and its error image
+//                   (nart_hip_render_denoised_cross, default parameters) to <out>.denoised.exr and
+//                   <out>.error.exr: the two half buffers of the render, each filtered with colour weights
+//                   from the other, averaged; the error is the squared half difference of the two.  With
+//                   --halves and/or --aovs the half buffers and AOVs are rendered anyway and go through
+//                   nart_hip_denoise_cross: the same images.  --follow-specular [N] next to it selects the
+//                   followed guides.  Needs -s >= 2.  Not offered together with --denoise, --denoise-parts,
+//                   --sample-variance, --adaptive, --robust, --mattes, --light-groups, --depth-cuts or
+//                   --cost: an error
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -245,6 +260,13 @@ int main(int argc, char* argv[]) {
     const bool denoise = take_flag(args, "--denoise");
     const bool sample_variance = take_flag(args, "--sample-variance");
     const bool denoise_parts = take_flag(args, "--denoise-parts");
+    const bool denoise_cross = take_flag(args, "--denoise-cross");
+    const char* const cross_alone = "Error: --denoise-cross is not offered together with --denoise, --denoise-parts, "
+                                    "--sample-variance, --adaptive, --robust, --mattes, --light-groups, --depth-cuts or --cost\n";
+    if (denoise_cross && (denoise || denoise_parts || sample_variance)) {
+        std::fputs(cross_alone, stderr);
+        return EXIT_FAILURE;
+    }
     if (sample_variance && !denoise) {
         std::fprintf(stderr, "Error: --sample-variance selects the denoiser's variance input and needs --denoise\n");
         return EXIT_FAILURE;
@@ -313,7 +335,7 @@ int main(int argc, char* argv[]) {
     nart_hip_guide_defaults(&gp);
     float follow_arg = (float)gp.max_follow;
     const bool follow = take_optional_value_flag(args, "--follow-specular", follow_arg);
-    if (follow && !aovs && !denoise && !denoise_parts) {
+    if (follow && !aovs && !denoise && !denoise_parts && !denoise_cross) {
         std::fprintf(stderr, "Error: --follow-specular selects the guides of --aovs and --denoise and needs one of them\n");
         return EXIT_FAILURE;
     }
@@ -416,6 +438,17 @@ int main(int argc, char* argv[]) {
                              "--mattes, --aovs, --denoise or --follow-specular\n");
         return EXIT_FAILURE;
     }
+    if (denoise_cross && (adaptive || robust || mattes || light_groups || depth_cuts || cost)) {
+        std::fputs(cross_alone, stderr);
+        return EXIT_FAILURE;
+    }
+    // --halves
+    const bool halves = take_flag(args, "--halves");
+    if (halves && (denoise || denoise_parts || adaptive || robust || mattes || light_groups || depth_cuts || cost)) {
+        std::fprintf(stderr, "Error: --halves is not offered together with --denoise, --denoise-parts, --adaptive, --robust, "
+                             "--mattes, --light-groups, --depth-cuts or --cost\n");
+        return EXIT_FAILURE;
+    }
     nart_adaptive_params ap;
     nart_hip_adaptive_params_init(&ap);
     if (adaptive) {
@@ -503,7 +536,35 @@ int main(int argc, char* argv[]) {
         std::vector<uint32_t> bucket_spp;
         std::vector<nart_pixel> group_imgs, mix_img, cut_imgs, layer_imgs, cost_img, part_imgs, parts_sum, parts_mix;
         const nart_guide_params* parts_gp = follow ? &gp : nullptr;
-        if (cost) {
+        std::vector<nart_pixel> half_imgs, error_img;
+        if (denoise_cross) {
+            denoised.resize(image.size());
+            error_img.resize(image.size());
+        }
+        if (denoise_cross && !halves && !aovs) {
+            rc = nart_hip_render_denoised_cross(ctx, &p, nullptr, follow ? &gp : nullptr, denoised.data(), error_img.data(),
+                                                image.data(), nullptr, nullptr);
+        } else if (denoise_cross) {
+            // the half buffers and the AOVs are rendered for their files anyway: the filter over them
+            half_imgs.resize(2 * image.size());
+            albedo.resize(image.size());
+            normal.resize(image.size());
+            nart_pixel* const half_b = half_imgs.data() + image.size();
+            rc = nart_hip_render_halves(ctx, &p, NART_AOV_ALBEDO | NART_AOV_NORMAL, follow ? &gp : nullptr, image.data(),
+                                        albedo.data(), normal.data(), half_imgs.data(), half_b, nullptr, nullptr);
+            if (rc == NART_OK)
+                rc = nart_hip_denoise_cross(ctx, &p, nullptr, half_imgs.data(), half_b, image.data(), albedo.data(),
+                                            normal.data(), denoised.data(), error_img.data(), nullptr);
+        } else if (halves) {
+            half_imgs.resize(2 * image.size());
+            if (aovs) {
+                albedo.resize(image.size());
+                normal.resize(image.size());
+            }
+            rc = nart_hip_render_halves(ctx, &p, aovs ? NART_AOV_ALBEDO | NART_AOV_NORMAL : 0u, follow ? &gp : nullptr,
+                                        image.data(), aovs ? albedo.data() : nullptr, aovs ? normal.data() : nullptr,
+                                        half_imgs.data(), half_imgs.data() + image.size(), nullptr, nullptr);
+        } else if (cost) {
             uint32_t gw = 0, gh = 0;
             rc = nart_hip_cost_grid(&p, &gw, &gh);
             std::vector<nart_cost_pixel> grid((size_t)gw * gh);
@@ -664,7 +725,8 @@ int main(int argc, char* argv[]) {
             extra.push_back({".albedo.exr", albedo.data()});
             extra.push_back({".normal.exr", normal.data()});
         }
-        if (denoise) extra.push_back({".denoised.exr", denoised.data()});
+        if (denoise || denoise_cross) extra.push_back({".denoised.exr", denoised.data()});
+        if (denoise_cross) extra.push_back({".error.exr", error_img.data()});
         if (robust) extra.push_back({".robust.exr", robust_img.data()});
         for (uint32_t i = 0; mattes && i < mp.ranks / 2; ++i)
             extra.push_back({".matte.0" + std::to_string(i) + ".exr", matte_ranks.data() + (size_t)i * image.size()});
@@ -686,6 +748,8 @@ int main(int argc, char* argv[]) {
             if (light_groups && gains_arg) extra.push_back({".mix.denoised.exr", parts_mix.data()});
         }
         if (cost) extra.push_back({".cost.exr", cost_img.data()});
+        for (size_t h = 0; halves && h < 2; ++h)
+            extra.push_back({".half." + std::to_string(h) + ".exr", half_imgs.data() + h * image.size()});
         std::vector<nart_pixel> spp_img;
         if (adaptive) {
             // pixel (x, y) of the cropped image was traced by bucket (x / B, y / B)

@@ -289,7 +289,7 @@ int render_multi(nart_ctx* ctx, const nart_render_params* p, const FramePlan& pl
     }
     HIPCHK(hipStreamSynchronize(s0));
     for (uint32_t d = 0; d < n; ++d)
-        for (uint32_t k = 0; k < N_PASSES; ++k) times.ms[k] = std::max(times.ms[k], pass[d].ms[k]);
+        for (uint32_t k = 0; k < PASS_SLOTS; ++k) times.ms[k] = std::max(times.ms[k], pass[d].ms[k]);
     if (stats) {
         // one render: device times of the slowest device (they run concurrently), work counts
         // summed; added to the caller's stats as the single-device path adds a render's

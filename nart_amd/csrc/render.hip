@@ -19,6 +19,8 @@
 #include "../../include/nart_hip.h"
 #include "device/adaptive.h"
 #include "device/cascade.h"
+#include "device/halves.h"
+#include "device/denoise_cross.h"
 #include "device/cost.h"
 #include "device/denoise.h"
 #include "device/denoise_parts.h"
@@ -110,7 +112,7 @@ struct nart_ctx {
     bool prim_valid = false;   // d_prim holds the current batch's camera-ray hits (first-hit AOVs)
     bool rows_pixel_major = false;  // d_slot_so as last written: every slot's samples a contiguous row (stride 1)
     // around each pass of a batch after the beauty's splat (render_buckets; host/frame_plan.h PassKind)
-    Event ev_pass[N_PASSES][2];
+    Event ev_pass[PASS_SLOTS][2];
     // around the error and scatter kernels of an adaptive level (render_buckets_adaptive)
     Event ev_ad[2];
     // around the cascade's reweighting (cascade_device) and the mattes' ranking (matte_rank_device)
@@ -146,6 +148,10 @@ struct nart_ctx {
     Buf d_dn, d_dn_img;
     Event ev_dn[12];
     double dn_ms[11] = {};  // prepare, variance, passes 0..7, finalise
+    // cross-filtered denoiser (denoise_cross_device): events between its kernels, the last run's times;
+    // its images and work buffers are temporaries of the call
+    Event ev_dnx[12];
+    double dnx_ms[11] = {};  // prepare, variance, passes 0..7, finalise
     // denoised parts (denoise_parts_device): events between its kernels (prepare, then per chunk the
     // variance, up to 8 passes and finalise, then the sum); the last run's times on the first device's
     // context: prepare, variance, passes 0..7, finalise, sum, each summed over the chunks; on the
@@ -567,8 +573,9 @@ int check_params(nart_ctx* ctx, const nart_render_params* p) {
 // (plus what this context already holds for it), at least 16 GiB: whole frames up to 4K x 512 spp
 // (119 GB) render in one batch -- fewer launch tails than the former fixed 16 GiB (C5 469 -> 413
 // ms, C4 5.27 -> 4.43 s per frame; profiles/r03a_bb_c4.log, r03a_bb_c5_s*.log).  NART_BATCH_BYTES
-// overrides.  A cascade call (nart_hip_render_cascade) holds a second record buffer while it runs:
-// extra_per_sample = 16, 44 B per sample; every other call passes 0 and sees what it saw before.
+// overrides.  A cascade or half-buffer call (nart_hip_render_cascade, nart_hip_render_halves) holds a
+// second record buffer while it runs: extra_per_sample = 16, 44 B per sample (FramePlan::record_bytes
+// has every frame's figure); a plain call passes 0 and sees what it saw before.
 size_t batch_slot_limit(const nart_ctx* ctx, uint32_t spp, size_t extra_per_sample = 0) {
     size_t budget = (size_t)16 << 30;
     size_t free_b = 0, total_b = 0;
@@ -1168,7 +1175,7 @@ struct FrameTiles {
 };
 // Device time of each pass of a render (frame_plan.h PassKind), added up over its batches.
 struct PassTimes {
-    double ms[N_PASSES] = {};
+    double ms[PASS_SLOTS] = {};
 };
 
 // Camera-ray hits of the batch in `a` into ctx->d_prim, for AOVs of a dispatch that did not run
@@ -1353,12 +1360,12 @@ int launch_splat(nart_ctx* ctx, const SplatPlan& plan, const SplatArgs& sa, uint
     return moment ? launch_splat_as<true>(ctx, plan, sa, nbk, st) : launch_splat_as<false>(ctx, plan, sa, nbk, st);
 }
 
-// The per-sample records of output `w` for the ns samples of the batch in `ra`, which the splat then takes
+// The per-sample records of output `w` for the ns samples of the nbk buckets of the batch in `ra`, which the splat then takes
 // into the output's tiles: one small kernel fills `records` from the beauty's records (ctx->d_L) or the
 // camera-ray hits (ctx->d_prim).  The guides' records were filled at the start of their pass (`ga`).
 // Returns the records to splat.
 int fill_records(nart_ctx* ctx, const FramePlan& frame, const FrameOutput& w, const RenderArgs& ra, const GuideArgs& ga,
-                 float4* records, uint64_t ns, hipStream_t st, const float4** filled) {
+                 float4* records, uint64_t ns, uint32_t nbk, hipStream_t st, const float4** filled) {
     const dim3 grid((uint32_t)((ns + 255) / 256)), block(256);
     *filled = records;
     switch (w.kind) {
@@ -1377,6 +1384,21 @@ int fill_records(nart_ctx* ctx, const FramePlan& frame, const FrameOutput& w, co
         ca.b_cur = lv.b[ca.j];
         ca.b_next = ca.j + 1 < lv.K ? lv.b[ca.j + 1] : 0.f;
         hipLaunchKernelGGL(k_cascade_split, grid, block, 0, st, ca);
+        break;
+    }
+    case OutputKind::HalfA:
+    case OutputKind::HalfB: {
+        HalfSplitArgs ha;
+        ha.L = ctx->d_L.as<float4>();
+        ha.out = records;
+        ha.n = ns;
+        ha.bucket_base = ctx->d_bucket_base.as<uint32_t>();
+        ha.nbk = nbk;
+        ha.n_slots = ra.n_slots;
+        ha.spp = ra.spp;
+        ha.h = w.kind == OutputKind::HalfA ? 0u : 1u;
+        ha.pixel_major = ctx->rows_pixel_major ? 1u : 0u;
+        hipLaunchKernelGGL(k_half_split, grid, block, 0, st, ha);
         break;
     }
     case OutputKind::Moment: hipLaunchKernelGGL(k_moment, grid, block, 0, st, ctx->d_L.as<float4>(), ns); break;
@@ -1461,8 +1483,9 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
     unsigned long long* const d_counters = ctx->d_counters.as<unsigned long long>();
     if (ctx->counters) HIPCHK(hipMemsetAsync(d_counters, 0, ctx->d_counters.bytes(), st));
     const size_t limit = batch_slot_limit(ctx, p->spp, frame.record_bytes);
-    Buf layer_records;  // cascade: the second per-sample record buffer, 16 B per sample; freed on return
-    Buf guide_records;  // both followed guides: the normal records, likewise
+    Buf layer_records;  // cascade, halves: the second per-sample record buffer, 16 B per sample; freed on return
+    Buf guide_records;  // both followed guides: the normal records, likewise (a halves frame: in layer_records,
+                        // which its first pass has left free)
     Buf group_records;  // light groups or depth cuts: R record arrays of the batch's samples, likewise
     const uint32_t G = beauty ? frame.ask.light_groups : 0u;
     if (G && !ctx->d_light_group) return fail(ctx, NART_E_INVALID, "no light-group map was set");
@@ -1576,28 +1599,30 @@ int render_buckets(nart_ctx* ctx, const nart_render_params* p, const uint32_t* i
         // the frame plan's passes
         for (uint32_t i = 0; i < frame.n_passes; ++i) {
             const PassKind pass = frame.passes[i];
-            if (pass == PASS_CASCADE &&
-                (rc = reserve(ctx, layer_records, ctx->device, ns * sizeof(float4), "cascade layer records")))
+            if ((pass == PASS_CASCADE || pass == PASS_HALVES) &&
+                (rc = reserve(ctx, layer_records, ctx->device, ns * sizeof(float4),
+                              pass == PASS_CASCADE ? "cascade layer records" : "half-buffer records")))
                 return rc;
             // the dispatch's own camera-ray hits where it traced them first, else k_primary now
             if ((pass == PASS_FIRST_HIT || pass == PASS_MATTE) && !ctx->prim_valid && (rc = launch_aov_primary(ctx, ra, st)))
                 return rc;
             const bool two_guides = pass == PASS_GUIDE && frame.ask.guide[0] && frame.ask.guide[1];
-            if (two_guides && (rc = reserve(ctx, guide_records, ctx->device, ns * sizeof(float4), "guide normal records")))
+            Buf& normal_records = frame.ask.halves ? layer_records : guide_records;
+            if (two_guides && (rc = reserve(ctx, normal_records, ctx->device, ns * sizeof(float4), "guide normal records")))
                 return rc;
             HIPCHK(record(ctx->ev_pass[pass][0], st));
-            float4* const records = (pass == PASS_CASCADE ? layer_records : ctx->d_L).as<float4>();
+            float4* const records = (pass == PASS_CASCADE || pass == PASS_HALVES ? layer_records : ctx->d_L).as<float4>();
             GuideArgs ga;
             if (pass == PASS_GUIDE) {
                 ga.max_follow = frame.ask.max_follow;
                 if (frame.ask.guide[0]) ga.albedo = records;
-                if (frame.ask.guide[1]) ga.normal = two_guides ? guide_records.as<float4>() : records;
+                if (frame.ask.guide[1]) ga.normal = two_guides ? normal_records.as<float4>() : records;
                 if ((rc = launch_guide<false>(ctx, ra, ga, st))) return rc;
             }
             for (uint32_t o = 0; o < frame.n_outputs; ++o) {
                 const FrameOutput& w = frame.outputs[o];
                 if (pass_of(w.kind) != pass) continue;
-                if ((rc = fill_records(ctx, frame, w, ra, ga, records, ns, st, &sa.Lout))) return rc;
+                if ((rc = fill_records(ctx, frame, w, ra, ga, records, ns, nbk, st, &sa.Lout))) return rc;
                 sa.tiles = out.tiles[o] + (size_t)b0 * tpx * 5;
                 if ((rc = launch_splat(ctx, plan, sa, nbk, st, pass == PASS_MOMENT))) return rc;
             }
@@ -2368,6 +2393,16 @@ int nart_hip_render_moment(nart_ctx* ctx, const nart_render_params* p, uint32_t 
     return render_aovs(ctx, p, nullptr, aovs, image, albedo, normal, moment, stats, aov_ms, moment_ms);
 }
 
+int nart_hip_render_halves(nart_ctx* ctx, const nart_render_params* p, uint32_t aovs, const nart_guide_params* gp,
+                           nart_pixel* image, nart_pixel* albedo, nart_pixel* normal, nart_pixel* half_a, nart_pixel* half_b,
+                           nart_render_stats* stats, double* halves_ms) {
+    if (!ctx || !p) return NART_E_INVALID;
+    nart_guide_params g;
+    if (gp)
+        if (const char* why = guide_params_error(gp, g)) return fail(ctx, NART_E_INVALID, why);
+    return render_halves(ctx, p, gp ? &g : nullptr, aovs, image, albedo, normal, half_a, half_b, stats, halves_ms);
+}
+
 void nart_hip_adaptive_params_init(nart_adaptive_params* ap) {
     if (ap) *ap = ADAPTIVE_DEFAULTS;
 }
@@ -2773,6 +2808,35 @@ int nart_hip_denoise_timings(const nart_ctx* ctx, double* prepare_ms, double* va
     if (pass_ms)
         for (int k = 0; k < 8; ++k) pass_ms[k] = c0->dn_ms[2 + k];
     if (finalize_ms) *finalize_ms = c0->dn_ms[10];
+    return NART_OK;
+}
+
+int nart_hip_denoise_cross(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp, const nart_pixel* half_a,
+                           const nart_pixel* half_b, const nart_pixel* beauty, const nart_pixel* albedo,
+                           const nart_pixel* normal, nart_pixel* out, nart_pixel* error, double* denoise_ms) {
+    if (!ctx || !p || !half_a || !half_b || !beauty || !albedo || !normal || !out) return NART_E_INVALID;
+    return denoise_cross_host(ctx, p, dp, half_a, half_b, beauty, albedo, normal, out, error, denoise_ms);
+}
+
+int nart_hip_render_denoised_cross(nart_ctx* ctx, const nart_render_params* p, const nart_denoise_params* dp,
+                                   const nart_guide_params* gp, nart_pixel* out, nart_pixel* error, nart_pixel* image,
+                                   nart_render_stats* stats, double* denoise_ms) {
+    if (!ctx || !p || !out || !error) return NART_E_INVALID;
+    nart_guide_params g;
+    if (gp)
+        if (const char* why = guide_params_error(gp, g)) return fail(ctx, NART_E_INVALID, why);
+    return render_denoised_cross(ctx, p, dp, gp ? &g : nullptr, out, error, image, stats, denoise_ms);
+}
+
+int nart_hip_denoise_cross_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
+                                   double* finalize_ms) {
+    if (!ctx) return NART_E_INVALID;
+    const nart_ctx* c0 = first_device(ctx);
+    if (prepare_ms) *prepare_ms = c0->dnx_ms[0];
+    if (variance_ms) *variance_ms = c0->dnx_ms[1];
+    if (pass_ms)
+        for (int k = 0; k < 8; ++k) pass_ms[k] = c0->dnx_ms[2 + k];
+    if (finalize_ms) *finalize_ms = c0->dnx_ms[10];
     return NART_OK;
 }
 
