@@ -12,7 +12,14 @@
 // The variance window and the passes of step 1 and 2 stage their tile plus halo in LDS (R = 3, 2, 4
 // pixels of halo: 36 B per staged pixel, at most 40 x 16 pixels = 22.5 KB); larger steps read global
 // memory (R = 0), where the 36 B per tap come out of the cache hierarchy.  Both ways run the same
-// arithmetic in the same order.
+// arithmetic in the same order.  Which kernel runs when, with which halo and between which signal
+// buffers, is host/denoise_passes.h's plan.
+//
+// What the cross-filtered and the parts denoiser (denoise_cross.h, denoise_parts.h) share with this one is
+// defined here once, each piece stating the operation order it fixes: the tile view DnTile<R, S, Args>
+// over S signals, the lane's pixel (dn_pixel, dn_cropped), the guide arithmetic (dn_guides, dn_slope,
+// dn_tap_guide, dn_tap_falloff, dn_window_weight), the 5-tap weight (dn_tap5), the 3x3 variance blur
+// (dn_blur_variance), the sums of a pass (DnSums) and the remodulation (dn_remodulate).
 //
 // The arithmetic is float32 + - * / sqrt and comparisons only, in the order the header fixes, built
 // without contraction: tests/denoise_py.py restates it in numpy and the images agree bit for bit.
@@ -26,7 +33,16 @@
 
 namespace nd {
 
-struct DnArgs {
+// What the three denoisers' argument structs (DnArgs, DnxArgs of denoise_cross.h, DnpArgs of
+// denoise_parts.h) share: the image layout, the step of the launch and nart_denoise_params' filter fields.
+struct DnFilterArgs {
+    uint32_t W, H, totalW, totalH, fb;
+    uint32_t step;
+    uint32_t normal_squarings;
+    float sigma_color, sigma_depth, depth_eps, sigma_coverage, albedo_floor;
+};
+
+struct DnArgs : DnFilterArgs {
     // inputs / output: nart_pixel images of totalW x totalH, 5 floats per pixel
     const float* beauty;
     const float* albedo;
@@ -36,14 +52,10 @@ struct DnArgs {
     // work buffers over the cropped W x H image
     float4* guide;       // {n.xyz, z}; an empty pixel is all zeros (z == 0 marks it)
     float* cov;
-    const float4* sig_in;  // {s.rgb, v}; v < 0 marks an invalid pixel (s = 0)
-    float4* sig_out;
+    const float4* sig_in[1];  // {s.rgb, v}; v < 0 marks an invalid pixel (s = 0)
+    float4* sig_out[1];
     float4* centre;      // {a_d.rgb, alpha}
     float* slope;
-    uint32_t W, H, totalW, totalH, fb;
-    uint32_t step;
-    uint32_t normal_squarings;
-    float sigma_color, sigma_depth, depth_eps, sigma_coverage, albedo_floor;
 };
 
 constexpr int DN_TW = 32, DN_TH = 8;  // pixels per block: 256 lanes, lanes along x
@@ -149,60 +161,107 @@ __device__ __forceinline__ float dn_sample_variance(const float* M, const float*
     return v < 1e30f ? v : 1e30f;
 }
 
+// The pixel of a lane of the 32 x 8 tile kernels: cropped coordinates (lanes along x), the pixel's index i
+// in the work buffers and ti in the total image; inside: the lane has a pixel.
+struct DnPixel {
+    int x, y;
+    size_t i, ti;
+    bool inside;
+};
+template <class Args>
+__device__ __forceinline__ DnPixel dn_pixel(const Args& a) {
+    DnPixel p;
+    p.x = blockIdx.x * DN_TW + (threadIdx.x & (DN_TW - 1));
+    p.y = blockIdx.y * DN_TH + threadIdx.x / DN_TW;
+    p.inside = p.x < (int)a.W && p.y < (int)a.H;
+    p.i = (size_t)p.y * a.W + p.x;
+    p.ti = (size_t)(p.y + a.fb) * a.totalW + (p.x + a.fb);
+    return p;
+}
+
+// The pixel of a lane of the finalize kernels, one lane per total-image pixel ti (the caller has checked
+// ti < totalW * totalH): whether it lies in the cropped window, and then its index i there.
+template <class Args>
+__device__ __forceinline__ bool dn_cropped(const Args& a, size_t ti, size_t& i) {
+    const uint32_t tx = (uint32_t)(ti % a.totalW), ty = (uint32_t)(ti / a.totalW);
+    const bool inside = tx >= a.fb && ty >= a.fb && tx - a.fb < a.W && ty - a.fb < a.H;
+    i = inside ? (size_t)(ty - a.fb) * a.W + (tx - a.fb) : 0;
+    return inside;
+}
+
+// Remodulate one pixel: {s.rgb * a_d.rgb, alpha, 1}, each channel one multiplication.
+__device__ __forceinline__ void dn_remodulate(const float4& s, const float4& ad, float alpha, float o[5]) {
+    o[0] = s.x * ad.x;
+    o[1] = s.y * ad.y;
+    o[2] = s.z * ad.z;
+    o[3] = alpha;
+    o[4] = 1.f;
+}
+__device__ __forceinline__ void dn_store_pixel(float* img, size_t ti, const float o[5]) {
+    for (int k = 0; k < 5; ++k) img[ti * 5 + k] = o[k];
+}
+
 // MOMENT: the sample-variance mode -- everything the spatial mode's prepare computes, and signal.v
 // from the moment image instead of 0 (k_dn_variance then does not run).
 template <bool MOMENT>
 __global__ void __launch_bounds__(256) k_dn_prepare(DnArgs a) {
-    const uint32_t x = blockIdx.x * DN_TW + (threadIdx.x & (DN_TW - 1));
-    const uint32_t y = blockIdx.y * DN_TH + threadIdx.x / DN_TW;
-    if (x >= a.W || y >= a.H) return;
-    const size_t ti = (size_t)(y + a.fb) * a.totalW + (x + a.fb);
-    const size_t i = (size_t)y * a.W + x;
+    const DnPixel p = dn_pixel(a);
+    if (!p.inside) return;
     float c[4];
-    dn_mean(a.beauty + ti * 5, c);
+    dn_mean(a.beauty + p.ti * 5, c);
     float4 g, ce;
     float cov;
-    dn_guides(a, ti, g, cov, ce);
+    dn_guides(a, p.ti, g, cov, ce);
     ce.w = c[3];
     const bool valid = dn_valid(c);
     float4 s = dn_invalid_signal();
-    if (valid) s = dn_signal(c, ce, MOMENT ? dn_sample_variance(a.moment + ti * 5, c, ce) : 0.f);
-    const float slope = dn_slope(a, x, y, ti, g.w);
-    a.guide[i] = g;
-    a.cov[i] = cov;
-    a.sig_out[i] = s;
-    a.centre[i] = ce;
-    a.slope[i] = slope;
+    if (valid) s = dn_signal(c, ce, MOMENT ? dn_sample_variance(a.moment + p.ti * 5, c, ce) : 0.f);
+    const float slope = dn_slope(a, p.x, p.y, p.ti, g.w);
+    a.guide[p.i] = g;
+    a.cov[p.i] = cov;
+    a.sig_out[0][p.i] = s;
+    a.centre[p.i] = ce;
+    a.slope[p.i] = slope;
 }
 
-// A block's view of the per-tap records: its tile plus R pixels of halo in LDS (R > 0), or global
-// memory (R == 0).  at() is only called with coordinates inside the image.
-template <int R>
-struct DnView {
+// A block's view of the per-tap records of S signals (1: denoise.h; 2 halves: denoise_cross.h; the C
+// parts of a chunk: denoise_parts.h): its tile plus R pixels of halo in LDS (R > 0), 20 + 16 S bytes per
+// staged pixel, or global memory (R == 0).  A staged pixel outside the image is empty and invalid.  The
+// accessors are only called with coordinates inside the image.
+template <int R, int S, class Args>
+struct DnTile {
     static constexpr int LW = DN_TW + 2 * R, LH = DN_TH + 2 * R;
-    float4* lg;
-    float4* ls;
-    float* lc;
-    const DnArgs& a;
+    static constexpr int N = R > 0 ? LW * LH : 1;
+    struct Lds {
+        float4 g[N];
+        float4 s[S * N];
+        float c[N];
+    };
+    Lds& l;
+    const Args& a;
     int x0, y0;  // image coordinates of the staged region's first pixel
 
-    __device__ DnView(const DnArgs& args, float4* g, float4* s, float* c) : lg(g), ls(s), lc(c), a(args) {
+    __device__ DnTile(const Args& args, Lds& lds) : l(lds), a(args) {
         x0 = (int)(blockIdx.x * DN_TW) - R;
         y0 = (int)(blockIdx.y * DN_TH) - R;
         if (R > 0) {
             for (int k = threadIdx.x; k < LW * LH; k += 256) {
                 const int gx = x0 + k % LW, gy = y0 + k / LW;
-                float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f), s4 = make_float4(0.f, 0.f, 0.f, -1.f);
+                float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f), s4[S];
                 float c1 = 0.f;
+#pragma unroll
+                for (int c = 0; c < S; ++c) s4[c] = dn_invalid_signal();
                 if (gx >= 0 && gy >= 0 && gx < (int)a.W && gy < (int)a.H) {
                     const size_t i = (size_t)gy * a.W + gx;
                     g4 = a.guide[i];
-                    s4 = a.sig_in[i];
+#pragma unroll
+                    for (int c = 0; c < S; ++c) s4[c] = a.sig_in[c][i];
                     c1 = a.cov[i];
                 }
-                lg[k] = g4;
-                ls[k] = s4;
-                lc[k] = c1;
+                l.g[k] = g4;
+#pragma unroll
+                for (int c = 0; c < S; ++c) l.s[c * N + k] = s4[c];
+                l.c[k] = c1;
             }
             __syncthreads();
         }
@@ -210,14 +269,17 @@ struct DnView {
     __device__ __forceinline__ size_t idx(int x, int y) const {
         return R > 0 ? (size_t)((y - y0) * LW + (x - x0)) : (size_t)y * a.W + x;
     }
-    __device__ __forceinline__ float4 guide(int x, int y) const { return R > 0 ? lg[idx(x, y)] : a.guide[idx(x, y)]; }
-    __device__ __forceinline__ float4 sig(int x, int y) const { return R > 0 ? ls[idx(x, y)] : a.sig_in[idx(x, y)]; }
-    __device__ __forceinline__ float cov(int x, int y) const { return R > 0 ? lc[idx(x, y)] : a.cov[idx(x, y)]; }
+    __device__ __forceinline__ float4 guide(int x, int y) const { return R > 0 ? l.g[idx(x, y)] : a.guide[idx(x, y)]; }
+    __device__ __forceinline__ float cov(int x, int y) const { return R > 0 ? l.c[idx(x, y)] : a.cov[idx(x, y)]; }
+    // c is a constant after unrolling
+    __device__ __forceinline__ float4 sig(int c, int x, int y) const {
+        return R > 0 ? l.s[c * N + idx(x, y)] : a.sig_in[c][idx(x, y)];
+    }
 };
 
 // The weight of a tap that is not the centre (include/nart_hip.h, "Guide terms"), in two halves.
 // The guide half: w_n and d_g, which the guides alone decide (the same for every image filtered with
-// them: denoise_parts.h computes them once per tap for several).
+// them: denoise_parts.h and denoise_cross.h compute them once per tap for several).
 template <class Args>
 __device__ __forceinline__ void dn_tap_guide(const Args& a, const float4& gp, float covp, float slope_p, const float4& gq,
                                              float covq, float cheb, float& wn, float& dg) {
@@ -238,30 +300,67 @@ __device__ __forceinline__ float dn_tap_falloff(float wn, float dg, float d_l) {
     return wn * (t4 * t4);
 }
 
-__device__ __forceinline__ float dn_tap_weight(const DnArgs& a, const float4& gp, float covp, float slope_p,
-                                               const float4& gq, float covq, float cheb, float d_l) {
+// The guide-only weight u of the variance window's tap (dx, dy) of the tile, the centre's 1: both halves
+// with d_l = 0 and the Chebyshev distance of the offset.
+template <class Tile, class Args>
+__device__ __forceinline__ float dn_window_weight(const Args& a, const Tile& v, const float4& gp, float covp, float slope_p,
+                                                  int dx, int dy, int qx, int qy) {
+    if (dx == 0 && dy == 0) return 1.f;
     float wn, dg;
-    dn_tap_guide(a, gp, covp, slope_p, gq, covq, cheb, wn, dg);
-    return dn_tap_falloff(wn, dg, d_l);
+    dn_tap_guide(a, gp, covp, slope_p, v.guide(qx, qy), v.cov(qx, qy), (float)max(abs(dx), abs(dy)), wn, dg);
+    return dn_tap_falloff(wn, dg, 0.f);
 }
+
+// The B-spline weight of the tap at offset o in -2..2 along one axis: 3/8, 1/4, 1/16.
+__device__ __forceinline__ float dn_tap5(int o) { return o == 0 ? 0.375f : (o == 1 || o == -1 ? 0.25f : 0.0625f); }
+
+// 3x3 blur of signal c's variance around (x, y): weights (1/4, 1/2, 1/4) per axis, coordinates clamped
+// to the image, an invalid pixel counting as variance 0; summed from 0 row by row, dy outer, dx inner.
+template <class Tile>
+__device__ __forceinline__ float dn_blur_variance(const Tile& v, int c, int x, int y, int W, int H) {
+    float vb = 0.f;
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int qy = min(max(y + dy, 0), H - 1);
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = min(max(x + dx, 0), W - 1);
+            const float k = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
+            vb = vb + k * dn_max(v.sig(c, qx, qy).w, 0.f);
+        }
+    }
+    return vb;
+}
+
+// The five sums of one signal's a-trous pass, from 0 in tap order: add() takes a valid tap of weight w,
+// result() normalises -- {sum w s / sum w, sum w^2 v / (sum w)^2}, invalid where no weight came in.
+struct DnSums {
+    float w = 0.f, r = 0.f, g = 0.f, b = 0.f, v = 0.f;
+    __device__ __forceinline__ void add(float wq, const float4& sq) {
+        w = w + wq;
+        r = r + wq * sq.x;
+        g = g + wq * sq.y;
+        b = b + wq * sq.z;
+        v = v + (wq * wq) * sq.w;
+    }
+    __device__ __forceinline__ float4 result() const {
+        return w > 0.f ? make_float4(r / w, g / w, b / w, v / (w * w)) : dn_invalid_signal();
+    }
+};
 
 __global__ void __launch_bounds__(256) k_dn_variance(DnArgs a) {
     constexpr int R = 3;
-    __shared__ float4 lg[DnView<R>::LW * DnView<R>::LH];
-    __shared__ float4 ls[DnView<R>::LW * DnView<R>::LH];
-    __shared__ float lc[DnView<R>::LW * DnView<R>::LH];
-    const DnView<R> v(a, lg, ls, lc);
-    const int x = blockIdx.x * DN_TW + (threadIdx.x & (DN_TW - 1));
-    const int y = blockIdx.y * DN_TH + threadIdx.x / DN_TW;
-    if (x >= (int)a.W || y >= (int)a.H) return;
-    const size_t i = (size_t)y * a.W + x;
-    float4 sp = v.sig(x, y);
+    using Tile = DnTile<R, 1, DnArgs>;
+    __shared__ Tile::Lds lds;
+    const Tile v(a, lds);
+    const DnPixel p = dn_pixel(a);
+    if (!p.inside) return;
+    const int x = p.x, y = p.y;
+    float4 sp = v.sig(0, x, y);
     if (sp.w < 0.f) {  // invalid: stays as it is
-        a.sig_out[i] = sp;
+        a.sig_out[0][p.i] = sp;
         return;
     }
     const float4 gp = v.guide(x, y);
-    const float covp = v.cov(x, y), slope_p = a.slope[i];
+    const float covp = v.cov(x, y), slope_p = a.slope[p.i];
     float su = 0.f, sl = 0.f, sl2 = 0.f;
     for (int dy = -R; dy <= R; ++dy) {
         const int qy = y + dy;
@@ -269,13 +368,9 @@ __global__ void __launch_bounds__(256) k_dn_variance(DnArgs a) {
         for (int dx = -R; dx <= R; ++dx) {
             const int qx = x + dx;
             if (qx < 0 || qx >= (int)a.W) continue;
-            const float4 sq = v.sig(qx, qy);
+            const float4 sq = v.sig(0, qx, qy);
             if (sq.w < 0.f) continue;
-            float u = 1.f;
-            if (dx != 0 || dy != 0) {
-                const int cheb = max(abs(dx), abs(dy));
-                u = dn_tap_weight(a, gp, covp, slope_p, v.guide(qx, qy), v.cov(qx, qy), (float)cheb, 0.f);
-            }
+            const float u = dn_window_weight(a, v, gp, covp, slope_p, dx, dy, qx, qy);
             const float l = dn_lum(sq);
             su = su + u;
             sl = sl + u * l;
@@ -284,68 +379,49 @@ __global__ void __launch_bounds__(256) k_dn_variance(DnArgs a) {
     }
     const float m1 = sl / su, m2 = sl2 / su;
     sp.w = dn_max(0.f, m2 - m1 * m1);
-    a.sig_out[i] = sp;
+    a.sig_out[0][p.i] = sp;
 }
 
 template <int R>
 __global__ void __launch_bounds__(256) k_dn_atrous(DnArgs a) {
-    constexpr int N = R > 0 ? DnView<R>::LW * DnView<R>::LH : 1;
-    __shared__ float4 lg[N];
-    __shared__ float4 ls[N];
-    __shared__ float lc[N];
-    const DnView<R> v(a, lg, ls, lc);
-    const int x = blockIdx.x * DN_TW + (threadIdx.x & (DN_TW - 1));
-    const int y = blockIdx.y * DN_TH + threadIdx.x / DN_TW;
-    const int W = (int)a.W, H = (int)a.H;
-    if (x >= W || y >= H) return;
-    const size_t i = (size_t)y * a.W + x;
+    using Tile = DnTile<R, 1, DnArgs>;
+    __shared__ typename Tile::Lds lds;
+    const Tile v(a, lds);
+    const DnPixel p = dn_pixel(a);
+    if (!p.inside) return;
+    const int x = p.x, y = p.y, W = (int)a.W, H = (int)a.H;
     const int step = (int)a.step;
-    const float4 sp = v.sig(x, y);
+    const float4 sp = v.sig(0, x, y);
     const float4 gp = v.guide(x, y);
-    const float covp = v.cov(x, y), slope_p = a.slope[i];
+    const float covp = v.cov(x, y), slope_p = a.slope[p.i];
     const bool valid_p = !(sp.w < 0.f);
-    // 3x3 blur of the variance, clamped coordinates; an invalid pixel counts as variance 0
     float den = 0.f, lp = 0.f;
     if (valid_p) {
-        float vb = 0.f;
-        for (int dy = -1; dy <= 1; ++dy) {
-            const int qy = min(max(y + dy, 0), H - 1);
-            for (int dx = -1; dx <= 1; ++dx) {
-                const int qx = min(max(x + dx, 0), W - 1);
-                const float k = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
-                vb = vb + k * dn_max(v.sig(qx, qy).w, 0.f);
-            }
-        }
-        den = a.sigma_color * sqrtf(vb) + 1e-6f;
+        den = a.sigma_color * sqrtf(dn_blur_variance(v, 0, x, y, W, H)) + 1e-6f;
         lp = dn_lum(sp);
     }
-    float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f;
+    DnSums sum;
     for (int iy = -2; iy <= 2; ++iy) {
         const int qy = y + iy * step;
         if (qy < 0 || qy >= H) continue;
-        const float hy = iy == 0 ? 0.375f : (iy == 1 || iy == -1 ? 0.25f : 0.0625f);
+        const float hy = dn_tap5(iy);
         for (int ix = -2; ix <= 2; ++ix) {
             const int qx = x + ix * step;
             if (qx < 0 || qx >= W) continue;
-            const float4 sq = v.sig(qx, qy);
+            const float4 sq = v.sig(0, qx, qy);
             if (sq.w < 0.f) continue;
-            const float hx = ix == 0 ? 0.375f : (ix == 1 || ix == -1 ? 0.25f : 0.0625f);
-            float w = hx * hy;
+            float w = dn_tap5(ix) * hy;
             if (ix != 0 || iy != 0) {
                 const float d_l = valid_p ? dn_abs(lp - dn_lum(sq)) / den : 0.f;
                 const int cheb = step * max(abs(ix), abs(iy));
-                w = w * dn_tap_weight(a, gp, covp, slope_p, v.guide(qx, qy), v.cov(qx, qy), (float)cheb, d_l);
+                float wn, dg;
+                dn_tap_guide(a, gp, covp, slope_p, v.guide(qx, qy), v.cov(qx, qy), (float)cheb, wn, dg);
+                w = w * dn_tap_falloff(wn, dg, d_l);
             }
-            sw = sw + w;
-            sr = sr + w * sq.x;
-            sg = sg + w * sq.y;
-            sb = sb + w * sq.z;
-            sv = sv + (w * w) * sq.w;
+            sum.add(w, sq);
         }
     }
-    float4 o = make_float4(0.f, 0.f, 0.f, -1.f);
-    if (sw > 0.f) o = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
-    a.sig_out[i] = o;
+    a.sig_out[0][p.i] = sum.result();
 }
 
 // Remodulate: cropped pixels {s * a_d, alpha, 1}, border pixels zero (sig_in: the last pass's output).
@@ -353,18 +429,13 @@ __global__ void __launch_bounds__(256) k_dn_finalize(DnArgs a) {
     const size_t n = (size_t)a.totalW * a.totalH;
     const size_t ti = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (ti >= n) return;
-    const uint32_t tx = (uint32_t)(ti % a.totalW), ty = (uint32_t)(ti / a.totalW);
+    size_t i;
     float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    if (tx >= a.fb && ty >= a.fb && tx - a.fb < a.W && ty - a.fb < a.H) {
-        const size_t i = (size_t)(ty - a.fb) * a.W + (tx - a.fb);
-        const float4 s = a.sig_in[i], ce = a.centre[i];
-        o[0] = s.x * ce.x;
-        o[1] = s.y * ce.y;
-        o[2] = s.z * ce.z;
-        o[3] = ce.w;
-        o[4] = 1.f;
+    if (dn_cropped(a, ti, i)) {
+        const float4 ce = a.centre[i];
+        dn_remodulate(a.sig_in[0][i], ce, ce.w, o);
     }
-    for (int k = 0; k < 5; ++k) a.out[ti * 5 + k] = o[k];
+    dn_store_pixel(a.out, ti, o);
 }
 
 }  // namespace nd

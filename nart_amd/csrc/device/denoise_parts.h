@@ -4,8 +4,9 @@
 // What a tap's weight takes from the guides -- w_n and d_g: the normal dot product and its squarings, the
 // depth division, the coverage division -- does not depend on the part, so a launch handles a chunk of
 // C parts (1..4, a template value) and computes it once per tap; per part it computes d_l, the falloff
-// f(d_g + d_l), the weight and the five sums.  The arithmetic is denoise.h's own (dn_guides, dn_slope, dn_signal,
-// dn_tap_guide, dn_tap_falloff, dn_lum): nothing of it is restated here.
+// f(d_g + d_l), the weight and the five sums.  The arithmetic and the tile view are denoise.h's own
+// (dn_guides, dn_slope, dn_signal, dn_tap_guide, dn_tap_falloff, dn_blur_variance, DnSums, dn_remodulate,
+// DnTile<R, C>): nothing of them is restated here.
 //   k_dnp_prepare       albedo and normal -> guide {n.xyz, z}, cov, a_d, slope, once; every part ->
 //                       its signal {s.rgb, v} and alpha
 //   k_dnp_variance<C>   7x7 guide-weighted luminance variance of C parts; u = w_n * f(d_g) is shared
@@ -26,7 +27,7 @@ namespace nd {
 constexpr uint32_t DNP_MAX_PARTS = 9;  // NART_DENOISE_PARTS_MAX: 8 light groups, or the 9 layers of 8 cuts
 constexpr int DNP_MAX_CHUNK = 4;
 
-struct DnpArgs {
+struct DnpArgs : DnFilterArgs {
     // guides of all parts: nart_pixel images of totalW x totalH
     const float* albedo;
     const float* normal;
@@ -43,10 +44,6 @@ struct DnpArgs {
     float4* ad;     // {a_d.rgb, 0}
     float* slope;
     uint32_t n;
-    uint32_t W, H, totalW, totalH, fb;
-    uint32_t step;
-    uint32_t normal_squarings;
-    float sigma_color, sigma_depth, depth_eps, sigma_coverage, albedo_floor;
 };
 
 struct PartsSumArgs {
@@ -57,83 +54,38 @@ struct PartsSumArgs {
 };
 
 __global__ void __launch_bounds__(256) k_dnp_prepare(DnpArgs a) {
-    const uint32_t x = blockIdx.x * DN_TW + (threadIdx.x & (DN_TW - 1));
-    const uint32_t y = blockIdx.y * DN_TH + threadIdx.x / DN_TW;
-    if (x >= a.W || y >= a.H) return;
-    const size_t ti = (size_t)(y + a.fb) * a.totalW + (x + a.fb);
-    const size_t i = (size_t)y * a.W + x;
+    const DnPixel p = dn_pixel(a);
+    if (!p.inside) return;
     float4 g, ce;
     float cov;
-    dn_guides(a, ti, g, cov, ce);
-    const float slope = dn_slope(a, x, y, ti, g.w);
-    a.guide[i] = g;
-    a.cov[i] = cov;
-    a.ad[i] = make_float4(ce.x, ce.y, ce.z, 0.f);
-    a.slope[i] = slope;
+    dn_guides(a, p.ti, g, cov, ce);
+    const float slope = dn_slope(a, p.x, p.y, p.ti, g.w);
+    a.guide[p.i] = g;
+    a.cov[p.i] = cov;
+    a.ad[p.i] = make_float4(ce.x, ce.y, ce.z, 0.f);
+    a.slope[p.i] = slope;
 #pragma unroll
     for (uint32_t k = 0; k < DNP_MAX_PARTS; ++k) {  // (constant indices: the arguments stay in registers)
         if (k < a.n) {
             float c[4];
-            dn_mean(a.part[k] + ti * 5, c);
-            a.sig_out[k][i] = dn_valid(c) ? dn_signal(c, ce, 0.f) : dn_invalid_signal();
-            a.alpha[k][i] = c[3];
+            dn_mean(a.part[k] + p.ti * 5, c);
+            a.sig_out[k][p.i] = dn_valid(c) ? dn_signal(c, ce, 0.f) : dn_invalid_signal();
+            a.alpha[k][p.i] = c[3];
         }
     }
 }
 
-// A block's view of the per-tap records of C parts, as DnView: tile plus R pixels of halo in LDS
-// (R > 0), or global memory (R == 0).  at() is only called with coordinates inside the image.
-template <int R, int C>
-struct DnpView {
-    static constexpr int LW = DN_TW + 2 * R, LH = DN_TH + 2 * R;
-    static constexpr int N = R > 0 ? LW * LH : 1;
-    float4* lg;
-    float4* ls;  // [C][N]
-    float* lc;
-    const DnpArgs& a;
-    int x0, y0;  // image coordinates of the staged region's first pixel
-
-    __device__ DnpView(const DnpArgs& args, float4* g, float4* s, float* c) : lg(g), ls(s), lc(c), a(args) {
-        x0 = (int)(blockIdx.x * DN_TW) - R;
-        y0 = (int)(blockIdx.y * DN_TH) - R;
-        if (R > 0) {
-            for (int k = threadIdx.x; k < LW * LH; k += 256) {
-                const int gx = x0 + k % LW, gy = y0 + k / LW;
-                const bool inside = gx >= 0 && gy >= 0 && gx < (int)a.W && gy < (int)a.H;
-                const size_t i = inside ? (size_t)gy * a.W + gx : 0;
-                lg[k] = inside ? a.guide[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-                lc[k] = inside ? a.cov[i] : 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) ls[c * N + k] = inside ? a.sig_in[c][i] : make_float4(0.f, 0.f, 0.f, -1.f);
-            }
-            __syncthreads();
-        }
-    }
-    __device__ __forceinline__ size_t idx(int x, int y) const {
-        return R > 0 ? (size_t)((y - y0) * LW + (x - x0)) : (size_t)y * a.W + x;
-    }
-    __device__ __forceinline__ float4 guide(int x, int y) const { return R > 0 ? lg[idx(x, y)] : a.guide[idx(x, y)]; }
-    __device__ __forceinline__ float cov(int x, int y) const { return R > 0 ? lc[idx(x, y)] : a.cov[idx(x, y)]; }
-    // c is a constant after unrolling
-    __device__ __forceinline__ float4 sig(int c, int x, int y) const {
-        return R > 0 ? ls[c * N + idx(x, y)] : a.sig_in[c][idx(x, y)];
-    }
-};
-
 template <int C>
 __global__ void __launch_bounds__(256) k_dnp_variance(DnpArgs a) {
     constexpr int R = 3;
-    using View = DnpView<R, C>;
-    __shared__ float4 lg[View::N];
-    __shared__ float4 ls[C * View::N];
-    __shared__ float lc[View::N];
-    const View v(a, lg, ls, lc);
-    const int x = blockIdx.x * DN_TW + (threadIdx.x & (DN_TW - 1));
-    const int y = blockIdx.y * DN_TH + threadIdx.x / DN_TW;
-    if (x >= (int)a.W || y >= (int)a.H) return;
-    const size_t i = (size_t)y * a.W + x;
+    using Tile = DnTile<R, C, DnpArgs>;
+    __shared__ typename Tile::Lds lds;
+    const Tile v(a, lds);
+    const DnPixel p = dn_pixel(a);
+    if (!p.inside) return;
+    const int x = p.x, y = p.y;
     const float4 gp = v.guide(x, y);
-    const float covp = v.cov(x, y), slope_p = a.slope[i];
+    const float covp = v.cov(x, y), slope_p = a.slope[p.i];
     float su[C], sl[C], sl2[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) su[c] = sl[c] = sl2[c] = 0.f;
@@ -143,13 +95,8 @@ __global__ void __launch_bounds__(256) k_dnp_variance(DnpArgs a) {
         for (int dx = -R; dx <= R; ++dx) {
             const int qx = x + dx;
             if (qx < 0 || qx >= (int)a.W) continue;
-            float u = 1.f;  // of every part: an invalid tap is skipped per part below
-            if (dx != 0 || dy != 0) {
-                const int cheb = max(abs(dx), abs(dy));
-                float wn, dg;
-                dn_tap_guide(a, gp, covp, slope_p, v.guide(qx, qy), v.cov(qx, qy), (float)cheb, wn, dg);
-                u = dn_tap_falloff(wn, dg, 0.f);
-            }
+            // of every part: an invalid tap is skipped per part below
+            const float u = dn_window_weight(a, v, gp, covp, slope_p, dx, dy, qx, qy);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 const float4 sq = v.sig(c, qx, qy);
@@ -168,26 +115,22 @@ __global__ void __launch_bounds__(256) k_dnp_variance(DnpArgs a) {
             const float m1 = sl[c] / su[c], m2 = sl2[c] / su[c];
             sp.w = dn_max(0.f, m2 - m1 * m1);
         }
-        a.sig_out[c][i] = sp;
+        a.sig_out[c][p.i] = sp;
     }
 }
 
 template <int R, int C>
 __global__ void __launch_bounds__(256) k_dnp_atrous(DnpArgs a) {
-    using View = DnpView<R, C>;
-    __shared__ float4 lg[View::N];
-    __shared__ float4 ls[C * View::N];
-    __shared__ float lc[View::N];
-    const View v(a, lg, ls, lc);
-    const int x = blockIdx.x * DN_TW + (threadIdx.x & (DN_TW - 1));
-    const int y = blockIdx.y * DN_TH + threadIdx.x / DN_TW;
-    const int W = (int)a.W, H = (int)a.H;
-    if (x >= W || y >= H) return;
-    const size_t i = (size_t)y * a.W + x;
+    using Tile = DnTile<R, C, DnpArgs>;
+    __shared__ typename Tile::Lds lds;
+    const Tile v(a, lds);
+    const DnPixel p = dn_pixel(a);
+    if (!p.inside) return;
+    const int x = p.x, y = p.y, W = (int)a.W, H = (int)a.H;
     const int step = (int)a.step;
     const float4 gp = v.guide(x, y);
-    const float covp = v.cov(x, y), slope_p = a.slope[i];
-    // per part: 3x3 blur of the variance, clamped coordinates; an invalid pixel counts as variance 0
+    const float covp = v.cov(x, y), slope_p = a.slope[p.i];
+    // per part: the colour distance's denominator from the blurred variance, where the centre is valid
     bool valid_p[C];
     float den[C], lp[C];
 #pragma unroll
@@ -197,30 +140,19 @@ __global__ void __launch_bounds__(256) k_dnp_atrous(DnpArgs a) {
         den[c] = 0.f;
         lp[c] = 0.f;
         if (valid_p[c]) {
-            float vb = 0.f;
-            for (int dy = -1; dy <= 1; ++dy) {
-                const int qy = min(max(y + dy, 0), H - 1);
-                for (int dx = -1; dx <= 1; ++dx) {
-                    const int qx = min(max(x + dx, 0), W - 1);
-                    const float k = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
-                    vb = vb + k * dn_max(v.sig(c, qx, qy).w, 0.f);
-                }
-            }
-            den[c] = a.sigma_color * sqrtf(vb) + 1e-6f;
+            den[c] = a.sigma_color * sqrtf(dn_blur_variance(v, c, x, y, W, H)) + 1e-6f;
             lp[c] = dn_lum(sp);
         }
     }
-    float sw[C], sr[C], sg[C], sb[C], sv[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) sw[c] = sr[c] = sg[c] = sb[c] = sv[c] = 0.f;
+    DnSums sum[C];
     for (int iy = -2; iy <= 2; ++iy) {
         const int qy = y + iy * step;
         if (qy < 0 || qy >= H) continue;
-        const float hy = iy == 0 ? 0.375f : (iy == 1 || iy == -1 ? 0.25f : 0.0625f);
+        const float hy = dn_tap5(iy);
         for (int ix = -2; ix <= 2; ++ix) {
             const int qx = x + ix * step;
             if (qx < 0 || qx >= W) continue;
-            const float hx = ix == 0 ? 0.375f : (ix == 1 || ix == -1 ? 0.25f : 0.0625f);
+            const float hx = dn_tap5(ix);
             const bool centre = ix == 0 && iy == 0;
             float wn = 1.f, dg = 0.f;  // of every part
             if (!centre) {
@@ -236,20 +168,12 @@ __global__ void __launch_bounds__(256) k_dnp_atrous(DnpArgs a) {
                     const float d_l = valid_p[c] ? dn_abs(lp[c] - dn_lum(sq)) / den[c] : 0.f;
                     w = w * dn_tap_falloff(wn, dg, d_l);
                 }
-                sw[c] = sw[c] + w;
-                sr[c] = sr[c] + w * sq.x;
-                sg[c] = sg[c] + w * sq.y;
-                sb[c] = sb[c] + w * sq.z;
-                sv[c] = sv[c] + (w * w) * sq.w;
+                sum[c].add(w, sq);
             }
         }
     }
 #pragma unroll
-    for (int c = 0; c < C; ++c) {
-        float4 o = make_float4(0.f, 0.f, 0.f, -1.f);
-        if (sw[c] > 0.f) o = make_float4(sr[c] / sw[c], sg[c] / sw[c], sb[c] / sw[c], sv[c] / (sw[c] * sw[c]));
-        a.sig_out[c][i] = o;
-    }
+    for (int c = 0; c < C; ++c) a.sig_out[c][p.i] = sum[c].result();
 }
 
 // Remodulate the a.n <= 4 parts of a chunk: cropped pixels {s * a_d, alpha, 1}, border pixels zero
@@ -258,23 +182,15 @@ __global__ void __launch_bounds__(256) k_dnp_finalize(DnpArgs a) {
     const size_t n = (size_t)a.totalW * a.totalH;
     const size_t ti = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (ti >= n) return;
-    const uint32_t tx = (uint32_t)(ti % a.totalW), ty = (uint32_t)(ti / a.totalW);
-    const bool inside = tx >= a.fb && ty >= a.fb && tx - a.fb < a.W && ty - a.fb < a.H;
-    const size_t i = inside ? (size_t)(ty - a.fb) * a.W + (tx - a.fb) : 0;
+    size_t i;
+    const bool inside = dn_cropped(a, ti, i);
     const float4 ce = inside ? a.ad[i] : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int c = 0; c < DNP_MAX_CHUNK; ++c) {
         if ((uint32_t)c < a.n) {
             float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-            if (inside) {
-                const float4 s = a.sig_in[c][i];
-                o[0] = s.x * ce.x;
-                o[1] = s.y * ce.y;
-                o[2] = s.z * ce.z;
-                o[3] = a.alpha[c][i];
-                o[4] = 1.f;
-            }
-            for (int k = 0; k < 5; ++k) a.out[c][ti * 5 + k] = o[k];
+            if (inside) dn_remodulate(a.sig_in[c][i], ce, a.alpha[c][i], o);
+            dn_store_pixel(a.out[c], ti, o);
         }
     }
 }

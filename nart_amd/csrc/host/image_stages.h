@@ -151,32 +151,18 @@ int render_halves(nart_ctx* ctx, const nart_render_params* p, const nart_guide_p
     return rc;
 }
 
-// ---------------------------------------------------------------- denoiser (device/denoise.h)
-// Denoise images of the view: prepare, variance, the a-trous passes (LDS tiles for steps 1 and 2,
-// global reads beyond), finalise; synchronous.  ms: device time.  moment >= 0: the sample-variance
-// mode -- k_dn_prepare<true> takes the variance from the second-moment image and k_dn_variance is not
-// launched (its time reads 0).
-int denoise_device(const Images& v, const nart_denoise_params& dp, int beauty, int albedo, int normal, int moment, int out,
-                   hipStream_t st, double* ms) {
-    nart_ctx* ctx = v.ctx;
-    const size_t npx = (size_t)v.layout.W * v.layout.H;
-    // guide, signal x 2, centre (float4 each), then cov and slope
-    const size_t work_bytes = npx * (4 * sizeof(float4) + 2 * sizeof(float));
-    if (int rc = reserve(ctx, ctx->d_dn, ctx->device, work_bytes, "denoiser work buffers")) return rc;
-    float4* f4 = ctx->d_dn.as<float4>();
-    float4* sig[2] = {f4 + npx, f4 + 2 * npx};
-    const bool sample_variance = moment >= 0;
-    DnArgs a;
-    a.beauty = v.at(beauty);
-    a.albedo = v.at(albedo);
-    a.normal = v.at(normal);
-    a.moment = sample_variance ? v.at(moment) : nullptr;
-    a.out = v.at(out);
-    a.guide = f4;
-    a.centre = f4 + 3 * npx;
-    a.cov = reinterpret_cast<float*>(f4 + 4 * npx);
-    a.slope = a.cov + npx;
-    v.layout.fill(a);
+// ---------------------------------------------------------------- the denoisers' driver (host/denoise_passes.h)
+// f(std::integral_constant<int, N>) for the N of Ns that equals n: a planned halo or chunk size into
+// the template argument of the kernel to launch.
+template <int... Ns, typename F>
+void with_constant(int n, F&& f) {
+    (void)((n == Ns && (f(std::integral_constant<int, Ns>{}), true)) || ...);
+}
+
+// The fields the three denoisers' arguments share, from the layout and dp; the tile kernels' grid (one
+// lane per cropped pixel) and the finalize kernels' (one lane per pixel of the total image).
+void fill_filter(DnFilterArgs& a, const ImageLayout& layout, const nart_denoise_params& dp) {
+    layout.fill(a);
     a.step = 1;
     a.normal_squarings = dp.normal_squarings;
     a.sigma_color = dp.sigma_color;
@@ -184,52 +170,106 @@ int denoise_device(const Images& v, const nart_denoise_params& dp, int beauty, i
     a.depth_eps = dp.depth_eps;
     a.sigma_coverage = dp.sigma_coverage;
     a.albedo_floor = dp.albedo_floor;
-    const dim3 grid((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH), block(256);
-    uint32_t e = 0;
-    HIPCHK(record(ctx->ev_dn[e++], st));
-    a.sig_in = nullptr;
-    if (sample_variance) {  // signal and variance at once, where the variance pass would have left them
-        a.sig_out = sig[1];
-        hipLaunchKernelGGL(k_dn_prepare<true>, grid, block, 0, st, a);
-        HIPCHK(record(ctx->ev_dn[e++], st));
-    } else {
-        a.sig_out = sig[0];
-        hipLaunchKernelGGL(k_dn_prepare<false>, grid, block, 0, st, a);
-        HIPCHK(record(ctx->ev_dn[e++], st));
-        a.sig_in = sig[0];
-        a.sig_out = sig[1];
-        hipLaunchKernelGGL(k_dn_variance, grid, block, 0, st, a);
+}
+dim3 tile_grid(const DnFilterArgs& a) { return dim3((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH); }
+dim3 total_grid(const DnFilterArgs& a) { return dim3((uint32_t)(((size_t)a.totalW * a.totalH + 255) / 256)); }
+
+// The planes of a work buffer laid out by `w` over npx pixels, once reserve_work has sized it.
+struct WorkPlanes {
+    DnWorkLayout w;
+    size_t npx;
+    uint8_t* base = nullptr;
+    float4* f4(uint32_t plane) const { return reinterpret_cast<float4*>(base + w.off4(plane, npx)); }
+    float* f1(uint32_t plane) const { return reinterpret_cast<float*>(base + w.off1(plane, npx)); }
+    float4* guide() const { return f4(w.guide()); }
+    float4* centre() const { return f4(w.centre()); }
+    // pingpong -1: none
+    float4* sig(int pingpong, uint32_t c) const { return pingpong < 0 ? nullptr : f4(w.sig((uint32_t)pingpong, c)); }
+    float* cov() const { return f1(w.cov()); }
+    float* slope() const { return f1(w.slope()); }
+    float* alpha(uint32_t k) const { return f1(w.alpha(k)); }
+};
+int reserve_work(nart_ctx* ctx, Buf& buf, WorkPlanes& planes, const char* what) {
+    if (int rc = reserve(ctx, buf, ctx->device, planes.npx * planes.w.bytes_per_pixel(), what)) return rc;
+    planes.base = buf.as<uint8_t>();
+    return NART_OK;
+}
+
+// Walks a planned sequence on `st`: an event before the first launch and one after each, launch(entry)
+// puts the entry's kernel on the stream; one synchronisation; then t.ms zeroed and every interval added
+// into its entry's slot.  ms: their total, the device time of the run.
+template <typename Launch>
+int run_denoise_passes(nart_ctx* ctx, DenoiseTimes& t, const DnSequence& seq, hipStream_t st, double* ms, Launch&& launch) {
+    HIPCHK(record(t.ev[0], st));
+    for (uint32_t k = 0; k < seq.n; ++k) {
+        launch(seq.launch[k]);
+        HIPCHK(hipGetLastError());
+        HIPCHK(record(t.ev[k + 1], st));
     }
-    HIPCHK(record(ctx->ev_dn[e++], st));
-    int cur = 1;
-    for (uint32_t i = 0; i < dp.iterations; ++i) {
-        a.sig_in = sig[cur];
-        a.sig_out = sig[cur ^ 1];
-        a.step = 1u << i;
-        if (i == 0) hipLaunchKernelGGL(k_dn_atrous<2>, grid, block, 0, st, a);
-        else if (i == 1) hipLaunchKernelGGL(k_dn_atrous<4>, grid, block, 0, st, a);
-        else hipLaunchKernelGGL(k_dn_atrous<0>, grid, block, 0, st, a);
-        HIPCHK(record(ctx->ev_dn[e++], st));
-        cur ^= 1;
-    }
-    a.sig_in = sig[cur];
-    const size_t n_total = (size_t)a.totalW * a.totalH;
-    hipLaunchKernelGGL(k_dn_finalize, dim3((uint32_t)((n_total + 255) / 256)), block, 0, st, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(record(ctx->ev_dn[e++], st));
-    HIPCHK(hipEventSynchronize(ctx->ev_dn[e - 1].handle()));
-    for (double& t : ctx->dn_ms) t = 0.0;
+    HIPCHK(hipEventSynchronize(t.ev[seq.n].handle()));
+    for (double& m : t.ms) m = 0.0;
     double total = 0.0;
-    for (uint32_t k = 0; k + 1 < e; ++k) {
-        if (sample_variance && k == 1) continue;  // no variance kernel ran between these two events
-        float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, ctx->ev_dn[k].handle(), ctx->ev_dn[k + 1].handle()));
-        // events 0..2 bracket prepare and variance, the last pair the finalise kernel
-        ctx->dn_ms[k + 2 == e ? 10 : k] = t;
-        total += t;
+    for (uint32_t k = 0; k < seq.n; ++k) {
+        float d = 0.f;
+        HIPCHK(hipEventElapsedTime(&d, t.ev[k].handle(), t.ev[k + 1].handle()));
+        t.ms[seq.launch[k].slot] += d;
+        total += d;
     }
     if (ms) *ms = total;
     return NART_OK;
+}
+
+// What the nart_hip_denoise*_timings getters share; any pointer may be null.
+void denoise_times(const DenoiseTimes& t, double* prepare_ms, double* variance_ms, double* pass_ms, double* finalize_ms) {
+    if (prepare_ms) *prepare_ms = t.ms[DN_SLOT_PREPARE];
+    if (variance_ms) *variance_ms = t.ms[DN_SLOT_VARIANCE];
+    if (pass_ms)
+        for (uint32_t k = 0; k < DN_MAX_ITERATIONS; ++k) pass_ms[k] = t.ms[DN_SLOT_PASS0 + k];
+    if (finalize_ms) *finalize_ms = t.ms[DN_SLOT_FINALIZE];
+}
+
+// ---------------------------------------------------------------- denoiser (device/denoise.h)
+// Denoise images of the view: the sequence of plan_denoise_passes (prepare, variance, the a-trous
+// passes, finalise); synchronous.  ms: device time.  moment >= 0: the sample-variance mode --
+// k_dn_prepare<true> takes the variance from the second-moment image and there is no variance launch
+// (its time reads 0).  The work buffer is the context's.
+int denoise_device(const Images& v, const nart_denoise_params& dp, int beauty, int albedo, int normal, int moment, int out,
+                   hipStream_t st, double* ms) {
+    nart_ctx* ctx = v.ctx;
+    WorkPlanes w = {DN_WORK_PLAIN, (size_t)v.layout.W * v.layout.H};
+    if (int rc = reserve_work(ctx, ctx->d_dn, w, "denoiser work buffers")) return rc;
+    const bool sample_variance = moment >= 0;
+    DnArgs a;
+    fill_filter(a, v.layout, dp);
+    a.beauty = v.at(beauty);
+    a.albedo = v.at(albedo);
+    a.normal = v.at(normal);
+    a.moment = sample_variance ? v.at(moment) : nullptr;
+    a.out = v.at(out);
+    a.guide = w.guide();
+    a.centre = w.centre();
+    a.cov = w.cov();
+    a.slope = w.slope();
+    const dim3 grid = tile_grid(a), block(256);
+    const DnSequence seq = plan_denoise_passes(dp.iterations, !sample_variance);
+    return run_denoise_passes(ctx, ctx->dn, seq, st, ms, [&](const DnLaunch& l) {
+        a.sig_in[0] = w.sig(l.in, 0);
+        a.sig_out[0] = w.sig(l.out, 0);
+        a.step = l.step;
+        switch (l.kind) {
+            case DnKind::Prepare:
+                if (sample_variance) hipLaunchKernelGGL(k_dn_prepare<true>, grid, block, 0, st, a);
+                else hipLaunchKernelGGL(k_dn_prepare<false>, grid, block, 0, st, a);
+                break;
+            case DnKind::Variance: hipLaunchKernelGGL(k_dn_variance, grid, block, 0, st, a); break;
+            case DnKind::Atrous:
+                with_constant<2, 4, 0>(l.halo, [&](auto R) {
+                    hipLaunchKernelGGL(k_dn_atrous<decltype(R)::value>, grid, block, 0, st, a);
+                });
+                break;
+            default: hipLaunchKernelGGL(k_dn_finalize, total_grid(a), block, 0, st, a); break;
+        }
+    });
 }
 
 // dp (null: the defaults) into d for a call that denoises, with the second-moment image or not.
@@ -283,20 +323,16 @@ int render_denoised(nart_ctx* ctx, const nart_render_params* p, const nart_denoi
 }
 
 // ---------------------------------------------------------------- cross-filtered denoiser (device/denoise_cross.h)
-// Cross-denoise images of the view: prepare, variance, the a-trous passes over both halves (LDS tiles
-// for steps 1 and 2, global reads beyond), finalise; synchronous.  error < 0: no error image.  The work
-// buffers are temporaries of the call.  ms: device time.
+// Cross-denoise images of the view: the sequence of plan_denoise_passes over both halves; synchronous.
+// error < 0: no error image.  The work buffers are temporaries of the call.  ms: device time.
 int denoise_cross_device(const Images& v, const nart_denoise_params& dp, int half_a, int half_b, int beauty, int albedo,
                          int normal, int out, int error, hipStream_t st, double* ms) {
     nart_ctx* ctx = v.ctx;
-    const size_t npx = (size_t)v.layout.W * v.layout.H;
-    // guide, centre, signal x 2 halves x 2 (float4 each), then cov and slope
     Buf work;  // freed on return
-    if (int rc = reserve(ctx, work, ctx->device, npx * (6 * sizeof(float4) + 2 * sizeof(float)), "cross denoiser work buffers"))
-        return rc;
-    float4* f4 = work.as<float4>();
-    float4* sig[2][2] = {{f4 + 2 * npx, f4 + 3 * npx}, {f4 + 4 * npx, f4 + 5 * npx}};  // [ping-pong][half]
+    WorkPlanes w = {DN_WORK_CROSS, (size_t)v.layout.W * v.layout.H};
+    if (int rc = reserve_work(ctx, work, w, "cross denoiser work buffers")) return rc;
     DnxArgs a;
+    fill_filter(a, v.layout, dp);
     a.half[0] = v.at(half_a);
     a.half[1] = v.at(half_b);
     a.beauty = v.at(beauty);
@@ -304,60 +340,28 @@ int denoise_cross_device(const Images& v, const nart_denoise_params& dp, int hal
     a.normal = v.at(normal);
     a.out = v.at(out);
     a.error = error >= 0 ? v.at(error) : nullptr;
-    a.guide = f4;
-    a.centre = f4 + npx;
-    a.cov = reinterpret_cast<float*>(f4 + 6 * npx);
-    a.slope = a.cov + npx;
-    v.layout.fill(a);
-    a.step = 1;
-    a.normal_squarings = dp.normal_squarings;
-    a.sigma_color = dp.sigma_color;
-    a.sigma_depth = dp.sigma_depth;
-    a.depth_eps = dp.depth_eps;
-    a.sigma_coverage = dp.sigma_coverage;
-    a.albedo_floor = dp.albedo_floor;
-    auto use = [&a, &sig](int in, int out_) {
-        for (int h = 0; h < 2; ++h) {
-            a.sig_in[h] = in < 0 ? nullptr : sig[in][h];
-            a.sig_out[h] = out_ < 0 ? nullptr : sig[out_][h];
+    a.guide = w.guide();
+    a.centre = w.centre();
+    a.cov = w.cov();
+    a.slope = w.slope();
+    const dim3 grid = tile_grid(a), block(256);
+    return run_denoise_passes(ctx, ctx->dnx, plan_denoise_passes(dp.iterations, true), st, ms, [&](const DnLaunch& l) {
+        for (uint32_t h = 0; h < 2; ++h) {
+            a.sig_in[h] = w.sig(l.in, h);
+            a.sig_out[h] = w.sig(l.out, h);
         }
-    };
-    const dim3 grid((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH), block(256);
-    uint32_t e = 0;
-    HIPCHK(record(ctx->ev_dnx[e++], st));
-    use(-1, 0);
-    hipLaunchKernelGGL(k_dnx_prepare, grid, block, 0, st, a);
-    HIPCHK(record(ctx->ev_dnx[e++], st));
-    use(0, 1);
-    hipLaunchKernelGGL(k_dnx_variance, grid, block, 0, st, a);
-    HIPCHK(record(ctx->ev_dnx[e++], st));
-    int cur = 1;
-    for (uint32_t i = 0; i < dp.iterations; ++i) {
-        use(cur, cur ^ 1);
-        a.step = 1u << i;
-        if (i == 0) hipLaunchKernelGGL(k_dnx_atrous<2>, grid, block, 0, st, a);
-        else if (i == 1) hipLaunchKernelGGL(k_dnx_atrous<4>, grid, block, 0, st, a);
-        else hipLaunchKernelGGL(k_dnx_atrous<0>, grid, block, 0, st, a);
-        HIPCHK(record(ctx->ev_dnx[e++], st));
-        cur ^= 1;
-    }
-    use(cur, -1);
-    const size_t n_total = (size_t)a.totalW * a.totalH;
-    hipLaunchKernelGGL(k_dnx_finalize, dim3((uint32_t)((n_total + 255) / 256)), block, 0, st, a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(record(ctx->ev_dnx[e++], st));
-    HIPCHK(hipEventSynchronize(ctx->ev_dnx[e - 1].handle()));
-    for (double& t : ctx->dnx_ms) t = 0.0;
-    double total = 0.0;
-    for (uint32_t k = 0; k + 1 < e; ++k) {
-        float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, ctx->ev_dnx[k].handle(), ctx->ev_dnx[k + 1].handle()));
-        // events 0..2 bracket prepare and variance, the last pair the finalise kernel
-        ctx->dnx_ms[k + 2 == e ? 10 : k] = t;
-        total += t;
-    }
-    if (ms) *ms = total;
-    return NART_OK;
+        a.step = l.step;
+        switch (l.kind) {
+            case DnKind::Prepare: hipLaunchKernelGGL(k_dnx_prepare, grid, block, 0, st, a); break;
+            case DnKind::Variance: hipLaunchKernelGGL(k_dnx_variance, grid, block, 0, st, a); break;
+            case DnKind::Atrous:
+                with_constant<2, 4, 0>(l.halo, [&](auto R) {
+                    hipLaunchKernelGGL(k_dnx_atrous<decltype(R)::value>, grid, block, 0, st, a);
+                });
+                break;
+            default: hipLaunchKernelGGL(k_dnx_finalize, total_grid(a), block, 0, st, a); break;
+        }
+    });
 }
 
 // dp (null: the defaults) into d for a call that cross-denoises: two halves need two samples.
@@ -658,132 +662,68 @@ int render_depth_cuts(nart_ctx* ctx, const nart_render_params* p, const uint32_t
 }
 
 // ---------------------------------------------------------------- denoised parts (device/denoise_parts.h)
-// One chunk of C parts, first + c the part of slot c: variance, the passes (LDS tiles for steps 1 and 2,
-// global reads beyond), finalise, an event after each (slot[e]: the time of dnp_ms the interval ending at
-// event e counts towards).  sig[0][k]: part k's prepared signal; sig[1][k]: its ping-pong partner.
-template <int C>
-int dnp_chunk(nart_ctx* ctx, DnpArgs a, uint32_t first, const nart_denoise_params& dp, float4* (&sig)[2][DNP_MAX_PARTS],
-              float* const* alpha, float* const* out, hipStream_t st, uint32_t& e, uint8_t* slot) {
-    const dim3 grid((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH), block(256);
-    a.n = C;
-    int cur = 0;
-    auto point = [&](int in) {
-        for (int c = 0; c < C; ++c) {
-            a.sig_in[c] = sig[in][first + c];
-            a.sig_out[c] = sig[in ^ 1][first + c];
-            a.alpha[c] = alpha[first + c];
-            a.out[c] = out[first + c];
-        }
-    };
-    point(cur);
-    a.step = 1;
-    hipLaunchKernelGGL(k_dnp_variance<C>, grid, block, 0, st, a);
-    slot[e] = 1;
-    HIPCHK(record(ctx->ev_dnp[e++], st));
-    cur ^= 1;
-    for (uint32_t i = 0; i < dp.iterations; ++i) {
-        point(cur);
-        a.step = 1u << i;
-        if (i == 0) hipLaunchKernelGGL((k_dnp_atrous<2, C>), grid, block, 0, st, a);
-        else if (i == 1) hipLaunchKernelGGL((k_dnp_atrous<4, C>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_dnp_atrous<0, C>), grid, block, 0, st, a);
-        slot[e] = (uint8_t)(2 + i);
-        HIPCHK(record(ctx->ev_dnp[e++], st));
-        cur ^= 1;
-    }
-    point(cur);
-    const size_t n_total = (size_t)a.totalW * a.totalH;
-    hipLaunchKernelGGL(k_dnp_finalize, dim3((uint32_t)((n_total + 255) / 256)), block, 0, st, a);
-    HIPCHK(hipGetLastError());
-    slot[e] = 10;
-    HIPCHK(record(ctx->ev_dnp[e++], st));
-    return NART_OK;
-}
-
-// Denoise K part images of the layout with shared guides, on ctx's device (current): prepare once, the
-// chunks of the plan (host/denoise_parts_plan.h; NART_DN_PARTS_CHUNK forces their size), and with `sum`
-// the sum of the outputs; synchronous.  sum may be one of the part images (they are consumed by
-// prepare), not an output.  The work buffers are temporaries of the call.  ms: device time.
+// Denoise K part images of the layout with shared guides, on ctx's device (current): the sequence of
+// plan_denoise_parts_passes -- prepare once, the rest per chunk of the plan (host/denoise_parts_plan.h;
+// NART_DN_PARTS_CHUNK forces the chunks' size), and with `sum` the sum of the outputs; synchronous.  sum
+// may be one of the part images (they are consumed by prepare), not an output.  The work buffers are
+// temporaries of the call.  ms: device time.
 int denoise_parts_device(nart_ctx* ctx, const ImageLayout& layout, const nart_denoise_params& dp, uint32_t K,
                          const float* const* parts, const float* albedo, const float* normal, float* const* out, float* sum,
                          hipStream_t st, double* ms) {
     const char* knob = env_opt("NART_DN_PARTS_CHUNK");
     const PartsPlan plan = plan_denoise_parts(K, knob && *knob ? (uint32_t)std::max(0, std::atoi(knob)) : 0u);
-    const size_t npx = (size_t)layout.W * layout.H;
-    // float4: guide, a_d, signal x 2 per part; then float: cov, slope, alpha per part
     Buf work;  // freed on return
-    const size_t n4 = 2 + 2 * (size_t)K, n1 = 2 + (size_t)K;
-    if (int rc = reserve(ctx, work, ctx->device, npx * (n4 * sizeof(float4) + n1 * sizeof(float)), "denoised parts work buffers"))
-        return rc;
-    float4* f4 = work.as<float4>();
-    float* f1 = reinterpret_cast<float*>(f4 + n4 * npx);
-    float4* sig[2][DNP_MAX_PARTS] = {};
-    float* alpha[DNP_MAX_PARTS] = {};
+    WorkPlanes w = {dn_work_parts(K), (size_t)layout.W * layout.H};
+    if (int rc = reserve_work(ctx, work, w, "denoised parts work buffers")) return rc;
     DnpArgs a = {};
+    fill_filter(a, layout, dp);
     a.albedo = albedo;
     a.normal = normal;
-    a.guide = f4;
-    a.ad = f4 + npx;
-    a.cov = f1;
-    a.slope = f1 + npx;
-    for (uint32_t k = 0; k < K; ++k) {
-        sig[0][k] = f4 + (2 + k) * npx;
-        sig[1][k] = f4 + (2 + K + k) * npx;
-        alpha[k] = f1 + (2 + k) * npx;
-        a.part[k] = parts[k];
-        a.sig_out[k] = sig[0][k];
-        a.alpha[k] = alpha[k];
-    }
-    layout.fill(a);
-    a.n = K;
-    a.step = 1;
-    a.normal_squarings = dp.normal_squarings;
-    a.sigma_color = dp.sigma_color;
-    a.sigma_depth = dp.sigma_depth;
-    a.depth_eps = dp.depth_eps;
-    a.sigma_coverage = dp.sigma_coverage;
-    a.albedo_floor = dp.albedo_floor;
-    const dim3 grid((a.W + DN_TW - 1) / DN_TW, (a.H + DN_TH - 1) / DN_TH), block(256);
-    uint32_t e = 0;
-    uint8_t slot[sizeof(ctx->ev_dnp) / sizeof(ctx->ev_dnp[0])] = {};
-    HIPCHK(record(ctx->ev_dnp[e++], st));
-    hipLaunchKernelGGL(k_dnp_prepare, grid, block, 0, st, a);
-    HIPCHK(hipGetLastError());
-    slot[e] = 0;
-    HIPCHK(record(ctx->ev_dnp[e++], st));
-    for (uint32_t k = 0; k < K; ++k) a.part[k] = nullptr, a.sig_out[k] = nullptr, a.alpha[k] = nullptr;
-    for (uint32_t j = 0; j < plan.n_chunks; ++j) {
-        int rc = NART_OK;
-        switch (plan.size[j]) {
-            case 1: rc = dnp_chunk<1>(ctx, a, plan.first[j], dp, sig, alpha, out, st, e, slot); break;
-            case 2: rc = dnp_chunk<2>(ctx, a, plan.first[j], dp, sig, alpha, out, st, e, slot); break;
-            case 3: rc = dnp_chunk<3>(ctx, a, plan.first[j], dp, sig, alpha, out, st, e, slot); break;
-            default: rc = dnp_chunk<4>(ctx, a, plan.first[j], dp, sig, alpha, out, st, e, slot); break;
+    a.guide = w.guide();
+    a.ad = w.centre();
+    a.cov = w.cov();
+    a.slope = w.slope();
+    const dim3 grid = tile_grid(a), block(256);
+    const DnSequence seq = plan_denoise_parts_passes(plan, dp.iterations, sum != nullptr);
+    return run_denoise_passes(ctx, ctx->dnp, seq, st, ms, [&](const DnLaunch& l) {
+        if (l.kind == DnKind::Sum) {
+            PartsSumArgs s = {};
+            for (uint32_t k = 0; k < K; ++k) s.in[k] = out[k];
+            s.out = sum;
+            s.n = K;
+            s.n_pixels = (uint64_t)a.totalW * a.totalH;
+            hipLaunchKernelGGL(k_parts_sum, total_grid(a), block, 0, st, s);
+            return;
         }
-        if (rc) return rc;
-    }
-    if (sum) {
-        PartsSumArgs s = {};
-        for (uint32_t k = 0; k < K; ++k) s.in[k] = out[k];
-        s.out = sum;
-        s.n = K;
-        s.n_pixels = (uint64_t)a.totalW * a.totalH;
-        hipLaunchKernelGGL(k_parts_sum, dim3((uint32_t)((s.n_pixels + 255) / 256)), block, 0, st, s);
-        HIPCHK(hipGetLastError());
-        slot[e] = 11;
-        HIPCHK(record(ctx->ev_dnp[e++], st));
-    }
-    HIPCHK(hipEventSynchronize(ctx->ev_dnp[e - 1].handle()));
-    for (double& t : ctx->dnp_ms) t = 0.0;
-    double total = 0.0;
-    for (uint32_t k = 1; k < e; ++k) {
-        float t = 0.f;
-        HIPCHK(hipEventElapsedTime(&t, ctx->ev_dnp[k - 1].handle(), ctx->ev_dnp[k].handle()));
-        ctx->dnp_ms[slot[k]] += t;
-        total += t;
-    }
-    if (ms) *ms = total;
-    return NART_OK;
+        // prepare takes all K parts, the others the parts of their chunk in the slots 0 .. n - 1
+        const bool prepare = l.kind == DnKind::Prepare;
+        const uint32_t first = prepare ? 0 : plan.first[l.chunk];
+        a.n = prepare ? K : plan.size[l.chunk];
+        for (uint32_t c = 0; c < a.n; ++c) {
+            a.part[c] = prepare ? parts[c] : nullptr;
+            a.sig_in[c] = w.sig(l.in, first + c);
+            a.sig_out[c] = w.sig(l.out, first + c);
+            a.alpha[c] = w.alpha(first + c);
+            a.out[c] = out[first + c];
+        }
+        a.step = l.step;
+        switch (l.kind) {
+            case DnKind::Prepare: hipLaunchKernelGGL(k_dnp_prepare, grid, block, 0, st, a); break;
+            case DnKind::Variance:
+                with_constant<1, 2, 3, 4>(a.n, [&](auto C) {
+                    hipLaunchKernelGGL(k_dnp_variance<decltype(C)::value>, grid, block, 0, st, a);
+                });
+                break;
+            case DnKind::Atrous:
+                with_constant<2, 4, 0>(l.halo, [&](auto R) {
+                    with_constant<1, 2, 3, 4>(a.n, [&](auto C) {
+                        hipLaunchKernelGGL((k_dnp_atrous<decltype(R)::value, decltype(C)::value>), grid, block, 0, st, a);
+                    });
+                });
+                break;
+            default: hipLaunchKernelGGL(k_dnp_finalize, total_grid(a), block, 0, st, a); break;
+        }
+    });
 }
 
 // nart_hip_denoise_parts: the K parts, the albedo, the normal, the K denoised images after them; the sum

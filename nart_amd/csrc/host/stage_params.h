@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../../include/nart_hip.h"
+#include "denoise_passes.h"
 #include "frame_plan.h"
 
 namespace nd {
@@ -27,7 +28,8 @@ constexpr nart_matte_params MATTE_DEFAULTS = {NART_MATTE_MESH, 6};
 // ---------------------------------------------------------------- denoiser
 inline const char* denoise_params_error(const nart_denoise_params* in, nart_denoise_params& out) {
     out = in ? *in : DENOISE_DEFAULTS;
-    if (out.iterations < 1 || out.iterations > 8) return "denoise iterations must be 1..8";
+    static_assert(DN_MAX_ITERATIONS == 8, "the message below, and pass_ms[8] of the timing getters");
+    if (out.iterations < 1 || out.iterations > DN_MAX_ITERATIONS) return "denoise iterations must be 1..8";
     if (out.normal_squarings > 16) return "denoise normal_squarings must be <= 16";
     if (!(out.sigma_color > 0.f) || !(out.sigma_depth > 0.f) || !(out.depth_eps > 0.f) || !(out.sigma_coverage > 0.f) ||
         !(out.albedo_floor > 0.f))

@@ -35,6 +35,7 @@
 #include "host/bucket_batch.h"
 #include "host/bvh_build.h"
 #include "host/denoise_parts_plan.h"
+#include "host/denoise_passes.h"
 #include "host/device_buf.h"
 #include "host/frame_plan.h"
 #include "host/latin_plan.h"
@@ -69,6 +70,13 @@ struct Stream {
         OnDevice<HipBackend> on(device);
         hipStreamDestroy(s);
     }
+};
+
+// The events around the launches of a denoise (run_denoise_passes: one before the first launch, one
+// after each) and the last run's device times by slot (host/denoise_passes.h, DN_SLOT_*).
+struct DenoiseTimes {
+    Event ev[DN_EVENT_BUDGET];
+    double ms[DN_SLOTS] = {};
 };
 
 struct nart_ctx {
@@ -143,22 +151,13 @@ struct nart_ctx {
     Event ev_cost[2], ev_cost_img[2];
     double cost_ms[2] = {0.0, 0.0};
     // denoiser (denoise_device): work buffers over the cropped image, the four device images of
-    // nart_hip_denoise / nart_hip_render_denoised (five with the moment image), events between its
-    // kernels, the last run's times
+    // nart_hip_denoise / nart_hip_render_denoised (five with the moment image)
     Buf d_dn, d_dn_img;
-    Event ev_dn[12];
-    double dn_ms[11] = {};  // prepare, variance, passes 0..7, finalise
-    // cross-filtered denoiser (denoise_cross_device): events between its kernels, the last run's times;
-    // its images and work buffers are temporaries of the call
-    Event ev_dnx[12];
-    double dnx_ms[11] = {};  // prepare, variance, passes 0..7, finalise
-    // denoised parts (denoise_parts_device): events between its kernels (prepare, then per chunk the
-    // variance, up to 8 passes and finalise, then the sum); the last run's times on the first device's
-    // context: prepare, variance, passes 0..7, finalise, sum, each summed over the chunks; on the
-    // caller's context the render_ms of the last whole-frame call's guides frame.  Its work buffers
-    // and images are temporaries of the call.
-    Event ev_dnp[2 + 9 * 10 + 1];
-    double dnp_ms[12] = {};
+    // the last run of the denoiser, of the cross-filtered denoiser (denoise_cross_device) and of the
+    // denoised parts (denoise_parts_device; each time summed over the chunks), on the first device's
+    // context.  The latter two's images and work buffers are temporaries of the call.
+    DenoiseTimes dn, dnx, dnp;
+    // on the caller's context: the render_ms of the guides frame of the last whole-frame parts call
     double dnp_guides_ms = 0.0;
     uint32_t sched = 0;        // NART_SCHED_* bits of the current render (nart_render_stats::schedule)
     // path-kernel scheduling buffers (ensure_queue, ensure_ilist, ensure_gstack; launch_render,
@@ -2802,12 +2801,7 @@ int nart_hip_render_denoised_moment(nart_ctx* ctx, const nart_render_params* p, 
 int nart_hip_denoise_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
                              double* finalize_ms) {
     if (!ctx) return NART_E_INVALID;
-    const nart_ctx* c0 = first_device(ctx);
-    if (prepare_ms) *prepare_ms = c0->dn_ms[0];
-    if (variance_ms) *variance_ms = c0->dn_ms[1];
-    if (pass_ms)
-        for (int k = 0; k < 8; ++k) pass_ms[k] = c0->dn_ms[2 + k];
-    if (finalize_ms) *finalize_ms = c0->dn_ms[10];
+    denoise_times(first_device(ctx)->dn, prepare_ms, variance_ms, pass_ms, finalize_ms);
     return NART_OK;
 }
 
@@ -2831,12 +2825,7 @@ int nart_hip_render_denoised_cross(nart_ctx* ctx, const nart_render_params* p, c
 int nart_hip_denoise_cross_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
                                    double* finalize_ms) {
     if (!ctx) return NART_E_INVALID;
-    const nart_ctx* c0 = first_device(ctx);
-    if (prepare_ms) *prepare_ms = c0->dnx_ms[0];
-    if (variance_ms) *variance_ms = c0->dnx_ms[1];
-    if (pass_ms)
-        for (int k = 0; k < 8; ++k) pass_ms[k] = c0->dnx_ms[2 + k];
-    if (finalize_ms) *finalize_ms = c0->dnx_ms[10];
+    denoise_times(first_device(ctx)->dnx, prepare_ms, variance_ms, pass_ms, finalize_ms);
     return NART_OK;
 }
 
@@ -2898,13 +2887,9 @@ int nart_hip_render_denoised_depth_layers(nart_ctx* ctx, const nart_render_param
 int nart_hip_denoise_parts_timings(const nart_ctx* ctx, double* prepare_ms, double* variance_ms, double* pass_ms,
                                    double* finalize_ms, double* sum_ms, double* guides_ms) {
     if (!ctx) return NART_E_INVALID;
-    const nart_ctx* c0 = first_device(ctx);
-    if (prepare_ms) *prepare_ms = c0->dnp_ms[0];
-    if (variance_ms) *variance_ms = c0->dnp_ms[1];
-    if (pass_ms)
-        for (int k = 0; k < 8; ++k) pass_ms[k] = c0->dnp_ms[2 + k];
-    if (finalize_ms) *finalize_ms = c0->dnp_ms[10];
-    if (sum_ms) *sum_ms = c0->dnp_ms[11];
+    const DenoiseTimes& t = first_device(ctx)->dnp;
+    denoise_times(t, prepare_ms, variance_ms, pass_ms, finalize_ms);
+    if (sum_ms) *sum_ms = t.ms[DN_SLOT_SUM];
     if (guides_ms) *guides_ms = ctx->dnp_guides_ms;
     return NART_OK;
 }
