@@ -1128,6 +1128,66 @@ enum {
 int nart_hip_trace(nart_ctx* ctx, uint32_t variant, uint32_t sk, int count, const float* in, uint32_t n,
                    uint32_t* out);
 
+/* Device scene probe (test hook, never launched by a render): one scene-bound device function of the
+   render path (patterns, lights, BSDF set-up, medium) on n caller-supplied records against the context's
+   own device scene, one lane per record, 256-lane blocks.  in: n records of NART_SCENE_IN_WORDS (16)
+   floats; out: n records of NART_SCENE_OUT_WORDS (32) floats; integer fields (u32) travel as their
+   bits; input words an op does not name are ignored and output words it does not name are 0.
+
+     op               in                                            out
+     TEX_FETCH        0 u32 texture, 1 su, 2 sv, 3 u32 rough        0-2 rgb (tex_fetch)
+     ENV_PDF          0 u32 light (an environment light), 1-2 st    0 env_ptn_pdf
+     LIGHT_LI         0 u32 light, 1-3 p, 4-6 wi (as given),        0-2 Li, 3 pdf, 4 tMax
+                      7 u32 want pdf (0: a null pdf pointer),
+                      8 theta_in (NaN: formed in the function),
+                      9 preset pdf, 10 preset tMax
+     LIGHT_BOUND      as LIGHT_LI (7-9 ignored)                     4 tMax (light_bound)
+     LIGHT_SAMPLE_LI  0 u32 light, 1-3 p, 4-5 sample,               0-2 Li, 3 pdf, 4 tMax, 5-7 wi
+                      9 preset pdf, 10 preset tMax
+     CREATE_BSDF      0 u32 material, 1-2 st, 3-5 sn, 6-8 dpds,     0-2 n, 3-5 n_t, 6-8 n_b, 9 u32 num,
+                      9 alphaTweak                                  10-20 b[0], 21-31 b[1]: u32 type, u32 flags,
+                                                                    rho (3), tau (3), eta, alpha_0, alpha_prime
+                                                                    (a lobe the BSDF does not have is all 0)
+     DG_LOOKUP        0-2 p (grid coordinates)                      0 dg_lookup on the global grid, 1 on the LDS copy
+                                                                    k_render_volume_sm stages (grids above its
+                                                                    4,096 cells: the global grid again), 2 dg_lookup2
+                                                                    (2x2x2 grids, else 0), 3 u32 1 where 2 is set
+     MEDIUM_WALK      0-2 o, 3-5 d (as given)                       0 u32 medium_sample_ray's answer, 1 u32 segments
+                                                                    listed, 2 tCurrent and 3 tMax after it, then per
+                                                                    maj_next call that returns true, up to
+                                                                    NART_SCENE_WALK_SEGMENTS (7): sigma, t0, t1,
+                                                                    u32 majorant index used (4 words from word 4)
+
+   A preset is what the output variable holds before the call: light_li leaves pdf and tMax alone on a
+   miss, light_sample_li's environment branch leaves pdf alone on a row of zero texels.
+
+   build: the (ENV, FM) pair of the path kernels that the light and BSDF ops are compiled for, exactly the
+   builds the renderer has: NART_SCENE_BUILD_ENV_ALL (true, NART_FT_ALL), _ALL (false, NART_FT_ALL),
+   _DIFFUSE (false, Lambert + disk), _GLASS (false, Lambert + glass + disk), _ENVTEX (true, Lambert +
+   plastic + environment + textures + normal maps).  The scene must fit the build by the renderer's rule:
+   its feature mask (nart_hip_scene_features) inside the build's mask, no environment light under an ENV =
+   false build, one under _ENVTEX.  The other ops ignore the build, which must still fit.
+
+   NART_E_INVALID: a null pointer, an unknown op or build, n above NART_EVAL_MAX_N (all before the
+   context is touched); a build the scene does not fit; DG_LOOKUP or MEDIUM_WALK on a scene without a
+   medium; a record whose texture, light or material index is outside the scene; an ENV_PDF record whose
+   light is no environment light or whose coordinates index outside the light's distribution, a LIGHT_SAMPLE_LI record for a textured
+   environment light whose sample is outside [0, 1] (both checked on the host: nothing is launched).
+   n == 0: NART_OK, nothing launched.  Multi-device contexts run it on their first device. */
+#define NART_SCENE_IN_WORDS 16
+#define NART_SCENE_OUT_WORDS 32
+#define NART_SCENE_WALK_SEGMENTS 7
+enum {
+    NART_SCENE_TEX_FETCH = 0, NART_SCENE_ENV_PDF = 1, NART_SCENE_LIGHT_LI = 2, NART_SCENE_LIGHT_BOUND = 3,
+    NART_SCENE_LIGHT_SAMPLE_LI = 4, NART_SCENE_CREATE_BSDF = 5, NART_SCENE_DG_LOOKUP = 6, NART_SCENE_MEDIUM_WALK = 7,
+    NART_SCENE_N_OPS = 8
+};
+enum {
+    NART_SCENE_BUILD_ENV_ALL = 0, NART_SCENE_BUILD_ALL = 1, NART_SCENE_BUILD_DIFFUSE = 2, NART_SCENE_BUILD_GLASS = 3,
+    NART_SCENE_BUILD_ENVTEX = 4, NART_SCENE_N_BUILDS = 5
+};
+int nart_hip_scene_eval(nart_ctx* ctx, uint32_t op, uint32_t build, const float* in, uint32_t n, float* out);
+
 /* Splat filter-index thresholds (host only, no device): thr65[k] = the least d2 whose AddSample
    filter index (render.cpp:43-49) is >= k.  NART_E_INVALID when filter_width is too small for
    them (the splat then evaluates sqrt and division per pair). */

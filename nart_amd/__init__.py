@@ -9,7 +9,9 @@ from .api import (HIP_SYMBOLS, PIXEL_FLOATS, SCENE_SYMBOLS, HipRenderer, bvh_inf
                   write_exr, DenoiseParams, sample_variance, AdaptiveParams, adaptive_levels, spp_image,
                   CascadeParams, cascade_levels, MatteParams, matte_ids, GuideParams, LIGHT_GROUPS_MAX,
                   DEPTH_CUTS_MAX, EVAL_OPS, EVAL_WORDS, EVAL_MASKS, FT_ALL, cost_grid, half_mean,
-                  TRACE_VARIANTS, TRACE_IN_WORDS, TRACE_OUT_WORDS, TRACE_NO_HIT, TRACE_CLOSEST, TRACE_ANY, trace_rays)
+                  TRACE_VARIANTS, TRACE_IN_WORDS, TRACE_OUT_WORDS, TRACE_NO_HIT, TRACE_CLOSEST, TRACE_ANY, trace_rays,
+                  SCENE_OPS, SCENE_IN_WORDS, SCENE_OUT_WORDS, SCENE_WALK_SEGMENTS, SCENE_BUILDS, SCENE_BUILD_MASKS,
+                  scene_builds_fitting)
 
 __all__ = ["HipRenderer", "bvh_info", "bvh_dump", "NartError", "NativeLibraryMissing", "RenderParams", "RenderStats", "Scene",
            "combine_tiles", "default_params", "filter_table", "finalize", "load_sessions", "parse_args", "read_exr",
@@ -17,4 +19,6 @@ __all__ = ["HipRenderer", "bvh_info", "bvh_dump", "NartError", "NativeLibraryMis
            "DenoiseParams", "sample_variance", "AdaptiveParams", "adaptive_levels", "spp_image",
            "CascadeParams", "cascade_levels", "MatteParams", "matte_ids", "GuideParams", "LIGHT_GROUPS_MAX",
            "DEPTH_CUTS_MAX", "EVAL_OPS", "EVAL_WORDS", "EVAL_MASKS", "FT_ALL", "cost_grid", "half_mean",
-           "TRACE_VARIANTS", "TRACE_IN_WORDS", "TRACE_OUT_WORDS", "TRACE_NO_HIT", "TRACE_CLOSEST", "TRACE_ANY", "trace_rays"]
+           "TRACE_VARIANTS", "TRACE_IN_WORDS", "TRACE_OUT_WORDS", "TRACE_NO_HIT", "TRACE_CLOSEST", "TRACE_ANY", "trace_rays",
+           "SCENE_OPS", "SCENE_IN_WORDS", "SCENE_OUT_WORDS", "SCENE_WALK_SEGMENTS", "SCENE_BUILDS", "SCENE_BUILD_MASKS",
+           "scene_builds_fitting"]

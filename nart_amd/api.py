@@ -103,6 +103,29 @@ def trace_rays(o, d, tmax=np.inf, kind=TRACE_CLOSEST):
     r[:, 4:7] = np.asarray(d, np.float32).reshape(-1, 3)
     r[:, 7] = np.broadcast_to(np.asarray(kind, np.uint32), (len(o),)).copy().view(np.float32)
     return r
+# nart_hip_scene_eval (include/nart_hip.h NART_SCENE_*; HipRenderer.scene_eval, oracle.scene_eval): ops,
+# record sizes and the (ENV, feature mask) builds of the path kernels its light and BSDF ops are compiled for
+SCENE_OPS = {"tex_fetch": 0, "env_pdf": 1, "light_li": 2, "light_bound": 3, "light_sample_li": 4, "create_bsdf": 5,
+             "dg_lookup": 6, "medium_walk": 7}
+SCENE_IN_WORDS, SCENE_OUT_WORDS, SCENE_WALK_SEGMENTS = 16, 32, 7
+SCENE_BUILDS = {"env_all": 0, "all": 1, "diffuse": 2, "glass": 3, "envtex": 4}
+SCENE_BUILD_MASKS = {"env_all": (True, FT_ALL), "all": (False, FT_ALL), "diffuse": (False, 0x21),
+                     "glass": (False, 0x25), "envtex": (True, 0x391)}
+
+
+def scene_builds_fitting(features, has_env):
+    """The SCENE_BUILDS a scene with this feature mask fits, by the renderer's rule (host/path_build.h
+    plan_build): the mask covers the scene's, a narrow build goes with the scene's has_env, and a build
+    without the environment code never meets an environment light."""
+    out = []
+    for name, (env, fm) in SCENE_BUILD_MASKS.items():
+        if features & ~fm:
+            continue
+        if (env or not has_env) if fm == FT_ALL else (env == has_env):
+            out.append(name)
+    return out
+
+
 # the feature masks the probe's templated ops are built for, with the BxDF kinds each creates
 # (path.h create_bsdf: 0 Lambert, 1 specular, 2 specular dielectric, 3 dielectric, 4 Torrance-Sparrow)
 EVAL_MASKS = {"all": (FT_ALL, (0, 1, 2, 3, 4)), "lambert": (0x1, (0,)), "specular": (0x2, (1, 4)),
@@ -217,6 +240,27 @@ class _BlobHead(ctypes.Structure):
                 ("num_textures", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("triangles", _P),
                 ("meshes", _P), ("materials", _P), ("lights", _P), ("textures", ctypes.POINTER(_Texture)),
                 ("cam_fov", ctypes.c_float), ("cam_m", ctypes.c_float * 16)]
+
+
+class Light(ctypes.Structure):
+    """nart_light (include/nart_scene.h); m is the glm::mat4 storage of the light's transform."""
+    _fields_ = [("type", ctypes.c_int32), ("radius", ctypes.c_float), ("inner_radius", ctypes.c_float),
+                ("intensity", ctypes.c_float), ("Le", Pattern), ("m", ctypes.c_float * 16)]
+
+
+LIGHT_DISK, LIGHT_RING, LIGHT_ENVIRONMENT = range(3)  # NART_LIGHT_*
+
+
+class _Medium(ctypes.Structure):
+    """nart_medium (include/nart_scene.h)."""
+    _fields_ = [("present", ctypes.c_int32), ("bounds_min", ctypes.c_float * 3), ("bounds_max", ctypes.c_float * 3),
+                ("sigma_a", ctypes.c_float), ("sigma_s", ctypes.c_float), ("Le", ctypes.c_float * 3),
+                ("res", ctypes.c_uint32 * 3), ("density", _P)]
+
+
+class _Blob(ctypes.Structure):
+    """nart_scene_blob (include/nart_scene.h) whole: _BlobHead's fields, then the medium."""
+    _fields_ = _BlobHead._fields_ + [("medium", _Medium)]
 
 
 _SCENE_SIGS = {
@@ -345,6 +389,7 @@ _HIP_SIGS = {
     "nart_hip_eval_sincos": (ctypes.c_int, [_P, _P, ctypes.c_uint32, _P, _P]),
     "nart_hip_eval": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, _P, ctypes.c_uint32, _P]),
     "nart_hip_trace": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, _P, ctypes.c_uint32, _P]),
+    "nart_hip_scene_eval": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, _P, ctypes.c_uint32, _P]),
     "nart_hip_set_variant": (ctypes.c_int, [_P, ctypes.c_int]),
     "nart_hip_set_splat_mode": (ctypes.c_int, [_P, ctypes.c_int]),
     "nart_hip_set_specialize": (ctypes.c_int, [_P, ctypes.c_int]),
@@ -596,6 +641,30 @@ class Scene:
             out.append(np.ctypeslib.as_array(ctypes.cast(t.rgba, ctypes.POINTER(ctypes.c_uint16)),
                                              shape=(t.height * t.width * 4,)).copy().reshape(t.height, t.width, 4))
         return out
+
+    def lights(self):
+        """Copies of the blob's nart_light records (Light: type, radius, inner_radius, intensity, Le, m),
+        in scene order."""
+        h = self._view()
+        src = ctypes.cast(h.lights, ctypes.POINTER(Light))
+        out = []
+        for i in range(h.num_lights):
+            L = Light()
+            ctypes.pointer(L)[0] = src[i]
+            out.append(L)
+        return out
+
+    def medium(self):
+        """The camera medium (nart_medium) as a dict -- bounds_min, bounds_max, sigma_a, sigma_s, Le, res
+        (x, y, z) and density as a (rz, ry, rx) float32 copy -- or None without one."""
+        m = ctypes.cast(self.blob, ctypes.POINTER(_Blob)).contents.medium
+        if not m.present:
+            return None
+        rx, ry, rz = m.res
+        dens = np.ctypeslib.as_array(ctypes.cast(m.density, ctypes.POINTER(ctypes.c_float)), shape=(rx * ry * rz,))
+        return {"bounds_min": np.array(m.bounds_min[:], np.float32), "bounds_max": np.array(m.bounds_max[:], np.float32),
+                "sigma_a": m.sigma_a, "sigma_s": m.sigma_s, "Le": np.array(m.Le[:], np.float32), "res": (rx, ry, rz),
+                "density": dens.copy().reshape(rz, ry, rx)}
 
     def close(self):
         if self._h:
@@ -1421,6 +1490,21 @@ class HipRenderer:
         out = np.zeros((len(x), TRACE_OUT_WORDS), np.uint32)
         self._check(self._lib.nart_hip_trace(self._ctx, TRACE_VARIANTS[variant] if isinstance(variant, str) else int(variant),
                                              int(sk), 1 if count else 0, x.ctypes.data, len(x), out.ctypes.data))
+        return out
+
+    def scene_eval(self, op, records, build=None):
+        """Device scene probe (nart_hip_scene_eval): one scene-bound device function (patterns, lights, BSDF
+        set-up, medium) on caller-supplied records against this context's device scene.  op: a name or
+        number of SCENE_OPS; records: (n, 16) float32, integer fields as their bits (include/nart_hip.h
+        documents the fields per op); build: a name or number of SCENE_BUILDS (None: "env_all", the generic
+        build, which every scene fits).  Returns (n, 32) float32."""
+        x = np.ascontiguousarray(records, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != SCENE_IN_WORDS:
+            raise ValueError("scene probe records must be (n, %d) float32, got %r" % (SCENE_IN_WORDS, x.shape))
+        out = np.zeros((len(x), SCENE_OUT_WORDS), np.float32)
+        b = 0 if build is None else (SCENE_BUILDS[build] if isinstance(build, str) else int(build))
+        self._check(self._lib.nart_hip_scene_eval(self._ctx, SCENE_OPS[op] if isinstance(op, str) else int(op), b,
+                                                  x.ctypes.data, len(x), out.ctypes.data))
         return out
 
     def close(self):

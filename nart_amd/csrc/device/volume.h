@@ -38,6 +38,12 @@ ND float glibc_logf_lds(float x, const double2* tab) {
     });
 }
 
+// The density grid's first n cells into LDS, by the whole block (a __syncthreads() must follow before
+// dg_lookup reads the copy): k_render_volume_sm's staging, shared with the scene probe.
+ND void dens_lds_stage(float* s_dens, const float* density, uint32_t n) {
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) s_dens[i] = density[i];
+}
+
 NHD float dg_at(const DMedium& m, const float* dens, uint32_t x, uint32_t y, uint32_t z) {  // media.cpp:3-7
     return dens[(m.rx * m.ry * z) + (m.rx * y) + x];
 }
@@ -209,7 +215,7 @@ __global__ __launch_bounds__(256, WV) void k_render_volume_sm(DScene S, RenderAr
     // lived in scratch memory: every field read in the loop was a scratch load)
     const float* dens = S.medium.density;
     if (A.lds_nodes) {
-        for (uint32_t i = threadIdx.x; i < A.lds_nodes; i += blockDim.x) s_dens[i] = S.medium.density[i];
+        dens_lds_stage(s_dens, S.medium.density, A.lds_nodes);
         dens = s_dens;
     }
     __syncthreads();

@@ -30,6 +30,7 @@
 #include "device/lightgroup.h"
 #include "device/matte.h"
 #include "device/probe.h"
+#include "device/scene_probe.h"
 #include "device/trace_probe.h"
 #include "device/volume.h"
 #include "host/bucket_batch.h"
@@ -130,6 +131,9 @@ struct nart_ctx {
     double cas_ms[2] = {0.0, 0.0};
     double mat_ms[2] = {0.0, 0.0};
     uint32_t num_meshes = 0, num_materials = 0;  // the scene's: the id counts of the two matte kinds
+    uint32_t num_textures = 0;  // the scene's: nart_hip_scene_eval checks a record's texture index against it
+    std::vector<DLight> lights;      // the host's copy of DScene::lights, and {w, h} of DScene::envs[k]:
+    std::vector<uint32_t> env_dims;  // nart_hip_scene_eval checks a record's coordinates against them
     // light groups: the group of every light, uploaded by the call (set_light_groups); events around a
     // batch's group splats (render_buckets) and the mix (light_mix_device); the last call's times: group
     // splats ([0] on the caller's context), mix ([1] on the first device's)
@@ -2197,12 +2201,16 @@ int nart_hip_create(const nart_scene_blob* blob, int device_id, nart_ctx** out) 
             if ((rc = build_env(ctx, blob->textures[L.Le.texture], d))) return bail(rc);
             lights.back().env = (int32_t)envs.size();
             envs.push_back(d);
+            ctx->env_dims.push_back(d.w);
+            ctx->env_dims.push_back(d.h);
         }
     }
     if ((rc = upload(ctx, ctx->d_envs, envs.data(), envs.size(), "environment distributions"))) return bail(rc);
     if ((rc = upload(ctx, ctx->d_lights, lights.data(), lights.size(), "lights"))) return bail(rc);
+    ctx->lights = lights;
     ctx->features = scene_features(blob);
     std::vector<DTexture> texs(blob->num_textures);
+    ctx->num_textures = blob->num_textures;
     size_t pool = 0;
     for (uint32_t t = 0; t < blob->num_textures; ++t) {
         texs[t].w = blob->textures[t].width;
@@ -3123,6 +3131,64 @@ int nart_hip_trace(nart_ctx* ctx, uint32_t variant, uint32_t sk, int count, cons
     HIPCHK(hipLaunchKernel(kern, dim3(grid), dim3(256), args, lds, 0));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, bo.as<uint32_t>(), bytes_out, hipMemcpyDeviceToHost));
+    return NART_OK;
+}
+
+int nart_hip_scene_eval(nart_ctx* ctx, uint32_t op, uint32_t build, const float* in, uint32_t n, float* out) {
+    if (!ctx || !in || !out || op >= NART_SCENE_N_OPS || build >= NART_SCENE_N_BUILDS || n > NART_EVAL_MAX_N)
+        return NART_E_INVALID;
+    if (!ctx->subs.empty()) return forwarded(ctx, nart_hip_scene_eval(first_device(ctx), op, build, in, n, out));
+    if (!scene_build_fits(build, ctx->features, ctx->has_env))
+        return fail(ctx, NART_E_INVALID, "the scene does not fit the probe build's feature mask");
+    const DMedium& med = ctx->scene.medium;
+    const bool medium_op = op == NART_SCENE_DG_LOOKUP || op == NART_SCENE_MEDIUM_WALK;
+    if (medium_op && !med.present) return fail(ctx, NART_E_INVALID, "the scene has no medium");
+    // every index a record carries lies inside the scene, and no coordinate of a record can index outside
+    // an environment distribution: the device functions check neither
+    const bool light_op = op >= NART_SCENE_ENV_PDF && op <= NART_SCENE_LIGHT_SAMPLE_LI;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* x = in + (size_t)i * NART_SCENE_IN_WORDS;
+        uint32_t idx;
+        std::memcpy(&idx, x, 4);
+        const uint32_t count = op == NART_SCENE_TEX_FETCH ? ctx->num_textures
+                               : light_op                 ? ctx->scene.num_lights
+                               : op == NART_SCENE_CREATE_BSDF ? ctx->num_materials
+                                                              : 0xFFFFFFFFu;
+        if (!medium_op && idx >= count) return fail(ctx, NART_E_INVALID, "a probe record's index is outside the scene");
+        if (!light_op) continue;
+        const DLight& L = ctx->lights[idx];
+        const bool dist = L.type == NART_LIGHT_ENVIRONMENT && L.Le.type != NART_PTN_CONSTANT && L.env >= 0;
+        if (op == NART_SCENE_ENV_PDF && L.type != NART_LIGHT_ENVIRONMENT)
+            return fail(ctx, NART_E_INVALID, "ENV_PDF needs an environment light");
+        if (op == NART_SCENE_ENV_PDF && dist) {
+            const uint32_t w = ctx->env_dims[2 * (size_t)L.env], h = ctx->env_dims[2 * (size_t)L.env + 1];
+            if (f2u32(gmin(x[1], 0.9999f) * (float)w) >= w || f2u32(gmin(x[2], 0.9999f) * (float)h) >= h)
+                return fail(ctx, NART_E_INVALID, "an ENV_PDF record's coordinates index outside the distribution");
+        }
+        if (op == NART_SCENE_LIGHT_SAMPLE_LI && dist &&
+            !(x[4] >= 0.f && x[4] <= 1.f && x[5] >= 0.f && x[5] <= 1.f))
+            return fail(ctx, NART_E_INVALID, "a LIGHT_SAMPLE_LI record's sample is outside [0, 1]");
+    }
+    if (!n) return NART_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    Buf bi, bo;  // freed on return
+    int rc = NART_OK;
+    const size_t bytes_in = (size_t)n * NART_SCENE_IN_WORDS * sizeof(float);
+    const size_t bytes_out = (size_t)n * NART_SCENE_OUT_WORDS * sizeof(float);
+    if ((rc = reserve(ctx, bi, ctx->device, bytes_in, "scene probe records"))) return rc;
+    if ((rc = reserve(ctx, bo, ctx->device, bytes_out, "scene probe answers"))) return rc;
+    SceneProbeArgs P;
+    P.in = bi.as<float>();
+    P.out = bo.as<float>();
+    P.n = n;
+    P.op = op;
+    P.build = build;
+    // the grid in LDS as dispatch_volume stages it
+    if (op == NART_SCENE_DG_LOOKUP) P.lds_cells = volume_lds_cells(med.rx * med.ry * med.rz);
+    HIPCHK(hipMemcpy(bi.as<float>(), in, bytes_in, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_scene_probe, dim3((n + 255) / 256), dim3(256), (size_t)P.lds_cells * sizeof(float), 0, ctx->scene, P);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, bo.as<float>(), bytes_out, hipMemcpyDeviceToHost));
     return NART_OK;
 }
 

@@ -527,12 +527,20 @@ static int bvh_intersect(const oracle_scene* s, const ray_t* ray, isect_t* is, h
 }
 
 /* ---------------------------------------------------------------- patterns */
+/* oracle_scene_eval only (never set while a render runs): with g_guard set, every table read below --
+   texel, mpdf / cpdf / mcdf / ccdf, density corner -- checks its index first; one outside the table sets
+   g_oob and is not made (the reference indexes unchecked, and some inputs run off its tables on x86) */
+static int g_guard = 0, g_oob = 0;
 static v3 tex_fetch(const oracle_scene* s, int tex, float su, float sv, int rough) { /* texturepattern.cpp:172-187 */
     const nart_texture* t = &s->blob->textures[tex];
     float u = gmin(gmax(su, 0.0001f), 0.9999f);
     float v = gmin(gmax(1.f - sv, 0.0001f), 0.9999f);
     int iu = (int)((float)t->width * u);
     int iv = (int)((float)t->height * v);
+    if (g_guard && (iu < 0 || iv < 0 || (uint32_t)iu >= t->width || (uint32_t)iv >= t->height)) {
+        g_oob = 1;
+        return V3(0.f, 0.f, 0.f);
+    }
     const float* px = &s->tex_f[s->tex_off[tex] + ((size_t)iv * t->width + (size_t)iu) * 3];
     float r = px[0], g = px[1], b = px[2];
     if (rough) { r *= r; g *= g; b *= b; }
@@ -936,20 +944,40 @@ static uint32_t binary_search(float value, const float* v, uint32_t start, uint3
 static float pw_pdf(const struct pw2d* d, v2 s) { /* texturepattern.cpp:104-109 */
     uint32_t u = f2u32(s.x * (float)d->w);
     uint32_t v = f2u32(s.y * (float)d->h);
+    if (g_guard && (u >= d->w || v >= d->h)) {
+        g_oob = 1;
+        return 0.f;
+    }
     return d->mpdf[v] * d->cpdf[v * d->w + u];
 }
 static v2 pw_sample(const struct pw2d* d, v2 s, float* pdf) { /* texturepattern.cpp:72-102 */
     uint32_t lb = binary_search(s.y, d->mcdf, 0, d->h);
     float uc = 0.f;
+    if (g_guard && lb >= d->h) {
+        g_oob = 1;
+        return V2(0.f, 0.f);
+    }
     float vc = ((s.y - d->mcdf[lb]) / d->mpdf[lb]) + ((float)lb * d->invH);
     vc = gmin(vc, 0.9999999f);
     uint32_t v = f2u32(vc * (float)d->h);
+    if (g_guard && v >= d->h) {
+        g_oob = 1;
+        return V2(0.f, 0.f);
+    }
     if (d->mpdf[v] > 0.f) {
         lb = binary_search(s.x, d->ccdf, v * (d->w + 1), v * (d->w + 1) + d->w);
         lb %= (d->w + 1);
+        if (g_guard && lb >= d->w) {
+            g_oob = 1;
+            return V2(0.f, 0.f);
+        }
         uc = ((s.x - d->ccdf[v * (d->w + 1) + lb]) / d->cpdf[v * d->w + lb]) + ((float)lb * d->invW);
         uc = gmin(uc, 0.9999999f);
         uint32_t u = f2u32(uc * (float)d->w);
+        if (g_guard && u >= d->w) {
+            g_oob = 1;
+            return V2(0.f, 0.f);
+        }
         *pdf = d->mpdf[v] * d->cpdf[v * d->w + u];
     }
     /* else: `pdf == 0.f;` is a no-op (texturepattern.cpp:99): pdf keeps its value */
@@ -1280,6 +1308,10 @@ static v3 uniform_sample_sphere(v2 smp) { /* sampling.cpp:33-45 (pdf = 1/(4 pi) 
 static float dg_at(const nart_medium* m, uint8_t x, uint8_t y, uint8_t z) { /* media.cpp:3-7 */
     uint8_t rx = (uint8_t)m->res[0], ry = (uint8_t)m->res[1];
     uint32_t index = (uint32_t)((rx * ry * z) + (rx * y) + x);
+    if (g_guard && index >= m->res[0] * m->res[1] * m->res[2]) {
+        g_oob = 1;
+        return 0.f;
+    }
     return m->density[index];
 }
 static float dg_lookup(const nart_medium* m, v3 p) { /* media.cpp:10-45, trilinear */
@@ -2166,6 +2198,135 @@ int oracle_eval(uint32_t op, const float* in, uint32_t n, float* out) {
                 break;
             }
         }
+    }
+    return 0;
+}
+
+/* ---------------------------------------------------------------- scene probe (oracle_scene_eval) */
+static void scene_lobe_out(const bxdf_t* b, float* y) {
+    y[0] = bits2f((uint32_t)b->type);
+    y[1] = bits2f((uint32_t)b->flags);
+    y[2] = b->rho.x; y[3] = b->rho.y; y[4] = b->rho.z;
+    y[5] = b->tau.x; y[6] = b->tau.y; y[7] = b->tau.z;
+    y[8] = b->eta;
+    y[9] = b->alpha_0;
+    y[10] = b->alpha_prime;
+}
+
+/* One scene-bound function of the restatement on n caller-supplied records against s: the ops and records
+   of nart_hip_scene_eval (include/nart_hip.h).  Every table read is bounds-checked while it runs (g_guard);
+   a record that would read outside a table gets ORACLE_SCENE_OOB in flags[i] and whatever was computed up
+   to there in out.  Returns 0, or -1 for a null pointer, an unknown op, a medium op on a scene without a
+   medium, a texture, light or material index outside the scene, or ENV_PDF on a light that is no
+   environment light (nothing is written then).  Not reentrant. */
+int oracle_scene_eval(const oracle_scene* s, uint32_t op, const float* in, uint32_t n, float* out, uint32_t* flags) {
+    if (!s || !in || !out || !flags || op >= NART_SCENE_N_OPS) return -1;
+    const nart_scene_blob* b = s->blob;
+    const int medium_op = op == NART_SCENE_DG_LOOKUP || op == NART_SCENE_MEDIUM_WALK;
+    const int light_op = op >= NART_SCENE_ENV_PDF && op <= NART_SCENE_LIGHT_SAMPLE_LI;
+    if (medium_op && !s->has_medium) return -1;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t idx = f2bits(in[(size_t)i * NART_SCENE_IN_WORDS]);
+        uint32_t count = op == NART_SCENE_TEX_FETCH ? b->num_textures : light_op ? b->num_lights : b->num_materials;
+        if (!medium_op && idx >= count) return -1;
+        if (op == NART_SCENE_ENV_PDF && b->lights[idx].type != NART_LIGHT_ENVIRONMENT) return -1;
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* x = in + (size_t)i * NART_SCENE_IN_WORDS;
+        float* y = out + (size_t)i * NART_SCENE_OUT_WORDS;
+        for (int k = 0; k < NART_SCENE_OUT_WORDS; ++k) y[k] = 0.f;
+        g_guard = 1;
+        g_oob = 0;
+        const int idx = (int)f2bits(x[0]);
+        switch (op) {
+            case NART_SCENE_TEX_FETCH: {
+                v3 c = tex_fetch(s, idx, x[1], x[2], (int)f2bits(x[3]));
+                y[0] = c.x; y[1] = c.y; y[2] = c.z;
+                break;
+            }
+            case NART_SCENE_ENV_PDF: y[0] = ptn_pdf(s, idx, &b->lights[idx].Le, V2(x[1], x[2])); break;
+            case NART_SCENE_LIGHT_LI:
+            case NART_SCENE_LIGHT_BOUND: {
+                lisect_t li;
+                memset(&li, 0, sizeof(li));
+                li.tMax = x[10];
+                float pdf = x[9];
+                int want = op == NART_SCENE_LIGHT_LI && f2bits(x[7]) != 0u;
+                v3 L = light_li(s, idx, &li, V3(x[1], x[2], x[3]), V3(x[4], x[5], x[6]), want ? &pdf : NULL);
+                if (op == NART_SCENE_LIGHT_LI) {
+                    y[0] = L.x; y[1] = L.y; y[2] = L.z;
+                    y[3] = pdf;
+                }
+                y[4] = li.tMax;
+                break;
+            }
+            case NART_SCENE_LIGHT_SAMPLE_LI: {
+                lisect_t li;
+                memset(&li, 0, sizeof(li));
+                li.tMax = x[10];
+                float pdf = x[9];
+                v3 wi = V3(0.f, 0.f, 0.f);
+                v3 L = light_sample_li(s, idx, &li, V3(x[1], x[2], x[3]), &wi, V2(x[4], x[5]), &pdf);
+                y[0] = L.x; y[1] = L.y; y[2] = L.z;
+                y[3] = pdf;
+                y[4] = li.tMax;
+                y[5] = wi.x; y[6] = wi.y; y[7] = wi.z;
+                break;
+            }
+            case NART_SCENE_CREATE_BSDF: {
+                isect_t is;
+                isect_init(&is);
+                is.mat = (uint32_t)idx;
+                is.st = V2(x[1], x[2]);
+                is.sn = V3(x[3], x[4], x[5]);
+                is.dpds = V3(x[6], x[7], x[8]);
+                bsdf_t bs;
+                create_bsdf(s, &is, x[9], &bs);
+                y[0] = bs.n.x; y[1] = bs.n.y; y[2] = bs.n.z;
+                y[3] = bs.n_t.x; y[4] = bs.n_t.y; y[5] = bs.n_t.z;
+                y[6] = bs.n_b.x; y[7] = bs.n_b.y; y[8] = bs.n_b.z;
+                y[9] = bits2f((uint32_t)bs.num);
+                scene_lobe_out(&bs.b[0], y + 10);
+                if (bs.num > 1) scene_lobe_out(&bs.b[1], y + 21);
+                break;
+            }
+            case NART_SCENE_DG_LOOKUP: {
+                const nart_medium* m = &b->medium;
+                float d = dg_lookup(m, V3(x[0], x[1], x[2]));
+                y[0] = d;
+                y[1] = d;
+                if ((uint8_t)m->res[0] == 2 && (uint8_t)m->res[1] == 2 && (uint8_t)m->res[2] == 2) {
+                    y[2] = d;
+                    y[3] = bits2f(1u);
+                }
+                break;
+            }
+            case NART_SCENE_MEDIUM_WALK: {
+                maj_iter_t it;
+                memset(&it, 0, sizeof(it));
+                int ok = medium_sample_ray(s, V3(x[0], x[1], x[2]), V3(x[3], x[4], x[5]), &it);
+                y[0] = bits2f(ok ? 1u : 0u);
+                uint32_t ns = 0;
+                if (ok) {
+                    y[2] = it.tCurrent;
+                    y[3] = it.tMax;
+                    while (ns < NART_SCENE_WALK_SEGMENTS) {
+                        float sigma, t0, t1;
+                        uint32_t used = it.currentIndex;
+                        if (!maj_next(s, &it, &sigma, &t0, &t1)) break;
+                        y[4 + 4 * ns] = sigma;
+                        y[5 + 4 * ns] = t0;
+                        y[6 + 4 * ns] = t1;
+                        y[7 + 4 * ns] = bits2f(used);
+                        ++ns;
+                    }
+                }
+                y[1] = bits2f(ns);
+                break;
+            }
+        }
+        flags[i] = g_oob ? ORACLE_SCENE_OOB : 0u;
+        g_guard = 0;
     }
     return 0;
 }

@@ -98,6 +98,19 @@ int oracle_eval(uint32_t op, const float* in, uint32_t n, float* out);
                                          triangle shares the winner's chunk */
 #define ORACLE_TRACE_NAN_HIDES 512u   /* ... it finds a hit where the reference's search finds none */
 int oracle_trace_n(const oracle_scene* s, const float* in, uint32_t n, uint32_t* out);
+/* One scene-bound function of the restatement (tex_fetch, ptn_pdf, light_li, light_sample_li, create_bsdf,
+   dg_lookup, medium_sample_ray + the majorant iterator) on n caller-supplied records against s: the CPU
+   side of the device probe nart_hip_scene_eval, whose ops (NART_SCENE_*) and records -- 16 floats in, 32
+   out -- these are (include/nart_hip.h).  LIGHT_BOUND answers light_li's tMax; the three DG_LOOKUP words
+   are dg_lookup; theta_in is ignored (the restatement always forms it).  The reference indexes its tables
+   without checks and some inputs run off them on x86 (a NaN texture coordinate: (int)NaN is INT_MIN), so
+   every table read made here -- texel, mpdf / cpdf / mcdf / ccdf, density corner -- is bounds-checked:
+   on a miss the read is not made and flags[i] is ORACLE_SCENE_OOB (such a record must never be sent to
+   the device); else flags[i] is 0.  (The majorant index is checked by the restatement itself.)
+   0, or -1: a null pointer, an unknown op, a medium op without a medium, a texture / light / material
+   index outside the scene, ENV_PDF on a light that is no environment light. */
+#define ORACLE_SCENE_OOB 1u
+int oracle_scene_eval(const oracle_scene* s, uint32_t op, const float* in, uint32_t n, float* out, uint32_t* flags);
 /* Test statistic: the longest nested-dielectric list a path of this process reached (reset: zero it). */
 uint32_t oracle_max_list(int reset);
 

@@ -86,6 +86,7 @@ def lib():
         _lib.oracle_trace.argtypes = [P, P, P, ctypes.c_float, P]
         _lib.oracle_eval.argtypes = [ctypes.c_uint32, P, ctypes.c_uint32, P]
         _lib.oracle_trace_n.argtypes = [P, P, ctypes.c_uint32, P]
+        _lib.oracle_scene_eval.argtypes = [P, ctypes.c_uint32, P, ctypes.c_uint32, P, P]
     return _lib
 
 
@@ -216,6 +217,26 @@ def trace_n(orc, rays):
     if rc:
         raise RuntimeError("oracle_trace_n failed: %d" % rc)
     return out
+
+
+SCENE_OOB = 1  # nart_oracle.h ORACLE_SCENE_OOB
+
+
+def scene_eval(orc, op, records):
+    """One scene-bound function of the restatement on (n, 16) float32 records (oracle_scene_eval): op a name
+    or number of nart_amd.SCENE_OPS, the records those of HipRenderer.scene_eval (include/nart_hip.h).
+    Returns ((n, 32) float32 answers, (n,) uint32 flags): SCENE_OOB marks a record that would read outside
+    one of the reference's tables, which must not be sent to the device."""
+    from nart_amd import SCENE_OPS, SCENE_IN_WORDS, SCENE_OUT_WORDS
+    x = np.ascontiguousarray(records, np.float32)
+    assert x.ndim == 2 and x.shape[1] == SCENE_IN_WORDS, x.shape
+    out = np.zeros((len(x), SCENE_OUT_WORDS), np.float32)
+    flags = np.zeros(len(x), np.uint32)
+    rc = lib().oracle_scene_eval(orc._h, SCENE_OPS[op] if isinstance(op, str) else int(op), x.ctypes.data, len(x),
+                                 out.ctypes.data, flags.ctypes.data)
+    if rc:
+        raise RuntimeError("oracle_scene_eval failed: %d" % rc)
+    return out, flags
 
 
 def max_list_length(reset=False):

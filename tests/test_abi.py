@@ -112,6 +112,52 @@ def test_eval_validates_its_arguments(built):
     assert oracle.lib().oracle_eval(0, None, 2, y.ctypes.data) == -1 and np.all(y == 5.0)
 
 
+def test_scene_eval_validates_its_arguments(built):
+    """nart_hip_scene_eval without a device: a null context, input or output, an unknown op or build and a
+    record count above the cap are NART_E_INVALID before anything touches the context or a GPU, n == 0
+    included (with a context: test_gpu_scene_probe.py).  The Python names number the ops and builds and size
+    the records as the header does, the builds' masks are the path kernels' (host/path_build.h), and the
+    oracle's side refuses the same unknown op."""
+    import numpy as np
+    import oracle
+    lib = nart_amd.api.hip_lib()
+    x = np.zeros((2, nart_amd.SCENE_IN_WORDS), np.float32)
+    y = np.full((2, nart_amd.SCENE_OUT_WORDS), 5.0, np.float32)
+    fake = ctypes.c_void_p(x.ctypes.data)  # never dereferenced: every call below fails on another argument
+    for n in (0, 2):
+        for b in nart_amd.SCENE_BUILDS.values():
+            assert lib.nart_hip_scene_eval(None, 0, b, x.ctypes.data, n, y.ctypes.data) == -1
+        assert lib.nart_hip_scene_eval(fake, 0, 0, None, n, y.ctypes.data) == -1
+        assert lib.nart_hip_scene_eval(fake, 0, 0, x.ctypes.data, n, None) == -1
+        for op in (len(nart_amd.SCENE_OPS), 0xFFFFFFFF):
+            assert lib.nart_hip_scene_eval(fake, op, 0, x.ctypes.data, n, y.ctypes.data) == -1
+        for b in (len(nart_amd.SCENE_BUILDS), 0x3FF, 0xFFFFFFFF):
+            assert lib.nart_hip_scene_eval(fake, 0, b, x.ctypes.data, n, y.ctypes.data) == -1
+    for n in ((1 << 24) + 1, 0xFFFFFF01, 0xFFFFFFFF):
+        assert lib.nart_hip_scene_eval(fake, 0, 0, x.ctypes.data, n, y.ctypes.data) == -1, n
+    assert np.all(y == 5.0)
+    header = open(os.path.join(REPO, "include", "nart_hip.h")).read()
+    enum = dict((k.lower(), int(v)) for k, v in re.findall(r"NART_SCENE_(\w+) = (\d+)", header))
+    assert enum.pop("n_ops") == len(nart_amd.SCENE_OPS) and enum.pop("n_builds") == len(nart_amd.SCENE_BUILDS)
+    assert {k[6:]: v for k, v in enum.items() if k.startswith("build_")} == nart_amd.SCENE_BUILDS
+    assert {k: v for k, v in enum.items() if not k.startswith("build_")} == nart_amd.SCENE_OPS
+    words = dict(re.findall(r"#define NART_SCENE_(\w+) (\d+)", header))
+    assert (int(words["IN_WORDS"]), int(words["OUT_WORDS"]), int(words["WALK_SEGMENTS"])) == (
+        nart_amd.SCENE_IN_WORDS, nart_amd.SCENE_OUT_WORDS, nart_amd.SCENE_WALK_SEGMENTS)
+    build_h = open(os.path.join(REPO, "nart_amd", "csrc", "host", "path_build.h")).read()
+    ft = {"FT_" + k: v for k, v in (("LAMBERT", 1), ("PLASTIC", 0x10), ("GLASS", 4), ("DISK", 0x20), ("ENV", 0x80), ("TEX", 0x100),
+                                    ("NMAP", 0x200))}
+    for name, key in (("diffuse", "FM_DIFFUSE"), ("glass", "FM_GLASS"), ("envtex", "FM_ENVTEX")):
+        expr = re.search(r"constexpr uint32_t %s = ([^;]+);" % key, build_h).group(1)
+        assert sum(ft[t.strip()] for t in expr.split("|")) == nart_amd.SCENE_BUILD_MASKS[name][1], name
+    assert nart_amd.scene_builds_fitting(0x21, False) == ["env_all", "all", "diffuse", "glass"]
+    assert nart_amd.scene_builds_fitting(0x391, True) == ["env_all", "envtex"]
+    assert nart_amd.scene_builds_fitting(0x1e1, True) == ["env_all"] and nart_amd.scene_builds_fitting(0x21, True) == ["env_all"]
+    fl = np.zeros(2, np.uint32)
+    assert oracle.lib().oracle_scene_eval(fake, len(nart_amd.SCENE_OPS), x.ctypes.data, 2, y.ctypes.data, fl.ctypes.data) == -1
+    assert oracle.lib().oracle_scene_eval(None, 0, x.ctypes.data, 2, y.ctypes.data, fl.ctypes.data) == -1 and np.all(y == 5.0)
+
+
 def test_splat_thresholds_reproduce_filter_index(built):
     """The splat's filter index from d2 thresholds equals AddSample's
     uint8((sqrt(d2) / fw) * 64) clamped to 63 (render.cpp:43-49), float32 throughout."""
